@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — M alignments/s through `iteres stat` (hg38 rmsk) on MI355X: the drop-in command, end to end, on files.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1 without WORLD_SIZE in the environment: bench.py starts `python -m torch.distributed.run` with N ranks itself,
      as a child process, before anything touches the GPU; under torch.distributed.run it is one rank per GPU.)
+
+A plain run makes the inputs (kept under /tmp per parameter set and reused), runs W warm-up steps and K timed steps and
+prints the JSON line; with --dump-outputs DIR it also writes what the last timed step computed as DIR/<name>.npy (see
+dump_outputs). Everything below that is not the headline figure — `strong_scaling`, `filter_leg`, `cpu_baseline`,
+`cpu_baseline_mt`, `roofline`, `config.content` — is measured only under --full.
 
 Workload, N = 1 (BASELINE.json configs[2]): a coordinate-sorted 500 M-read synthetic hg38 BAM whose records carry 100 bases
 + qualities (tools/mkbam.c, BGZF level 1) with the CONTENT of a sequencer's BAM — `--content hiseq` (the default): independent
@@ -87,7 +92,13 @@ def parse_args():
                     "when the command reserved 50 GB per run — it reserves 12 GB now and the warm-up runs see to those)")
     ap.add_argument("--no-settle", action="store_true", help="(the default now; kept for old command lines)")
     ap.add_argument("--no-replay-check", action="store_true", help="profiling runs: skip the small oracle-checked launch, so that every k_stream launch of this process has the replay's size")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure what is not the headline figure: strong scaling (N > 1), the filter leg, the CPU baselines, "
+                    "the resident roofline and the BAM's content statistics (--cpu-reads, --filter-steps and --replay-steps apply only here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step computed as DIR/<name>.npy (float64)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------ device memory
@@ -131,7 +142,7 @@ def vram_settle(device, gb=176.0, pause=6.0):
 
 # ------------------------------------------------------------------------------------------------ inputs (rank 0)
 def ensure_inputs(a, threads):
-    """chrom.sizes / rep.sizes / rmsk.txt / reads.bam / sample.bam for these parameters, generated once per box."""
+    """chrom.sizes / rep.sizes / rmsk.txt / reads.bam for these parameters, generated once per box."""
     from iteres_amd import synth
     mkopts = mkbam_options(a)
     key = f"r{a.reads}_s{a.seq_len}_t{a.rows}_c{a.cpu_reads if getattr(a, 'gpus', 1) == 1 else 0}_" + "_".join(o.split("=")[1] for o in mkopts)
@@ -151,18 +162,8 @@ def ensure_inputs(a, threads):
     t1 = time.time()
     env = dict(os.environ, OMP_NUM_THREADS=str(threads))
     subprocess.check_call([MKBAM, os.path.join(wd, "chrom.sizes"), str(a.reads), os.path.join(wd, "reads.bam"), str(a.seq_len), "7"] + mkopts, env=env)
-    if a.cpu_reads > 0 and getattr(a, 'gpus', 1) == 1:
-        subprocess.check_call([MKBAM, os.path.join(wd, "chrom.sizes"), str(a.cpu_reads), os.path.join(wd, "sample.bam"), str(a.seq_len), "7"] + mkopts, env=env)
     info = {"table_s": round(t1 - t0, 1), "bam_s": round(time.time() - t1, 1), "bam_bytes": os.path.getsize(os.path.join(wd, "reads.bam")),
             "n_rep": len(tb.names), "n_fam": len(tb.fams), "n_cla": len(tb.clas)}
-    # what the decoder has to chew: literals / matches per BGZF block, bytes per read (a sample of blocks spread over the file,
-    # counted by pass 1 of the product's decoder built for the host and compared with zlib)
-    try:
-        sys.path.insert(0, os.path.join(ROOT, "tools"))
-        import bam_content
-        info["content"] = bam_content.content_stats(os.path.join(wd, "reads.bam"), 200)
-    except Exception as e:                                                    # never fatal: it is a description
-        info["content"] = {"error": str(e)[:200]}
     # the filter leg (configs[4]) takes the biggest class: how many of the rows it holds
     import numpy as np
     per_cla = np.bincount(np.asarray(tb.cla_of_row), minlength=len(tb.clas))
@@ -170,6 +171,31 @@ def ensure_inputs(a, threads):
     info["filter_class"] = {"name": tb.clas[k], "rows": int(per_cla[k]), "fraction_of_rows": round(float(per_cla[k]) / max(len(tb.cla_of_row), 1), 4)}
     json.dump(info, open(done, "w"))
     return wd, info
+
+
+def ensure_full_inputs(a, wd, info, threads):
+    """What only --full reads, added to ensure_inputs' directory once per box: sample.bam (the reference binary's sample)
+    and the content statistics of reads.bam."""
+    done = os.path.join(wd, "inputs.json")
+    if a.cpu_reads > 0 and getattr(a, 'gpus', 1) == 1 and "sample_s" not in info:
+        t0 = time.time()
+        if not os.path.exists(MKBAM):
+            subprocess.check_call(["gcc", "-O2", "-fopenmp", "-o", MKBAM, os.path.join(ROOT, "tools", "mkbam.c"), "-lz", "-ldl"])
+        env = dict(os.environ, OMP_NUM_THREADS=str(threads))
+        subprocess.check_call([MKBAM, os.path.join(wd, "chrom.sizes"), str(a.cpu_reads), os.path.join(wd, "sample.bam"), str(a.seq_len), "7"] + mkbam_options(a), env=env)
+        info["sample_s"] = round(time.time() - t0, 1)
+        json.dump(info, open(done, "w"))
+    if "content" not in info:
+        # what the decoder has to chew: literals / matches per BGZF block, bytes per read (a sample of blocks spread over the file,
+        # counted by pass 1 of the product's decoder built for the host and compared with zlib)
+        try:
+            sys.path.insert(0, os.path.join(ROOT, "tools"))
+            import bam_content
+            info["content"] = bam_content.content_stats(os.path.join(wd, "reads.bam"), 200)
+        except Exception as e:                                                # never fatal: it is a description
+            info["content"] = {"error": str(e)[:200]}
+        json.dump(info, open(done, "w"))
+    return info
 
 
 def mkbam_options(a):
@@ -222,6 +248,58 @@ def report_counts(path):
                     out.append(int(tok))
                     break
     return out
+
+
+WIG_SAMPLE = 1 << 21                   # positions of the wigs kept by dump_outputs: 3 x 16 MB, the rest of the dump ~1.5 MB
+WIG_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(run_dir, dest):
+    """What one run of the command computed, from the files it wrote into run_dir, as dest/<name>.npy (float64):
+    <level>_stat        the numeric columns of out.iteres.<level>.stat, one row per line in file order (level: subfamily,
+                        family, class)
+    report              the numbers of out.iteres.report in file order
+    wig_track_lengths   bases per fixedStep block of out.iteres.wig (both wigs have the same blocks, in the same order)
+    wig_track_sums      the coverage of each block summed, unique_wig_track_sums the same for out.iteres.unique.wig
+    wig_sample_index    WIG_SAMPLE positions of the concatenated blocks, drawn once with a fixed seed (all of them when
+                        there are fewer), and wig_sample / unique_wig_sample the coverage there
+    The bigWig files hold the wigs' numbers again and are left out. Returns {name: shape}."""
+    import re
+    import numpy as np
+    os.makedirs(dest, exist_ok=True)
+    arrays = {}
+    for level, n_text in (("subfamily", 3), ("family", 2), ("class", 1)):
+        with open(os.path.join(run_dir, f"out.iteres.{level}.stat")) as f:
+            rows = [ln.rstrip("\n").split("\t")[n_text:] for ln in f if ln.strip() and not ln.startswith("#")]
+        arrays[f"{level}_stat"] = np.array(rows, dtype=np.float64).reshape(len(rows), -1)
+    arrays["report"] = np.array(report_counts(os.path.join(run_dir, "out.iteres.report")), dtype=np.float64)
+    head = re.compile(rb"^fixedStep [^\n]*\n", re.M)
+    index = None
+    for prefix, fn in (("", "out.iteres.wig"), ("unique_", "out.iteres.unique.wig")):
+        with open(os.path.join(run_dir, fn), "rb") as f:
+            data = f.read()
+        ms = list(head.finditer(data))
+        ends = [m.start() for m in ms[1:]] + [len(data)]
+        lengths = np.array([data.count(b"\n", m.end(), e) for m, e in zip(ms, ends)], dtype=np.int64)
+        values = np.array(head.sub(b"", data).split(), dtype=np.float64)
+        if values.size != int(lengths.sum()):
+            raise RuntimeError(f"{fn}: {values.size} values in blocks of {int(lengths.sum())} lines")
+        offsets = np.concatenate(([0], np.cumsum(lengths)[:-1]))
+        sums = np.zeros(len(lengths))
+        nz = lengths > 0
+        sums[nz] = np.add.reduceat(values, offsets[nz]) if values.size else 0.0
+        if index is None:
+            arrays["wig_track_lengths"] = lengths.astype(np.float64)
+            index = (np.arange(values.size) if values.size <= WIG_SAMPLE
+                     else np.sort(np.random.default_rng(WIG_SAMPLE_SEED).choice(values.size, WIG_SAMPLE, replace=False)))
+            arrays["wig_sample_index"] = index.astype(np.float64)
+        elif values.size != arrays["wig_track_lengths"].sum():
+            raise RuntimeError(f"{fn}: {values.size} values, out.iteres.wig has {int(arrays['wig_track_lengths'].sum())}")
+        arrays[f"{prefix}wig_track_sums"] = sums
+        arrays[f"{prefix}wig_sample"] = values[index]
+    for name, arr in arrays.items():
+        np.save(os.path.join(dest, f"{name}.npy"), arr)
+    return {name: list(arr.shape) for name, arr in arrays.items()}
 
 
 # ------------------------------------------------------------------------------------------------ resident replay
@@ -397,8 +475,12 @@ def main():
         a.gpus = world
     threads = a.threads or max(1, min(16, len(os.sched_getaffinity(0))))
 
-    import torch
-    import torch.distributed as dist
+    # torch only where this process talks to the GPU or to other ranks itself: one rank's timed steps are runs of the command.
+    # It is imported before build() loads the engine's library (tests/conftest.py: torch has to bring up the runtime first).
+    use_torch = world > 1 or (a.full and a.replay_steps > 0)
+    if use_torch:
+        import torch
+        import torch.distributed as dist
     from __graft_entry__ import build
     if rank == 0:
         build()
@@ -414,11 +496,13 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
         dist.barrier()
-    torch.cuda.set_device(local_rank)
-    dev = torch.device("cuda", local_rank)
+    if use_torch:
+        torch.cuda.set_device(local_rank)
+        dev = torch.device("cuda", local_rank)
 
     def fence():
-        torch.cuda.synchronize()
+        if use_torch:
+            torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
             torch.cuda.synchronize()
@@ -431,6 +515,8 @@ def main():
     if rank == 0:
         t0 = time.time()
         wd, info = ensure_inputs(a, threads)
+        if a.full:
+            info = ensure_full_inputs(a, wd, info, threads)
         info["setup_s"] = round(time.time() - t0, 1)
         box = [wd, info]
         log(f"inputs in {wd}: {info}")
@@ -493,10 +579,12 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     total_reads = a.reads * world * a.steps
+    # the files of the last timed step, before any other run of the command writes into the same directory
+    dumped = dump_outputs(scratch, a.dump_outputs) if rank == 0 and a.dump_outputs else None
 
     # strong scaling beside it: the ONE BAM split over the ranks (N > 1 only; two runs, the second timed)
     strong = None
-    if world > 1:
+    if world > 1 and a.full:
         one_run(bam, "strongwarm", 0)
         fence()
         ts = time.perf_counter()
@@ -533,7 +621,7 @@ def main():
                                          "what": {"hiseq": "independent bases per nibble, 40-value HiSeq-like qualities, Illumina-style names: literal-heavy DEFLATE streams — the content `value` is timed on",
                                                   "novaseq": "independent bases, 4-bin run-structured qualities",
                                                   "legacy": "round 2's file: one base per byte pair and a period-32 quality pattern — 97 % of the bytes come out of LZ77 matches (a best case)"}[a.content]},
-                                        **(info.get("content") or {})),
+                                        **((info.get("content") if a.full else None) or {})),
                        "reads_per_step": a.reads * world, "seq_len": a.seq_len, "bam_bytes": info["bam_bytes"], "rmsk_rows": a.rows,
                        "host_threads_per_rank": threads, "host_cores_visible": os.cpu_count(),
                        "timed_region": "K runs of the whole command (process start to exit), files in the page cache"},
@@ -550,9 +638,11 @@ def main():
         }
         if strong:
             out["strong_scaling"] = strong
+        if dumped:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "shapes": dumped}
 
     # ---------------------------------------------------------------- CPU baseline: the reference binary on a bounded sample (rank 0, N = 1)
-    if rank == 0 and world == 1 and a.cpu_reads > 0 and os.path.exists(REF):
+    if rank == 0 and world == 1 and a.full and a.cpu_reads > 0 and os.path.exists(REF):
         sample = os.path.join(wd, "sample.bam")
         renv = dict(os.environ)
         runs = []
@@ -598,7 +688,7 @@ def main():
         out["cpu_baseline"] = None
 
     # ---------------------------------------------------------------- configs[4]: `iteres filter -c <class>` on the same BAM (rank 0, N = 1)
-    if rank == 0 and world == 1 and a.filter_steps > 0 and info.get("filter_class"):
+    if rank == 0 and world == 1 and a.full and a.filter_steps > 0 and info.get("filter_class"):
         fc = info["filter_class"]
         fargs = lambda aln: ["filter", "-c", fc["name"], "-o", "out", os.path.join(wd, "chrom.sizes"), os.path.join(wd, "rep.sizes"), os.path.join(wd, "rmsk.txt"), aln]
         fdir = os.path.join(wd, "filter_run")
@@ -625,7 +715,7 @@ def main():
         out["filter_leg"] = leg
 
     # ---------------------------------------------------------------- roofline of the overlap kernel, records resident in HBM (rank 0)
-    if rank == 0 and a.replay_steps > 0:
+    if rank == 0 and a.full and a.replay_steps > 0:
         n_res = a.replay_reads or a.reads
         roof, rchecks = resident_roofline(a, n_res, a.replay_steps, rank, with_check=(world == 1 and not a.no_replay_check))
         for k in ("cpu_baseline_mt", "filter_kernel"):                        # measured inside the replay, reported beside it

@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT"
 out=$PWD/gpurun_out/prof_${ITX_PROF_ROUND:-r03}
 mkdir -p "$out"
 export TMPDIR=/tmp
-args="bench.py --steps 1 --warmup 0 --cpu-reads 0 --filter-steps 1 --replay-steps 10 --no-replay-check --no-settle"
+args="bench.py --full --steps 1 --warmup 0 --cpu-reads 0 --filter-steps 1 --replay-steps 10 --no-replay-check --no-settle"
 python3 $args > "$out/bench_plain.json" 2> "$out/bench_plain.err"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o bench -- python3 $args > "$out/bench_stats.json" 2> "$out/bench_stats.err"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/fetch" -o bench -- python3 $args > "$out/bench_fetch.json" 2> "$out/bench_fetch.err"
