@@ -372,6 +372,34 @@ int itx_bamwin_dedup(itx_inflater *h, itx_dedup *d);
  * one line on stderr; also printed when the process exits normally. */
 void itx_timing_report(void);
 
+/* bigWig files of `iteres stat` built on the device from the engine's coverage (csrc/itx_bigwig.hip): every section's
+ * payload and every zoom level's summaries (the arithmetic of host/bigwig.c), each block deflated into a zlib stream by
+ * csrc/itx_deflate_core.h. The host lays the files down around what comes back (host/bigwig.c write_bigwig_from).
+ *   start    after itx_engine_finish / itx_engine_finish_partial; uniq: the unique-read coverage instead of all reads;
+ *            the chromosomes in bigWig id order as (offset into the coverage, length > 0), the zoom reductions (each a
+ *            power-of-4 multiple of the one before). Launches on a stream of its own and returns.
+ *   collect  waits, then hands out the results (owned by the build until destroy): the compressed blocks packed one after
+ *            the other (sections in file order, then each level's zoom blocks of 1024 summaries), block i at
+ *            bytes [block_off[i], block_off[i+1]), and each level's summaries. */
+typedef struct itx_bigwig itx_bigwig;
+typedef struct {
+    uint32_t chrom_id, start, end, valid_count;
+    float min_val, max_val, sum_data, sum_squares;
+} itx_bw_summary;
+typedef struct {
+    uint64_t n_sec, n_blocks;
+    uint32_t n_levels;
+    uint64_t n_sum[10], slot_first[10];       /* summaries per level; index of the level's first zoom block */
+    const itx_bw_summary *sum[10];
+    const uint64_t *block_off;                /* n_blocks + 1 */
+    const uint8_t *blocks;
+    double device_ms;                         /* from the first kernel to the end of the last */
+} itx_bw_result;
+int itx_bigwig_start(itx_engine *e, int uniq, const uint64_t *cov_off, const uint32_t *len, uint32_t n_chrom, const uint32_t *reduction,
+                     uint32_t n_levels, itx_bigwig **out);
+int itx_bigwig_collect(itx_bigwig *b, itx_bw_result *out);
+void itx_bigwig_destroy(itx_bigwig *b);
+
 /* Page-locked host memory for the buffers that cross PCIe on every call (NULL when it cannot be had). */
 void *itx_pinned_alloc(size_t bytes);
 void itx_pinned_free(void *p);

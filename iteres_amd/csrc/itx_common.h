@@ -97,6 +97,8 @@ struct itx_table {
 };
 
 void itx_set_error(const char *fmt, ...);
+// internal: the engine's finished per-base coverage in HBM (all reads, or unique reads), for csrc/itx_bigwig.hip
+int itxe_cov_device(itx_engine *e, int uniq, const uint32_t **cov, uint64_t *cov_len, int *device);
 #define ITX_HIP(call)                                                                         \
     do {                                                                                      \
         hipError_t err__ = (call);                                                            \

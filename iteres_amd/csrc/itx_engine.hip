@@ -586,6 +586,18 @@ extern "C" int itx_engine_finish(itx_engine *e, const itx_result *out)
     return itx_engine_finish_partial(e, e->p64, e->p32, out);
 }
 
+int itxe_cov_device(itx_engine *e, int uniq, const uint32_t **cov, uint64_t *cov_len, int *device)
+{
+    if (!e || !e->d_cov || e->p.mode != ITX_MODE_STAT) {
+        itx_set_error("the engine holds no finished coverage (itx_engine_finish first)");
+        return ITX_E_STATE;
+    }
+    *cov = uniq ? e->d_cov_uniq : e->d_cov;
+    *cov_len = e->t->cov_len;
+    *device = e->t->device;
+    return ITX_OK;
+}
+
 extern "C" int itx_engine_get_stats(itx_engine *e, itx_stats *out)
 {
     if (!e || !out) return ITX_E_ARG;

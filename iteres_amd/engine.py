@@ -29,6 +29,7 @@ EXPORTS = [
     "itx_engine_submit_device_own", "itx_engine_wait_own",
     "itx_engine_partial_buffers", "itx_inflater_reserve", "itx_inflater_last_resolve_all_ms", "itx_timing_report", "itx_xaveto_create", "itx_xaveto_destroy", "itx_xaveto_set_tidmap", "itx_xaveto_hits", "itx_xaveto_stream", "itx_bamwin_xa_veto", "itx_comm_create", "itx_comm_destroy", "itx_comm_reduce_sum",
     "itx_backlog_create", "itx_backlog_destroy", "itx_backlog_room", "itx_backlog_append", "itx_backlog_batch", "itx_dedup_create", "itx_dedup_destroy", "itx_dedup_set_tidmap", "itx_dedup_run", "itx_dedup_counts", "itx_bamwin_dedup",
+    "itx_bigwig_start", "itx_bigwig_collect", "itx_bigwig_destroy",
 ]
 
 

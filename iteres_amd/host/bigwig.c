@@ -436,7 +436,8 @@ static void bpt_write(FILE *f, const bw_chrom *chroms, uint64_t n, uint32_t bloc
 }
 
 /* cuskent/bbiWrite.c:478-536: the zoom records, itemsPerSlot to a deflated block, then their R tree */
-static uint64_t write_summary_and_index(FILE *f, bw_sumlist *L, uint32_t block_size, uint32_t items_per_slot)
+static uint64_t write_summary_and_index(FILE *f, bw_sumlist *L, uint32_t block_size, uint32_t items_per_slot, const itx_bw_result *dev,
+                                        uint64_t first_block)
 {
     const uint32_t count = (uint32_t)L->n;
     PUT(f, count);
@@ -448,10 +449,11 @@ static uint64_t write_summary_and_index(FILE *f, bw_sumlist *L, uint32_t block_s
     size_t *csize = xcalloc(group, sizeof *csize);
     for (size_t g0 = 0; g0 < n_slots; g0 += group) {
         const size_t g1 = g0 + group < n_slots ? g0 + group : n_slots;
-#pragma omp parallel for schedule(dynamic, 4)
+#pragma omp parallel for schedule(dynamic, 4) if (!dev)
         for (long sl = (long)g0; sl < (long)g1; sl++) {
             const uint32_t i = (uint32_t)sl * items_per_slot;
             const uint32_t in_slot = count - i > items_per_slot ? items_per_slot : count - i;
+            if (dev) continue;
             char *unc = xmalloc(unc_cap), *w = unc;
             for (uint32_t k = 0; k < in_slot; k++) {
                 const bw_summary *s = &L->v[i + k];
@@ -479,7 +481,8 @@ static uint64_t write_summary_and_index(FILE *f, bw_sumlist *L, uint32_t block_s
                 items[i + k].end = s->end;
                 items[i + k].off = pos;
             }
-            put(f, comp + (sl - g0) * comp_cap, csize[sl - g0]);
+            if (dev) put(f, dev->blocks + dev->block_off[first_block + sl], (size_t)(dev->block_off[first_block + sl + 1] - dev->block_off[first_block + sl]));
+            else put(f, comp + (sl - g0) * comp_cap, csize[sl - g0]);
         }
     }
     free(csize);
@@ -509,13 +512,30 @@ static void bw_tick(const char *what)
 }
 #define BW_T(x) bw_tick(x)
 
-void write_bigwig(const char *path, const char *wig_name, const char *const *names, const uint32_t *len, const float *const *val,
-                  size_t n_names)
+/* The layout of a file, made from the names and lengths alone: chromosomes in strcmp order (the section sort,
+ * bwgCreate.c:138-151) with ids in that order (:584-627), the sections, and the zoom reductions. Both block sources —
+ * zlib on the host (write_bigwig) and the device builder (write_bigwig_device) — are laid down by the one skeleton below
+ * from such a plan, so their files can only differ in how the blocks are deflated. */
+struct bw_plan {
+    const char *wig_name;
+    size_t n_names, n_sec;
+    bw_chrom *chroms;
+    size_t *src;                  /* chroms[i] is names[src[i]] */
+    bw_section *sec;
+    size_t *sec_of;
+    uint32_t max_name;
+    uint64_t n_first;
+    int n_sums;
+    uint32_t reductions[10];
+};
+
+bw_plan *bw_plan_make(const char *wig_name, const char *const *names, const uint32_t *len, size_t n_names)
 {
-    const uint32_t block_size = 256, items_per_slot = 1024;                  /* stat.c:157-158 */
-    BW_T("start");
+    const uint32_t items_per_slot = 1024;                                    /* stat.c:157-158 */
     if (n_names == 0) die("%s is empty of data", wig_name);                  /* bwgCreate.c:1108-1109 */
-    /* chromosomes in strcmp order (the section sort, bwgCreate.c:138-151), ids in that order (:584-627) */
+    bw_plan *P = xcalloc(1, sizeof *P);
+    P->wig_name = wig_name;
+    P->n_names = n_names;
     bw_chrom *chroms = xcalloc(n_names, sizeof *chroms);
     size_t *src = xcalloc(n_names, sizeof *src);
     for (size_t i = 0; i < n_names; i++) {
@@ -545,25 +565,20 @@ void write_bigwig(const char *path, const char *wig_name, const char *const *nam
             sec[k].start = s;
             sec[k].end = s + c;
             sec[k].item_count = c;
-            sec[k].val = val[src[i]] + s;
+            sec[k].val = NULL;
             full_size += 24 + 4 * (uint64_t)c;
             k++;
         }
     }
     sec_of[n_names] = k;
-
-    BW_T("sections");
-    /* zoom levels (bwgCreate.c:826-885): step 1 everywhere, so the average resolution is 1 and the first try is 10 */
+    /* zoom levels (bwgCreate.c:826-885): step 1 everywhere, so the average resolution is 1 and the first try is 10.
+     * How many summaries a reduction gives needs no arithmetic on the values: every sequence is covered base by base from 0
+     * to its size, so its summaries tile it in steps of the reduction (bbiWrite.c:381-395). */
     int initial_reduction = 1 * 10;
     const uint64_t max_reduced = full_size / 2;
-    uint64_t last_summary_size = 0;
-    bw_sumlist sums[10];
-    uint32_t reductions[10];
+    uint64_t last_summary_size = 0, n_first = 0;
     for (;;) {
-        /* How many summaries a reduction gives needs no arithmetic on the values: every sequence is covered base by base from
-         * 0 to its size, so its summaries tile it in steps of the reduction (bbiWrite.c:381-395). The values are reduced once,
-         * with the reduction the loop settles on. */
-        uint64_t n_first = 0;
+        n_first = 0;
         for (size_t c = 0; c < n_names; c++) n_first += ((uint64_t)chroms[c].size + (uint64_t)initial_reduction - 1) / (uint64_t)initial_reduction;
         uint64_t size = n_first * 32;
         size *= 2;                                                             /* "summary not compressing as well as primary data" */
@@ -572,28 +587,114 @@ void write_bigwig(const char *path, const char *wig_name, const char *const *nam
             if (next < initial_reduction * 2) next = initial_reduction * 2;
             initial_reduction = next;
             last_summary_size = size;
-        } else {
-            sums[0] = reduce_sections(sec, sec_of, chroms, n_names, initial_reduction);
-            if ((uint64_t)sums[0].n != n_first) die("internal error: bigWig first zoom level has %zu summaries, %llu expected", sums[0].n, (unsigned long long)n_first);
+        } else
             break;
-        }
     }
     int n_sums = 1;
-    reductions[0] = (uint32_t)initial_reduction;
+    P->reductions[0] = (uint32_t)initial_reduction;
     uint64_t reduction = (uint64_t)initial_reduction;
     for (int i = 0; i < 9; i++) {
         reduction *= 4;
         if (reduction > 1000000000) break;
-        bw_sumlist L = reduce_summaries(&sums[n_sums - 1], chroms, n_names, (int)reduction);
-        const uint64_t size = (uint64_t)L.n * 32;
-        const size_t items = L.n;
-        if (size != last_summary_size) {
-            sums[n_sums] = L;
-            reductions[n_sums] = (uint32_t)reduction;
+        /* reduce_summaries of the last level kept: its summaries tile every chromosome in steps of the new reduction too */
+        uint64_t items = 0;
+        for (size_t c = 0; c < n_names; c++) items += ((uint64_t)chroms[c].size + reduction - 1) / reduction;
+        if (items * 32 != last_summary_size) {
+            P->reductions[n_sums] = (uint32_t)reduction;
             n_sums++;
-        } else
-            free(L.v);
+        }
         if (items <= n_names) break;
+    }
+    P->chroms = chroms;
+    P->src = src;
+    P->sec = sec;
+    P->sec_of = sec_of;
+    P->n_sec = n_sec;
+    P->max_name = max_name;
+    P->n_first = n_first;
+    P->n_sums = n_sums;
+    return P;
+}
+
+void bw_plan_free(bw_plan *P)
+{
+    if (!P) return;
+    free(P->sec);
+    free(P->sec_of);
+    free(P->src);
+    free(P->chroms);
+    free(P);
+}
+
+size_t bw_plan_chroms(const bw_plan *P, const size_t **src, uint32_t *size_out)
+{
+    for (size_t i = 0; i < P->n_names; i++) size_out[i] = P->chroms[i].size;
+    *src = P->src;
+    return P->n_names;
+}
+
+int bw_plan_levels(const bw_plan *P, const uint32_t **reductions)
+{
+    *reductions = P->reductions;
+    return P->n_sums;
+}
+
+static void bw_write(const bw_plan *P, const char *path, const float *const *val, const itx_bw_result *dev);
+
+void write_bigwig(const char *path, const char *wig_name, const char *const *names, const uint32_t *len, const float *const *val,
+                  size_t n_names)
+{
+    bw_plan *P = bw_plan_make(wig_name, names, len, n_names);
+    bw_write(P, path, val, NULL);
+    bw_plan_free(P);
+}
+
+void write_bigwig_device(const bw_plan *P, const char *path, const itx_bw_result *dev)
+{
+    if ((uint64_t)dev->n_sec != (uint64_t)P->n_sec || (int)dev->n_levels != P->n_sums || dev->n_sum[0] != P->n_first)
+        die("internal error: the device bigWig build does not fit the layout of %s", path);
+    bw_write(P, path, NULL, dev);
+}
+
+/* val: the values of names[i] (zlib source), or dev: the device builder's blocks and summaries */
+static void bw_write(const bw_plan *P, const char *path, const float *const *val, const itx_bw_result *dev)
+{
+    const uint32_t block_size = 256, items_per_slot = 1024;                  /* stat.c:157-158 */
+    BW_T("start");
+    const size_t n_names = P->n_names, n_sec = P->n_sec;
+    const bw_chrom *chroms = P->chroms;
+    const uint32_t max_name = P->max_name;
+    bw_section *sec = xcalloc(n_sec ? n_sec : 1, sizeof *sec);
+    memcpy(sec, P->sec, n_sec * sizeof *sec);
+    const size_t *sec_of = P->sec_of;
+    const int n_sums = P->n_sums;
+    const uint32_t *reductions = P->reductions;
+    bw_sumlist sums[10];
+    if (dev) {
+        for (int i = 0; i < n_sums; i++) {
+            const size_t n = (size_t)dev->n_sum[i];
+            sums[i].v = xmalloc((n ? n : 1) * sizeof *sums[i].v);
+            sums[i].n = sums[i].cap = n;
+            for (size_t j = 0; j < n; j++) {
+                const itx_bw_summary *d = &dev->sum[i][j];
+                bw_summary *s = &sums[i].v[j];
+                s->chrom_id = d->chrom_id;
+                s->start = d->start;
+                s->end = d->end;
+                s->valid_count = d->valid_count;
+                s->min_val = d->min_val;
+                s->max_val = d->max_val;
+                s->sum_data = d->sum_data;
+                s->sum_squares = d->sum_squares;
+                s->file_offset = 0;
+            }
+        }
+    } else {
+        for (size_t i = 0; i < n_sec; i++) sec[i].val = val[P->src[sec[i].chrom_id]] + sec[i].start;
+        BW_T("sections");
+        sums[0] = reduce_sections(sec, sec_of, chroms, n_names, (int)reductions[0]);
+        if ((uint64_t)sums[0].n != P->n_first) die("internal error: bigWig first zoom level has %zu summaries, %llu expected", sums[0].n, (unsigned long long)P->n_first);
+        for (int i = 1; i < n_sums; i++) sums[i] = reduce_summaries(&sums[i - 1], chroms, n_names, (int)reductions[i]);
     }
 
     BW_T("zoom lists");
@@ -636,7 +737,14 @@ void write_bigwig(const char *path, const char *wig_name, const char *const *nam
     data_off = (uint64_t)ftello(f);
     const uint64_t section_count = n_sec;
     PUT(f, section_count);
-    {
+    if (dev) {
+        for (size_t i = 0; i < n_sec; i++) {
+            const uint32_t unc = 24 + 4 * sec[i].item_count;
+            if (unc > unc_buf) unc_buf = unc;
+            sec[i].file_offset = (uint64_t)ftello(f);
+            put(f, dev->blocks + dev->block_off[i], (size_t)(dev->block_off[i + 1] - dev->block_off[i]));
+        }
+    } else {
         /* sections are deflated in parallel into memory, then laid down in order (their offsets feed the index) */
         const size_t cap = 24 + 4 * (size_t)items_per_slot, ccap = z_buf_size(cap);
         const size_t group = 4096;
@@ -695,7 +803,7 @@ void write_bigwig(const char *path, const char *wig_name, const char *const *nam
     uint64_t zoom_data[10], zoom_index[10];
     for (int i = 0; i < n_sums; i++) {
         zoom_data[i] = (uint64_t)ftello(f);
-        zoom_index[i] = write_summary_and_index(f, &sums[i], block_size, items_per_slot);
+        zoom_index[i] = write_summary_and_index(f, &sums[i], block_size, items_per_slot, dev, dev ? dev->slot_first[i] : 0);
     }
     BW_T("zooms");
     /* the file-wide summary from the first zoom level (bwgCreate.c:966-988) */
@@ -740,7 +848,4 @@ void write_bigwig(const char *path, const char *wig_name, const char *const *nam
     if (fclose(f) != 0) die("carefulClose: error closing %s", path);
     for (int i = 0; i < n_sums; i++) free(sums[i].v);
     free(sec);
-    free(sec_of);
-    free(src);
-    free(chroms);
 }

@@ -170,15 +170,58 @@ int main_stat(int argc, char **argv)
     cnt[12] = hc.diff_subfam;                     /* reads_diff_subfam (generic.c:978) */
     uint64_t *cov_off = xcalloc((size_t)rm.reps.n + 1, sizeof(uint64_t));
     itx_table_cov_offsets(tab, cov_off);
+    /* the bigWig blocks are built on the device (itx_bigwig_*) while the host writes the text files; ITX_BW_HOST=1: zlib on the
+     * host afterwards, as the reference's converter does */
+    const char **nm = xcalloc((size_t)rm.reps.n + 1, sizeof *nm);
+    uint32_t *ln = xcalloc((size_t)rm.reps.n + 1, sizeof *ln);
+    uint64_t *lo = xcalloc((size_t)rm.reps.n + 1, sizeof *lo);
+    size_t n_bw = 0;
+    for (uint32_t i = 0; i < rm.reps.n; i++)
+        if (rm.rep_len[i]) {
+            nm[n_bw] = rm.reps.name[i];
+            ln[n_bw] = rm.rep_len[i];
+            lo[n_bw] = cov_off[i];
+            n_bw++;
+        }
+    /* no names at all: the host path, which stops where the reference's converter does, after the stat files */
+    const int bw_host = (getenv("ITX_BW_HOST") && atoi(getenv("ITX_BW_HOST")) != 0) || n_bw == 0;
+    bw_plan *plan = NULL;
+    itx_bigwig *bwb[2] = {NULL, NULL};
+    if (!bw_host) {
+        plan = bw_plan_make(outWig, nm, ln, n_bw);
+        const size_t *src;
+        uint32_t *size = xcalloc(n_bw + 1, sizeof *size);
+        uint64_t *off = xcalloc(n_bw + 1, sizeof *off);
+        const size_t nc = bw_plan_chroms(plan, &src, size);
+        for (size_t i = 0; i < nc; i++) off[i] = lo[src[i]];
+        const uint32_t *red;
+        const int nl = bw_plan_levels(plan, &red);
+        for (int u = 0; u < 2; u++)
+            if (itx_bigwig_start(eng, u, off, size, (uint32_t)nc, red, (uint32_t)nl, &bwb[u]) != ITX_OK) die("itx_bigwig_start: %s", itx_last_error());
+        free(size);
+        free(off);
+    }
+    const double t_bw_started = now_s();
     write_wig_and_stat(&rm, &res, cov_off, outStat, o.keep_wig ? outWig : NULL, outFam, outCla, o.keep_wig ? outWigUniq : NULL, cnt[nindex],
                        cnt[nindex2]);
 
     const double t_stats = now_s();
     /* stat.c:156-158: the two wigs as bigWig (written from the vectors, not by re-reading the text) */
     fprintf(stderr, "* Generating bigWig files\n");
-    {
-        const char **nm = xcalloc((size_t)rm.reps.n + 1, sizeof *nm);
-        uint32_t *ln = xcalloc((size_t)rm.reps.n + 1, sizeof *ln);
+    double t_bw_wait = 0, bw_dev_ms[2] = {0, 0};
+    if (!bw_host) {
+        const char *out_bw[2] = {outBigWig, outBigWigUniq};
+        for (int u = 0; u < 2; u++) {
+            const double t0 = now_s();
+            itx_bw_result r;
+            if (itx_bigwig_collect(bwb[u], &r) != ITX_OK) die("itx_bigwig_collect: %s", itx_last_error());
+            t_bw_wait += now_s() - t0;
+            bw_dev_ms[u] = r.device_ms;
+            write_bigwig_device(plan, out_bw[u], &r);
+            itx_bigwig_destroy(bwb[u]);
+        }
+        bw_plan_free(plan);
+    } else {
         const float **va = xcalloc((size_t)rm.reps.n + 1, sizeof *va), **vu = xcalloc((size_t)rm.reps.n + 1, sizeof *vu);
         /* the converter reads "%u" back as a double and stores a float */
         float *fa = xmalloc(sizeof(float) * (info.cov_len + 1)), *fu = xmalloc(sizeof(float) * (info.cov_len + 1));
@@ -190,8 +233,6 @@ int main_stat(int argc, char **argv)
         size_t k = 0;
         for (uint32_t i = 0; i < rm.reps.n; i++)
             if (rm.rep_len[i]) {
-                nm[k] = rm.reps.name[i];
-                ln[k] = rm.rep_len[i];
                 va[k] = fa + cov_off[i];
                 vu[k] = fu + cov_off[i];
                 k++;
@@ -220,9 +261,13 @@ int main_stat(int argc, char **argv)
             }
         }
         free(fa); free(fu);
-        free(nm); free(ln); free(va); free(vu);
+        free(va); free(vu);
     }
 
+    const double t_bw_done = now_s();
+    free(nm);
+    free(ln);
+    free(lo);
     fprintf(stderr, "* Preparing report file\n");
     write_report(outReport, cnt, o.mapq, "ALL");
 
@@ -231,6 +276,9 @@ int main_stat(int argc, char **argv)
                 now_s() - t_streamed);
         fprintf(stderr, "[itx timing] finish %.3f s, stat + wig files %.3f s, bigWig files + report %.3f s\n", t_finished - t_streamed,
                 t_stats - t_finished, now_s() - t_stats);
+        if (!bw_host)
+            fprintf(stderr, "[itx timing] bigWig: device build %.3f + %.3f s (started %.3f s before the stat files ended), host waited %.3f s, "
+                    "files %.3f s\n", 1e-3 * bw_dev_ms[0], 1e-3 * bw_dev_ms[1], t_stats - t_bw_started, t_bw_wait, t_bw_done - t_stats - t_bw_wait);
     }
     const double t_free0 = now_s();
     itx_engine_destroy(eng);

@@ -210,6 +210,15 @@ void write_filter_out(const rmsk_t *rm, const uint32_t *locus_cnt, char **locus_
 /* bigwig.c: the bigWig of one set of wig blocks (stat.c:156-158); only names with a consensus length belong here */
 void write_bigwig(const char *path, const char *wig_name, const char *const *names, const uint32_t *len, const float *const *val,
                   size_t n_names);
+/* The same file in two steps, with the blocks from the device (include/iteres_amd.h: itx_bigwig_*): the plan is the layout,
+ * made from names and lengths alone — chromosome i of the file is names[src[i]] with size[i], and the zoom reductions —
+ * and write_bigwig_device lays the file down around what the device built for that plan. */
+typedef struct bw_plan bw_plan;
+bw_plan *bw_plan_make(const char *wig_name, const char *const *names, const uint32_t *len, size_t n_names);
+size_t bw_plan_chroms(const bw_plan *p, const size_t **src, uint32_t *size);
+int bw_plan_levels(const bw_plan *p, const uint32_t **reductions);
+void write_bigwig_device(const bw_plan *p, const char *path, const itx_bw_result *dev);
+void bw_plan_free(bw_plan *p);
 /* tables.c: a whole text file in memory, through the same openers as the rmsk file (plain, .gz/.Z, .bz2, .zip) */
 char *slurp_text(const char *path, size_t *len);
 
