@@ -25,6 +25,7 @@
 //                dropped unless their number is `first_ok`.
 // The table grows by rehashing on the device (cells never move otherwise). Everything is exact: hashes only pick cells.
 #include "itx_device.h"
+#include "itx_derive.h"
 
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -45,8 +46,7 @@
 #define DD_OVER_CAP 65536u                 // overflow entries (records whose key shares a 64-bit hash with another key) the list holds
 
 struct DdParams {
-    uint32_t mapq_min, extension, isize_max;
-    int32_t treat, discard;
+    ItxDeriveOpts o;
     const int2 *tid;                       // [n_tid]: (chromosome index or < 0, chromosome size)
     const uint32_t *tid_name;              // [n_tid]: identity of the chromosome's (renamed) name, equal across files for equal strings
     int32_t n_tid;
@@ -74,54 +74,16 @@ struct DdState {
     unsigned long long dup_unique, dropped;
 };
 
-// generic.c:764-905 for one record (iteres_amd/host/side.c host_derive, itx_stream.hip derive_one): does it reach the point, with which key
+// does the record reach the point (itx_derive.h), and with which key
 static __device__ inline bool dd_key(const DdParams &P, int32_t t, int32_t pos, int32_t tmpend, uint32_t mq, uint32_t f5, int32_t mpos, int32_t isz,
                                      unsigned long long *ka, uint32_t *kb, bool *uniq)
 {
-    if (f5 & F5_UNMAP) return false;                                   // generic.c:764
     const int2 tr = (t >= 0 && t < P.n_tid) ? P.tid[t] : make_int2(-1, 0);
-    if (tr.x < 0) return false;                                        // generic.c:781-801
-    const uint32_t cend = (uint32_t)(tr.y - 1);                        // generic.c:796
-    if (cend == 1u) return false;
-    bool se;
-    if (P.treat || !(f5 & F5_PAIRED)) {
-        se = true;
-    } else if (!(f5 & F5_MUNMAP)) {                                    // generic.c:836-860
-        if (!(f5 & F5_READ1)) return false;
-        const uint32_t a = isz < 0 ? 0u - (uint32_t)isz : (uint32_t)isz;
-        if (a > P.isize_max || isz == 0) return false;
-        se = false;
-    } else {
-        if (P.discard) return false;                                   // generic.c:862-863
-        se = true;
-    }
     uint32_t st, en, strand;
-    if (se) {                                                          // generic.c:819-833
-        st = (uint32_t)pos;
-        en = cend < (uint32_t)tmpend ? cend : (uint32_t)tmpend;
-        strand = (f5 & F5_REVERSE) ? 1u : 0u;
-        if (P.extension) {
-            if (!strand) {
-                const uint32_t e2 = st + P.extension;
-                en = e2 < cend ? e2 : cend;
-            } else {
-                st = en < P.extension ? 0u : en - P.extension;
-            }
-        }
-    } else if (isz > 0) {                                              // generic.c:845-855
-        st = (uint32_t)pos;
-        const uint32_t e2 = st + (uint32_t)isz;
-        en = cend < e2 ? cend : e2;
-        strand = 0u;
-    } else {
-        st = (uint32_t)mpos;
-        const uint32_t e2 = st - (uint32_t)isz;
-        en = cend < e2 ? cend : e2;
-        strand = 1u;
-    }
+    if (!itx_derive(&P.o, tr.x, tr.y, f5, pos, tmpend, mpos, isz, &st, &en, &strand)) return false;
     *ka = (unsigned long long)st | (unsigned long long)en << 32;
     *kb = P.tid_name[t] << 1 | strand;
-    *uniq = mq >= P.mapq_min;
+    *uniq = mq >= P.o.mapq_min;
     return true;
 }
 
@@ -331,11 +293,11 @@ extern "C" int itx_dedup_create(int device, const int64_t *chrom_size, int n_chr
     d->chrom_size.resize((size_t)n_chrom + 1);
     for (int c = 0; c < n_chrom; c++) d->chrom_size[(size_t)c] = (int32_t)chrom_size[c];
     memset(&d->p, 0, sizeof d->p);
-    d->p.mapq_min = (uint32_t)p->mapq_min;
-    d->p.extension = p->extension;
-    d->p.isize_max = p->isize_max;
-    d->p.treat = p->treat_pe_as_se;
-    d->p.discard = p->discard_half_mapped;
+    d->p.o.mapq_min = (uint32_t)p->mapq_min;
+    d->p.o.extension = p->extension;
+    d->p.o.isize_max = p->isize_max;
+    d->p.o.treat = p->treat_pe_as_se;
+    d->p.o.discard = p->discard_half_mapped;
     d->p.hash_mask = ~0ull;
     if (const char *e = getenv("ITX_DEDUP_HASH_BITS"))
         if (atoi(e) >= 8 && atoi(e) < 64) d->p.hash_mask = (1ull << atoi(e)) - 1ull;

@@ -1,25 +1,11 @@
-// itx_device.h — device functions shared by the kernels: per-record coordinate derivation
-// (generic.c:748-905) and overlap classification (cuskent/binRange.c:196-227 + generic.c:950-970).
+// itx_device.h — device functions shared by the kernels: overlap classification (cuskent/binRange.c:196-227 +
+// generic.c:950-970), the consensus range of a classified read and the wave-wide helpers. The per-record coordinate
+// derivation (generic.c:764-905) and the flag5 bits are in itx_derive.h.
 #pragma once
 #include "itx_common.h"
-
-// flag5 bits (include/iteres_amd.h)
-#define F5_PAIRED 1u
-#define F5_UNMAP 2u
-#define F5_MUNMAP 4u
-#define F5_REVERSE 8u
-#define F5_READ1 16u
-#define F5_NOLOOKUP 32u
+#include "itx_derive.h"
 
 #define ITX_WIN 128          // intervals a wave stages in LDS for its tile of records (ItxIv each)
-
-// One record's raw fields as the host decoder hands them over.
-struct ItxRaw {
-    int32_t tid, pos, tmpend;
-    uint32_t mapq, fl;
-};
-
-__device__ __forceinline__ uint32_t umin32(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
 // generic.c:296-301 getCov, with the interval already loaded.
 __device__ __forceinline__ float itx_cov(uint32_t start, uint32_t end, int32_t s, int32_t e)
@@ -172,8 +158,6 @@ __device__ __forceinline__ int32_t itx_first_lane(const ItxDevTable &T, uint32_t
 // row_shr steps lane 15 of each 16-lane row holds the row's result; row_bcast:15 folds rows 0->1 and 2->3,
 // row_bcast:31 folds the lower half into the upper one; lane 63 then holds the wave's result.
 #define ITX_DPP_STEP(op, v, id, ctrl, rowmask) v = op(v, __builtin_amdgcn_update_dpp((int)(id), (int)(v), ctrl, rowmask, 0xf, false))
-__device__ __forceinline__ int32_t imin32(int32_t a, int32_t b) { return a < b ? a : b; }
-__device__ __forceinline__ int32_t imax32(int32_t a, int32_t b) { return a > b ? a : b; }
 __device__ __forceinline__ int32_t wave_min_i32(int32_t v)
 {
     const int32_t id = 0x7fffffff;

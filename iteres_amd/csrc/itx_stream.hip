@@ -19,6 +19,7 @@
 // and nested divergent branches cost more exec-mask bookkeeping than the arithmetic they skip.
 // No MFMA: the path is integer compares and one f32 ratio; the roofline that bounds it is HBM.
 #include "itx_device.h"
+#include "itx_derive.h"     // lut_entry, derive_one: the record derivation in the form this kernel runs
 #include <stdlib.h>
 
 #define SB 256
@@ -30,32 +31,6 @@
 #endif
 #define RPL ITX_RPL
 #define WTILE (64 * RPL)
-
-// Everything generic.c:748-922 decides from a record's flag bits alone, tabulated once per workgroup.
-// Index: flag5 (6 bits) | 64 the reference is known and usable (generic.c:781-801) | 128 a proper-pair insert size
-// (generic.c:838-840) | 256 MAPQ >= -Q. Entry: bit 3k set => cnt[k] += 1 for k in 0..7 (generic.c:1048-1055;
-// cnt[11] == cnt[7] without -R), LUT_OK the record goes on to the lookup, LUT_SE it is measured as a single end.
-#define LUT_OK (1u << 24)
-#define LUT_SE (1u << 25)
-__device__ __forceinline__ uint32_t lut_entry(const ItxRunParams &P, uint32_t idx)
-{
-    const bool paired = idx & F5_PAIRED, unmap = idx & F5_UNMAP, munmap = idx & F5_MUNMAP, read1 = idx & F5_READ1;
-    const bool ref_ok = idx & 64u, isz_ok = idx & 128u, uniq = idx & 256u;
-    const bool treat = P.treat != 0;
-    const bool end1 = !paired || read1 || treat;                                   // generic.c:748-759
-    const bool mapped = !unmap;                                                    // generic.c:764
-    const bool chrom_ok = mapped && ref_ok;                                        // generic.c:781-801
-    const bool se = treat || !paired || munmap;                                    // generic.c:815,836-837,885
-    const bool pe_ok = read1 && isz_ok;                                            // generic.c:838-840,858-860
-    const bool se_ok = treat || !paired || P.discard == 0;                         // generic.c:862-863
-    const bool ok = chrom_ok && (se ? se_ok : pe_ok);
-    uint32_t e = end1 ? 1u : 1u << 3;
-    e |= mapped ? (end1 ? 1u << 6 : 1u << 9) : 0u;
-    e |= chrom_ok ? (end1 ? 1u << 12 : 1u << 15) : 0u;
-    e |= ok ? 1u << 18 : 0u;
-    e |= (ok && uniq) ? 1u << 21 : 0u;
-    return e | ((ok && !(idx & F5_NOLOOKUP)) ? LUT_OK : 0u) | (se ? LUT_SE : 0u);      // the caller's -R / XA `continue`
-}
 
 __device__ __forceinline__ uint32_t uadd32(uint32_t a, uint32_t b) { return a + b; }
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
@@ -82,46 +57,6 @@ __device__ __forceinline__ uint32_t top_entry(uint32_t bsx, uint32_t bsx_hi, boo
         h1 = b >= 64u ? h2 : h1;
     }
     return __builtin_elementwise_sub_sat(h1, lo_w);
-}
-
-// generic.c:748-922 for one record. (tx, ty) = chrom and size of the record's ItxTidRec, has_rows = its reference
-// has table rows. Out: the flag table's entry, the reference's unsigned start/end, binKeeperFind's clipped query
-// (binRange.c:204-206), whether the record goes on to the lookup, and MAPQ >= -Q.
-__device__ __forceinline__ void derive_one(const ItxRunParams &P, const uint32_t *s_lut, const ItxRaw &r, int32_t iz, int32_t mpos, bool tile_pe,
-                                           uint32_t tx, uint32_t ty, bool has_rows, uint32_t &lut, uint32_t &st, uint32_t &en, int32_t &qs,
-                                           int32_t &qe, bool &q, bool &uq)
-{
-    const uint32_t cend = ty - 1u;                                                 // generic.c:796
-    uq = r.mapq >= P.mapq_min;
-    uint32_t idx = r.fl | (((int32_t)tx >= 0 && cend != 1u) ? 64u : 0u) | (uq ? 256u : 0u);
-    // generic.c:819-833
-    uint32_t s_se = (uint32_t)r.pos;
-    uint32_t e_se = umin32(cend, (uint32_t)r.tmpend);
-    if (P.extension) {                                                             // wave-uniform
-        const bool rev = r.fl & F5_REVERSE;
-        const uint32_t e_plus = umin32(s_se + P.extension, cend);
-        const uint32_t s_minus = __builtin_elementwise_sub_sat(e_se, P.extension);
-        s_se = rev ? s_minus : s_se;
-        e_se = rev ? e_se : e_plus;
-    }
-    st = s_se;
-    en = e_se;
-    if (tile_pe) {                                                                 // wave-uniform; generic.c:838-855
-        const uint32_t aisz = iz < 0 ? 0u - (uint32_t)iz : (uint32_t)iz;
-        idx |= (aisz <= P.isize_max && iz != 0) ? 128u : 0u;
-        lut = s_lut[idx];
-        const bool se = lut & LUT_SE;
-        const bool fwd = iz > 0;
-        const uint32_t s_pe = fwd ? (uint32_t)r.pos : (uint32_t)mpos;
-        const uint32_t e_pe = umin32(cend, fwd ? s_pe + (uint32_t)iz : s_pe - (uint32_t)iz);
-        st = se ? s_se : s_pe;
-        en = se ? e_se : e_pe;
-    } else {
-        lut = s_lut[idx];
-    }
-    qs = imax32((int32_t)st, 0);
-    qe = imin32((int32_t)en, (int32_t)ty);
-    q = (lut & LUT_OK) && qs < qe && has_rows;
 }
 
 // One record classified straight from global memory (any record order), and the slots its chosen row marks.

@@ -20,6 +20,7 @@
 // Integer and byte work; every lane walks its own record (divergent by nature, a few hundred bytes each): bound by latency,
 // not by anything a roofline prices — it has to beat a PCIe round trip of the window, and does by an order of magnitude.
 #include "itx_device.h"
+#include "itx_derive.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -46,8 +47,7 @@ struct XaDev {
     uint32_t name_mask;
     const int2 *tid;              // [n_tid] (chromosome index or < 0, chromosome size)
     int32_t n_tid;
-    uint32_t extension, isize_max;
-    int32_t treat, discard;
+    ItxDeriveOpts o;
 };
 
 struct itx_xaveto {
@@ -114,34 +114,11 @@ __global__ __launch_bounds__(256) void k_xa_verdict(ItxDevTable T, XaDev D, cons
     uint8_t out = 0;
     const int32_t h = hit[i];
     if (xa_mark[i] && h >= 0) {
-        // ---- the record's interval as the loop derives it (generic.c:764-905; a classified record has passed every test there)
+        // ---- the record's interval as the loop derives it (itx_derive.h; a classified record has passed every test there)
         const int32_t t = tid_a[i];
         const int2 tr = (t >= 0 && t < D.n_tid) ? D.tid[t] : make_int2(-1, 0);
-        const uint32_t cend = (uint32_t)(tr.y - 1);
-        const uint32_t f5 = f5_a[i];
-        const int32_t pos = pos_a[i], tmpend = end_a[i], mpos = mpos_a ? mpos_a[i] : 0, isz = isize_a ? isize_a[i] : 0;
-        const bool se = D.treat || !(f5 & F5_PAIRED) || (f5 & F5_MUNMAP);
-        uint32_t st, en;
-        if (se) {
-            st = (uint32_t)pos;
-            en = cend < (uint32_t)tmpend ? cend : (uint32_t)tmpend;
-            if (D.extension) {
-                if (!(f5 & F5_REVERSE)) {
-                    const uint32_t e2 = st + D.extension;
-                    en = e2 < cend ? e2 : cend;
-                } else {
-                    st = en < D.extension ? 0u : en - D.extension;
-                }
-            }
-        } else if (isz > 0) {
-            st = (uint32_t)pos;
-            const uint32_t e2 = st + (uint32_t)isz;
-            en = cend < e2 ? cend : e2;
-        } else {
-            st = (uint32_t)mpos;
-            const uint32_t e2 = st - (uint32_t)isz;
-            en = cend < e2 ? cend : e2;
-        }
+        uint32_t st = 0, en = 0, strand;
+        (void)itx_derive(&D.o, tr.x, tr.y, f5_a[i], pos_a[i], end_a[i], mpos_a ? mpos_a[i] : 0, isize_a ? isize_a[i] : 0, &st, &en, &strand);
         const int32_t qlen = (int32_t)(en - st);
         const uint32_t word = D.rep_word[D.row_rep[h]];
         // ---- the tags: first XA (any type) and first NM, each by the walk of bam_aux_get
@@ -335,10 +312,11 @@ extern "C" int itx_xaveto_create(const itx_table *t, const itx_params *p, const 
     x->d.names = (const XaName *)x->d_names;
     x->d.pool = (const uint8_t *)x->d_pool;
     x->d.name_mask = cells - 1;
-    x->d.extension = p->extension;
-    x->d.isize_max = p->isize_max;
-    x->d.treat = p->treat_pe_as_se;
-    x->d.discard = p->discard_half_mapped;
+    x->d.o.mapq_min = (uint32_t)p->mapq_min;
+    x->d.o.extension = p->extension;
+    x->d.o.isize_max = p->isize_max;
+    x->d.o.treat = p->treat_pe_as_se;
+    x->d.o.discard = p->discard_half_mapped;
     *out = x;
     return ITX_OK;
 }

@@ -169,7 +169,7 @@ typedef struct {
     uint32_t start, end;
     char strand;
 } host_iv;
-/* generic.c:764-905: 1 when the record reaches reads_mapped++ (then *d is its interval), chrom as in the tid map */
+/* generic.c:764-905 (itx_derive of ../csrc/itx_derive.h): 1 when the record reaches reads_mapped++ (then *d is its interval), chrom as in the tid map */
 int host_derive(const run_opts *o, int32_t chrom, int64_t chrom_size, unsigned flag5, int32_t pos, int32_t tmpend, int32_t mpos, int32_t isize,
                 host_iv *d);
 typedef struct dup_set dup_set;

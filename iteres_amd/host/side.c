@@ -6,60 +6,21 @@
  *   - the XA/NM multi-mapping veto (generic.c:303-341, 972-982). */
 #define _GNU_SOURCE
 #include "itx_host.h"
+#include "../csrc/itx_derive.h"
 
 #include <ctype.h>
 #include <stdlib.h>
 #include <string.h>
 
-/* ---- generic.c:764-905 for one record: does it reach reads_mapped++, and with which interval and strand -------- */
+/* ---- generic.c:764-905 for one record: does it reach reads_mapped++, and with which interval and strand (the rule
+ * itself: ../csrc/itx_derive.h, shared with the device's -R and XA kernels) ---------------------------------------- */
 int host_derive(const run_opts *o, int32_t chrom, int64_t chrom_size, unsigned flag5, int32_t pos, int32_t tmpend, int32_t mpos, int32_t isize,
                 host_iv *d)
 {
-    enum { PAIRED = 1, UNMAP = 2, MUNMAP = 4, REVERSE = 8, READ1 = 16 };
-    if (flag5 & UNMAP) return 0;                                      /* generic.c:764 */
-    if (chrom < 0) return 0;                                          /* generic.c:781-801 (dropped by -C / not in the size file) */
-    const uint32_t cend = (uint32_t)((int)chrom_size - 1);            /* generic.c:796 */
-    if (cend == 1u) return 0;
-    int se;
-    if (o->treat || !(flag5 & PAIRED)) {
-        se = 1;
-    } else if (!(flag5 & MUNMAP)) {                                   /* generic.c:836-860 */
-        if (!(flag5 & READ1)) return 0;
-        const uint32_t a = isize < 0 ? 0u - (uint32_t)isize : (uint32_t)isize;
-        if (a > o->isize || isize == 0) return 0;
-        se = 0;
-    } else {
-        if (o->discard) return 0;                                     /* generic.c:862-863 */
-        se = 1;
-    }
-    uint32_t start, end;
-    char strand;
-    if (se) {                                                         /* generic.c:819-833 */
-        start = (uint32_t)pos;
-        end = cend < (uint32_t)tmpend ? cend : (uint32_t)tmpend;
-        strand = (flag5 & REVERSE) ? '-' : '+';
-        if (o->extension) {
-            if (strand == '+') {
-                const uint32_t e2 = start + o->extension;
-                end = e2 < cend ? e2 : cend;
-            } else {
-                start = end < o->extension ? 0u : end - o->extension;
-            }
-        }
-    } else if (isize > 0) {                                           /* generic.c:845-855 */
-        start = (uint32_t)pos;
-        const uint32_t e2 = start + (uint32_t)isize;
-        end = cend < e2 ? cend : e2;
-        strand = '+';
-    } else {
-        start = (uint32_t)mpos;
-        const uint32_t e2 = start - (uint32_t)isize;
-        end = cend < e2 ? cend : e2;
-        strand = '-';
-    }
-    d->start = start;
-    d->end = end;
-    d->strand = strand;
+    const ItxDeriveOpts opt = {.mapq_min = o->mapq, .extension = o->extension, .isize_max = o->isize, .treat = o->treat, .discard = o->discard};
+    uint32_t strand;
+    if (!itx_derive(&opt, chrom, (int32_t)chrom_size, flag5, pos, tmpend, mpos, isize, &d->start, &d->end, &strand)) return 0;
+    d->strand = strand ? '-' : '+';
     return 1;
 }
 
