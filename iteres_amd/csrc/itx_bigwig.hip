@@ -255,16 +255,22 @@ static int bw_start(itx_bigwig *b, itx_engine *e, int uniq, const uint64_t *cov_
     if (rc) return rc;
     ITX_HIP(hipSetDevice(b->device));
     for (uint32_t c = 0; c < n_chrom; c++)
-        if (!len[c] || cov_off[c] + len[c] > cov_len) {
+        if (!len[c] || cov_off[c] > cov_len || len[c] > cov_len - cov_off[c]) {     // (no sum of the two: it could wrap)
             itx_set_error("itx_bigwig_start: chromosome %u (offset %llu, length %u) is empty or outside the coverage", c,
                           (unsigned long long)cov_off[c], len[c]);
             return ITX_E_ARG;
         }
-    for (uint32_t k = 1; k < n_levels; k++)
-        if (reduction[k] % reduction[k - 1] || reduction[k] / reduction[k - 1] % 4) {
-            itx_set_error("itx_bigwig_start: reduction %u is no power-of-4 multiple of %u", reduction[k], reduction[k - 1]);
+    if (n_levels && (!reduction[0] || reduction[0] >= 1u << 31)) {
+        itx_set_error("itx_bigwig_start: reduction %u is outside 1 .. 2^31 - 1", reduction[0]);
+        return ITX_E_ARG;
+    }
+    for (uint32_t k = 1; k < n_levels; k++) {
+        const uint32_t q = reduction[k] / reduction[k - 1];                // 4, 16, 64, ...: one bit, at an even place
+        if (reduction[k] % reduction[k - 1] || q < 4 || (q & (q - 1)) || (__builtin_ctz(q) & 1) || reduction[k] >= 1u << 31) {
+            itx_set_error("itx_bigwig_start: reduction %u is no power-of-4 multiple of %u below 2^31", reduction[k], reduction[k - 1]);
             return ITX_E_ARG;
         }
+    }
     // per-chromosome tables: sections, then the summaries of each level
     const size_t nc1 = (size_t)n_chrom + 1;
     std::vector<uint64_t> h(n_chrom + nc1 * (1 + n_levels));

@@ -75,6 +75,21 @@ class Stats(C.Structure):
                 ("submits", C.c_uint64), ("keys", C.c_uint64)]
 
 
+class BwSummary(C.Structure):
+    _fields_ = [("chrom_id", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("valid_count", C.c_uint32),
+                ("min_val", C.c_float), ("max_val", C.c_float), ("sum_data", C.c_float), ("sum_squares", C.c_float)]
+
+
+class BwResult(C.Structure):
+    _fields_ = [("n_sec", C.c_uint64), ("n_blocks", C.c_uint64), ("n_levels", C.c_uint32), ("n_sum", C.c_uint64 * 10),
+                ("slot_first", C.c_uint64 * 10), ("sum", C.POINTER(BwSummary) * 10), ("block_off", C.POINTER(C.c_uint64)),
+                ("blocks", C.POINTER(C.c_uint8)), ("device_ms", C.c_double)]
+
+
+BW_SUMMARY_DTYPE = np.dtype([("chrom_id", "<u4"), ("start", "<u4"), ("end", "<u4"), ("valid_count", "<u4"),
+                             ("min_val", "<f4"), ("max_val", "<f4"), ("sum_data", "<f4"), ("sum_squares", "<f4")])
+assert BW_SUMMARY_DTYPE.itemsize == C.sizeof(BwSummary) == 32
+
 _lib = None
 
 
@@ -138,6 +153,10 @@ def load():
     L.itx_dedup_set_tidmap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.itx_dedup_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.itx_dedup_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.itx_bigwig_start.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.itx_bigwig_collect.argtypes = [C.c_void_p, C.POINTER(BwResult)]
+    L.itx_bigwig_destroy.argtypes = [C.c_void_p]
+    L.itx_bigwig_destroy.restype = None
     L.itx_pinned_alloc.argtypes = [C.c_size_t]
     L.itx_pinned_alloc.restype = C.c_void_p
     L.itx_pinned_free.argtypes = [C.c_void_p]
@@ -340,6 +359,45 @@ class Engine:
     def close(self):
         if getattr(self, "_h", None):
             load().itx_engine_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Bigwig:
+    """itx_bigwig_start / collect / destroy (include/iteres_amd.h): the blocks and summaries of one bigWig built on the
+    device from a finished engine's coverage. seqs: (offset into the coverage, length) in bigWig id order."""
+
+    def __init__(self, engine: Engine, uniq: bool, seqs, reductions):
+        off = np.ascontiguousarray([o for o, _ in seqs], np.uint64)
+        ln = np.ascontiguousarray([n for _, n in seqs], np.uint32)
+        red = np.ascontiguousarray(reductions, np.uint32)
+        self._h = C.c_void_p()
+        _chk(load().itx_bigwig_start(engine._h, int(bool(uniq)), _p(off), _p(ln), len(ln), _p(red), len(red), C.byref(self._h)),
+             "itx_bigwig_start")
+
+    def collect(self):
+        """{"n_sec", "n_blocks", "n_sum": [..], "slot_first": [..], "levels": [BW_SUMMARY_DTYPE array], "block_off": uint64
+        [n_blocks + 1], "blocks": bytes, "device_ms"}, copied out of the build's own buffers"""
+        r = BwResult()
+        _chk(load().itx_bigwig_collect(self._h, C.byref(r)), "itx_bigwig_collect")
+        nl, nb = int(r.n_levels), int(r.n_blocks)
+        block_off = np.ctypeslib.as_array(r.block_off, shape=(nb + 1,)).copy()
+        levels = []
+        for k in range(nl):
+            n = int(r.n_sum[k])
+            levels.append(np.frombuffer(C.string_at(r.sum[k], 32 * n), BW_SUMMARY_DTYPE).copy() if n else np.zeros(0, BW_SUMMARY_DTYPE))
+        return {"n_sec": int(r.n_sec), "n_blocks": nb, "n_levels": nl, "n_sum": [int(r.n_sum[k]) for k in range(nl)],
+                "slot_first": [int(r.slot_first[k]) for k in range(nl)], "levels": levels, "block_off": block_off,
+                "blocks": C.string_at(r.blocks, int(block_off[nb])), "device_ms": float(r.device_ms)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().itx_bigwig_destroy(self._h)
             self._h = None
 
     def __del__(self):

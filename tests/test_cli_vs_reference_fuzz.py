@@ -189,6 +189,40 @@ def test_file_list_matches_reference_binary(exe, tmp_path):
             assert a == b, fn
 
 
+def test_pileup_matches_reference_binary(exe, tmp_path):
+    """The rounding regime of the bigWig zoom summaries through the whole command: the pile-up input of tests/bwcases.py
+    (400 000 reads on two consensus sequences: sum_squares passes 2^24 inside level-0 summaries, sum_data at the top),
+    the bigWig blocks built on the device (the default) and by the host writer (ITX_BW_HOST=1), against the reference
+    binary: text files byte for byte, bigWigs by decoded content."""
+    import bwcases
+    inp = tmp_path / "in"
+    inp.mkdir()
+    paths = bwcases.write_pileup_input(inp)
+    outs = {}
+    for who, prog, env in (("ref", REF, {}), ("dev", exe, {"ITX_TIMING": "1"}), ("host", exe, {"ITX_TIMING": "1", "ITX_BW_HOST": "1"})):
+        work = tmp_path / who
+        work.mkdir()
+        pr = subprocess.run([prog, "stat"] + bwcases.PILEUP_OPTS + ["-o", "out"] + paths, cwd=work, capture_output=True, text=True, timeout=600,
+                            env=dict(os.environ, **env))
+        assert pr.returncode == 0, (who, pr.stderr[-1500:])
+        assert ("bigWig: device build" in pr.stderr) == (who == "dev"), (who, pr.stderr[-1500:])
+        outs[who] = work
+    files = sorted(os.listdir(outs["ref"]))
+    for fn in ("out.iteres.wig", "out.iteres.unique.wig"):
+        vals, order = refio.parse_wig(str(outs["ref"] / fn))
+        dec = refio.bigwig_decode((outs["ref"] / fn.replace(".wig", ".bigWig")).read_bytes())
+        n_sq, n_sd = bwcases.wig_depth(vals, [nm for nm, _, _ in dec["chroms"]], [z[0] for z in dec["zooms"]])
+        assert n_sq >= 1 and n_sd >= 1, (fn, n_sq, n_sd)
+    for who in ("dev", "host"):
+        assert sorted(os.listdir(outs[who])) == files, who
+        for fn in files:
+            a, b = (outs["ref"] / fn).read_bytes(), (outs[who] / fn).read_bytes()
+            if fn.endswith(".bigWig"):
+                assert refio.bigwig_digest(b) == refio.bigwig_digest(a), f"{who}: {fn} decodes differently"
+            else:
+                assert a == b, f"{who}: {fn} differs"
+
+
 def test_long_reads_match_reference_binary(exe, tmp_path):
     """Records of tens of kilobytes (long reads): they span BGZF blocks and the decoder's 16 KiB pieces; -E 0 so that the
     CIGAR end decides the interval on both strands."""

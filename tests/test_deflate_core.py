@@ -2,14 +2,14 @@
 built for the host with a one-lane wave (tests/deflate_host.cpp) and checked against zlib: every stream inflates to its
 input, two encodings of one input are the same bytes, incompressible input takes a stored block, and on bigWig-like blocks
 the compressed size stays within 1.25x of zlib level 6."""
-import ctypes as C
 import gzip
 import os
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
+
+import deflatehost
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -17,20 +17,7 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 @pytest.fixture(scope="module")
 def enc(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("deflate") / "libdeflate_host.so")
-    subprocess.check_call(["g++", "-O2", "-g", "-shared", "-fPIC", "-Wall", "-o", so, os.path.join(ROOT, "tests", "deflate_host.cpp")])
-    L = C.CDLL(so)
-    L.itxd_deflate_host.restype = C.c_uint32
-    L.itxd_deflate_host.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p]
-
-    def run(b):
-        cap = ((len(b) + 16) + 3) & ~3
-        out = C.create_string_buffer(cap + 64)
-        n = L.itxd_deflate_host(b, len(b), out)
-        assert 0 < n <= cap
-        assert out.raw[cap:] == bytes(64), "wrote past its room"
-        return out.raw[:n]
-    return run
+    return deflatehost.build_encoder(tmp_path_factory.mktemp("deflate"))
 
 
 def _coverage(rng, n):

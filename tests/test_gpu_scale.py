@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import enginecase as ec
+import refio
 from iteres_amd import engine as eng, synth
 
 pytestmark = pytest.mark.gpu
@@ -139,13 +140,18 @@ def _same_files(a, b, skip_suffix=(".bigWig",)):
 @pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref/iteres (the reference, built in the container) did not travel")
 def test_config1_cli_50M_vs_reference(files):
     """configs[1] through the command, next to the reference binary on the same 50 M-read BAM: .subfamily/.family/.class
-    stat, .report, both per-base wigs (stat -w) and .loci/.reportloci (filter -n) byte for byte."""
+    stat, .report, both per-base wigs (stat -w) and .loci/.reportloci (filter -n) byte for byte, and both bigWig files by the
+    digest of their decoded content (tests/refio.py: every section and every zoom record of the ~13 M consensus bases, all
+    blocks inflated, nothing sampled; the whole test, both programs' runs and the decoding of the four files, takes about
+    70 s on the box)."""
     _cli(REF, ["stat", "-w"], files, "r50M.bam", os.path.join(files, "ref_stat"))
     _cli(OURS, ["stat", "-w"], files, "r50M.bam", os.path.join(files, "our_stat"))
     names = _same_files(os.path.join(files, "ref_stat"), os.path.join(files, "our_stat"))
     assert len(names) == 6
     for fn in ("out.iteres.bigWig", "out.iteres.unique.bigWig"):
         assert os.path.getsize(os.path.join(files, "our_stat", fn)) > 0
+        ours, ref = (open(os.path.join(files, d, fn), "rb").read() for d in ("our_stat", "ref_stat"))
+        assert refio.bigwig_digest(ours) == refio.bigwig_digest(ref), f"{fn} decodes differently from the reference's"
     _cli(REF, ["filter", "-n", "Rep1"], files, "r50M.bam", os.path.join(files, "ref_filter"))
     _cli(OURS, ["filter", "-n", "Rep1"], files, "r50M.bam", os.path.join(files, "our_filter"))
     assert len(_same_files(os.path.join(files, "ref_filter"), os.path.join(files, "our_filter"))) == 2
