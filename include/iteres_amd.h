@@ -82,8 +82,10 @@ int itx_table_cov_offsets(const itx_table *t, uint64_t *off);
  * The engine: replaces the body of the record loop, generic.c:748-1036 (stat copy) ==
  * generic.c:385-697 (filter copy): read-end / mapped / used counters, coordinate derivation,
  * binKeeperFind + best-hit rule (generic.c:945-970), and the accumulate step
- * (generic.c:983-1032). Host-side, order-dependent features stay with the caller: -R dedup
- * (generic.c:907-919), bed emission (925-936), the XA/NM veto (972-982), qname lists (662-666).
+ * (generic.c:983-1032). The order-dependent features around it reach the engine as one flag bit per
+ * record (ITX_F5_NOLOOKUP) and have device implementations of their own further down: -R dedup
+ * (generic.c:907-919, itx_dedup_*), the XA/NM veto (972-982, itx_xaveto_*), bed emission (925-936,
+ * itx_bed_*). Only the qname lists of filter -r (662-666) stay with the caller.
  * ------------------------------------------------------------------------------------------- */
 typedef struct itx_engine itx_engine;
 
@@ -367,6 +369,50 @@ int itx_dedup_run(itx_dedup *d, const int32_t *tid, const int32_t *pos, const in
                   const int32_t *isize, size_t n);
 int itx_dedup_counts(itx_dedup *d, uint64_t *dup_unique, uint64_t *dropped, uint64_t *keys);
 int itx_bamwin_dedup(itx_inflater *h, itx_dedup *d);
+
+/* ---- the bed files of stat -B / -V on the device ------------------------------------------------------------------------
+ * Replaces generic.c:925-936 for the records of a window the device decoder has parsed: the text of both files is built where
+ * the records lie (csrc/itx_bed.hip; the line itself: csrc/itx_bedline.h) and comes back as finished bytes, one line per
+ * record that reaches the bed stage, in file order:
+ *     -B  chr \t start \t end \t qname \t mapq \t strand [ \t NM \t XA ] \n        (ITX_BED_ALL; NM / XA iff the record has an XA tag)
+ *     -V  chr \t start \t end \t qname \t mapq \t strand \n                        (ITX_BED_UNIQ; only records with MAPQ >= mapq_min)
+ * A record with ITX_F5_NOLOOKUP set has no line (-R comes before the bed stage, generic.c:907-919), so a caller runs this AFTER
+ * the -R pass and BEFORE the XA veto (generic.c:972 comes after 925).
+ *   create      chrom_size[n_chrom] as for itx_table_create; p: mapq_min, extension, isize_max, treat_pe_as_se,
+ *               discard_half_mapped; want: ITX_BED_ALL | ITX_BED_UNIQ; batch_capacity: the most records a batch may carry
+ *   set_tidmap  per BAM header: tid2chrom as for itx_engine_set_tidmap, tid2name[t] the reference name as it is printed (after
+ *               the -C rule; NULL for a reference -C drops). Not while a batch is waiting to be collected.
+ *   itx_bamwin_bed  starts the build over records [first, first + n) of the inflater's last parsed window: measures the lines,
+ *               waits for the sizes, enqueues the formatting and the copy to page-locked host memory, and returns. *n_hard > 0:
+ *               some record needs the host's reading (a read name without a NUL inside its record): NOTHING was started, the
+ *               caller takes the host route for these records. At most two batches may be started and not yet collected.
+ *   run         the same over plain DEVICE arrays: the records' bytes, rec_off[i] = where record i (its block_len field)
+ *               starts in them, and the per-record arrays of an itx_batch (mpos / isize NULL: no record is paired)
+ *   collect     waits for the OLDEST started batch and hands out its two texts (host pointers, owned by the object, valid until
+ *               the next-but-one start; a text that was not asked for has 0 bytes). Two calls instead of one so that the copy
+ *               and the caller's fwrite of batch k overlap the kernels of batch k + 1.
+ *   wait_kernels  returns when the kernels of every started batch are through (their copies may still run): the window's bytes
+ *               and arrays may then be overwritten by the decoder
+ *   get_stats   batches collected, their bytes, device time of the kernels, and how long the calls waited for the device */
+typedef struct itx_bed itx_bed;
+#define ITX_BED_ALL 1
+#define ITX_BED_UNIQ 2
+typedef struct itx_bed_text {
+    const char *all, *uniq;
+    uint64_t all_bytes, uniq_bytes;
+} itx_bed_text;
+typedef struct itx_bed_stats {
+    uint64_t batches, hard_batches, bytes;
+    double kernel_ms, wait_s;
+} itx_bed_stats;
+int itx_bed_create(int device, const int64_t *chrom_size, int n_chrom, const itx_params *p, int want, size_t batch_capacity, itx_bed **out);
+void itx_bed_destroy(itx_bed *b);
+int itx_bed_set_tidmap(itx_bed *b, const int32_t *tid2chrom, const char *const *tid2name, int n_tid);
+int itx_bamwin_bed(itx_inflater *h, itx_bed *b, size_t first, size_t n, uint64_t *n_hard);
+int itx_bed_run(itx_bed *b, const void *d_bytes, const uint32_t *d_rec_off, const itx_batch *d_batch, size_t n, uint64_t *n_hard);
+int itx_bed_wait_kernels(itx_bed *b);
+int itx_bed_collect(itx_bed *b, itx_bed_text *out);
+int itx_bed_get_stats(const itx_bed *b, itx_bed_stats *out);
 
 /* ITX_TIMING: what the device decoder measured about itself (pushes, mean duration of the two passes, device allocations),
  * one line on stderr; also printed when the process exits normally. */

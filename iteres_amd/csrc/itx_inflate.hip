@@ -1278,6 +1278,18 @@ extern "C" int itx_bamwin_dedup(itx_inflater *h, itx_dedup *d)
     return itx_dedup_run(d, h->d_tid, h->d_pos, h->d_end, h->d_mapq, h->d_f5, h->d_mpos, h->d_isize, h->n_rec);
 }
 
+int itx_bed_start(itx_bed *b, const uint8_t *u, const uint32_t *rec_off, const int32_t *tid, const int32_t *pos, const int32_t *end, const uint8_t *mapq,
+                  const uint8_t *f5, const int32_t *mpos, const int32_t *isize, size_t n, uint64_t *n_hard);      // itx_bed.hip
+
+/* the bed text of records [first, first + n) of the last parsed window (csrc/itx_bed.hip): started, collected with itx_bed_collect */
+extern "C" int itx_bamwin_bed(itx_inflater *h, itx_bed *b, size_t first, size_t n, uint64_t *n_hard)
+{
+    if (!h || !b || !n_hard || first + n > h->n_rec) return ITX_E_ARG;
+    const int w = h->parsed_w;
+    return itx_bed_start(b, h->win[w].buf, h->d_recoff + first, h->d_tid + first, h->d_pos + first, h->d_end + first, h->d_mapq + first, h->d_f5 + first,
+                         h->d_mpos + first, h->d_isize + first, n, n_hard);
+}
+
 extern "C" int itx_bamwin_device_batch(itx_inflater *h, size_t first, int with_mates, itx_batch *out)
 {
     if (!h || !out || first > h->n_rec || (first & 15u)) return ITX_E_ARG;

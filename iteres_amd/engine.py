@@ -30,6 +30,7 @@ EXPORTS = [
     "itx_engine_partial_buffers", "itx_inflater_reserve", "itx_inflater_last_resolve_all_ms", "itx_timing_report", "itx_xaveto_create", "itx_xaveto_destroy", "itx_xaveto_set_tidmap", "itx_xaveto_hits", "itx_xaveto_stream", "itx_bamwin_xa_veto", "itx_comm_create", "itx_comm_destroy", "itx_comm_reduce_sum",
     "itx_backlog_create", "itx_backlog_destroy", "itx_backlog_room", "itx_backlog_append", "itx_backlog_batch", "itx_dedup_create", "itx_dedup_destroy", "itx_dedup_set_tidmap", "itx_dedup_run", "itx_dedup_counts", "itx_bamwin_dedup",
     "itx_bigwig_start", "itx_bigwig_collect", "itx_bigwig_destroy",
+    "itx_bed_create", "itx_bed_destroy", "itx_bed_set_tidmap", "itx_bamwin_bed", "itx_bed_run", "itx_bed_wait_kernels", "itx_bed_collect", "itx_bed_get_stats",
 ]
 
 
@@ -89,6 +90,16 @@ class BwResult(C.Structure):
 BW_SUMMARY_DTYPE = np.dtype([("chrom_id", "<u4"), ("start", "<u4"), ("end", "<u4"), ("valid_count", "<u4"),
                              ("min_val", "<f4"), ("max_val", "<f4"), ("sum_data", "<f4"), ("sum_squares", "<f4")])
 assert BW_SUMMARY_DTYPE.itemsize == C.sizeof(BwSummary) == 32
+
+class BedText(C.Structure):
+    _fields_ = [("all", C.c_void_p), ("uniq", C.c_void_p), ("all_bytes", C.c_uint64), ("uniq_bytes", C.c_uint64)]
+
+
+class BedStats(C.Structure):
+    _fields_ = [("batches", C.c_uint64), ("hard_batches", C.c_uint64), ("bytes", C.c_uint64), ("kernel_ms", C.c_double), ("wait_s", C.c_double)]
+
+
+BED_ALL, BED_UNIQ = 1, 2
 
 _lib = None
 
@@ -157,6 +168,16 @@ def load():
     L.itx_bigwig_collect.argtypes = [C.c_void_p, C.POINTER(BwResult)]
     L.itx_bigwig_destroy.argtypes = [C.c_void_p]
     L.itx_bigwig_destroy.restype = None
+    L.itx_bamwin_dedup.argtypes = [C.c_void_p, C.c_void_p]
+    L.itx_bed_create.argtypes = [C.c_int, C.c_void_p, C.c_int, C.POINTER(Params), C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
+    L.itx_bed_destroy.argtypes = [C.c_void_p]
+    L.itx_bed_destroy.restype = None
+    L.itx_bed_set_tidmap.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_int]
+    L.itx_bamwin_bed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
+    L.itx_bed_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Batch), C.c_size_t, C.POINTER(C.c_uint64)]
+    L.itx_bed_wait_kernels.argtypes = [C.c_void_p]
+    L.itx_bed_collect.argtypes = [C.c_void_p, C.POINTER(BedText)]
+    L.itx_bed_get_stats.argtypes = [C.c_void_p, C.POINTER(BedStats)]
     L.itx_pinned_alloc.argtypes = [C.c_size_t]
     L.itx_pinned_alloc.restype = C.c_void_p
     L.itx_pinned_free.argtypes = [C.c_void_p]
@@ -490,6 +511,60 @@ class Dedup:
     def close(self):
         if self._h:
             load().itx_dedup_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Bed:
+    """The bed text of stat -B / -V built on the device (include/iteres_amd.h itx_bed_*, replacing generic.c:925-936). `start_window`
+    takes records of an Inflater's last parsed window, `run` plain torch DEVICE tensors (uint8 record bytes, uint32-as-int32
+    offsets, and the per-record arrays); both return how many records need the host's reading (then nothing was started).
+    `collect` hands out the (-B, -V) text of the oldest started batch as bytes."""
+
+    def __init__(self, chrom_size, params: dict | None = None, want: int = BED_ALL | BED_UNIQ, batch_capacity: int = 1 << 20, device: int = 0):
+        q = dict(mapq_min=10, min_cov=1e-4, extension=150, isize_max=500, treat_pe_as_se=False, discard_half_mapped=False)
+        q.update(params or {})
+        p = Params(int(q["mapq_min"]), float(q["min_cov"]), int(q["extension"]), int(q["isize_max"]), int(bool(q["treat_pe_as_se"])),
+                   int(bool(q["discard_half_mapped"])), MODE_STAT, ACCUM_DEFAULT)
+        cs = np.ascontiguousarray(chrom_size, np.int64)
+        self._h = C.c_void_p()
+        _chk(load().itx_bed_create(device, _p(cs), len(cs), C.byref(p), want, batch_capacity, C.byref(self._h)), "itx_bed_create")
+
+    def set_tidmap(self, tid2chrom, tid2name):
+        a = np.ascontiguousarray(tid2chrom, np.int32)
+        names = (C.c_char_p * max(len(a), 1))(*[None if s is None else (s if isinstance(s, bytes) else s.encode()) for s in tid2name])
+        _chk(load().itx_bed_set_tidmap(self._h, _p(a), names, len(a)), "itx_bed_set_tidmap")
+
+    def start_window(self, inflater, first, n):
+        hard = C.c_uint64()
+        _chk(load().itx_bamwin_bed(inflater._h, self._h, first, n, C.byref(hard)), "itx_bamwin_bed")
+        return hard.value
+
+    def run(self, rec_bytes, rec_off, tid, pos, tmpend, mapq, flag5, mpos=None, isize=None):
+        ptr = lambda t: None if t is None else t.data_ptr()
+        b = Batch(ptr(tid), ptr(pos), ptr(tmpend), ptr(mapq), ptr(flag5), ptr(mpos), ptr(isize))
+        hard = C.c_uint64()
+        _chk(load().itx_bed_run(self._h, ptr(rec_bytes), ptr(rec_off), C.byref(b), int(tid.numel()), C.byref(hard)), "itx_bed_run")
+        return hard.value
+
+    def collect(self):
+        t = BedText()
+        _chk(load().itx_bed_collect(self._h, C.byref(t)), "itx_bed_collect")
+        return (C.string_at(t.all, t.all_bytes) if t.all_bytes else b"", C.string_at(t.uniq, t.uniq_bytes) if t.uniq_bytes else b"")
+
+    def stats(self):
+        s = BedStats()
+        _chk(load().itx_bed_get_stats(self._h, C.byref(s)), "itx_bed_get_stats")
+        return {k: getattr(s, k) for k, _ in BedStats._fields_}
+
+    def close(self):
+        if self._h:
+            load().itx_bed_destroy(self._h)
             self._h = None
 
     def __del__(self):

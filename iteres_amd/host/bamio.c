@@ -1700,6 +1700,13 @@ int aln_device_xa_veto(aln_reader *r, itx_xaveto *x, size_t n, uint64_t *n_vetoe
     return 0;
 }
 
+int aln_device_bed(aln_reader *r, itx_bed *b, size_t n, uint64_t *n_hard)
+{
+    if (!r->dev || !dev.bed || n > r->drec_next) return -1;
+    DEV_CHK(dev.bed(dev.ctx, b, r->drec_next - n, n, n_hard), "bed");
+    return 0;
+}
+
 void aln_device_rewind(aln_reader *r, size_t n)
 {
     if (r->dev && r->dparsed) r->drec_next = n <= r->drec_next ? r->drec_next - n : 0;

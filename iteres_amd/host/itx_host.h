@@ -99,6 +99,7 @@ typedef struct aln_device_ops {
     size_t max_blocks, max_bytes;
     int (*xa_veto)(itx_inflater *, itx_xaveto *, size_t, size_t, uint64_t *, uint64_t *);      /* itx_bamwin_xa_veto */
     int (*push_copied)(itx_inflater *, int);       /* itx_bamwin_push_copied: lane s's compressed bytes have left the caller's buffer */
+    int (*bed)(itx_inflater *, itx_bed *, size_t, size_t, uint64_t *);                         /* itx_bamwin_bed */
 } aln_device_ops;
 void aln_use_device(const aln_device_ops *ops);
 size_t aln_raw_step(size_t left);           /* bytes per read step of a regular file with `left` bytes to go (after aln_use_device) */
@@ -122,6 +123,8 @@ size_t aln_read_batch_device(aln_reader *r, size_t cap, itx_batch *b);
 /* the XA veto over the batch aln_read_batch_device has just handed out (its chosen rows are in the veto object's buffer);
  * aln_device_rewind: hand the current window's records out again from its first one (the host route after all) */
 int aln_device_xa_veto(aln_reader *r, itx_xaveto *x, size_t n, uint64_t *n_vetoed, uint64_t *n_hard);
+/* the bed text of the batch aln_read_batch_device has just handed out, started on the device (itx_bed_collect delivers it) */
+int aln_device_bed(aln_reader *r, itx_bed *b, size_t n, uint64_t *n_hard);
 void aln_device_rewind(aln_reader *r, size_t n);       /* the last n records handed out by aln_read_batch_device are handed out again (by whichever route reads next) */
 size_t aln_device_left(const aln_reader *r);  /* device decoder: records of the current window not yet taken */
 int aln_device_exhausted(aln_reader *r);

@@ -2,7 +2,8 @@
  * the engine as one flag bit per record (ITX_F5_NOLOOKUP) or written straight to a file:
  *   - the coordinates of a record as the loop derives them (generic.c:764-905), needed by everything below,
  *   - -R, the duplicate filter on "chr:start:end:strand" keys (generic.c:907-919),
- *   - -B / -V, the bed lines of mapped reads (generic.c:925-936),
+ *   - -B / -V, the bed lines of mapped reads (generic.c:925-936) — of the batches that take the host route (stream.c); BAM
+ *     windows that stay in HBM get their text built there (../csrc/itx_bed.hip),
  *   - the XA/NM multi-mapping veto (generic.c:303-341, 972-982). */
 #define _GNU_SOURCE
 #include "itx_host.h"

@@ -2,7 +2,8 @@
  * pipeline around the GPU engine: decode a batch into one pinned staging slot while the other slot is in
  * flight (itx_engine_staging / submit_slot / wait_slot), keep what is order-dependent or text on the host
  * (progress banners, the "chromosome not in the size file" warnings, read names for filter -r, and — side.c —
- * the -R duplicate filter, the -B/-V bed lines and the XA veto, which reach the engine as one flag bit per record). */
+ * the -R duplicate filter, the -B/-V bed lines and the XA veto for the batches the device cannot take: BAM windows the device
+ * decoder parsed get all three where they lie, include/iteres_amd.h itx_dedup_* / itx_bed_* / itx_xaveto_*). */
 #define _GNU_SOURCE
 #include "itx_host.h"
 
@@ -93,7 +94,8 @@ static void use_device_reader(void)
 {
     const aln_device_ops ops = {g_inflater,       itx_bamwin_push_begin, itx_bamwin_push_end, itx_bamwin_patch, itx_bamwin_truncate, itx_bamwin_carry, itx_bamwin_avail, itx_bamwin_peek,
                                 itx_bamwin_skip, itx_bamwin_parse, itx_bamwin_fetch, itx_bamwin_bytes,    itx_bamwin_tids,  itx_bamwin_device_batch,
-                                pool_alloc,      pool_release,     itx_last_error,   g_dev_windows,       g_dev_max_blocks, g_dev_max_bytes, itx_bamwin_xa_veto, itx_bamwin_push_copied};
+                                pool_alloc,      pool_release,     itx_last_error,   g_dev_windows,       g_dev_max_blocks, g_dev_max_bytes, itx_bamwin_xa_veto, itx_bamwin_push_copied,
+                                itx_bamwin_bed};
     aln_use_device(&ops);
 }
 
@@ -426,6 +428,20 @@ static void dedup_window(void *ctx, size_t n_rec)
     t_dedup += now_s() - t0;
 }
 
+/* -B / -V on the device (csrc/itx_bed.hip): the text of a batch is started right after the batch is taken and written to the
+ * files one batch later, so that the copy and the fwrite run beside the next batch's kernels. Both routes write to the same
+ * FILE: whatever is pending is written before the host route prints a line. */
+static int bed_pending;
+static void bed_write_out(itx_bed *bd, FILE *bed_f, FILE *bed_uniq_f, int discard)
+{
+    itx_bed_text tx;
+    chk(itx_bed_collect(bd, &tx), "itx_bed_collect");
+    bed_pending--;
+    if (discard) return;
+    if (bed_f && tx.all_bytes && fwrite(tx.all, 1, tx.all_bytes, bed_f) != tx.all_bytes) die("writing the bed file: %s", strerror(errno));
+    if (bed_uniq_f && tx.uniq_bytes && fwrite(tx.uniq, 1, tx.uniq_bytes, bed_uniq_f) != tx.uniq_bytes) die("writing the unique bed file: %s", strerror(errno));
+}
+
 /* generic.c:781-791 (-C): NULL when the record is skipped ("GL*"), else the (possibly renamed) chromosome */
 static const char *rename_chr(const char *name, int add_chr, char *buf, size_t bufsz)
 {
@@ -563,6 +579,8 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
     itx_xaveto *xv = NULL;                                             /* the veto on the device (windows that stay in HBM) */
     const int dev_veto = !getenv("ITX_HOST_VETO");
     unsigned long long veto_dev_batches = 0, veto_host_batches = 0;
+    itx_bed *bd = NULL;                                                /* the bed text built on the device (windows that stay in HBM) */
+    unsigned long long bed_host_batches = 0;
     FILE *bed_f = NULL, *bed_uniq_f = NULL;
     /* mustOpen, cuskent/common.c:2543-2568 */
     if (o->bed_path && !(bed_f = fopen(o->bed_path, "w"))) die("mustOpen: Can't open %s to write: %s", o->bed_path, strerror(errno));
@@ -663,6 +681,7 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
         }
         chk(itx_engine_set_tidmap(eng, t2c, nt > 0 ? nt : 0), "itx_engine_set_tidmap");
         if (xv) chk(itx_xaveto_set_tidmap(xv, t2c, nt > 0 ? nt : 0), "itx_xaveto_set_tidmap");
+        if (bd) chk(itx_bed_set_tidmap(bd, t2c, (const char *const *)t2name, nt > 0 ? nt : 0), "itx_bed_set_tidmap");
         if (dd) {
             chk(itx_dedup_set_tidmap(dd, t2c, t2id, nt > 0 ? nt : 0), "itx_dedup_set_tidmap");
             aln_set_window_hook(rd, dedup_window, dd);
@@ -678,7 +697,15 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
          * device decoder parsed then goes to the engine where it lies, in HBM. What is left for the host to look at comes with
          * the window — does a record carry an XA tag (the veto needs its strings: host route for that window), is a mapped
          * record on a chromosome the size file lacks (the warning is per record, in file order: host route). */
-        const int handoff_ok = !dups && !bed_f && !bed_uniq_f && !want_qnames;
+        /* The bed lines no longer keep a window on the host: the device decoder's windows get their text built where they lie
+         * (ITX_HOST_BED=1: by the host, as before). */
+        const int dev_bed = want_bed && g_inflater && !o->is_sam && !getenv("ITX_HOST_BED");
+        const int handoff_ok = !dups && (!want_bed || dev_bed) && !want_qnames;
+        if (dev_bed && !bd) {
+            chk(itx_bed_create(multi_device(), chr_sizes->value, (int)n_chrom, &p, (bed_f ? ITX_BED_ALL : 0) | (bed_uniq_f ? ITX_BED_UNIQ : 0), BATCH_RECORDS, &bd),
+                "itx_bed_create");
+            chk(itx_bed_set_tidmap(bd, t2c, (const char *const *)t2name, nt > 0 ? nt : 0), "itx_bed_set_tidmap");
+        }
         if (drain_backlog) {
             /* the records the helper thread parsed while the table was being built: first, in file order */
             const double td = now_s();
@@ -734,6 +761,22 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
                             const size_t n = aln_read_batch_device(rd, BATCH_RECORDS, &db);
                             t_read += now_s() - tq;
                             if (n == 0) break;
+                            if (bd) {
+                                /* the bed lines come before the veto (generic.c:925 vs 972): built from the window as -R left it.
+                                 * The batch before this one is written out while this one's kernels run. */
+                                const double tb = now_s();
+                                uint64_t bhard = 0;
+                                if (aln_device_bed(rd, bd, n, &bhard) != 0) die("device bed: %s", itx_last_error());
+                                if (!bhard) bed_pending++;
+                                while (bed_pending > (bhard ? 0 : 1)) bed_write_out(bd, bed_f, bed_uniq_f, 0);
+                                t_host += now_s() - tb;
+                                if (bhard) {                                      /* a record only the host can print: this batch and the rest of the window */
+                                    aln_device_rewind(rd, n);
+                                    direct = 0;
+                                    tq = now_s();
+                                    break;
+                                }
+                            }
                             if (xa_window) {
                                 /* classify, let the device read the tags of the classified records, mark the vetoed ones */
                                 const double tv = now_s();
@@ -743,6 +786,7 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
                                 t_host += now_s() - tv;
                                 if (hard) {                                       /* an alternative only strtol / the reference's assert can judge: this batch
                                                                                    * and the rest of the window take the host route (the batches before are through) */
+                                    if (bd) bed_write_out(bd, bed_f, bed_uniq_f, 1);              /* the host prints this batch's lines */
                                     aln_device_rewind(rd, n);
                                     direct = 0;
                                     tq = now_s();
@@ -758,7 +802,10 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
                             chk(itx_engine_submit_device_own(eng, &db, n, NULL), "itx_engine_submit_device_own");
                             /* the window's arrays are the decoder's again once its last batch is through: the next parse
                              * overwrites them */
-                            if (aln_device_left(rd) == 0) chk(itx_engine_wait_own(eng), "itx_engine_wait_own");
+                            if (aln_device_left(rd) == 0) {
+                                chk(itx_engine_wait_own(eng), "itx_engine_wait_own");
+                                if (bd) chk(itx_bed_wait_kernels(bd), "itx_bed_wait_kernels");
+                            }
                             t_submit += now_s() - tq;
                             tq = now_s();
                         } while (!aln_device_window(rd, &wfl2, &seen));                        /* until the next window's start (or the end) */
@@ -768,6 +815,7 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
                 t_read += now_s() - tq;
                 if (aln_device_exhausted(rd)) break;
             }
+            while (bd && bed_pending) bed_write_out(bd, bed_f, bed_uniq_f, 0);        /* before the host prints a line of its own */
             if (!have_slots) {
                 chk(itx_engine_staging(eng, 0, &st[0]), "itx_engine_staging");
                 chk(itx_engine_staging(eng, 1, &st[1]), "itx_engine_staging");
@@ -818,6 +866,7 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
             /* ---- in file order: -R and the bed lines (generic.c:907-936) */
             int batch_xa = 0;
             if (dups || dd || bed_f || bed_uniq_f) {
+                if (want_bed) bed_host_batches++;
                 for (size_t i = 0; i < n; i++) {
                     const int32_t t = st[s].tid[i];
                     const int32_t chrom = (t >= 0 && t < nt) ? t2c[t] : -1;
@@ -882,6 +931,7 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
             pend[s] = n;
             s ^= 1;
         }
+        while (bd && bed_pending) bed_write_out(bd, bed_f, bed_uniq_f, 0);
         const double t_loop_done = now_s();
         /* drain both slots before the tid map of the next file replaces this one */
         for (int k = 0; k < 2; k++) {
@@ -998,6 +1048,14 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
     }
     if (timing && veto_on)
         fprintf(stderr, "[itx timing] XA veto: %llu batches judged on the device, %llu by the host\n", veto_dev_batches, veto_host_batches);
+    if (timing && want_bed) {
+        itx_bed_stats bs;
+        memset(&bs, 0, sizeof bs);
+        if (bd) chk(itx_bed_get_stats(bd, &bs), "itx_bed_get_stats");
+        fprintf(stderr, "[itx timing] bed: %llu batches built on the device (%llu bytes, %.3f ms in its kernels, host waited %.3f s), %llu by the host\n",
+                (unsigned long long)bs.batches, (unsigned long long)bs.bytes, bs.kernel_ms, bs.wait_s, bed_host_batches);
+    }
+    itx_bed_destroy(bd);
     names_free(&warned);
     names_free(&chr_names);
     free(arg);
