@@ -85,7 +85,7 @@ int itx_table_cov_offsets(const itx_table *t, uint64_t *off);
  * (generic.c:983-1032). The order-dependent features around it reach the engine as one flag bit per
  * record (ITX_F5_NOLOOKUP) and have device implementations of their own further down: -R dedup
  * (generic.c:907-919, itx_dedup_*), the XA/NM veto (972-982, itx_xaveto_*), bed emission (925-936,
- * itx_bed_*). Only the qname lists of filter -r (662-666) stay with the caller.
+ * itx_bed_*), the qname lists of filter -r (662-666, itx_names_*).
  * ------------------------------------------------------------------------------------------- */
 typedef struct itx_engine itx_engine;
 
@@ -413,6 +413,51 @@ int itx_bed_run(itx_bed *b, const void *d_bytes, const uint32_t *d_rec_off, cons
 int itx_bed_wait_kernels(itx_bed *b);
 int itx_bed_collect(itx_bed *b, itx_bed_text *out);
 int itx_bed_get_stats(const itx_bed *b, itx_bed_stats *out);
+
+/* ---- the read lists of filter -r on the device ----------------------------------------------------------------------------
+ * Replaces generic.c:662-666 (a classified record's name is head-inserted into its row's list) and the list part of
+ * writeFilterOut (generic.c:1729-1731: the list reversed back to file order and joined with ','): batches leave (row, name)
+ * entries in a pool in device memory, in record order; the end of the stream sorts them by row, stable, and lays the lists down
+ * as one text (csrc/itx_names.hip). -R duplicates carry ITX_F5_NOLOOKUP and never choose a row; filter has no XA veto.
+ *   create      batch_capacity: the most records a batch may carry; pool_bytes: a first size for the pool of name bytes
+ *               (0: ITX_NAMES_POOL_BYTES from the environment, else 64 MiB). The pool and the entry list grow.
+ *   hits/stream a device int32[batch_capacity] and a stream of the object's own, for itx_engine_classify_device to leave the
+ *               chosen rows in (any other buffer / stream will do: `stream` below names it)
+ *   itx_bamwin_names  records [first, first + n) of the inflater's last parsed window: every record with d_hit_row[i] >= 0 appends
+ *               (d_hit_row[i], its name). `stream`: where d_hit_row was written (the object waits behind it). Waits for the
+ *               batch's two totals, enqueues the gather, returns. *n_hard > 0: some record needs the host's reading (a read name
+ *               without a NUL inside its record): NOTHING was appended, the caller takes the host route for these records.
+ *   run         the same over plain DEVICE arrays: the records' bytes and rec_off[i] = where record i (its block_len field) starts
+ *   wait_kernels  returns when every gather is through: the window's bytes may then be overwritten by the decoder
+ *   append_host n hits the caller read itself, in stream order between the device batches: rows[i], and name i =
+ *               name_bytes[name_off[i] .. name_off[i + 1]) (no NUL; name_off has n + 1 elements)
+ *   finish      once: the lists of rows [0, n_rows). text: the names of a row in append order, each followed by ',' and the last
+ *               by NUL, the rows one after the other; row_off[r]: where row r's list starts in text, UINT64_MAX when it has none;
+ *               row_cnt[r]: its number of names. Host memory owned by the object, valid until destroy.
+ * More than 2^32 - 2 names, or a pool the device cannot hold: ITX_E_NOMEM, nothing appended (ITX_HOST_NAMES=1 keeps the
+ * command's lists on the host; ITX_HOST_NAMES=0 asks for this route). */
+typedef struct itx_names itx_names;
+typedef struct itx_names_result {
+    const char *text;
+    uint64_t text_bytes;
+    const uint64_t *row_off;
+    const uint32_t *row_cnt;
+    uint64_t n_entries;
+} itx_names_result;
+typedef struct itx_names_stats {
+    uint64_t batches, hard_batches, host_batches, entries, bytes, grows;   /* device batches appended; ...; pool reallocations */
+    double gather_ms, finish_ms;                                           /* device time: measure + gather kernels; sort + text */
+} itx_names_stats;
+int itx_names_create(int device, size_t batch_capacity, size_t pool_bytes, itx_names **out);
+void itx_names_destroy(itx_names *nm);
+int32_t *itx_names_hits(itx_names *nm);
+void *itx_names_stream(itx_names *nm);
+int itx_bamwin_names(itx_inflater *h, itx_names *nm, size_t first, size_t n, const int32_t *d_hit_row, void *stream, uint64_t *n_hard);
+int itx_names_run(itx_names *nm, const void *d_bytes, const uint32_t *d_rec_off, const int32_t *d_hit_row, size_t n, void *stream, uint64_t *n_hard);
+int itx_names_wait_kernels(itx_names *nm);
+int itx_names_append_host(itx_names *nm, const uint32_t *rows, const char *name_bytes, const uint64_t *name_off, size_t n);
+int itx_names_finish(itx_names *nm, size_t n_rows, itx_names_result *out);
+int itx_names_get_stats(const itx_names *nm, itx_names_stats *out);
 
 /* ITX_TIMING: what the device decoder measured about itself (pushes, mean duration of the two passes, device allocations),
  * one line on stderr; also printed when the process exits normally. */

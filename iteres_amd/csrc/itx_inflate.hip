@@ -1290,6 +1290,16 @@ extern "C" int itx_bamwin_bed(itx_inflater *h, itx_bed *b, size_t first, size_t 
                          h->d_mpos + first, h->d_isize + first, n, n_hard);
 }
 
+int itx_names_start(itx_names *nm, const uint8_t *u, const uint32_t *rec_off, const int32_t *d_hit_row, size_t n, void *stream, uint64_t *n_hard);   // itx_names.hip
+
+/* the names of records [first, first + n) of the last parsed window that chose a row, appended to the lists (csrc/itx_names.hip) */
+extern "C" int itx_bamwin_names(itx_inflater *h, itx_names *nm, size_t first, size_t n, const int32_t *d_hit_row, void *stream, uint64_t *n_hard)
+{
+    if (!h || !nm || !n_hard || first + n > h->n_rec) return ITX_E_ARG;
+    const int w = h->parsed_w;
+    return itx_names_start(nm, h->win[w].buf, h->d_recoff + first, d_hit_row, n, stream, n_hard);
+}
+
 extern "C" int itx_bamwin_device_batch(itx_inflater *h, size_t first, int with_mates, itx_batch *out)
 {
     if (!h || !out || first > h->n_rec || (first & 15u)) return ITX_E_ARG;

@@ -31,6 +31,8 @@ EXPORTS = [
     "itx_backlog_create", "itx_backlog_destroy", "itx_backlog_room", "itx_backlog_append", "itx_backlog_batch", "itx_dedup_create", "itx_dedup_destroy", "itx_dedup_set_tidmap", "itx_dedup_run", "itx_dedup_counts", "itx_bamwin_dedup",
     "itx_bigwig_start", "itx_bigwig_collect", "itx_bigwig_destroy",
     "itx_bed_create", "itx_bed_destroy", "itx_bed_set_tidmap", "itx_bamwin_bed", "itx_bed_run", "itx_bed_wait_kernels", "itx_bed_collect", "itx_bed_get_stats",
+    "itx_names_create", "itx_names_destroy", "itx_names_hits", "itx_names_stream", "itx_bamwin_names", "itx_names_run", "itx_names_wait_kernels", "itx_names_append_host",
+    "itx_names_finish", "itx_names_get_stats",
 ]
 
 
@@ -100,6 +102,15 @@ class BedStats(C.Structure):
 
 
 BED_ALL, BED_UNIQ = 1, 2
+
+
+class NamesResult(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("text_bytes", C.c_uint64), ("row_off", C.c_void_p), ("row_cnt", C.c_void_p), ("n_entries", C.c_uint64)]
+
+
+class NamesStats(C.Structure):
+    _fields_ = [("batches", C.c_uint64), ("hard_batches", C.c_uint64), ("host_batches", C.c_uint64), ("entries", C.c_uint64), ("bytes", C.c_uint64),
+                ("grows", C.c_uint64), ("gather_ms", C.c_double), ("finish_ms", C.c_double)]
 
 _lib = None
 
@@ -178,6 +189,19 @@ def load():
     L.itx_bed_wait_kernels.argtypes = [C.c_void_p]
     L.itx_bed_collect.argtypes = [C.c_void_p, C.POINTER(BedText)]
     L.itx_bed_get_stats.argtypes = [C.c_void_p, C.POINTER(BedStats)]
+    L.itx_names_create.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]
+    L.itx_names_destroy.argtypes = [C.c_void_p]
+    L.itx_names_destroy.restype = None
+    L.itx_names_hits.argtypes = [C.c_void_p]
+    L.itx_names_hits.restype = C.c_void_p
+    L.itx_names_stream.argtypes = [C.c_void_p]
+    L.itx_names_stream.restype = C.c_void_p
+    L.itx_bamwin_names.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.itx_names_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.itx_names_wait_kernels.argtypes = [C.c_void_p]
+    L.itx_names_append_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.itx_names_finish.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(NamesResult)]
+    L.itx_names_get_stats.argtypes = [C.c_void_p, C.POINTER(NamesStats)]
     L.itx_pinned_alloc.argtypes = [C.c_size_t]
     L.itx_pinned_alloc.restype = C.c_void_p
     L.itx_pinned_free.argtypes = [C.c_void_p]
@@ -565,6 +589,72 @@ class Bed:
     def close(self):
         if self._h:
             load().itx_bed_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Names:
+    """The read lists of filter -r built on the device (include/iteres_amd.h itx_names_*, replacing generic.c:662-666 and the list
+    part of generic.c:1729-1731). `append_window` takes records of an Inflater's last parsed window and a torch DEVICE int32 tensor
+    of their chosen rows (-1: none), `run` plain torch DEVICE tensors (uint8 record bytes, uint32-as-int32 offsets, int32 rows);
+    both return how many records need the host's reading (then nothing was appended). `append_host` takes (row, name bytes) pairs.
+    `finish(n_rows)` sorts by row, stable in append order, and returns {row: b",".join(names)} with the per-row counts."""
+
+    def __init__(self, batch_capacity: int = 1 << 20, pool_bytes: int = 0, device: int = 0):
+        self._h = C.c_void_p()
+        _chk(load().itx_names_create(device, batch_capacity, pool_bytes, C.byref(self._h)), "itx_names_create")
+
+    @staticmethod
+    def _stream():
+        import torch
+        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def append_window(self, inflater, first, n, hit_row):
+        hard = C.c_uint64()
+        _chk(load().itx_bamwin_names(inflater._h, self._h, first, n, C.c_void_p(hit_row.data_ptr()), self._stream(), C.byref(hard)), "itx_bamwin_names")
+        return hard.value
+
+    def run(self, rec_bytes, rec_off, hit_row):
+        hard = C.c_uint64()
+        _chk(load().itx_names_run(self._h, C.c_void_p(rec_bytes.data_ptr()), C.c_void_p(rec_off.data_ptr()), C.c_void_p(hit_row.data_ptr()), int(hit_row.numel()),
+                                  self._stream(), C.byref(hard)), "itx_names_run")
+        return hard.value
+
+    def append_host(self, rows, names):
+        r = np.ascontiguousarray(rows, np.uint32)
+        off = np.zeros(len(r) + 1, np.uint64)
+        off[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(names) + b"\0", np.uint8).copy()
+        _chk(load().itx_names_append_host(self._h, _p(r), _p(blob), _p(off), len(r)), "itx_names_append_host")
+
+    def wait_kernels(self):
+        _chk(load().itx_names_wait_kernels(self._h), "itx_names_wait_kernels")
+
+    def finish(self, n_rows):
+        res = NamesResult()
+        _chk(load().itx_names_finish(self._h, n_rows, C.byref(res)), "itx_names_finish")
+        row_off = np.ctypeslib.as_array(C.cast(res.row_off, C.POINTER(C.c_uint64)), (n_rows,))
+        row_cnt = np.ctypeslib.as_array(C.cast(res.row_cnt, C.POINTER(C.c_uint32)), (n_rows,)).copy()
+        text = C.string_at(res.text, res.text_bytes) if res.text_bytes else b""
+        lists = {}
+        for r in np.flatnonzero(row_off != np.uint64(0xffffffffffffffff)):
+            o = int(row_off[r])
+            lists[int(r)] = text[o:text.index(b"\0", o)]
+        return lists, row_cnt, text, int(res.n_entries)
+
+    def stats(self):
+        s = NamesStats()
+        _chk(load().itx_names_get_stats(self._h, C.byref(s)), "itx_names_get_stats")
+        return {k: getattr(s, k) for k, _ in NamesStats._fields_}
+
+    def close(self):
+        if self._h:
+            load().itx_names_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -1707,6 +1707,13 @@ int aln_device_bed(aln_reader *r, itx_bed *b, size_t n, uint64_t *n_hard)
     return 0;
 }
 
+int aln_device_names(aln_reader *r, itx_names *nm, size_t n, const int32_t *d_hit_row, void *stream, uint64_t *n_hard)
+{
+    if (!r->dev || !dev.names || n > r->drec_next) return -1;
+    DEV_CHK(dev.names(dev.ctx, nm, r->drec_next - n, n, d_hit_row, stream, n_hard), "names");
+    return 0;
+}
+
 void aln_device_rewind(aln_reader *r, size_t n)
 {
     if (r->dev && r->dparsed) r->drec_next = n <= r->drec_next ? r->drec_next - n : 0;

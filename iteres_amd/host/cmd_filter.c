@@ -136,7 +136,18 @@ int main_filter(int argc, char **argv)
     res.locus_cnt = xcalloc(rm.n_rows + 1, sizeof(uint32_t));
     if (stream_finish(eng, &res) != ITX_OK) die("itx_engine_finish: %s", itx_last_error());
     cnt[11] -= hc.dup_unique;                     /* reads_nonredundant_unique: -R duplicates never reach it (generic.c:524-539) */
+    const uint32_t *names_cnt = stream_names_counts();
+    if (names_cnt)                                /* the lists came from the device: one name per counted read, or something is wrong */
+        for (size_t r = 0; r < rm.n_rows; r++)
+            if (names_cnt[r] != res.locus_cnt[r])
+                die("read lists: row %zu has %u names but %u counted reads (ITX_HOST_NAMES=1 builds the lists on the host)", r, names_cnt[r], res.locus_cnt[r]);
     write_filter_out(&rm, res.locus_cnt, locus_names, out, optreadlist, optthreshold, subfam, cnt[nindex]);
+    if (names_cnt) {
+        stream_names_free(locus_names);
+    } else if (locus_names) {
+        for (size_t r = 0; r < rm.n_rows; r++) free(locus_names[r]);
+        free(locus_names);
+    }
     fprintf(stderr, "* Preparing report file\n");
     write_report(outReport, cnt, o.mapq, subfam);
     itx_engine_destroy(eng);

@@ -100,6 +100,7 @@ typedef struct aln_device_ops {
     int (*xa_veto)(itx_inflater *, itx_xaveto *, size_t, size_t, uint64_t *, uint64_t *);      /* itx_bamwin_xa_veto */
     int (*push_copied)(itx_inflater *, int);       /* itx_bamwin_push_copied: lane s's compressed bytes have left the caller's buffer */
     int (*bed)(itx_inflater *, itx_bed *, size_t, size_t, uint64_t *);                         /* itx_bamwin_bed */
+    int (*names)(itx_inflater *, itx_names *, size_t, size_t, const int32_t *, void *, uint64_t *);   /* itx_bamwin_names */
 } aln_device_ops;
 void aln_use_device(const aln_device_ops *ops);
 size_t aln_raw_step(size_t left);           /* bytes per read step of a regular file with `left` bytes to go (after aln_use_device) */
@@ -125,6 +126,9 @@ size_t aln_read_batch_device(aln_reader *r, size_t cap, itx_batch *b);
 int aln_device_xa_veto(aln_reader *r, itx_xaveto *x, size_t n, uint64_t *n_vetoed, uint64_t *n_hard);
 /* the bed text of the batch aln_read_batch_device has just handed out, started on the device (itx_bed_collect delivers it) */
 int aln_device_bed(aln_reader *r, itx_bed *b, size_t n, uint64_t *n_hard);
+/* the names of the batch aln_read_batch_device has just handed out, appended to the read lists on the device: d_hit_row holds the
+ * batch's chosen rows, written on `stream` */
+int aln_device_names(aln_reader *r, itx_names *nm, size_t n, const int32_t *d_hit_row, void *stream, uint64_t *n_hard);
 void aln_device_rewind(aln_reader *r, size_t n);       /* the last n records handed out by aln_read_batch_device are handed out again (by whichever route reads next) */
 size_t aln_device_left(const aln_reader *r);  /* device decoder: records of the current window not yet taken */
 int aln_device_exhausted(aln_reader *r);
@@ -189,7 +193,7 @@ int xa_veto(const xa_index *x, uint32_t chosen_rep, int nm, char *xa, int qlen);
 char *filename_without_ext(const char *path);
 /* Runs the record loop (generic.c:700-1062 / 343-697) over one or more files through the engine.
  * progress_every: 100000 (stat, generic.c:760) or 10000 (filter, generic.c:397). want_qnames: per-locus read
- * names (filter -r): *locus_names[row] receives a comma-joined list in BAM order. */
+ * names (filter -r): *locus_names[row] receives a comma-joined list in BAM order (NULL: no read chose the row). */
 /* records parsed ahead of the table by the helper thread (stream.c): allowed when nothing per record is the host's business;
  * the size file's table has to be announced once it is loaded */
 void stream_prefetch_allow(const run_opts *o, int filter_mode, int allowed);
@@ -251,6 +255,10 @@ int multi_selftest(void);
 const char *multi_comm_id(void);
 /* stream.c: what the writers read — itx_engine_finish, or, after a multi-GPU stream, the same from the reduced partial */
 int stream_finish(itx_engine *eng, const itx_result *res);
+/* filter -r with the lists built on the device: after run_stream, the number of names per table row (NULL: the host built the
+ * lists, every locus_names[row] is a string of its own); stream_names_free releases the lists (locus_names[] point into them) */
+const uint32_t *stream_names_counts(void);
+void stream_names_free(char **locus_names);
 
 int main_cpgstat(int argc, char **argv);
 int main_cpgfilter(int argc, char **argv);

@@ -95,7 +95,7 @@ static void use_device_reader(void)
     const aln_device_ops ops = {g_inflater,       itx_bamwin_push_begin, itx_bamwin_push_end, itx_bamwin_patch, itx_bamwin_truncate, itx_bamwin_carry, itx_bamwin_avail, itx_bamwin_peek,
                                 itx_bamwin_skip, itx_bamwin_parse, itx_bamwin_fetch, itx_bamwin_bytes,    itx_bamwin_tids,  itx_bamwin_device_batch,
                                 pool_alloc,      pool_release,     itx_last_error,   g_dev_windows,       g_dev_max_blocks, g_dev_max_bytes, itx_bamwin_xa_veto, itx_bamwin_push_copied,
-                                itx_bamwin_bed};
+                                itx_bamwin_bed,  itx_bamwin_names};
     aln_use_device(&ops);
 }
 
@@ -465,9 +465,73 @@ typedef struct {
     size_t n, cap;
 } hit_names;
 
+/* filter -r on the device (csrc/itx_names.hip): the lists are gathered where the records lie; what the host route reads goes to
+ * the same pool, in stream order (itx_names_append_host), so the end of the stream has one list to sort whatever route a window
+ * took. The host route (ITX_HOST_NAMES=1), SAM text and the host decoder keep the lists on the host as before. */
+static itx_names *g_names;
+/* Which route builds the lists when ITX_HOST_NAMES is not set. The device route becomes the default only on a measurement of the
+ * whole command ("Read lists on the device"); until one exists the host builds them, as before. ITX_HOST_NAMES=0 asks
+ * for the device route, ITX_HOST_NAMES=1 for the host's. */
+#define NAMES_HOST_DEFAULT 1
+static int names_by_host(void)
+{
+    const char *e = getenv("ITX_HOST_NAMES");
+    return e && *e ? atoi(e) != 0 : NAMES_HOST_DEFAULT;
+}
+static unsigned long long names_host_batches;
+static struct {
+    uint32_t *rows;
+    uint64_t *off;
+    char *bytes;
+    size_t cap_n, cap_b;
+} nbuf;
+static const uint32_t *g_names_cnt;                                   /* after the stream: names per row (stream_names_counts) */
+
+const uint32_t *stream_names_counts(void) { return g_names_cnt; }
+void stream_names_free(char **locus_names)
+{
+    free(locus_names);                                                 /* (the strings are the names object's one text) */
+    itx_names_destroy(g_names);
+    g_names = NULL;
+    g_names_cnt = NULL;
+}
+
+/* the batch's hits to the device pool: (row, name) in record order */
+static void names_to_device(const itx_staging *st, aln_side *side, size_t n)
+{
+    size_t m = 0, b = 0;
+    if (nbuf.cap_n < n + 1) {
+        nbuf.cap_n = n + n / 4 + 1;
+        nbuf.rows = xrealloc(nbuf.rows, sizeof(uint32_t) * nbuf.cap_n);
+        nbuf.off = xrealloc(nbuf.off, sizeof(uint64_t) * (nbuf.cap_n + 1));
+    }
+    for (size_t i = 0; i < n; i++) {
+        if (st->hit_row[i] >= 0) {
+            const size_t k = strlen(side->qname[i]);
+            if (nbuf.cap_b < b + k + 1) {
+                nbuf.cap_b = (b + k + 1) * 2;
+                nbuf.bytes = xrealloc(nbuf.bytes, nbuf.cap_b);
+            }
+            nbuf.rows[m] = (uint32_t)st->hit_row[i];
+            nbuf.off[m++] = b;
+            memcpy(nbuf.bytes + b, side->qname[i], k);
+            b += k;
+        }
+        free(side->qname[i]);
+        side->qname[i] = NULL;
+    }
+    nbuf.off[m] = b;
+    chk(itx_names_append_host(g_names, nbuf.rows, nbuf.bytes, nbuf.off, m), "itx_names_append_host");
+}
+
 /* filter -r: keep the names of the records that chose a row, free the others */
 static void collect_names(hit_names *hn, const itx_staging *st, aln_side *side, size_t n)
 {
+    names_host_batches++;
+    if (g_names) {
+        names_to_device(st, side, n);
+        return;
+    }
     for (size_t i = 0; i < n; i++) {
         const int32_t row = st->hit_row[i];
         if (row >= 0) {
@@ -581,6 +645,8 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
     unsigned long long veto_dev_batches = 0, veto_host_batches = 0;
     itx_bed *bd = NULL;                                                /* the bed text built on the device (windows that stay in HBM) */
     unsigned long long bed_host_batches = 0;
+    itx_names *nm = NULL;                                              /* the read lists gathered on the device (filter -r) */
+    names_host_batches = 0;
     FILE *bed_f = NULL, *bed_uniq_f = NULL;
     /* mustOpen, cuskent/common.c:2543-2568 */
     if (o->bed_path && !(bed_f = fopen(o->bed_path, "w"))) die("mustOpen: Can't open %s to write: %s", o->bed_path, strerror(errno));
@@ -700,7 +766,14 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
         /* The bed lines no longer keep a window on the host: the device decoder's windows get their text built where they lie
          * (ITX_HOST_BED=1: by the host, as before). */
         const int dev_bed = want_bed && g_inflater && !o->is_sam && !getenv("ITX_HOST_BED");
-        const int handoff_ok = !dups && (!want_bed || dev_bed) && !want_qnames;
+        /* Nor do the read lists of filter -r on the device route (ITX_HOST_NAMES=0): the names are gathered from the window where
+         * it lies. */
+        const int dev_names = want_qnames && g_inflater && !o->is_sam && !names_by_host();
+        const int handoff_ok = !dups && (!want_bed || dev_bed) && (!want_qnames || dev_names);
+        if (dev_names && !nm) {
+            chk(itx_names_create(multi_device(), BATCH_RECORDS, 0, &nm), "itx_names_create");
+            g_names = nm;
+        }
         if (dev_bed && !bd) {
             chk(itx_bed_create(multi_device(), chr_sizes->value, (int)n_chrom, &p, (bed_f ? ITX_BED_ALL : 0) | (bed_uniq_f ? ITX_BED_UNIQ : 0), BATCH_RECORDS, &bd),
                 "itx_bed_create");
@@ -777,6 +850,31 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
                                     break;
                                 }
                             }
+                            if (nm) {
+                                /* Classify into the lists' buffer first, gather, and only then submit: a batch whose names
+                                 * only the host can read (*n_hard) has then not been counted yet, and the host route counts
+                                 * it once. (filter runs no veto: the rows are final.) What the host route still holds of
+                                 * earlier batches goes to the pool first — the lists are in file order. */
+                                const double tn = now_s();
+                                for (int k = 0; k < 2; k++) {
+                                    const int sk = s ^ k;                             /* the older of the two slots first */
+                                    if (!pend[sk]) continue;
+                                    chk(itx_engine_wait_slot(eng, sk), "itx_engine_wait_slot");
+                                    collect_names(&hn, &st[sk], &side[sk], pend[sk]);
+                                    side_release(&side[sk], pend[sk], want_qnames);
+                                    pend[sk] = 0;
+                                }
+                                uint64_t nhard = 0;
+                                chk(itx_engine_classify_device(eng, &db, n, itx_names_hits(nm), itx_names_stream(nm)), "itx_engine_classify_device");
+                                if (aln_device_names(rd, nm, n, itx_names_hits(nm), itx_names_stream(nm), &nhard) != 0) die("device read lists: %s", itx_last_error());
+                                t_host += now_s() - tn;
+                                if (nhard) {                                      /* this batch and the rest of the window: the host route */
+                                    aln_device_rewind(rd, n);
+                                    direct = 0;
+                                    tq = now_s();
+                                    break;
+                                }
+                            }
                             if (xa_window) {
                                 /* classify, let the device read the tags of the classified records, mark the vetoed ones */
                                 const double tv = now_s();
@@ -805,6 +903,7 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
                             if (aln_device_left(rd) == 0) {
                                 chk(itx_engine_wait_own(eng), "itx_engine_wait_own");
                                 if (bd) chk(itx_bed_wait_kernels(bd), "itx_bed_wait_kernels");
+                                if (nm) chk(itx_names_wait_kernels(nm), "itx_names_wait_kernels");
                             }
                             t_submit += now_s() - tq;
                             tq = now_s();
@@ -816,6 +915,7 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
                 if (aln_device_exhausted(rd)) break;
             }
             while (bd && bed_pending) bed_write_out(bd, bed_f, bed_uniq_f, 0);        /* before the host prints a line of its own */
+            if (nm) chk(itx_names_wait_kernels(nm), "itx_names_wait_kernels");
             if (!have_slots) {
                 chk(itx_engine_staging(eng, 0, &st[0]), "itx_engine_staging");
                 chk(itx_engine_staging(eng, 1, &st[1]), "itx_engine_staging");
@@ -934,7 +1034,8 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
         while (bd && bed_pending) bed_write_out(bd, bed_f, bed_uniq_f, 0);
         const double t_loop_done = now_s();
         /* drain both slots before the tid map of the next file replaces this one */
-        for (int k = 0; k < 2; k++) {
+        for (int kk = 0; kk < 2; kk++) {
+            const int k = s ^ kk;                                        /* the older batch first: the read lists are in file order */
             chk(itx_engine_wait_slot(eng, k), "itx_engine_wait_slot");
             if (pend[k]) {
                 if (want_qnames) collect_names(&hn, &st[k], &side[k], pend[k]);
@@ -1075,7 +1176,16 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
     free(iv);
     free(live);
 
-    if (want_qnames && locus_names) {
+    if (want_qnames && locus_names && nm) {
+        /* one sort by row, stable in append order, and one text: every list is a NUL-terminated piece of it */
+        itx_names_result nr;
+        chk(itx_names_finish(nm, rm->n_rows ? rm->n_rows : 1, &nr), "itx_names_finish");
+        char **out = xcalloc(rm->n_rows ? rm->n_rows : 1, sizeof(char *));
+        for (size_t r = 0; r < rm->n_rows; r++)
+            if (nr.row_off[r] != UINT64_MAX) out[r] = (char *)nr.text + nr.row_off[r];
+        g_names_cnt = nr.row_cnt;
+        *locus_names = out;
+    } else if (want_qnames && locus_names) {
         /* names per locus in BAM order (generic.c:1729 reverses the head-inserted list back to file order) */
         char **out = xcalloc(rm->n_rows ? rm->n_rows : 1, sizeof(char *));
         size_t *len = xcalloc(rm->n_rows ? rm->n_rows : 1, sizeof(size_t));
@@ -1098,6 +1208,18 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
         *locus_names = out;
     }
     free(hn.v);
+    if (timing && want_qnames) {
+        itx_names_stats ns;
+        memset(&ns, 0, sizeof ns);
+        if (nm) chk(itx_names_get_stats(nm, &ns), "itx_names_get_stats");
+        fprintf(stderr, "[itx timing] names: %llu batches gathered on the device (%llu names, %llu bytes, %.3f ms in the gather kernels, %.3f ms sort + text), %llu batches by the host\n",
+                (unsigned long long)ns.batches, (unsigned long long)ns.entries, (unsigned long long)ns.bytes, ns.gather_ms, ns.finish_ms, names_host_batches);
+    }
+    if (nm && !(want_qnames && locus_names)) stream_names_free(NULL);
+    free(nbuf.rows);
+    free(nbuf.off);
+    free(nbuf.bytes);
+    memset(&nbuf, 0, sizeof nbuf);
     for (int k = 0; k < 2; k++) {
         free(side[k].qname);
         free(side[k].xa);

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Scratch A/B of the whole command on one box: python tools/ab_cli.py <n_reads> <seq_len> <reps> NAME:VAR=VAL,VAR=VAL ...
 Generates the bench inputs once (bench.py's generator), then runs `iteres stat -w` <reps> times per setting, interleaved.
-LD_LIBRARY_PATH in a setting selects another build of libiteres_amd.so (the program's RUNPATH comes after it)."""
+LD_LIBRARY_PATH in a setting selects another build of libiteres_amd.so (the program's RUNPATH comes after it).
+ITX_AB_FILTER=1 runs `iteres filter -c <the table's biggest class>` instead (ITX_AB_OPTS="-r": with the read lists) and compares
+the .loci / .reportloci files."""
 import json
 import os
 import subprocess
@@ -42,6 +44,8 @@ def main():
             args = bench.base_args(wd)
             extra = os.environ.get("ITX_AB_OPTS", "").split()              # e.g. ITX_AB_OPTS="-R": options behind `stat -w`
             args = args[:2] + extra + args[2:]
+            if os.environ.get("ITX_AB_FILTER"):
+                args = ["filter", "-c", info["filter_class"]["name"]] + extra + args[2:]
             wall, rc, err, seen = bench.run_timed(bench.OURS, args + [os.path.join(wd, "reads.bam")], out, env, (bench.SCAN_BEGIN, bench.SCAN_END))
             assert rc == 0, err[-800:]
             walls[name].append(round(wall, 3))
@@ -49,7 +53,11 @@ def main():
             notes[name] = [ln[13:] for ln in err.replace("\r", "\n").split("\n") if ln.startswith("[itx timing]")]
     same = {}
     for name, _ in settings[1:]:
-        same[name] = all(open(os.path.join(wd, "ab_base", fn), "rb").read() == open(os.path.join(wd, "ab_" + name, fn), "rb").read() for fn in bench.TEXT_OUTPUTS)
+        outputs = bench.TEXT_OUTPUTS
+        if os.environ.get("ITX_AB_FILTER"):
+            outputs = sorted(fn for fn in os.listdir(os.path.join(wd, "ab_base")) if fn.endswith("loci"))
+            assert len(outputs) == 2, outputs
+        same[name] = all(open(os.path.join(wd, "ab_base", fn), "rb").read() == open(os.path.join(wd, "ab_" + name, fn), "rb").read() for fn in outputs)
     print(json.dumps({"reads": a.reads, "seq_len": a.seq_len, "walls_s": walls, "scan_s": scans, "same_outputs_as_base": same, "notes": notes, "inputs": info}), flush=True)
 
 
