@@ -7,13 +7,11 @@
 //                  925); itx_bed_scan (itx_bedline.h) walks the record for its name and its XA / NM tags; the byte lengths of
 //                  the -B and of the -V line (-V only when MAPQ >= -Q). What the walk found is kept per record, so the tags
 //                  are walked once. A tile of BED_TILE records adds up its lengths (64 bit).
-//   k_bed_scan     exclusive prefix sums of the tiles' lengths, 64 bit: where every tile's text starts, and the totals.
-//   k_bed_write    one workgroup per tile, one lane per record. The tile's text is ONE contiguous range of the output by
-//                  construction; lines are 50-100 bytes at offsets unrelated to anything, so they are not stored from the
-//                  lanes. The range is cut into windows of BED_LDS bytes that start on 16-byte boundaries of the output; every
-//                  lane writes the part of its line that falls into the window into LDS (itx_bed_write takes a byte range of a
-//                  line, so a long XA string simply spans windows), and the workgroup stores the window with one 16-byte
-//                  vector per lane, coalesced; only the ragged first and last vector of a tile go byte by byte.
+//   k_tile_scan2   (itx_textpack.h) exclusive prefix sums of the tiles' lengths, 64 bit: where every tile's text starts, and the
+//                  totals.
+//   k_bed_write    one workgroup per tile, one lane per record. The tile's text is ONE contiguous range of the output; it is
+//                  staged in LDS a window of BED_LDS bytes at a time and stored with 16-byte vectors (itx_textpack.h says why and
+//                  how). itx_bed_write takes a byte range of a line, so a long XA string simply spans windows.
 //
 // "The host has to look" (nothing of the batch is emitted, the caller takes the host route): a read name without a NUL before
 // the end of its record — the host's strdup then reads on into the next record, which is not modelled here.
@@ -21,12 +19,11 @@
 // Byte and integer work, bound by the latency of the scattered record reads in k_bed_measure; the text leaves through pinned
 // double buffers on a copy stream of its own, so that the copy of batch k and the host's fwrite overlap the kernels of batch
 // k + 1 and the engine's work.
-#include "itx_device.h"
+#include "itx_textpack.h"
 #include "itx_derive.h"
 #include "itx_bedline.h"
 
 #include <string.h>
-#include <time.h>
 
 #include <string>
 #include <vector>
@@ -101,66 +98,18 @@ __global__ __launch_bounds__(BED_TILE) void k_bed_measure(BedDev D, const uint8_
     if (threadIdx.x < 2) tile_sum[2u * blockIdx.x + threadIdx.x] = s_sum[threadIdx.x];
 }
 
-// exclusive sums over the tiles, both texts at once; one workgroup (a batch of 4 Mi records is 16 Ki tiles)
-__global__ __launch_bounds__(1024) void k_bed_scan(const unsigned long long *__restrict__ tile_sum, uint32_t nt, unsigned long long *__restrict__ tile_base,
-                                                   unsigned long long *__restrict__ tot)
-{
-    __shared__ unsigned long long s[2][1024];
-    const uint32_t per = (nt + 1023u) / 1024u;
-    const uint32_t lo = threadIdx.x * per < nt ? threadIdx.x * per : nt, hi = lo + per < nt ? lo + per : nt;
-    unsigned long long a = 0, b = 0;
-    for (uint32_t k = lo; k < hi; k++) {
-        a += tile_sum[2u * k];
-        b += tile_sum[2u * k + 1u];
-    }
-    s[0][threadIdx.x] = a;
-    s[1][threadIdx.x] = b;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024u; d <<= 1) {
-        const unsigned long long va = threadIdx.x >= d ? s[0][threadIdx.x - d] : 0ull, vb = threadIdx.x >= d ? s[1][threadIdx.x - d] : 0ull;
-        __syncthreads();
-        s[0][threadIdx.x] += va;
-        s[1][threadIdx.x] += vb;
-        __syncthreads();
-    }
-    unsigned long long ea = s[0][threadIdx.x] - a, eb = s[1][threadIdx.x] - b;
-    for (uint32_t k = lo; k < hi; k++) {
-        tile_base[2u * k] = ea;
-        tile_base[2u * k + 1u] = eb;
-        ea += tile_sum[2u * k];
-        eb += tile_sum[2u * k + 1u];
-    }
-    if (threadIdx.x == 1023u) {
-        tot[0] = s[0][1023];
-        tot[1] = s[1][1023];
-    }
-}
-
 template <bool WITH_XA>
 __global__ __launch_bounds__(BED_TILE) void k_bed_write(BedDev D, const uint8_t *__restrict__ u, const uint32_t *__restrict__ rec_off, BedRecs R, uint32_t n, BedFound F,
                                                         const unsigned long long *__restrict__ tile_base, uint8_t *__restrict__ out)
 {
     __shared__ uint4 s_buf[BED_LDS / 16u];
     __shared__ uint32_t s_w[BED_TILE / 64u];
-    uint8_t *s_bytes = reinterpret_cast<uint8_t *>(s_buf);
     const uint32_t i = blockIdx.x * BED_TILE + threadIdx.x;
     const uint32_t len = i < n ? (WITH_XA ? F.len_b[i] : F.len_v[i]) : 0u;
-    // where the lane's line starts inside the tile
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint32_t x = len;
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63u) s_w[w] = x;
-    __syncthreads();
-    uint32_t woff = 0, total = 0;
-    for (uint32_t k = 0; k < BED_TILE / 64u; k++) {
-        if (k < w) woff += s_w[k];
-        total += s_w[k];
-    }
+    uint32_t total = 0;
+    const uint32_t moff = itx_tile_offsets<BED_TILE>(len, s_w, &total);
     const unsigned long long tb = tile_base[2u * blockIdx.x + (WITH_XA ? 0u : 1u)], te = tb + total;
-    const unsigned long long mb = tb + woff + (x - len), me = mb + len;
+    const unsigned long long mb = tb + moff, me = mb + len;
     ItxBedLine L;
     if (len) {
         const int32_t t = R.tid[i];                                   // in range: the record has a line
@@ -179,34 +128,8 @@ __global__ __launch_bounds__(BED_TILE) void k_bed_write(BedDev D, const uint8_t 
         L.xa_len = F.xa_len[i];
         L.nm = F.nm[i];
     }
-    for (unsigned long long win = tb & ~15ull; win < te; win += BED_LDS) {
-        if (len) {
-            const unsigned long long a = mb > win ? mb : win, b = me < win + BED_LDS ? me : win + BED_LDS;
-            if (a < b) itx_bed_write(&L, WITH_XA, s_bytes + (uint32_t)(a - win), (uint32_t)(a - mb), (uint32_t)(b - mb));
-        }
-        __syncthreads();
-        for (uint32_t v = threadIdx.x; v < BED_LDS / 16u; v += BED_TILE) {
-            const unsigned long long ab = win + 16ull * v;
-            if (ab >= te) break;
-            if (ab >= tb && ab + 16ull <= te) {
-                *reinterpret_cast<uint4 *>(out + ab) = s_buf[v];
-            } else {
-                for (uint32_t k = 0; k < 16u; k++)
-                    if (ab + k >= tb && ab + k < te) out[ab + k] = s_bytes[16u * v + k];
-            }
-        }
-        __syncthreads();
-    }
+    itx_pack_tile<BED_TILE, BED_LDS>(s_buf, out, tb, te, mb, me, [=](uint8_t *dst, uint32_t from, uint32_t to) { itx_bed_write(&L, WITH_XA, dst, from, to); });
 }
-
-#define BED_HIP(call)                                                                                     \
-    do {                                                                                                  \
-        hipError_t err__ = (call);                                                                        \
-        if (err__ != hipSuccess) {                                                                        \
-            itx_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
-            return ITX_E_NO_DEVICE;                                                                       \
-        }                                                                                                 \
-    } while (0)
 
 struct BedSlot {
     uint8_t *d_out[2], *h_out[2];     // [0] -B, [1] -V
@@ -229,48 +152,6 @@ struct itx_bed {
     int next, in_flight;
     itx_bed_stats stats;
 };
-
-static double bed_now(void)
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
-extern "C" int itx_bed_create(int device, const int64_t *chrom_size, int n_chrom, const itx_params *p, int want, size_t batch_capacity, itx_bed **out)
-{
-    if (!chrom_size || n_chrom < 0 || !p || !out || batch_capacity == 0 || batch_capacity > 0xffffff00u || !(want & (ITX_BED_ALL | ITX_BED_UNIQ)) ||
-        (want & ~(ITX_BED_ALL | ITX_BED_UNIQ))) {
-        itx_set_error("itx_bed_create: bad argument");
-        return ITX_E_ARG;
-    }
-    *out = nullptr;
-    BED_HIP(hipSetDevice(device));
-    itx_bed *b = new itx_bed();
-    b->device = device;
-    b->chrom_size.assign(chrom_size, chrom_size + n_chrom);
-    b->cap = batch_capacity;
-    b->d.want = (uint32_t)want;
-    b->d.o.mapq_min = (uint32_t)p->mapq_min;
-    b->d.o.extension = p->extension;
-    b->d.o.isize_max = p->isize_max;
-    b->d.o.treat = p->treat_pe_as_se;
-    b->d.o.discard = p->discard_half_mapped;
-    const size_t n = batch_capacity + 64, nt = (batch_capacity + BED_TILE - 1) / BED_TILE + 1;
-    uint32_t **u32s[5] = {&b->f.len_b, &b->f.len_v, &b->f.qlen, &b->f.xa_off, &b->f.xa_len};
-    for (auto pp : u32s) BED_HIP(hipMalloc((void **)pp, 4 * n));
-    BED_HIP(hipMalloc((void **)&b->f.nm, 4 * n));
-    BED_HIP(hipMalloc((void **)&b->d_tile_sum, 16 * nt));
-    BED_HIP(hipMalloc((void **)&b->d_tile_base, 16 * nt));
-    BED_HIP(hipMalloc((void **)&b->d_tot, 32));
-    BED_HIP(hipHostMalloc((void **)&b->h_tot, 32, hipHostMallocDefault));
-    BED_HIP(hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
-    BED_HIP(hipStreamCreateWithFlags(&b->st_copy, hipStreamNonBlocking));
-    for (auto &s : b->slot)
-        for (auto &e : s.ev) BED_HIP(hipEventCreate(&e));
-    *out = b;
-    return ITX_OK;
-}
 
 extern "C" void itx_bed_destroy(itx_bed *b)
 {
@@ -304,6 +185,52 @@ extern "C" void itx_bed_destroy(itx_bed *b)
     delete b;
 }
 
+// fills the object; on a non-zero return the caller destroys what there is of it
+static int bed_create(itx_bed *b, int device, const int64_t *chrom_size, int n_chrom, const itx_params *p, int want, size_t batch_capacity)
+{
+    b->device = device;
+    ITX_HIP(hipSetDevice(device));
+    b->chrom_size.assign(chrom_size, chrom_size + n_chrom);
+    b->cap = batch_capacity;
+    b->d.want = (uint32_t)want;
+    b->d.o.mapq_min = (uint32_t)p->mapq_min;
+    b->d.o.extension = p->extension;
+    b->d.o.isize_max = p->isize_max;
+    b->d.o.treat = p->treat_pe_as_se;
+    b->d.o.discard = p->discard_half_mapped;
+    const size_t n = batch_capacity + 64, nt = (batch_capacity + BED_TILE - 1) / BED_TILE + 1;
+    uint32_t **u32s[5] = {&b->f.len_b, &b->f.len_v, &b->f.qlen, &b->f.xa_off, &b->f.xa_len};
+    for (auto pp : u32s) ITX_HIP(hipMalloc((void **)pp, 4 * n));
+    ITX_HIP(hipMalloc((void **)&b->f.nm, 4 * n));
+    ITX_HIP(hipMalloc((void **)&b->d_tile_sum, 16 * nt));
+    ITX_HIP(hipMalloc((void **)&b->d_tile_base, 16 * nt));
+    ITX_HIP(hipMalloc((void **)&b->d_tot, 32));
+    ITX_HIP(hipHostMalloc((void **)&b->h_tot, 32, hipHostMallocDefault));
+    ITX_HIP(hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
+    ITX_HIP(hipStreamCreateWithFlags(&b->st_copy, hipStreamNonBlocking));
+    for (auto &s : b->slot)
+        for (auto &e : s.ev) ITX_HIP(hipEventCreate(&e));
+    return ITX_OK;
+}
+
+extern "C" int itx_bed_create(int device, const int64_t *chrom_size, int n_chrom, const itx_params *p, int want, size_t batch_capacity, itx_bed **out)
+{
+    if (!chrom_size || n_chrom < 0 || !p || !out || batch_capacity == 0 || batch_capacity > 0xffffff00u || !(want & (ITX_BED_ALL | ITX_BED_UNIQ)) ||
+        (want & ~(ITX_BED_ALL | ITX_BED_UNIQ))) {
+        itx_set_error("itx_bed_create: bad argument");
+        return ITX_E_ARG;
+    }
+    *out = nullptr;
+    itx_bed *b = new itx_bed();
+    const int rc = bed_create(b, device, chrom_size, n_chrom, p, want, batch_capacity);
+    if (rc) {
+        itx_bed_destroy(b);
+        return rc;
+    }
+    *out = b;
+    return ITX_OK;
+}
+
 /* the BAM header in use: tid2chrom as for itx_engine_set_tidmap, tid2name[t] the reference name after the -C rule (NULL: dropped) */
 extern "C" int itx_bed_set_tidmap(itx_bed *b, const int32_t *tid2chrom, const char *const *tid2name, int n_tid)
 {
@@ -315,7 +242,7 @@ extern "C" int itx_bed_set_tidmap(itx_bed *b, const int32_t *tid2chrom, const ch
         itx_set_error("itx_bed_set_tidmap: a batch has not been collected");
         return ITX_E_STATE;
     }
-    BED_HIP(hipSetDevice(b->device));
+    ITX_HIP(hipSetDevice(b->device));
     std::vector<int2> v((size_t)n_tid + 1);
     std::vector<uint2> nm((size_t)n_tid + 1);
     std::string pool;
@@ -327,19 +254,19 @@ extern "C" int itx_bed_set_tidmap(itx_bed *b, const int32_t *tid2chrom, const ch
         pool.append(s);
     }
     pool.append(16, '\0');
-    BED_HIP(hipStreamSynchronize(b->st));
-    BED_HIP(hipStreamSynchronize(b->st_copy));
+    ITX_HIP(hipStreamSynchronize(b->st));
+    ITX_HIP(hipStreamSynchronize(b->st_copy));
     void **old[3] = {&b->d_tid, &b->d_name, &b->d_pool};
     for (auto pp : old) {
-        if (*pp) BED_HIP(hipFree(*pp));
+        if (*pp) ITX_HIP(hipFree(*pp));
         *pp = nullptr;
     }
-    BED_HIP(hipMalloc(&b->d_tid, sizeof(int2) * v.size()));
-    BED_HIP(hipMalloc(&b->d_name, sizeof(uint2) * nm.size()));
-    BED_HIP(hipMalloc(&b->d_pool, pool.size()));
-    BED_HIP(hipMemcpy(b->d_tid, v.data(), sizeof(int2) * v.size(), hipMemcpyHostToDevice));
-    BED_HIP(hipMemcpy(b->d_name, nm.data(), sizeof(uint2) * nm.size(), hipMemcpyHostToDevice));
-    BED_HIP(hipMemcpy(b->d_pool, pool.data(), pool.size(), hipMemcpyHostToDevice));
+    ITX_HIP(hipMalloc(&b->d_tid, sizeof(int2) * v.size()));
+    ITX_HIP(hipMalloc(&b->d_name, sizeof(uint2) * nm.size()));
+    ITX_HIP(hipMalloc(&b->d_pool, pool.size()));
+    ITX_HIP(hipMemcpy(b->d_tid, v.data(), sizeof(int2) * v.size(), hipMemcpyHostToDevice));
+    ITX_HIP(hipMemcpy(b->d_name, nm.data(), sizeof(uint2) * nm.size(), hipMemcpyHostToDevice));
+    ITX_HIP(hipMemcpy(b->d_pool, pool.data(), pool.size(), hipMemcpyHostToDevice));
     b->d.tid = (const int2 *)b->d_tid;
     b->d.name = (const uint2 *)b->d_name;
     b->d.pool = (const uint8_t *)b->d_pool;
@@ -360,25 +287,25 @@ int itx_bed_start(itx_bed *b, const uint8_t *u, const uint32_t *rec_off, const i
         return ITX_E_STATE;
     }
     *n_hard = 0;
-    BED_HIP(hipSetDevice(b->device));
+    ITX_HIP(hipSetDevice(b->device));
     BedSlot &s = b->slot[b->next];
     s.bytes[0] = s.bytes[1] = 0;
     const BedRecs R = {tid, pos, end, mapq, f5, mpos, isize};
     const uint32_t nt = (uint32_t)((n + BED_TILE - 1) / BED_TILE);
-    BED_HIP(hipEventRecord(s.ev[0], b->st));
+    ITX_HIP(hipEventRecord(s.ev[0], b->st));
     if (n) {
-        BED_HIP(hipMemsetAsync(b->d_tot, 0, 32, b->st));
+        ITX_HIP(hipMemsetAsync(b->d_tot, 0, 32, b->st));
         hipLaunchKernelGGL(k_bed_measure, dim3(nt), dim3(BED_TILE), 0, b->st, b->d, u, rec_off, R, (uint32_t)n, b->f, b->d_tile_sum, b->d_tot);
-        BED_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(1024), 0, b->st, b->d_tile_sum, nt, b->d_tile_base, b->d_tot);
-        BED_HIP(hipGetLastError());
+        ITX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, b->st, b->d_tile_sum, nt, b->d_tile_base, b->d_tot);
+        ITX_HIP(hipGetLastError());
     }
-    BED_HIP(hipEventRecord(s.ev[1], b->st));
+    ITX_HIP(hipEventRecord(s.ev[1], b->st));
     if (n) {
-        const double t0 = bed_now();
-        BED_HIP(hipMemcpyAsync(b->h_tot, b->d_tot, 32, hipMemcpyDeviceToHost, b->st));
-        BED_HIP(hipStreamSynchronize(b->st));
-        b->stats.wait_s += bed_now() - t0;
+        const double t0 = itx_wall_now();
+        ITX_HIP(hipMemcpyAsync(b->h_tot, b->d_tot, 32, hipMemcpyDeviceToHost, b->st));
+        ITX_HIP(hipStreamSynchronize(b->st));
+        b->stats.wait_s += itx_wall_now() - t0;
         if (b->h_tot[2]) {                                                 // the host has to look: nothing of this batch is emitted
             *n_hard = b->h_tot[2];
             b->stats.hard_batches++;
@@ -389,7 +316,7 @@ int itx_bed_start(itx_bed *b, const uint8_t *u, const uint32_t *rec_off, const i
             s.bytes[k] = need;
             if (need > s.dcap[k]) {
                 const size_t want = (size_t)(need + need / 4 + 4096);
-                if (s.d_out[k]) BED_HIP(hipFree(s.d_out[k]));
+                if (s.d_out[k]) ITX_HIP(hipFree(s.d_out[k]));
                 s.d_out[k] = nullptr;
                 s.dcap[k] = 0;
                 if (hipMalloc((void **)&s.d_out[k], want) != hipSuccess) {
@@ -400,7 +327,7 @@ int itx_bed_start(itx_bed *b, const uint8_t *u, const uint32_t *rec_off, const i
             }
             if (need > s.hcap[k]) {
                 const size_t want = (size_t)(need + need / 4 + 4096);
-                if (s.h_out[k]) BED_HIP(hipHostFree(s.h_out[k]));
+                if (s.h_out[k]) ITX_HIP(hipHostFree(s.h_out[k]));
                 s.h_out[k] = nullptr;
                 s.hcap[k] = 0;
                 if (hipHostMalloc((void **)&s.h_out[k], want, hipHostMallocDefault) != hipSuccess) {
@@ -411,20 +338,20 @@ int itx_bed_start(itx_bed *b, const uint8_t *u, const uint32_t *rec_off, const i
             }
         }
     }
-    BED_HIP(hipEventRecord(s.ev[2], b->st));
+    ITX_HIP(hipEventRecord(s.ev[2], b->st));
     if (s.bytes[0]) {
         hipLaunchKernelGGL(k_bed_write<true>, dim3(nt), dim3(BED_TILE), 0, b->st, b->d, u, rec_off, R, (uint32_t)n, b->f, b->d_tile_base, s.d_out[0]);
-        BED_HIP(hipGetLastError());
+        ITX_HIP(hipGetLastError());
     }
     if (s.bytes[1]) {
         hipLaunchKernelGGL(k_bed_write<false>, dim3(nt), dim3(BED_TILE), 0, b->st, b->d, u, rec_off, R, (uint32_t)n, b->f, b->d_tile_base, s.d_out[1]);
-        BED_HIP(hipGetLastError());
+        ITX_HIP(hipGetLastError());
     }
-    BED_HIP(hipEventRecord(s.ev[3], b->st));
-    BED_HIP(hipStreamWaitEvent(b->st_copy, s.ev[3], 0));
+    ITX_HIP(hipEventRecord(s.ev[3], b->st));
+    ITX_HIP(hipStreamWaitEvent(b->st_copy, s.ev[3], 0));
     for (int k = 0; k < 2; k++)
-        if (s.bytes[k]) BED_HIP(hipMemcpyAsync(s.h_out[k], s.d_out[k], s.bytes[k], hipMemcpyDeviceToHost, b->st_copy));
-    BED_HIP(hipEventRecord(s.ev[4], b->st_copy));
+        if (s.bytes[k]) ITX_HIP(hipMemcpyAsync(s.h_out[k], s.d_out[k], s.bytes[k], hipMemcpyDeviceToHost, b->st_copy));
+    ITX_HIP(hipEventRecord(s.ev[4], b->st_copy));
     s.started = 1;
     b->next ^= 1;
     b->in_flight++;
@@ -447,10 +374,10 @@ extern "C" int itx_bed_wait_kernels(itx_bed *b)
         itx_set_error("itx_bed_wait_kernels: bad argument");
         return ITX_E_ARG;
     }
-    BED_HIP(hipSetDevice(b->device));
-    const double t0 = bed_now();
-    BED_HIP(hipStreamSynchronize(b->st));
-    b->stats.wait_s += bed_now() - t0;
+    ITX_HIP(hipSetDevice(b->device));
+    const double t0 = itx_wall_now();
+    ITX_HIP(hipStreamSynchronize(b->st));
+    b->stats.wait_s += itx_wall_now() - t0;
     return ITX_OK;
 }
 
@@ -464,14 +391,14 @@ extern "C" int itx_bed_collect(itx_bed *b, itx_bed_text *out)
         itx_set_error("itx_bed_collect: no batch has been started");
         return ITX_E_STATE;
     }
-    BED_HIP(hipSetDevice(b->device));
+    ITX_HIP(hipSetDevice(b->device));
     BedSlot &s = b->slot[(b->next + 2 - b->in_flight) & 1];
-    const double t0 = bed_now();
-    BED_HIP(hipEventSynchronize(s.ev[4]));
-    b->stats.wait_s += bed_now() - t0;
+    const double t0 = itx_wall_now();
+    ITX_HIP(hipEventSynchronize(s.ev[4]));
+    b->stats.wait_s += itx_wall_now() - t0;
     float ma = 0, mw = 0;
-    BED_HIP(hipEventElapsedTime(&ma, s.ev[0], s.ev[1]));
-    BED_HIP(hipEventElapsedTime(&mw, s.ev[2], s.ev[3]));
+    ITX_HIP(hipEventElapsedTime(&ma, s.ev[0], s.ev[1]));
+    ITX_HIP(hipEventElapsedTime(&mw, s.ev[2], s.ev[3]));
     b->stats.kernel_ms += (double)ma + (double)mw;
     b->stats.batches++;
     b->stats.bytes += s.bytes[0] + s.bytes[1];

@@ -10,7 +10,7 @@
 //                multiples of each other): f = overlap / item size is exactly 1.0 everywhere.
 //   zoom blocks  1024 summaries of 32 bytes, one wave per block, deflated like the sections
 // Then the compressed blocks are packed one after the other, and the host copies back only them and the summaries.
-#include "itx_common.h"
+#include "itx_device.h"
 
 #include <cstring>
 #include <vector>
@@ -178,31 +178,20 @@ __global__ void k_bw_levelk(BwDev d, uint32_t k)
     d.sum[k][i] = itx_bw_summary{c, start, end, vc, mn, mx, sd, sq};
 }
 
-// exclusive prefix sum of the compressed sizes: poff[0..n] (one workgroup)
-__global__ __launch_bounds__(1024) void k_bw_scan(const uint32_t *csize, uint64_t n, uint64_t *poff)
+// exclusive prefix sum of the compressed sizes: poff[0..n] (one workgroup, itx_device.h)
+__global__ __launch_bounds__(ITX_SCAN_WG) void k_bw_scan(const uint32_t *csize, uint64_t n, uint64_t *poff)
 {
-    __shared__ uint64_t part[1024];
-    const uint32_t t = threadIdx.x;
-    const uint64_t per = (n + 1023) / 1024, a = t * per < n ? t * per : n, b = a + per < n ? a + per : n;
-    uint64_t s = 0;
-    for (uint64_t i = a; i < b; i++) s += csize[i];
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        uint64_t run = 0;
-        for (int j = 0; j < 1024; j++) {
-            const uint64_t v = part[j];
-            part[j] = run;
-            run += v;
-        }
-        poff[n] = run;
+    __shared__ uint64_t s[ITX_SCAN_WG];
+    uint64_t lo, hi;
+    itx_scan_chunk(n, &lo, &hi);
+    uint64_t a = 0, total;
+    for (uint64_t i = lo; i < hi; i++) a += csize[i];
+    uint64_t e = itx_scan_wg(a, s, &total);
+    for (uint64_t i = lo; i < hi; i++) {
+        poff[i] = e;
+        e += csize[i];
     }
-    __syncthreads();
-    s = part[t];
-    for (uint64_t i = a; i < b; i++) {
-        poff[i] = s;
-        s += csize[i];
-    }
+    if (threadIdx.x == 0) poff[n] = total;
 }
 
 __global__ __launch_bounds__(256) void k_bw_gather(const uint8_t *out, const uint64_t *out_off, const uint32_t *csize, const uint64_t *poff,
@@ -353,7 +342,7 @@ static int bw_start(itx_bigwig *b, itx_engine *e, int uniq, const uint64_t *cov_
     }
     if (b->n_blocks > b->n_sec) k_bw_zoom<<<dim3((uint32_t)(b->n_blocks - b->n_sec)), dim3(64), 0, b->st>>>(d);
     if (b->n_blocks) {
-        k_bw_scan<<<dim3(1), dim3(1024), 0, b->st>>>(b->d_csize, b->n_blocks, b->d_poff);
+        k_bw_scan<<<dim3(1), dim3(ITX_SCAN_WG), 0, b->st>>>(b->d_csize, b->n_blocks, b->d_poff);
         k_bw_gather<<<dim3((uint32_t)b->n_blocks), dim3(256), 0, b->st>>>(b->d_out, b->d_out_off, b->d_csize, b->d_poff, b->d_packed);
     }
     ITX_HIP(hipGetLastError());

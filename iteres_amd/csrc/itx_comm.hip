@@ -40,14 +40,6 @@ struct itx_comm {
     uint64_t *d_meta;
 };
 
-#define COMM_HIP(call)                                                                                    \
-    do {                                                                                                  \
-        hipError_t err__ = (call);                                                                        \
-        if (err__ != hipSuccess) {                                                                        \
-            itx_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
-            return ITX_E_NO_DEVICE;                                                                       \
-        }                                                                                                 \
-    } while (0)
 #define COMM_NCCL(c, call)                                                                                \
     do {                                                                                                  \
         ncclResult_t r__ = (call);                                                                        \
@@ -57,21 +49,14 @@ struct itx_comm {
         }                                                                                                 \
     } while (0)
 
-static double now_s()
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
 // waits until `path` exists (written under another name and renamed, so it is complete when it appears)
 static int wait_for(const itx_comm *c, const std::string &path)
 {
-    const double t0 = now_s();
+    const double t0 = itx_wall_now();
     struct stat sb;
     unsigned spins = 0;
     while (stat(path.c_str(), &sb) != 0) {
-        if (now_s() - t0 > c->timeout_s) {
+        if (itx_wall_now() - t0 > c->timeout_s) {
             itx_set_error("rank %d: gave up waiting for %s after %.0f s (a rank of the job has died?)", c->rank, path.c_str(), c->timeout_s);
             return ITX_E_STATE;
         }
@@ -217,31 +202,31 @@ extern "C" int itx_comm_reduce_sum(itx_comm *c, void *d_u64, size_t n64, void *d
         itx_set_error("itx_comm_reduce_sum: bad argument");
         return ITX_E_ARG;
     }
-    COMM_HIP(hipSetDevice(c->device));
+    ITX_HIP(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     if (c->world == 1 && !c->comm) {
-        COMM_HIP(hipStreamSynchronize(st));
+        ITX_HIP(hipStreamSynchronize(st));
         return ITX_OK;
     }
     if (c->mode == ITX_COMM_RCCL) {
         if (n_meta) {
-            if (!c->d_meta) COMM_HIP(hipMalloc((void **)&c->d_meta, sizeof(uint64_t) * 64));
+            if (!c->d_meta) ITX_HIP(hipMalloc((void **)&c->d_meta, sizeof(uint64_t) * 64));
             if (n_meta > 64) return ITX_E_ARG;
-            COMM_HIP(hipMemcpyAsync(c->d_meta, meta, sizeof(uint64_t) * n_meta, hipMemcpyHostToDevice, st));
+            ITX_HIP(hipMemcpyAsync(c->d_meta, meta, sizeof(uint64_t) * n_meta, hipMemcpyHostToDevice, st));
         }
         if (n64) COMM_NCCL(c, c->p_reduce(d_u64, d_u64, n64, ncclUint64, ncclSum, 0, c->comm, st));
         if (n32) COMM_NCCL(c, c->p_reduce(d_u32, d_u32, n32, ncclUint32, ncclSum, 0, c->comm, st));
         if (n_meta) COMM_NCCL(c, c->p_reduce(c->d_meta, c->d_meta, n_meta, ncclUint64, ncclSum, 0, c->comm, st));
-        if (n_meta && c->rank == 0) COMM_HIP(hipMemcpyAsync(meta, c->d_meta, sizeof(uint64_t) * n_meta, hipMemcpyDeviceToHost, st));
-        COMM_HIP(hipStreamSynchronize(st));
+        if (n_meta && c->rank == 0) ITX_HIP(hipMemcpyAsync(meta, c->d_meta, sizeof(uint64_t) * n_meta, hipMemcpyDeviceToHost, st));
+        ITX_HIP(hipStreamSynchronize(st));
         return ITX_OK;
     }
     // ---- through files
-    COMM_HIP(hipStreamSynchronize(st));
+    ITX_HIP(hipStreamSynchronize(st));
     std::vector<uint64_t> h64(n64 + 1);
     std::vector<uint32_t> h32(n32 + 1);
-    if (n64) COMM_HIP(hipMemcpy(h64.data(), d_u64, sizeof(uint64_t) * n64, hipMemcpyDeviceToHost));
-    if (n32) COMM_HIP(hipMemcpy(h32.data(), d_u32, sizeof(uint32_t) * n32, hipMemcpyDeviceToHost));
+    if (n64) ITX_HIP(hipMemcpy(h64.data(), d_u64, sizeof(uint64_t) * n64, hipMemcpyDeviceToHost));
+    if (n32) ITX_HIP(hipMemcpy(h32.data(), d_u32, sizeof(uint32_t) * n32, hipMemcpyDeviceToHost));
     if (c->rank != 0) {
         int rc = write_whole(c->id_path + ".part" + std::to_string(c->rank), h64.data(), sizeof(uint64_t) * n64, h32.data(), sizeof(uint32_t) * n32, meta,
                              sizeof(uint64_t) * n_meta);
@@ -268,7 +253,7 @@ extern "C" int itx_comm_reduce_sum(itx_comm *c, void *d_u64, size_t n64, void *d
         for (size_t i = 0; i < n32; i++) h32[i] += p32[i];
         for (size_t i = 0; i < n_meta; i++) meta[i] += pm[i];
     }
-    if (n64) COMM_HIP(hipMemcpy(d_u64, h64.data(), sizeof(uint64_t) * n64, hipMemcpyHostToDevice));
-    if (n32) COMM_HIP(hipMemcpy(d_u32, h32.data(), sizeof(uint32_t) * n32, hipMemcpyHostToDevice));
+    if (n64) ITX_HIP(hipMemcpy(d_u64, h64.data(), sizeof(uint64_t) * n64, hipMemcpyHostToDevice));
+    if (n32) ITX_HIP(hipMemcpy(d_u32, h32.data(), sizeof(uint32_t) * n32, hipMemcpyHostToDevice));
     return ITX_OK;
 }

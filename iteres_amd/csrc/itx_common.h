@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <time.h>
 
 #include "../../include/iteres_amd.h"
 
@@ -107,6 +108,13 @@ int itxe_cov_device(itx_engine *e, int uniq, const uint32_t **cov, uint64_t *cov
             return ITX_E_NO_DEVICE;                                                           \
         }                                                                                     \
     } while (0)
+// the host's monotonic clock in seconds (time spent waiting for the device, allocation times)
+static inline double itx_wall_now(void)
+{
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
 
 // Per-record parameters handed to the kernels.
 struct ItxRunParams {

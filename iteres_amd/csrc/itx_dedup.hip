@@ -32,14 +32,6 @@
 #include <string.h>
 #include <vector>
 
-#define DD_HIP(call)                                                                                     \
-    do {                                                                                                  \
-        hipError_t err__ = (call);                                                                        \
-        if (err__ != hipSuccess) {                                                                        \
-            itx_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
-            return ITX_E_NO_DEVICE;                                                                       \
-        }                                                                                                 \
-    } while (0)
 
 #define DD_EMPTY 0xffffffffffffffffull
 #define DD_NOIDX 0xffffffffu
@@ -263,13 +255,13 @@ struct itx_dedup {
 static int dd_alloc(DdTable *T, size_t cap, hipStream_t st)
 {
     memset(T, 0, sizeof *T);
-    DD_HIP(hipMalloc((void **)&T->h, cap * 8));
-    DD_HIP(hipMalloc((void **)&T->idx, cap * 4));
-    DD_HIP(hipMalloc((void **)&T->ka, cap * 8));
-    DD_HIP(hipMalloc((void **)&T->kb, cap * 4));
+    ITX_HIP(hipMalloc((void **)&T->h, cap * 8));
+    ITX_HIP(hipMalloc((void **)&T->idx, cap * 4));
+    ITX_HIP(hipMalloc((void **)&T->ka, cap * 8));
+    ITX_HIP(hipMalloc((void **)&T->kb, cap * 4));
     T->mask = (uint32_t)(cap - 1);
     hipLaunchKernelGGL(k_dd_clear, dim3(4096), dim3(256), 0, st, *T, (uint32_t)cap);
-    DD_HIP(hipGetLastError());
+    ITX_HIP(hipGetLastError());
     return ITX_OK;
 }
 static void dd_free(DdTable *T)
@@ -286,7 +278,7 @@ extern "C" int itx_dedup_create(int device, const int64_t *chrom_size, int n_chr
 {
     if (!out || !p || n_chrom < 0 || (n_chrom && !chrom_size)) return ITX_E_ARG;
     *out = nullptr;
-    DD_HIP(hipSetDevice(device));
+    ITX_HIP(hipSetDevice(device));
     itx_dedup *d = new itx_dedup();
     d->device = device;
     d->n_chrom = n_chrom;
@@ -304,19 +296,19 @@ extern "C" int itx_dedup_create(int device, const int64_t *chrom_size, int n_chr
     d->d_tid = d->d_tid_name = nullptr;
     d->base = 0;
     d->n_over_seen = 0;
-    DD_HIP(hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking));
+    ITX_HIP(hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking));
     size_t cap = 1u << 16;
     while (cap < first_cells && cap < ((size_t)1 << 31)) cap <<= 1;
     d->cap = cap;
     int rc = dd_alloc(&d->t, cap, d->st);
     if (rc != ITX_OK) return rc;
-    DD_HIP(hipMalloc((void **)&d->d_state, sizeof(DdState)));
-    DD_HIP(hipMalloc((void **)&d->d_over, sizeof(DdOver) * DD_OVER_CAP));
+    ITX_HIP(hipMalloc((void **)&d->d_state, sizeof(DdState)));
+    ITX_HIP(hipMalloc((void **)&d->d_over, sizeof(DdOver) * DD_OVER_CAP));
     DdState s0;
     memset(&s0, 0, sizeof s0);
     s0.first_ok = DD_NOIDX;
-    DD_HIP(hipMemcpyAsync(d->d_state, &s0, sizeof s0, hipMemcpyHostToDevice, d->st));
-    DD_HIP(hipStreamSynchronize(d->st));
+    ITX_HIP(hipMemcpyAsync(d->d_state, &s0, sizeof s0, hipMemcpyHostToDevice, d->st));
+    ITX_HIP(hipStreamSynchronize(d->st));
     *out = d;
     return ITX_OK;
 }
@@ -342,7 +334,7 @@ extern "C" void itx_dedup_destroy(itx_dedup *d)
 extern "C" int itx_dedup_set_tidmap(itx_dedup *d, const int32_t *tid2chrom, const uint32_t *tid2name, int n_tid)
 {
     if (!d || n_tid < 0 || (n_tid && (!tid2chrom || !tid2name))) return ITX_E_ARG;
-    DD_HIP(hipSetDevice(d->device));
+    ITX_HIP(hipSetDevice(d->device));
     std::vector<int2> v((size_t)n_tid + 1);
     std::vector<uint32_t> nm((size_t)n_tid + 1);
     for (int k = 0; k < n_tid; k++) {
@@ -354,14 +346,14 @@ extern "C" int itx_dedup_set_tidmap(itx_dedup *d, const int32_t *tid2chrom, cons
         }
         nm[(size_t)k] = tid2name[k];
     }
-    DD_HIP(hipStreamSynchronize(d->st));
+    ITX_HIP(hipStreamSynchronize(d->st));
     (void)hipFree(d->d_tid);
     (void)hipFree(d->d_tid_name);
     d->d_tid = d->d_tid_name = nullptr;
-    DD_HIP(hipMalloc(&d->d_tid, sizeof(int2) * ((size_t)n_tid + 1)));
-    DD_HIP(hipMalloc(&d->d_tid_name, 4 * ((size_t)n_tid + 1)));
-    DD_HIP(hipMemcpy(d->d_tid, v.data(), sizeof(int2) * ((size_t)n_tid + 1), hipMemcpyHostToDevice));
-    DD_HIP(hipMemcpy(d->d_tid_name, nm.data(), 4 * ((size_t)n_tid + 1), hipMemcpyHostToDevice));
+    ITX_HIP(hipMalloc(&d->d_tid, sizeof(int2) * ((size_t)n_tid + 1)));
+    ITX_HIP(hipMalloc(&d->d_tid_name, 4 * ((size_t)n_tid + 1)));
+    ITX_HIP(hipMemcpy(d->d_tid, v.data(), sizeof(int2) * ((size_t)n_tid + 1), hipMemcpyHostToDevice));
+    ITX_HIP(hipMemcpy(d->d_tid_name, nm.data(), 4 * ((size_t)n_tid + 1), hipMemcpyHostToDevice));
     d->p.tid = (const int2 *)d->d_tid;
     d->p.tid_name = (const uint32_t *)d->d_tid_name;
     d->p.n_tid = n_tid;
@@ -383,10 +375,10 @@ extern "C" int itx_dedup_run(itx_dedup *d, const int32_t *tid, const int32_t *po
         itx_set_error("itx_dedup_run: more than 2^32 records");
         return ITX_E_LIMIT;
     }
-    DD_HIP(hipSetDevice(d->device));
+    ITX_HIP(hipSetDevice(d->device));
     DdState s;
-    DD_HIP(hipMemcpyAsync(&s, d->d_state, sizeof s, hipMemcpyDeviceToHost, d->st));
-    DD_HIP(hipStreamSynchronize(d->st));
+    ITX_HIP(hipMemcpyAsync(&s, d->d_state, sizeof s, hipMemcpyDeviceToHost, d->st));
+    ITX_HIP(hipStreamSynchronize(d->st));
     // room for every record of the window to bring a new key, at a load factor below 0.7
     if (((size_t)s.n_cells + n) * 10 > d->cap * 7) {
         size_t ncap = d->cap;
@@ -399,8 +391,8 @@ extern "C" int itx_dedup_run(itx_dedup *d, const int32_t *tid, const int32_t *po
         int rc = dd_alloc(&nt, ncap, d->st);
         if (rc != ITX_OK) return rc;
         hipLaunchKernelGGL(k_dd_rehash, dim3(4096), dim3(256), 0, d->st, d->t, (uint32_t)d->cap, nt);
-        DD_HIP(hipGetLastError());
-        DD_HIP(hipStreamSynchronize(d->st));
+        ITX_HIP(hipGetLastError());
+        ITX_HIP(hipStreamSynchronize(d->st));
         dd_free(&d->t);
         d->t = nt;
         d->cap = ncap;
@@ -410,17 +402,17 @@ extern "C" int itx_dedup_run(itx_dedup *d, const int32_t *tid, const int32_t *po
     hipLaunchKernelGGL(k_dd_claim, grid, blk, 0, d->st, d->p, d->t, d->d_state, (const uint8_t *)flag5, tid, pos, tmpend, mapq, mpos, isize, (uint32_t)n, base);
     hipLaunchKernelGGL(k_dd_owner, grid, blk, 0, d->st, d->p, d->t, (const uint8_t *)flag5, tid, pos, tmpend, mapq, mpos, isize, (uint32_t)n, base);
     hipLaunchKernelGGL(k_dd_verdict, grid, blk, 0, d->st, d->p, d->t, d->d_state, d->d_over, flag5, tid, pos, tmpend, mapq, mpos, isize, (uint32_t)n, base);
-    DD_HIP(hipGetLastError());
-    DD_HIP(hipMemcpyAsync(&s, d->d_state, sizeof s, hipMemcpyDeviceToHost, d->st));
-    DD_HIP(hipStreamSynchronize(d->st));
+    ITX_HIP(hipGetLastError());
+    ITX_HIP(hipMemcpyAsync(&s, d->d_state, sizeof s, hipMemcpyDeviceToHost, d->st));
+    ITX_HIP(hipStreamSynchronize(d->st));
     if (s.n_over > DD_OVER_CAP) {
         itx_set_error("itx_dedup_run: more than %u keys share a 64-bit hash with another key", DD_OVER_CAP);
         return ITX_E_LIMIT;
     }
     if (s.n_over > d->n_over_seen) {
         hipLaunchKernelGGL(k_dd_overflow, dim3(1), blk, 0, d->st, d->d_state, (const DdOver *)d->d_over, d->n_over_seen, s.n_over, flag5, base);
-        DD_HIP(hipGetLastError());
-        DD_HIP(hipStreamSynchronize(d->st));
+        ITX_HIP(hipGetLastError());
+        ITX_HIP(hipStreamSynchronize(d->st));
         d->n_over_seen = s.n_over;
     }
     d->base += n;
@@ -431,9 +423,9 @@ extern "C" int itx_dedup_run(itx_dedup *d, const int32_t *tid, const int32_t *po
 extern "C" int itx_dedup_counts(itx_dedup *d, uint64_t *dup_unique, uint64_t *dropped, uint64_t *keys)
 {
     if (!d) return ITX_E_ARG;
-    DD_HIP(hipSetDevice(d->device));
+    ITX_HIP(hipSetDevice(d->device));
     DdState s;
-    DD_HIP(hipMemcpy(&s, d->d_state, sizeof s, hipMemcpyDeviceToHost));
+    ITX_HIP(hipMemcpy(&s, d->d_state, sizeof s, hipMemcpyDeviceToHost));
     if (dup_unique) *dup_unique = s.dup_unique;
     if (dropped) *dropped = s.dropped;
     if (keys) *keys = (uint64_t)s.n_cells + s.n_over;

@@ -181,6 +181,45 @@ __device__ __forceinline__ int32_t wave_max_i32(int32_t v)
     return __builtin_amdgcn_readlane(v, 63);
 }
 
+// Inclusive prefix sum of v over the 64 lanes of a wave (every lane must call). The add is a select, not a branch: the form
+// the BGZF decoder (itx_inflate_core.h, through its ITXI_SCAN_ADD hook) was measured with.
+__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, uint32_t lane)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = (uint32_t)__shfl_up((int32_t)v, o, 64);
+        v += lane >= (uint32_t)o ? t : 0u;
+    }
+    return v;
+}
+
+// The exclusive scan of ONE workgroup of ITX_SCAN_WG threads over n items, for the few-thousand-entry arrays that sit between
+// two grids (tile sums, digit counts, block sizes). A kernel over it is three steps: itx_scan_chunk gives the thread its
+// contiguous chunk [lo, hi) of the items (64-bit bounds; the last chunk is ragged and the threads past it are empty), the
+// thread adds its chunk up, itx_scan_wg turns the 1024 chunk sums into the thread's exclusive prefix and the grand total
+// (every thread calls it; s is the workgroup's LDS, one array per call), and the thread walks its chunk again from the prefix.
+#define ITX_SCAN_WG 1024u
+__device__ __forceinline__ void itx_scan_chunk(uint64_t n, uint64_t *lo, uint64_t *hi)
+{
+    const uint64_t per = (n + ITX_SCAN_WG - 1) / ITX_SCAN_WG, a = threadIdx.x * per;
+    *lo = a < n ? a : n;
+    *hi = *lo + per < n ? *lo + per : n;
+}
+template <class T>
+__device__ __forceinline__ T itx_scan_wg(T sum, T *s, T *total)
+{
+    s[threadIdx.x] = sum;
+    __syncthreads();
+    for (uint32_t d = 1; d < ITX_SCAN_WG; d <<= 1) {
+        const T v = threadIdx.x >= d ? s[threadIdx.x - d] : T(0);
+        __syncthreads();
+        s[threadIdx.x] += v;
+        __syncthreads();
+    }
+    *total = s[ITX_SCAN_WG - 1];
+    return s[threadIdx.x] - sum;
+}
+
 // Runs of equal values over the lanes of a wave (every lane must call). Returns whether this lane starts a
 // run; *len = length of the run starting here; *leader = first lane of the run this lane belongs to.
 __device__ __forceinline__ bool wave_run(uint32_t v, bool has, uint32_t lane, uint32_t *len, uint32_t *leader)

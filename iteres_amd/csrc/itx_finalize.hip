@@ -5,20 +5,9 @@
 //   k_finish_unit   per unit: coverage = prefix sum of D (mod 2^32, like bp_total's unsigned int),
 //                   counts added to the unit's repName / repFamily / repClass
 //   k_permute_locus filter mode: per-locus counts from sorted-row order to the caller's row order
-#include "itx_common.h"
+#include "itx_device.h"
 
 #define FB 256
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(FB) void k_finish_unit(const uint32_t *__restrict__ unit_slot, const uint4 *__restrict__ unit_ids,
                                                     const uint64_t *__restrict__ unit_covoff, const uint64_t *__restrict__ p64,
@@ -57,7 +46,7 @@ __global__ __launch_bounds__(FB) void k_finish_unit(const uint32_t *__restrict__
             da = p32[s0 + j];
             du = p32[(size_t)n_slots + s0 + j];
         }
-        uint32_t pa = wave_incl_scan(da), pu = wave_incl_scan(du);
+        uint32_t pa = wave_incl_scan_u32(da, lane), pu = wave_incl_scan_u32(du, lane);
         if (lane == 63) {
             s_w[0][w] = pa;
             s_w[1][w] = pu;

@@ -6,23 +6,14 @@
 // alignment), the inflated bytes of all blocks are contiguous in d_out at the offsets the caller computed from the ISIZE
 // trailers. A call is cut into groups of blocks that alternate between two streams: copy-in, kernel and copy-out of one
 // group overlap the neighbours'.
-#include "itx_common.h"
+#include "itx_device.h"
 
 #define ITXI_WAVE 64u
 #define ITXI_SIMPLE_IN          /* one word of input look-ahead: 10.96 ms per 24 k blocks against 11.27 with the 16-byte FIFO */
 #define ITXI_FN static __device__ inline
 #define ITXI_UNI(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(x)))
 #define ITXI_BCAST(v, j) ((uint32_t)__builtin_amdgcn_readlane((int32_t)(v), (int32_t)(j)))
-static __device__ inline uint32_t itxi_scan_add(uint32_t v, uint32_t lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int32_t)v, o, 64);
-        v += lane >= (uint32_t)o ? t : 0u;
-    }
-    return v;
-}
-#define ITXI_SCAN_ADD(v, lane) itxi_scan_add(v, lane)
+#define ITXI_SCAN_ADD(v, lane) wave_incl_scan_u32(v, lane)
 #define ITXI_LANE_READ(v, j) ((uint32_t)__builtin_amdgcn_ds_bpermute((int32_t)((j) << 2), (int32_t)(v)))
 #define ITXI_BALLOT(p) ((uint64_t)__ballot(p))
 #define ITXI_MBCNT(m, lane) ((uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)((m) >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)(m), 0u)))
@@ -411,14 +402,6 @@ struct itx_inflater {
     size_t n_rec;
 };
 
-#define INF_HIP(call)                                                                                     \
-    do {                                                                                                  \
-        hipError_t err__ = (call);                                                                        \
-        if (err__ != hipSuccess) {                                                                        \
-            itx_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
-            return ITX_E_NO_DEVICE;                                                                       \
-        }                                                                                                 \
-    } while (0)
 
 extern "C" int itx_inflater_create(int device, itx_inflater **out)
 {
@@ -435,26 +418,26 @@ extern "C" int itx_inflater_create(int device, itx_inflater **out)
         }                                                                                                                     \
     } while (0)
     clock_gettime(CLOCK_MONOTONIC, &tsa);
-    INF_HIP(hipSetDevice(device));
+    ITX_HIP(hipSetDevice(device));
     SETUP_TICK("hipSetDevice");
     itx_inflater *h = (itx_inflater *)calloc(1, sizeof *h);
     if (!h) return ITX_E_NOMEM;
     h->device = device;
-    for (int k = 0; k < 2; k++) INF_HIP(hipStreamCreateWithFlags(&h->st[k], hipStreamNonBlocking));
+    for (int k = 0; k < 2; k++) ITX_HIP(hipStreamCreateWithFlags(&h->st[k], hipStreamNonBlocking));
     SETUP_TICK("first two streams");
-    for (int k = 0; k < 4; k++) INF_HIP(hipEventCreate(&h->ev[k]));
-    for (int k = 0; k < 2; k++) INF_HIP(hipEventCreate(&h->ev_res_end[k]));
+    for (int k = 0; k < 4; k++) ITX_HIP(hipEventCreate(&h->ev[k]));
+    for (int k = 0; k < 2; k++) ITX_HIP(hipEventCreate(&h->ev_res_end[k]));
     for (int k = 0; k < lanes_in_use(); k++) {
-        INF_HIP(hipEventCreateWithFlags(&h->lane[k].copied, hipEventDisableTiming));
-        for (int q = 0; q < 3; q++) INF_HIP(hipEventCreate(&h->lane[k].ev[q]));
-        INF_HIP(hipEventCreateWithFlags(&h->lane[k].p1_done, hipEventDisableTiming));
-        INF_HIP(hipEventCreateWithFlags(&h->lane[k].done, hipEventDisableTiming));
+        ITX_HIP(hipEventCreateWithFlags(&h->lane[k].copied, hipEventDisableTiming));
+        for (int q = 0; q < 3; q++) ITX_HIP(hipEventCreate(&h->lane[k].ev[q]));
+        ITX_HIP(hipEventCreateWithFlags(&h->lane[k].p1_done, hipEventDisableTiming));
+        ITX_HIP(hipEventCreateWithFlags(&h->lane[k].done, hipEventDisableTiming));
     }
     // ONE stream carries every push's bytes across PCIe, in push order (the link is one: copies side by side only finish later,
     // all of them); a stream per slot also meant more streams than hardware queues, and streams that share a queue run one
     // after the other — two compute lanes on one queue halved pass 1's overlap (1.8 kernels in flight instead of 3)
-    INF_HIP(hipStreamCreateWithFlags(&h->copy_st, hipStreamNonBlocking));
-    for (int k = 0; k < compute_lanes(); k++) INF_HIP(hipStreamCreateWithFlags(&h->clane[k].cst, hipStreamNonBlocking));
+    ITX_HIP(hipStreamCreateWithFlags(&h->copy_st, hipStreamNonBlocking));
+    for (int k = 0; k < compute_lanes(); k++) ITX_HIP(hipStreamCreateWithFlags(&h->clane[k].cst, hipStreamNonBlocking));
     SETUP_TICK("lane streams, events, counters");
     h->n_cu = 256;
     if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->n_cu <= 0) h->n_cu = 256;
@@ -466,8 +449,8 @@ extern "C" int itx_inflater_create(int device, itx_inflater **out)
         }
     }
     hipLaunchKernelGGL(k_warm, dim3(1), dim3(1), 0, h->st[0], (uint32_t *)nullptr);
-    INF_HIP(hipGetLastError());
-    INF_HIP(hipStreamSynchronize(h->st[0]));
+    ITX_HIP(hipGetLastError());
+    ITX_HIP(hipStreamSynchronize(h->st[0]));
     SETUP_TICK("first kernel (code object load)");
 #undef SETUP_TICK
     *out = h;
@@ -628,7 +611,7 @@ extern "C" int itx_backlog_create(int device, size_t max_records, itx_backlog **
 {
     if (!out || max_records == 0 || max_records >= ((size_t)1 << 31)) return ITX_E_ARG;
     *out = nullptr;
-    INF_HIP(hipSetDevice(device));
+    ITX_HIP(hipSetDevice(device));
     itx_backlog *b = (itx_backlog *)calloc(1, sizeof *b);
     if (!b) return ITX_E_NOMEM;
     b->device = device;
@@ -668,23 +651,23 @@ extern "C" int itx_backlog_append(itx_backlog *b, const itx_batch *src, size_t n
 {
     if (!b || !src || !at || !src->tid || !src->pos || !src->tmpend || !src->mapq || !src->flag5) return ITX_E_ARG;
     if (n > b->cap - b->used) return ITX_E_LIMIT;
-    INF_HIP(hipSetDevice(b->device));
+    ITX_HIP(hipSetDevice(b->device));
     const size_t o = b->used;
     if (src->mpos && src->isize && !b->mpos) {
         const size_t m = b->cap + 64;
-        INF_HIP(hipMalloc((void **)&b->mpos, m * 4));
-        INF_HIP(hipMalloc((void **)&b->isize, m * 4));
+        ITX_HIP(hipMalloc((void **)&b->mpos, m * 4));
+        ITX_HIP(hipMalloc((void **)&b->isize, m * 4));
     }
-    INF_HIP(hipMemcpyAsync(b->tid + o, src->tid, n * 4, hipMemcpyDeviceToDevice, b->st));
-    INF_HIP(hipMemcpyAsync(b->pos + o, src->pos, n * 4, hipMemcpyDeviceToDevice, b->st));
-    INF_HIP(hipMemcpyAsync(b->end + o, src->tmpend, n * 4, hipMemcpyDeviceToDevice, b->st));
-    INF_HIP(hipMemcpyAsync(b->mapq + o, src->mapq, n, hipMemcpyDeviceToDevice, b->st));
-    INF_HIP(hipMemcpyAsync(b->f5 + o, src->flag5, n, hipMemcpyDeviceToDevice, b->st));
+    ITX_HIP(hipMemcpyAsync(b->tid + o, src->tid, n * 4, hipMemcpyDeviceToDevice, b->st));
+    ITX_HIP(hipMemcpyAsync(b->pos + o, src->pos, n * 4, hipMemcpyDeviceToDevice, b->st));
+    ITX_HIP(hipMemcpyAsync(b->end + o, src->tmpend, n * 4, hipMemcpyDeviceToDevice, b->st));
+    ITX_HIP(hipMemcpyAsync(b->mapq + o, src->mapq, n, hipMemcpyDeviceToDevice, b->st));
+    ITX_HIP(hipMemcpyAsync(b->f5 + o, src->flag5, n, hipMemcpyDeviceToDevice, b->st));
     if (src->mpos && src->isize) {
-        INF_HIP(hipMemcpyAsync(b->mpos + o, src->mpos, n * 4, hipMemcpyDeviceToDevice, b->st));
-        INF_HIP(hipMemcpyAsync(b->isize + o, src->isize, n * 4, hipMemcpyDeviceToDevice, b->st));
+        ITX_HIP(hipMemcpyAsync(b->mpos + o, src->mpos, n * 4, hipMemcpyDeviceToDevice, b->st));
+        ITX_HIP(hipMemcpyAsync(b->isize + o, src->isize, n * 4, hipMemcpyDeviceToDevice, b->st));
     }
-    INF_HIP(hipStreamSynchronize(b->st));
+    ITX_HIP(hipStreamSynchronize(b->st));
     *at = o;
     b->used = (o + n + 15) & ~(size_t)15;
     return ITX_OK;
@@ -707,12 +690,6 @@ extern "C" int itx_backlog_batch(const itx_backlog *b, size_t at, int with_mates
 // ITX_TIMING: where the decoder's device-side time goes (printed when the process ends)
 static double g_alloc_s, g_tok_ms, g_res_ms;
 static unsigned long g_allocs, g_pushes;
-static double wall_now()
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
 static bool g_reported;
 static void report_at_exit()
 {
@@ -727,22 +704,22 @@ extern "C" void itx_timing_report(void) { report_at_exit(); }
 template <typename T> static int grow(T **p, size_t *cap, size_t need, bool exact = false)
 {
     if (need <= *cap) return ITX_OK;
-    const double t_alloc0 = wall_now();
+    const double t_alloc0 = itx_wall_now();
     struct Acc {
         double t0;
         ~Acc()
         {
-            g_alloc_s += wall_now() - t0;
+            g_alloc_s += itx_wall_now() - t0;
             g_allocs++;
         }
     } acc{t_alloc0};
-    if (*p) INF_HIP(hipFree(*p));
+    if (*p) ITX_HIP(hipFree(*p));
     *p = nullptr;
     *cap = 0;
     const size_t want = exact ? need : need + need / 4;
-    const double tm0 = wall_now();
-    INF_HIP(hipMalloc((void **)p, want * sizeof(T)));
-    if (getenv("ITX_TIMING_ALLOC")) fprintf(stderr, "[itx alloc] hipMalloc %.1f MB: %.2f ms\n", (double)(want * sizeof(T)) / 1e6, 1e3 * (wall_now() - tm0));
+    const double tm0 = itx_wall_now();
+    ITX_HIP(hipMalloc((void **)p, want * sizeof(T)));
+    if (getenv("ITX_TIMING_ALLOC")) fprintf(stderr, "[itx alloc] hipMalloc %.1f MB: %.2f ms\n", (double)(want * sizeof(T)) / 1e6, 1e3 * (itx_wall_now() - tm0));
     *cap = want;
     return ITX_OK;
 }
@@ -764,7 +741,7 @@ extern "C" int itx_inflate_bgzf(itx_inflater *h, const void *comp, size_t comp_l
         }
         uat += b.usize;
     }
-    INF_HIP(hipSetDevice(h->device));
+    ITX_HIP(hipSetDevice(h->device));
     int rc;
     if ((rc = grow(&h->d_comp, &h->comp_cap, comp_len + 64)) != ITX_OK) return rc;
     if ((rc = grow(&h->d_out, &h->out_cap, out_len + 64)) != ITX_OK) return rc;
@@ -773,31 +750,31 @@ extern "C" int itx_inflate_bgzf(itx_inflater *h, const void *comp, size_t comp_l
     if ((rc = grow(&h->d_lit, &h->lit_cap, n_blk * (size_t)SCR_STRIDE)) != ITX_OK) return rc;
     if ((rc = grow(&h->d_meta, &h->meta_cap, 3 * n_blk)) != ITX_OK) return rc;
     // pass 1 over all blocks at once (a lane per block: it takes many blocks to fill the chip)
-    INF_HIP(hipMemcpyAsync(h->d_blk, blk, n_blk * sizeof *blk, hipMemcpyHostToDevice, h->st[0]));
-    INF_HIP(hipMemcpyAsync(h->d_comp, comp, comp_len, hipMemcpyHostToDevice, h->st[0]));
-    INF_HIP(hipEventRecord(h->ev[0], h->st[0]));
+    ITX_HIP(hipMemcpyAsync(h->d_blk, blk, n_blk * sizeof *blk, hipMemcpyHostToDevice, h->st[0]));
+    ITX_HIP(hipMemcpyAsync(h->d_comp, comp, comp_len, hipMemcpyHostToDevice, h->st[0]));
+    ITX_HIP(hipEventRecord(h->ev[0], h->st[0]));
     hipLaunchKernelGGL(k_tokens, dim3((unsigned)((n_blk + 63) / 64)), dim3(64), 0, h->st[0], (const uint32_t *)h->d_comp, h->d_blk, (uint32_t)n_blk, h->d_lit,
                        h->d_meta);
-    INF_HIP(hipGetLastError());
-    INF_HIP(hipEventRecord(h->ev[1], h->st[0]));
-    INF_HIP(hipStreamSynchronize(h->st[0]));
+    ITX_HIP(hipGetLastError());
+    ITX_HIP(hipEventRecord(h->ev[1], h->st[0]));
+    ITX_HIP(hipStreamSynchronize(h->st[0]));
     // pass 2 in groups that alternate between two streams: one group's copy-out overlaps the next one's kernel
     const size_t per = n_blk < 2048 ? n_blk : (n_blk + 3) / 4;
     int s = 0;
-    INF_HIP(hipEventRecord(h->ev[2], h->st[0]));
+    ITX_HIP(hipEventRecord(h->ev[2], h->st[0]));
     for (size_t b0 = 0; b0 < n_blk; b0 += per, s ^= 1) {
         const size_t b1 = b0 + per < n_blk ? b0 + per : n_blk;
         hipLaunchKernelGGL(k_resolve, dim3((unsigned)(b1 - b0)), dim3(64), 0, h->st[s], h->d_blk, (uint32_t)b0, (uint32_t)(b1 - b0), h->d_lit, h->d_meta,
                            h->d_out, h->d_status);
-        INF_HIP(hipGetLastError());
-        if (b0 == 0) INF_HIP(hipEventRecord(h->ev[3], h->st[0]));
+        ITX_HIP(hipGetLastError());
+        if (b0 == 0) ITX_HIP(hipEventRecord(h->ev[3], h->st[0]));
         const size_t u0 = blk[b0].uoff, u1 = (size_t)blk[b1 - 1].uoff + blk[b1 - 1].usize;
-        if (out && u1 > u0) INF_HIP(hipMemcpyAsync((uint8_t *)out + u0, h->d_out + u0, u1 - u0, hipMemcpyDeviceToHost, h->st[s]));
-        INF_HIP(hipEventRecord(h->ev_res_end[s], h->st[s]));
-        INF_HIP(hipMemcpyAsync(status + b0, h->d_status + b0, b1 - b0, hipMemcpyDeviceToHost, h->st[s]));
+        if (out && u1 > u0) ITX_HIP(hipMemcpyAsync((uint8_t *)out + u0, h->d_out + u0, u1 - u0, hipMemcpyDeviceToHost, h->st[s]));
+        ITX_HIP(hipEventRecord(h->ev_res_end[s], h->st[s]));
+        ITX_HIP(hipMemcpyAsync(status + b0, h->d_status + b0, b1 - b0, hipMemcpyDeviceToHost, h->st[s]));
     }
-    INF_HIP(hipStreamSynchronize(h->st[0]));
-    INF_HIP(hipStreamSynchronize(h->st[1]));
+    ITX_HIP(hipStreamSynchronize(h->st[0]));
+    ITX_HIP(hipStreamSynchronize(h->st[1]));
     (void)hipEventElapsedTime(&h->ms_tokens, h->ev[0], h->ev[1]);
     (void)hipEventElapsedTime(&h->ms_resolve, h->ev[2], h->ev[3]);
     {
@@ -857,7 +834,7 @@ extern "C" int itx_bamwin_push_begin(itx_inflater *h, int w, int s, const void *
     int rc = check_blocks(blk, n_blk, comp_len, &total);
     if (rc != ITX_OK) return rc;
     if (comp_len > 0xfffffff0u || total + WIN_HEAD > 0xfffffff0u || n_blk > 0x7fffffffu) return ITX_E_LIMIT;
-    INF_HIP(hipSetDevice(h->device));
+    ITX_HIP(hipSetDevice(h->device));
     if (h->arena && (w >= h->n_reserved_win || WIN_HEAD + total + 64 > h->win[w].cap || comp_len + 64 > Ln.comp_cap || n_blk > Ln.status_cap)) {
         itx_set_error("push of %zu blocks / %zu bytes into window %d exceeds what itx_inflater_reserve set up", n_blk, total, w);
         return ITX_E_LIMIT;
@@ -876,8 +853,8 @@ extern "C" int itx_bamwin_push_begin(itx_inflater *h, int w, int s, const void *
         Ln.h_status = nullptr;
         Ln.h_cap = 0;
         const size_t want = n_blk + n_blk / 4 + 64;
-        INF_HIP(hipHostMalloc((void **)&Ln.h_blk, want * sizeof(itx_bgzf_block), hipHostMallocDefault));
-        INF_HIP(hipHostMalloc((void **)&Ln.h_status, want, hipHostMallocDefault));
+        ITX_HIP(hipHostMalloc((void **)&Ln.h_blk, want * sizeof(itx_bgzf_block), hipHostMallocDefault));
+        ITX_HIP(hipHostMalloc((void **)&Ln.h_status, want, hipHostMallocDefault));
         Ln.h_cap = want;
     }
     for (size_t i = 0; i < n_blk; i++) {
@@ -891,24 +868,24 @@ extern "C" int itx_bamwin_push_begin(itx_inflater *h, int w, int s, const void *
     if ((rc = grow(&CL.d_lit, &CL.lit_cap, n_blk * (size_t)SCR_STRIDE)) != ITX_OK) return rc;      // (growing frees: that waits for whatever still runs)
     if ((rc = grow(&CL.d_meta, &CL.meta_cap, 3 * n_blk)) != ITX_OK) return rc;
     // the bytes cross PCIe on the copy stream ...
-    INF_HIP(hipMemcpyAsync(Ln.d_blk, Ln.h_blk, n_blk * sizeof *blk, hipMemcpyHostToDevice, h->copy_st));
-    INF_HIP(hipMemcpyAsync(Ln.d_comp, comp, comp_len, hipMemcpyHostToDevice, h->copy_st));
-    INF_HIP(hipEventRecord(Ln.copied, h->copy_st));
+    ITX_HIP(hipMemcpyAsync(Ln.d_blk, Ln.h_blk, n_blk * sizeof *blk, hipMemcpyHostToDevice, h->copy_st));
+    ITX_HIP(hipMemcpyAsync(Ln.d_comp, comp, comp_len, hipMemcpyHostToDevice, h->copy_st));
+    ITX_HIP(hipEventRecord(Ln.copied, h->copy_st));
     // ... and both passes run on the compute lane, behind the push that had the lane (and its scratch) before
     hipStream_t st = CL.cst;
-    INF_HIP(hipStreamWaitEvent(st, Ln.copied, 0));
-    INF_HIP(hipEventRecord(Ln.ev[0], st));
+    ITX_HIP(hipStreamWaitEvent(st, Ln.copied, 0));
+    ITX_HIP(hipEventRecord(Ln.ev[0], st));
     hipLaunchKernelGGL(k_tokens, dim3((unsigned)((n_blk + 63) / 64)), dim3(64), 0, st, (const uint32_t *)Ln.d_comp, Ln.d_blk, (uint32_t)n_blk, CL.d_lit, CL.d_meta);
-    INF_HIP(hipGetLastError());
+    ITX_HIP(hipGetLastError());
     // pass 2 on the same stream, one wave per block (every push's pass 2 on one shared stream, or a fixed set of waves
     // that take blocks in turn, were measured slower: DESIGN.md)
     hipStream_t sr = st;
-    INF_HIP(hipEventRecord(Ln.ev[1], sr));
+    ITX_HIP(hipEventRecord(Ln.ev[1], sr));
     hipLaunchKernelGGL(k_resolve, dim3((unsigned)n_blk), dim3(64), 0, sr, Ln.d_blk, 0u, (uint32_t)n_blk, CL.d_lit, CL.d_meta, h->win[w].buf, Ln.d_status);
-    INF_HIP(hipGetLastError());
-    INF_HIP(hipEventRecord(Ln.ev[2], sr));
-    INF_HIP(hipMemcpyAsync(Ln.h_status, Ln.d_status, n_blk, hipMemcpyDeviceToHost, sr));
-    INF_HIP(hipEventRecord(Ln.done, sr));
+    ITX_HIP(hipGetLastError());
+    ITX_HIP(hipEventRecord(Ln.ev[2], sr));
+    ITX_HIP(hipMemcpyAsync(Ln.h_status, Ln.d_status, n_blk, hipMemcpyDeviceToHost, sr));
+    ITX_HIP(hipEventRecord(Ln.done, sr));
     return ITX_OK;
 }
 
@@ -917,8 +894,8 @@ extern "C" int itx_bamwin_push_copied(itx_inflater *h, int s)
 {
     if (!h || BAD_S(s)) return ITX_E_ARG;
     if (!h->lane[s].busy || h->lane[s].n_blk == 0) return ITX_OK;
-    INF_HIP(hipSetDevice(h->device));
-    INF_HIP(hipEventSynchronize(h->lane[s].copied));
+    ITX_HIP(hipSetDevice(h->device));
+    ITX_HIP(hipEventSynchronize(h->lane[s].copied));
     return ITX_OK;
 }
 
@@ -928,8 +905,8 @@ extern "C" int itx_bamwin_push_end(itx_inflater *h, int s, uint8_t *status, size
     if (!h || BAD_S(s) || !status || !n_new) return ITX_E_ARG;
     auto &Ln = h->lane[s];
     if (!Ln.busy) return ITX_E_STATE;
-    INF_HIP(hipSetDevice(h->device));
-    if (Ln.n_blk) INF_HIP(hipEventSynchronize(Ln.done));
+    ITX_HIP(hipSetDevice(h->device));
+    if (Ln.n_blk) ITX_HIP(hipEventSynchronize(Ln.done));
     if (Ln.n_blk) {
         float a = 0, b = 0;
         if (hipEventElapsedTime(&a, Ln.ev[0], Ln.ev[1]) == hipSuccess && hipEventElapsedTime(&b, Ln.ev[1], Ln.ev[2]) == hipSuccess) {
@@ -953,12 +930,12 @@ extern "C" int itx_inflater_reserve(itx_inflater *h, size_t comp_bytes, size_t m
 {
     if (!h || !n_windows || max_blocks == 0 || max_blocks > 0x7fffffffu || max_bytes + WIN_HEAD > 0xfffffff0u) return ITX_E_ARG;
     if (h->arena) return ITX_E_STATE;
-    INF_HIP(hipSetDevice(h->device));
+    ITX_HIP(hipSetDevice(h->device));
     const int n_lanes = lanes_in_use();
     for (int k = 0; k < n_lanes; k++)
         if (h->lane[k].busy || h->lane[k].d_comp) return ITX_E_STATE;
     size_t free_b = 0, total_b = 0;
-    INF_HIP(hipMemGetInfo(&free_b, &total_b));
+    ITX_HIP(hipMemGetInfo(&free_b, &total_b));
     const size_t per = (WIN_HEAD + max_bytes + 64 + 255) & ~(size_t)255;
     size_t n = (free_b / 5 * 2) / per;                              // two fifths of what is free now
     if (n > ITX_BAMWIN_WINDOWS) n = ITX_BAMWIN_WINDOWS;
@@ -974,9 +951,9 @@ extern "C" int itx_inflater_reserve(itx_inflater *h, size_t comp_bytes, size_t m
     const int n_comp = compute_lanes();
     const size_t total = (sz_comp + sz_status + sz_blk) * (size_t)n_lanes + (sz_lit + sz_meta) * (size_t)n_comp + per * n;
     uint8_t *base = nullptr;
-    const double t0 = wall_now();
+    const double t0 = itx_wall_now();
     hipError_t he = hipMalloc((void **)&base, total);
-    g_alloc_s += wall_now() - t0;
+    g_alloc_s += itx_wall_now() - t0;
     g_allocs++;
     if (he != hipSuccess) {
         itx_set_error("itx_inflater_reserve: hipMalloc(%zu) failed: %s", total, hipGetErrorString(he));
@@ -996,8 +973,8 @@ extern "C" int itx_inflater_reserve(itx_inflater *h, size_t comp_bytes, size_t m
             Ln.h_blk = nullptr;
             Ln.h_status = nullptr;
             Ln.h_cap = 0;
-            INF_HIP(hipHostMalloc((void **)&Ln.h_blk, (max_blocks + 64) * sizeof(itx_bgzf_block), hipHostMallocDefault));
-            INF_HIP(hipHostMalloc((void **)&Ln.h_status, max_blocks + 64, hipHostMallocDefault));
+            ITX_HIP(hipHostMalloc((void **)&Ln.h_blk, (max_blocks + 64) * sizeof(itx_bgzf_block), hipHostMallocDefault));
+            ITX_HIP(hipHostMalloc((void **)&Ln.h_status, max_blocks + 64, hipHostMallocDefault));
             Ln.h_cap = max_blocks + 64;
         }
     }
@@ -1028,8 +1005,8 @@ extern "C" int itx_bamwin_push(itx_inflater *h, int w, const void *comp, size_t 
 extern "C" int itx_bamwin_patch(itx_inflater *h, int w, size_t uoff, const void *bytes, size_t len)
 {
     if (!h || BAD_W(w) || !bytes || WIN_HEAD + uoff + len > h->win[w].len) return ITX_E_ARG;
-    INF_HIP(hipSetDevice(h->device));
-    INF_HIP(hipMemcpy(h->win[w].buf + WIN_HEAD + uoff, bytes, len, hipMemcpyHostToDevice));
+    ITX_HIP(hipSetDevice(h->device));
+    ITX_HIP(hipMemcpy(h->win[w].buf + WIN_HEAD + uoff, bytes, len, hipMemcpyHostToDevice));
     return ITX_OK;
 }
 
@@ -1045,7 +1022,7 @@ extern "C" int itx_bamwin_carry(itx_inflater *h, int from, int to)
     if (!h || BAD_W(from) || BAD_W(to) || from == to) return ITX_E_ARG;
     const uint32_t tail = h->win[from].len - h->win[from].consumed;
     if (h->win[to].start != WIN_HEAD) return ITX_E_STATE;
-    INF_HIP(hipSetDevice(h->device));
+    ITX_HIP(hipSetDevice(h->device));
     if (tail > WIN_HEAD) {
         // A record of more than 4 MiB straddles the chunks (a very long read): the head room in front of the fresh bytes is too
         // small, so the fresh bytes move back instead — as long as the window's buffer holds both (the reference reads such
@@ -1065,23 +1042,23 @@ extern "C" int itx_bamwin_carry(itx_inflater *h, int from, int to)
             for (size_t done = 0; done < fresh;) {
                 const size_t n = fresh - done < shift ? fresh - done : shift;
                 const size_t src = WIN_HEAD + fresh - done - n;
-                INF_HIP(hipMemcpyAsync(h->win[to].buf + src + shift, h->win[to].buf + src, n, hipMemcpyDeviceToDevice, h->st[1]));
+                ITX_HIP(hipMemcpyAsync(h->win[to].buf + src + shift, h->win[to].buf + src, n, hipMemcpyDeviceToDevice, h->st[1]));
                 done += n;
             }
         } else if (fresh) {
             hipLaunchKernelGGL(k_move_up, dim3(1), dim3(MOVE_THREADS), 0, h->st[1], h->win[to].buf, (size_t)WIN_HEAD, fresh, shift);
-            INF_HIP(hipGetLastError());
+            ITX_HIP(hipGetLastError());
         }
-        INF_HIP(hipMemcpyAsync(h->win[to].buf, h->win[from].buf + h->win[from].consumed, tail, hipMemcpyDeviceToDevice, h->st[1]));
-        INF_HIP(hipStreamSynchronize(h->st[1]));
+        ITX_HIP(hipMemcpyAsync(h->win[to].buf, h->win[from].buf + h->win[from].consumed, tail, hipMemcpyDeviceToDevice, h->st[1]));
+        ITX_HIP(hipStreamSynchronize(h->st[1]));
         h->win[to].start = h->win[to].consumed = 0;
         h->win[to].len = tail + (uint32_t)fresh;
         h->win[from].consumed = h->win[from].len;
         return ITX_OK;
     }
     if (tail) {
-        INF_HIP(hipMemcpyAsync(h->win[to].buf + WIN_HEAD - tail, h->win[from].buf + h->win[from].consumed, tail, hipMemcpyDeviceToDevice, h->st[1]));
-        INF_HIP(hipStreamSynchronize(h->st[1]));
+        ITX_HIP(hipMemcpyAsync(h->win[to].buf + WIN_HEAD - tail, h->win[from].buf + h->win[from].consumed, tail, hipMemcpyDeviceToDevice, h->st[1]));
+        ITX_HIP(hipStreamSynchronize(h->st[1]));
     }
     h->win[to].start = h->win[to].consumed = WIN_HEAD - tail;
     h->win[from].consumed = h->win[from].len;
@@ -1099,8 +1076,8 @@ extern "C" int itx_bamwin_avail(const itx_inflater *h, int w, size_t *bytes)
 extern "C" int itx_bamwin_peek(itx_inflater *h, int w, size_t off, void *dst, size_t len)
 {
     if (!h || BAD_W(w) || !dst || (size_t)h->win[w].consumed + off + len > h->win[w].len) return ITX_E_ARG;
-    INF_HIP(hipSetDevice(h->device));
-    if (len) INF_HIP(hipMemcpy(dst, h->win[w].buf + h->win[w].consumed + off, len, hipMemcpyDeviceToHost));
+    ITX_HIP(hipSetDevice(h->device));
+    if (len) ITX_HIP(hipMemcpy(dst, h->win[w].buf + h->win[w].consumed + off, len, hipMemcpyDeviceToHost));
     return ITX_OK;
 }
 
@@ -1122,7 +1099,7 @@ extern "C" int itx_bamwin_parse(itx_inflater *h, int w, int n_targets, size_t *n
     h->parsed_w = w;
     const uint32_t p0 = h->win[w].consumed, L = h->win[w].len;
     if (p0 >= L) return ITX_OK;
-    INF_HIP(hipSetDevice(h->device));
+    ITX_HIP(hipSetDevice(h->device));
     hipStream_t st = h->st[1];
     const uint32_t T = (L - p0 + PIECE - 1) / PIECE;
     int rc;
@@ -1132,7 +1109,7 @@ extern "C" int itx_bamwin_parse(itx_inflater *h, int w, int n_targets, size_t *n
         if (cap != h->sum_cap) {
             if (h->h_sum) (void)hipHostFree(h->h_sum);
             h->h_sum = nullptr;
-            INF_HIP(hipHostMalloc(&h->h_sum, cap * sizeof(PieceSum), hipHostMallocDefault));
+            ITX_HIP(hipHostMalloc(&h->h_sum, cap * sizeof(PieceSum), hipHostMallocDefault));
             h->sum_cap = cap;
         }
         cap = h->pb_cap;
@@ -1140,20 +1117,20 @@ extern "C" int itx_bamwin_parse(itx_inflater *h, int w, int n_targets, size_t *n
         if (cap != h->pb_cap) {
             if (h->h_pb) (void)hipHostFree(h->h_pb);
             h->h_pb = nullptr;
-            INF_HIP(hipHostMalloc((void **)&h->h_pb, cap * sizeof(uint32_t), hipHostMallocDefault));
+            ITX_HIP(hipHostMalloc((void **)&h->h_pb, cap * sizeof(uint32_t), hipHostMallocDefault));
             h->pb_cap = cap;
         }
     }
     if ((rc = grow(&h->d_spec, &h->spec_cap, (size_t)T * PIECE_SLOTS)) != ITX_OK) return rc;
-    if (!h->d_flags) INF_HIP(hipMalloc((void **)&h->d_flags, 16));
+    if (!h->d_flags) ITX_HIP(hipMalloc((void **)&h->d_flags, 16));
     if ((rc = grow(&h->d_seen, &h->seen_cap, (size_t)(n_targets > 0 ? n_targets : 1))) != ITX_OK) return rc;
-    INF_HIP(hipMemsetAsync(h->d_seen, 0, (size_t)(n_targets > 0 ? n_targets : 1), st));
+    ITX_HIP(hipMemsetAsync(h->d_seen, 0, (size_t)(n_targets > 0 ? n_targets : 1), st));
     PieceSum *d_sum = (PieceSum *)h->d_sum, *sum = (PieceSum *)h->h_sum;
     const uint8_t *u = h->win[w].buf;
     hipLaunchKernelGGL(k_guess, dim3((T + 63) / 64), dim3(64), 0, st, u, p0, L, T, (int32_t)n_targets, d_sum, h->d_spec);
-    INF_HIP(hipGetLastError());
-    INF_HIP(hipMemcpyAsync(sum, d_sum, (size_t)T * sizeof(PieceSum), hipMemcpyDeviceToHost, st));
-    INF_HIP(hipStreamSynchronize(st));
+    ITX_HIP(hipGetLastError());
+    ITX_HIP(hipMemcpyAsync(sum, d_sum, (size_t)T * sizeof(PieceSum), hipMemcpyDeviceToHost, st));
+    ITX_HIP(hipStreamSynchronize(st));
     // in stream order: a piece counts if its guess is where the chain arrives, else it is walked again from there
     uint32_t cur = p0, endp = p0, why = 0, tot = 0;
     uint32_t *base = h->h_pb, *cnt = h->h_pb + T;
@@ -1165,9 +1142,9 @@ extern "C" int itx_bamwin_parse(itx_inflater *h, int w, int n_targets, size_t *n
         if (why || cur >= lim) continue;                        // the stream ended, or a record reaches over the whole piece
         if (sum[t].c != cur) {
             hipLaunchKernelGGL(k_rewalk, dim3(1), dim3(1), 0, st, u, cur, lim, L, t, d_sum, h->d_spec);
-            INF_HIP(hipGetLastError());
-            INF_HIP(hipMemcpyAsync(&sum[t], d_sum + t, sizeof(PieceSum), hipMemcpyDeviceToHost, st));
-            INF_HIP(hipStreamSynchronize(st));
+            ITX_HIP(hipGetLastError());
+            ITX_HIP(hipMemcpyAsync(&sum[t], d_sum + t, sizeof(PieceSum), hipMemcpyDeviceToHost, st));
+            ITX_HIP(hipStreamSynchronize(st));
             redo++;
         }
         cnt[t] = sum[t].n;
@@ -1189,27 +1166,27 @@ extern "C" int itx_bamwin_parse(itx_inflater *h, int w, int n_targets, size_t *n
         int32_t **i32s[5] = {&h->d_tid, &h->d_pos, &h->d_end, &h->d_mpos, &h->d_isize};
         uint8_t **u8s[3] = {&h->d_mapq, &h->d_f5, &h->d_xa};
         for (auto pp : i32s) {
-            if (*pp) INF_HIP(hipFree(*pp));
+            if (*pp) ITX_HIP(hipFree(*pp));
             *pp = nullptr;
-            INF_HIP(hipMalloc((void **)pp, want * 4));
+            ITX_HIP(hipMalloc((void **)pp, want * 4));
         }
         for (auto pp : u8s) {
-            if (*pp) INF_HIP(hipFree(*pp));
+            if (*pp) ITX_HIP(hipFree(*pp));
             *pp = nullptr;
-            INF_HIP(hipMalloc((void **)pp, want));
+            ITX_HIP(hipMalloc((void **)pp, want));
         }
         h->soa_cap = want;
     }
-    INF_HIP(hipMemcpyAsync(h->d_pb, h->h_pb, 2 * (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    INF_HIP(hipMemsetAsync(h->d_flags, 0, 4, st));
+    ITX_HIP(hipMemcpyAsync(h->d_pb, h->h_pb, 2 * (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    ITX_HIP(hipMemsetAsync(h->d_flags, 0, 4, st));
     hipLaunchKernelGGL(k_compact, dim3(T), dim3(64), 0, st, h->d_spec, h->d_pb, h->d_pb + T, T, h->d_recoff);
-    INF_HIP(hipGetLastError());
+    ITX_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_parse, dim3((tot + 255) / 256), dim3(256), 0, st, u, h->d_recoff, tot, h->d_tid, h->d_pos, h->d_end, h->d_mapq, h->d_f5, h->d_mpos, h->d_isize,
                        h->d_xa, h->d_flags, h->d_seen, (int32_t)n_targets);
-    INF_HIP(hipGetLastError());
+    ITX_HIP(hipGetLastError());
     uint32_t fl = 0;
-    INF_HIP(hipMemcpyAsync(&fl, h->d_flags, 4, hipMemcpyDeviceToHost, st));
-    INF_HIP(hipStreamSynchronize(st));
+    ITX_HIP(hipMemcpyAsync(&fl, h->d_flags, 4, hipMemcpyDeviceToHost, st));
+    ITX_HIP(hipStreamSynchronize(st));
     *flags = (int)fl;
     *n_rec = tot;
     h->n_rec = tot;
@@ -1222,21 +1199,21 @@ extern "C" int itx_bamwin_fetch(itx_inflater *h, size_t first, size_t n, const i
 {
     if (!h || first + n > h->n_rec) return ITX_E_ARG;
     if (n == 0) return ITX_OK;
-    INF_HIP(hipSetDevice(h->device));
+    ITX_HIP(hipSetDevice(h->device));
     hipStream_t st = h->st[1];
     if (dst) {
         if (dst_at + n > dst->capacity) return ITX_E_ARG;
-        if (dst->tid) INF_HIP(hipMemcpyAsync(dst->tid + dst_at, h->d_tid + first, n * 4, hipMemcpyDeviceToHost, st));
-        if (dst->pos) INF_HIP(hipMemcpyAsync(dst->pos + dst_at, h->d_pos + first, n * 4, hipMemcpyDeviceToHost, st));
-        if (dst->tmpend) INF_HIP(hipMemcpyAsync(dst->tmpend + dst_at, h->d_end + first, n * 4, hipMemcpyDeviceToHost, st));
-        if (dst->mapq) INF_HIP(hipMemcpyAsync(dst->mapq + dst_at, h->d_mapq + first, n, hipMemcpyDeviceToHost, st));
-        if (dst->flag5) INF_HIP(hipMemcpyAsync(dst->flag5 + dst_at, h->d_f5 + first, n, hipMemcpyDeviceToHost, st));
-        if (dst->mpos) INF_HIP(hipMemcpyAsync(dst->mpos + dst_at, h->d_mpos + first, n * 4, hipMemcpyDeviceToHost, st));
-        if (dst->isize) INF_HIP(hipMemcpyAsync(dst->isize + dst_at, h->d_isize + first, n * 4, hipMemcpyDeviceToHost, st));
+        if (dst->tid) ITX_HIP(hipMemcpyAsync(dst->tid + dst_at, h->d_tid + first, n * 4, hipMemcpyDeviceToHost, st));
+        if (dst->pos) ITX_HIP(hipMemcpyAsync(dst->pos + dst_at, h->d_pos + first, n * 4, hipMemcpyDeviceToHost, st));
+        if (dst->tmpend) ITX_HIP(hipMemcpyAsync(dst->tmpend + dst_at, h->d_end + first, n * 4, hipMemcpyDeviceToHost, st));
+        if (dst->mapq) ITX_HIP(hipMemcpyAsync(dst->mapq + dst_at, h->d_mapq + first, n, hipMemcpyDeviceToHost, st));
+        if (dst->flag5) ITX_HIP(hipMemcpyAsync(dst->flag5 + dst_at, h->d_f5 + first, n, hipMemcpyDeviceToHost, st));
+        if (dst->mpos) ITX_HIP(hipMemcpyAsync(dst->mpos + dst_at, h->d_mpos + first, n * 4, hipMemcpyDeviceToHost, st));
+        if (dst->isize) ITX_HIP(hipMemcpyAsync(dst->isize + dst_at, h->d_isize + first, n * 4, hipMemcpyDeviceToHost, st));
     }
-    if (rec_off) INF_HIP(hipMemcpyAsync(rec_off, h->d_recoff + first, n * 4, hipMemcpyDeviceToHost, st));
-    if (xa) INF_HIP(hipMemcpyAsync(xa, h->d_xa + first, n, hipMemcpyDeviceToHost, st));
-    INF_HIP(hipStreamSynchronize(st));
+    if (rec_off) ITX_HIP(hipMemcpyAsync(rec_off, h->d_recoff + first, n * 4, hipMemcpyDeviceToHost, st));
+    if (xa) ITX_HIP(hipMemcpyAsync(xa, h->d_xa + first, n, hipMemcpyDeviceToHost, st));
+    ITX_HIP(hipStreamSynchronize(st));
     return ITX_OK;
 }
 
@@ -1246,16 +1223,16 @@ extern "C" int itx_bamwin_bytes(itx_inflater *h, size_t off, void *dst, size_t l
     if (!h || !dst) return ITX_E_ARG;
     const int w = h->parsed_w;
     if (off + len > h->win[w].cap) return ITX_E_ARG;
-    INF_HIP(hipSetDevice(h->device));
-    if (len) INF_HIP(hipMemcpy(dst, h->win[w].buf + off, len, hipMemcpyDeviceToHost));
+    ITX_HIP(hipSetDevice(h->device));
+    if (len) ITX_HIP(hipMemcpy(dst, h->win[w].buf + off, len, hipMemcpyDeviceToHost));
     return ITX_OK;
 }
 
 extern "C" int itx_bamwin_tids(itx_inflater *h, uint8_t *seen, int n_targets)
 {
     if (!h || !seen || n_targets < 0 || (size_t)n_targets > h->seen_cap) return ITX_E_ARG;
-    INF_HIP(hipSetDevice(h->device));
-    if (n_targets) INF_HIP(hipMemcpy(seen, h->d_seen, (size_t)n_targets, hipMemcpyDeviceToHost));
+    ITX_HIP(hipSetDevice(h->device));
+    if (n_targets) ITX_HIP(hipMemcpy(seen, h->d_seen, (size_t)n_targets, hipMemcpyDeviceToHost));
     return ITX_OK;
 }
 

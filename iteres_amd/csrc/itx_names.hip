@@ -7,10 +7,9 @@
 //   k_names_measure  one lane per record: a record with hit_row >= 0 gets itx_bed_scan (itx_bedline.h: the name is the bytes up to
 //                    the first NUL; no NUL inside the record is `hard`). A tile of NM_TILE records adds up its entries and its
 //                    name bytes (64 bit).
-//   k_names_scan     exclusive sums over the tiles, one workgroup; the two totals are all the host waits for.
+//   k_tile_scan2     (itx_textpack.h) exclusive sums over the tiles, one workgroup; the two totals are all the host waits for.
 //   k_names_gather   one workgroup per tile: every hit appends {row, len, pool offset}; the tile's names are ONE contiguous range
-//                    of the pool, staged in LDS a window at a time and stored with one 16-byte vector per lane (only the ragged
-//                    first and last vector of a tile go byte by byte) — names are 20-40 bytes at offsets unrelated to anything.
+//                    of the pool, staged in LDS a window at a time and stored with 16-byte vectors (itx_textpack.h says why and how).
 //   n_hard > 0: nothing of the batch is appended, the caller takes the host route (the bed route's contract). The host route
 //   hands its hits to the same pool (itx_names_append_host), so the stream is one ordered list whatever route a window took.
 //
@@ -22,12 +21,11 @@
 //   and the last of its row by NUL; the first of a row writes row_off[row]. k_names_write copies pool -> text like the gather.
 //
 // Byte and integer work; the sort's scatter moves the most bytes. No kernel uses scratch (DESIGN.md has the figures).
-#include "itx_device.h"
+#include "itx_textpack.h"
 #include "itx_bedline.h"
 
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 #include <vector>
 
@@ -70,84 +68,12 @@ __global__ __launch_bounds__(NM_TILE) void k_names_measure(const uint8_t *__rest
     if (threadIdx.x < 2) tile_sum[2u * blockIdx.x + threadIdx.x] = s_sum[threadIdx.x];
 }
 
-// exclusive sums over the tiles, two columns at once; one workgroup
-__global__ __launch_bounds__(1024) void k_names_scan(const ull *__restrict__ tile_sum, uint32_t nt, ull *__restrict__ tile_base, ull *__restrict__ tot)
-{
-    __shared__ ull s[2][1024];
-    const uint32_t per = (nt + 1023u) / 1024u;
-    const uint32_t lo = (ull)threadIdx.x * per < nt ? threadIdx.x * per : nt, hi = lo + per < nt ? lo + per : nt;
-    ull a = 0, b = 0;
-    for (uint32_t k = lo; k < hi; k++) {
-        a += tile_sum[2u * k];
-        b += tile_sum[2u * k + 1u];
-    }
-    s[0][threadIdx.x] = a;
-    s[1][threadIdx.x] = b;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024u; d <<= 1) {
-        const ull va = threadIdx.x >= d ? s[0][threadIdx.x - d] : 0ull, vb = threadIdx.x >= d ? s[1][threadIdx.x - d] : 0ull;
-        __syncthreads();
-        s[0][threadIdx.x] += va;
-        s[1][threadIdx.x] += vb;
-        __syncthreads();
-    }
-    ull ea = s[0][threadIdx.x] - a, eb = s[1][threadIdx.x] - b;
-    for (uint32_t k = lo; k < hi; k++) {
-        const ull ta = tile_sum[2u * k], tb = tile_sum[2u * k + 1u];
-        tile_base[2u * k] = ea;
-        tile_base[2u * k + 1u] = eb;
-        ea += ta;
-        eb += tb;
-    }
-    if (threadIdx.x == 1023u) {
-        tot[0] = s[0][1023];
-        tot[1] = s[1][1023];
-    }
-}
-
-// where the lane's `len` bytes start inside the tile, and the tile's total: wave scan, then the waves' sums through LDS
-__device__ __forceinline__ uint32_t tile_offsets(uint32_t len, uint32_t *s_w, uint32_t *total)
-{
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint32_t x = len;
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63u) s_w[w] = x;
-    __syncthreads();
-    uint32_t woff = 0, t = 0;
-    for (uint32_t k = 0; k < NM_TILE / 64u; k++) {
-        if (k < w) woff += s_w[k];
-        t += s_w[k];
-    }
-    *total = t;
-    return woff + (x - len);
-}
-
-// the staged window [win, win + NM_LDS) of the output range [tb, te): full vectors where they lie inside the range
-__device__ __forceinline__ void store_window(const uint4 *s_buf, uint8_t *__restrict__ out, ull win, ull tb, ull te)
-{
-    const uint8_t *s_bytes = reinterpret_cast<const uint8_t *>(s_buf);
-    for (uint32_t v = threadIdx.x; v < NM_LDS / 16u; v += NM_TILE) {
-        const ull ab = win + 16ull * v;
-        if (ab >= te) break;
-        if (ab >= tb && ab + 16ull <= te) {
-            *reinterpret_cast<uint4 *>(out + ab) = s_buf[v];
-        } else {
-            for (uint32_t k = 0; k < 16u; k++)
-                if (ab + k >= tb && ab + k < te) out[ab + k] = s_bytes[16u * v + k];
-        }
-    }
-}
-
 __global__ __launch_bounds__(NM_TILE) void k_names_gather(const uint8_t *__restrict__ u, const uint32_t *__restrict__ rec_off, const int32_t *__restrict__ hit_row, uint32_t n,
                                                            const uint32_t *__restrict__ len_in, const ull *__restrict__ tile_base, ull ent_base, ull pool_base,
                                                            NameEnt *__restrict__ ent, uint8_t *__restrict__ pool)
 {
     __shared__ uint4 s_buf[NM_LDS / 16u];
     __shared__ uint32_t s_w[NM_TILE / 64u], s_c[NM_TILE / 64u];
-    uint8_t *s_bytes = reinterpret_cast<uint8_t *>(s_buf);
     const uint32_t i = blockIdx.x * NM_TILE + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const uint32_t l0 = i < n ? len_in[i] : NM_NOHIT;
@@ -156,7 +82,7 @@ __global__ __launch_bounds__(NM_TILE) void k_names_gather(const uint8_t *__restr
     const ull hm = __ballot(hit);
     if (lane == 0) s_c[w] = (uint32_t)__popcll(hm);
     uint32_t total = 0;
-    const uint32_t moff = tile_offsets(len, s_w, &total);               // (its barrier covers s_c)
+    const uint32_t moff = itx_tile_offsets<NM_TILE>(len, s_w, &total);  // (its barrier covers s_c)
     uint32_t rank = (uint32_t)__popcll(hm & ((1ull << lane) - 1ull));
     for (uint32_t k = 0; k < w; k++) rank += s_c[k];
     const ull tb = pool_base + tile_base[2u * blockIdx.x + 1u], te = tb + total;
@@ -166,15 +92,11 @@ __global__ __launch_bounds__(NM_TILE) void k_names_gather(const uint8_t *__restr
         const ull k = ent_base + tile_base[2u * blockIdx.x] + rank;
         *reinterpret_cast<uint4 *>(&ent[k]) = make_uint4((uint32_t)hit_row[i], len, (uint32_t)mb, (uint32_t)(mb >> 32));
     }
-    for (ull win = tb & ~15ull; win < te; win += NM_LDS) {
-        if (len) {
-            const ull a = mb > win ? mb : win, b = me < win + NM_LDS ? me : win + NM_LDS;
-            for (ull q = a; q < b; q++) s_bytes[(uint32_t)(q - win)] = src[(uint32_t)(q - mb)];
-        }
-        __syncthreads();
-        store_window(s_buf, pool, win, tb, te);
-        __syncthreads();
-    }
+    itx_pack_tile<NM_TILE, NM_LDS>(s_buf, pool, tb, te, mb, me, [=](uint8_t *dst, uint32_t from, uint32_t to) {
+        // 20-40 bytes at any alignment: kept a byte loop (the vectoriser would make unaligned 8-byte loads and 16-byte LDS stores of it)
+#pragma clang loop vectorize(disable)
+        for (uint32_t k = from; k < to; k++) dst[k - from] = src[k];
+    });
 }
 
 // ---- the sort
@@ -199,23 +121,15 @@ __global__ __launch_bounds__(256) void k_sort_hist(const uint2 *__restrict__ key
 }
 
 // exclusive scan in place, one workgroup; digit-major counts: the scanned value is where (digit, workgroup) starts
-__global__ __launch_bounds__(1024) void k_sort_scan(uint32_t *__restrict__ v, uint32_t n)
+__global__ __launch_bounds__(ITX_SCAN_WG) void k_sort_scan(uint32_t *__restrict__ v, uint32_t n)
 {
-    __shared__ uint32_t s[1024];
-    const uint32_t per = (n + 1023u) / 1024u;
-    const uint32_t lo = (ull)threadIdx.x * per < n ? threadIdx.x * per : n, hi = lo + per < n ? lo + per : n;
-    uint32_t a = 0;
-    for (uint32_t k = lo; k < hi; k++) a += v[k];
-    s[threadIdx.x] = a;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024u; d <<= 1) {
-        const uint32_t x = threadIdx.x >= d ? s[threadIdx.x - d] : 0u;
-        __syncthreads();
-        s[threadIdx.x] += x;
-        __syncthreads();
-    }
-    uint32_t e = s[threadIdx.x] - a;
-    for (uint32_t k = lo; k < hi; k++) {
+    __shared__ uint32_t s[ITX_SCAN_WG];
+    uint64_t lo, hi;
+    itx_scan_chunk(n, &lo, &hi);
+    uint32_t a = 0, total;
+    for (uint64_t k = lo; k < hi; k++) a += v[k];
+    uint32_t e = itx_scan_wg(a, s, &total);
+    for (uint64_t k = lo; k < hi; k++) {
         const uint32_t c = v[k];
         v[k] = e;
         e += c;
@@ -268,7 +182,7 @@ __global__ __launch_bounds__(NM_TILE) void k_text_measure(const uint2 *__restric
     __shared__ uint32_t s_w[NM_TILE / 64u];
     const ull j = (ull)blockIdx.x * NM_TILE + threadIdx.x;
     uint32_t total = 0;
-    (void)tile_offsets(j < n ? ent[keys[j].y].len + 1u : 0u, s_w, &total);
+    (void)itx_tile_offsets<NM_TILE>(j < n ? ent[keys[j].y].len + 1u : 0u, s_w, &total);
     if (threadIdx.x == 0) {
         tile_sum[2u * blockIdx.x] = total;
         tile_sum[2u * blockIdx.x + 1u] = 0;
@@ -281,7 +195,6 @@ __global__ __launch_bounds__(NM_TILE) void k_names_write(const uint2 *__restrict
 {
     __shared__ uint4 s_buf[NM_LDS / 16u];
     __shared__ uint32_t s_w[NM_TILE / 64u];
-    uint8_t *s_bytes = reinterpret_cast<uint8_t *>(s_buf);
     const ull j = (ull)blockIdx.x * NM_TILE + threadIdx.x;
     const bool valid = j < n;
     uint2 key = make_uint2(0u, 0u);
@@ -295,7 +208,7 @@ __global__ __launch_bounds__(NM_TILE) void k_names_write(const uint2 *__restrict
     }
     const uint32_t l1 = valid ? e.len + 1u : 0u;
     uint32_t total = 0;
-    const uint32_t moff = tile_offsets(l1, s_w, &total);
+    const uint32_t moff = itx_tile_offsets<NM_TILE>(l1, s_w, &total);
     const ull tb = tile_base[2u * blockIdx.x], te = tb + total;
     const ull mb = tb + moff, me = mb + l1;
     uint8_t term = 0;
@@ -307,18 +220,10 @@ __global__ __launch_bounds__(NM_TILE) void k_names_write(const uint2 *__restrict
         }
     }
     const uint8_t *src = pool + e.off;
-    for (ull win = tb & ~15ull; win < te; win += NM_LDS) {
-        if (l1) {
-            const ull a = mb > win ? mb : win, b = me < win + NM_LDS ? me : win + NM_LDS;
-            for (ull q = a; q < b; q++) {
-                const uint32_t k = (uint32_t)(q - mb);
-                s_bytes[(uint32_t)(q - win)] = k < e.len ? src[k] : term;
-            }
-        }
-        __syncthreads();
-        store_window(s_buf, text, win, tb, te);
-        __syncthreads();
-    }
+    const uint32_t len = e.len;
+    itx_pack_tile<NM_TILE, NM_LDS>(s_buf, text, tb, te, mb, me, [=](uint8_t *dst, uint32_t from, uint32_t to) {
+        for (uint32_t k = from; k < to; k++) dst[k - from] = k < len ? src[k] : term;
+    });
 }
 
 // ---- host side
@@ -513,7 +418,7 @@ int itx_names_start(itx_names *nm, const uint8_t *u, const uint32_t *rec_off, co
     NM_TRY(hipMemsetAsync(nm->d_tot, 0, 32, nm->st));
     hipLaunchKernelGGL(k_names_measure, dim3(nt), dim3(NM_TILE), 0, nm->st, u, rec_off, d_hit_row, (uint32_t)n, nm->d_len, nm->d_tile_sum, nm->d_tot);
     NM_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_names_scan, dim3(1), dim3(1024), 0, nm->st, nm->d_tile_sum, nt, nm->d_tile_base, nm->d_tot);
+    hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, nm->st, nm->d_tile_sum, nt, nm->d_tile_base, nm->d_tot);
     NM_TRY(hipGetLastError());
     NM_TRY(hipEventRecord(nm->ev[1], nm->st));
     NM_TRY(hipMemcpyAsync(nm->h_tot, nm->d_tot, 32, hipMemcpyDeviceToHost, nm->st));
@@ -680,7 +585,7 @@ extern "C" int itx_names_finish(itx_names *nm, size_t n_rows, itx_names_result *
         for (uint32_t p = 0; p < passes; p++) {
             hipLaunchKernelGGL(k_sort_hist, dim3(nwg), dim3(256), 0, nm->st, d_key[cur], n, 8u * p, d_hist, nwg);
             NM_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(1024), 0, nm->st, d_hist, 256u * nwg);
+            hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(ITX_SCAN_WG), 0, nm->st, d_hist, 256u * nwg);
             NM_TRY(hipGetLastError());
             hipLaunchKernelGGL(k_sort_scatter, dim3(nwg), dim3(256), 0, nm->st, d_key[cur], d_key[cur ^ 1], n, 8u * p, d_hist, nwg);
             NM_TRY(hipGetLastError());
@@ -688,7 +593,7 @@ extern "C" int itx_names_finish(itx_names *nm, size_t n_rows, itx_names_result *
         }
         hipLaunchKernelGGL(k_text_measure, dim3(nt), dim3(NM_TILE), 0, nm->st, d_key[cur], nm->d_ent, n, d_tsum);
         NM_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_names_scan, dim3(1), dim3(1024), 0, nm->st, d_tsum, nt, d_tbase, nm->d_tot);
+        hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, nm->st, d_tsum, nt, d_tbase, nm->d_tot);
         NM_TRY(hipGetLastError());
         NM_TRY(hipMemcpyAsync(nm->h_tot, nm->d_tot, 32, hipMemcpyDeviceToHost, nm->st));
         NM_TRY(hipStreamSynchronize(nm->st));

@@ -242,14 +242,6 @@ __global__ __launch_bounds__(256) void k_xa_apply(const uint8_t *__restrict__ ve
     if ((threadIdx.x & 63u) == 0 && m) atomicAdd(&count[0], (uint32_t)__popcll(m));
 }
 
-#define XA_HIP(call)                                                                                      \
-    do {                                                                                                  \
-        hipError_t err__ = (call);                                                                        \
-        if (err__ != hipSuccess) {                                                                        \
-            itx_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), __FILE__, __LINE__); \
-            return ITX_E_NO_DEVICE;                                                                       \
-        }                                                                                                 \
-    } while (0)
 
 extern "C" int itx_xaveto_create(const itx_table *t, const itx_params *p, const uint32_t *row_rep, const uint32_t *rep_word, const char *const *chrom_name, int n_chrom,
                                  size_t batch_capacity, itx_xaveto **out)
@@ -259,7 +251,7 @@ extern "C" int itx_xaveto_create(const itx_table *t, const itx_params *p, const 
         return ITX_E_ARG;
     }
     *out = nullptr;
-    XA_HIP(hipSetDevice(t->device));
+    ITX_HIP(hipSetDevice(t->device));
     itx_xaveto *x = new itx_xaveto();
     memset((void *)x, 0, sizeof *x);
     x->device = t->device;
@@ -297,15 +289,15 @@ extern "C" int itx_xaveto_create(const itx_table *t, const itx_params *p, const 
         if (e != hipSuccess) return e;
         return bytes ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
     };
-    XA_HIP(up(&x->d_rep_word, rep_word, sizeof(uint32_t) * (size_t)t->n_rep));
-    XA_HIP(up(&x->d_row_rep, row_rep, sizeof(uint32_t) * (size_t)t->n_rows));
-    XA_HIP(up(&x->d_chrom, ch.data(), sizeof(XaChrom) * ch.size()));
-    XA_HIP(up(&x->d_names, names.data(), sizeof(XaName) * names.size()));
-    XA_HIP(up(&x->d_pool, pool.data(), pool.size()));
-    XA_HIP(hipMalloc((void **)&x->d_hit, sizeof(int32_t) * (batch_capacity + 64)));
-    XA_HIP(hipMalloc((void **)&x->d_verdict, batch_capacity + 64));
-    XA_HIP(hipMalloc((void **)&x->d_count, 16));
-    XA_HIP(hipStreamCreateWithFlags(&x->st, hipStreamNonBlocking));
+    ITX_HIP(up(&x->d_rep_word, rep_word, sizeof(uint32_t) * (size_t)t->n_rep));
+    ITX_HIP(up(&x->d_row_rep, row_rep, sizeof(uint32_t) * (size_t)t->n_rows));
+    ITX_HIP(up(&x->d_chrom, ch.data(), sizeof(XaChrom) * ch.size()));
+    ITX_HIP(up(&x->d_names, names.data(), sizeof(XaName) * names.size()));
+    ITX_HIP(up(&x->d_pool, pool.data(), pool.size()));
+    ITX_HIP(hipMalloc((void **)&x->d_hit, sizeof(int32_t) * (batch_capacity + 64)));
+    ITX_HIP(hipMalloc((void **)&x->d_verdict, batch_capacity + 64));
+    ITX_HIP(hipMalloc((void **)&x->d_count, 16));
+    ITX_HIP(hipStreamCreateWithFlags(&x->st, hipStreamNonBlocking));
     x->d.rep_word = (const uint32_t *)x->d_rep_word;
     x->d.row_rep = (const uint32_t *)x->d_row_rep;
     x->d.chrom = (const XaChrom *)x->d_chrom;
@@ -345,17 +337,17 @@ extern "C" void itx_xaveto_destroy(itx_xaveto *x)
 extern "C" int itx_xaveto_set_tidmap(itx_xaveto *x, const int32_t *tid2chrom, int n_tid)
 {
     if (!x || n_tid < 0 || (n_tid && !tid2chrom)) return ITX_E_ARG;
-    XA_HIP(hipSetDevice(x->device));
+    ITX_HIP(hipSetDevice(x->device));
     std::vector<int2> v((size_t)n_tid + 1);
     for (int k = 0; k < n_tid; k++) {
         const int32_t c = tid2chrom[k];
         v[(size_t)k] = make_int2(c, (c >= 0 && c < x->t->n_chrom) ? x->t->h_chrom_size[c] : 0);
     }
-    XA_HIP(hipStreamSynchronize(x->st));
-    if (x->d_tid) XA_HIP(hipFree(x->d_tid));
+    ITX_HIP(hipStreamSynchronize(x->st));
+    if (x->d_tid) ITX_HIP(hipFree(x->d_tid));
     x->d_tid = nullptr;
-    XA_HIP(hipMalloc(&x->d_tid, sizeof(int2) * ((size_t)n_tid + 1)));
-    XA_HIP(hipMemcpy(x->d_tid, v.data(), sizeof(int2) * ((size_t)n_tid + 1), hipMemcpyHostToDevice));
+    ITX_HIP(hipMalloc(&x->d_tid, sizeof(int2) * ((size_t)n_tid + 1)));
+    ITX_HIP(hipMemcpy(x->d_tid, v.data(), sizeof(int2) * ((size_t)n_tid + 1), hipMemcpyHostToDevice));
     x->d.tid = (const int2 *)x->d_tid;
     x->d.n_tid = n_tid;
     return ITX_OK;
@@ -374,20 +366,20 @@ int itx_xaveto_run(itx_xaveto *x, const uint8_t *u, const uint32_t *rec_off, con
     }
     *n_vetoed = *n_hard = 0;
     if (n == 0) return ITX_OK;
-    XA_HIP(hipSetDevice(x->device));
-    XA_HIP(hipMemsetAsync(x->d_count, 0, 8, x->st));
+    ITX_HIP(hipSetDevice(x->device));
+    ITX_HIP(hipMemsetAsync(x->d_count, 0, 8, x->st));
     hipLaunchKernelGGL(k_xa_verdict, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, x->st, x->t->dev, x->d, u, rec_off, xa_mark, tid, pos, end, f5, mpos, isize, x->d_hit,
                        (uint32_t)n, x->d_verdict, x->d_count);
-    XA_HIP(hipGetLastError());
+    ITX_HIP(hipGetLastError());
     uint32_t c[2] = {0, 0};
-    XA_HIP(hipMemcpyAsync(c, x->d_count, 8, hipMemcpyDeviceToHost, x->st));
-    XA_HIP(hipStreamSynchronize(x->st));
+    ITX_HIP(hipMemcpyAsync(c, x->d_count, 8, hipMemcpyDeviceToHost, x->st));
+    ITX_HIP(hipStreamSynchronize(x->st));
     *n_hard = c[1];
     if (c[1]) return ITX_OK;                                          // the host has to look: nothing is marked
     hipLaunchKernelGGL(k_xa_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, x->st, x->d_verdict, f5, (uint32_t)n, x->d_count);
-    XA_HIP(hipGetLastError());
-    XA_HIP(hipMemcpyAsync(c, x->d_count, 8, hipMemcpyDeviceToHost, x->st));
-    XA_HIP(hipStreamSynchronize(x->st));
+    ITX_HIP(hipGetLastError());
+    ITX_HIP(hipMemcpyAsync(c, x->d_count, 8, hipMemcpyDeviceToHost, x->st));
+    ITX_HIP(hipStreamSynchronize(x->st));
     *n_vetoed = c[0];
     return ITX_OK;
 }

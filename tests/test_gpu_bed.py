@@ -171,6 +171,12 @@ def test_geometries(inf):
     got_b, got_v, want_b, want_v, _, _ = device_texts(inf, recs, p)
     assert got_b == want_b and got_v == want_v
     assert b"A" * 40_000 + b"\n" in got_b and b"C" * 150_000 + b"\n" in got_b
+    # one batch of 1026 tiles: every thread of the tile scan's workgroup (1024) takes two tiles, the last chunk ragged, the rest empty
+    n = 1024 * TILE + 257
+    recs = [bc.record(tid=i % 4, pos=100 + i, mapq=[37, 3][i % 5 == 4], flag=16 if i % 3 == 0 else 0, qname=b"t%d\0" % i, cigar=((0, 20),)) for i in range(n)]
+    got_b, got_v, want_b, want_v, _, st = device_texts(inf, recs, p, cap=n)
+    assert got_b == want_b and got_v == want_v and st["batches"] == 1
+    assert want_b.count(b"\n") > 1025 * TILE > want_v.count(b"\n") > 0
 
 
 def test_plain_device_arrays_and_two_batches_in_flight(inf):

@@ -119,6 +119,24 @@ def test_one_window(inf, n, kind):
     nm.close()
 
 
+def test_one_batch_of_more_than_1024_tiles(inf):
+    """1026 tiles in ONE batch: the tile scan's workgroup has 1024 threads, so each takes a chunk of two tiles, walks it twice (sum,
+    then write back), the last chunk is ragged and the threads behind it are empty. (finish scans the text over 684 tiles.)"""
+    import torch
+    n = 1024 * 256 + 257
+    recs = [bc.record(tid=i % 4, pos=100 + i, qname=b"t%d\0" % i, cigar=((0, 20),)) for i in range(n)]
+    names = [b"t%d" % i for i in range(n)]
+    idx = np.arange(n)
+    rows = np.where(idx % 3 != 1, idx % 50, -1).astype(np.int32)
+    nm = eng.Names(batch_capacity=n)
+    assert window(inf, bc.bam_bytes(HEADER, recs)) == n
+    assert nm.append_window(inf, 0, n, torch.from_numpy(rows).cuda()) == 0
+    nm.wait_kernels()
+    check(nm.finish(50), rows, names, 50)
+    assert nm.stats()["batches"] == 1 and nm.stats()["entries"] == int((rows >= 0).sum())
+    nm.close()
+
+
 # ---- 2. batches, two windows, growth
 
 def test_batches_two_windows_and_a_growing_pool(inf, monkeypatch):
