@@ -19,11 +19,6 @@
 
 #define BATCH_RECORDS (4u << 20)
 
-static void chk(int rc, const char *what)
-{
-    if (rc != ITX_OK) die("%s: %s", what, itx_last_error());
-}
-
 /* ---- the bedGraph file (generic.c:1064-1078): lines chopped on white space, parsed in parallel pieces -------------- */
 typedef struct {
     int32_t *tid;              /* index into rm->chroms (the chromosomes that have rows), -1 otherwise */

@@ -39,13 +39,6 @@ static int stat_usage(void)
 }
 
 /* ITX_TIMING=1: phase wall times on stderr (not part of the reference's output) */
-static double now_s(void)
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
 static char *fmt_name(const char *prefix, const char *suffix)
 {
     char *s = NULL;

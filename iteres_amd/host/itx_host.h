@@ -8,6 +8,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stddef.h>
+#include <time.h>
 
 #include "../../include/iteres_amd.h"
 
@@ -19,6 +20,16 @@ void warnf(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 extern FILE *itx_err_stream;             /* where die / warnf write when not stderr (ranks > 0 of a multi-GPU job) */
 extern const char *itx_err_prefix;
 extern void (*itx_die_hook)(void);        /* run by die() before it leaves (rank 0 ends the ranks it started) */
+static inline double now_s(void)           /* seconds on the monotonic clock */
+{
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+static inline void chk(int rc, const char *what)   /* an ABI call that must not fail */
+{
+    if (rc != ITX_OK) die("%s: %s", what, itx_last_error());
+}
 void *xmalloc(size_t n);
 void *xcalloc(size_t n, size_t sz);
 void *xrealloc(void *p, size_t n);
@@ -253,6 +264,11 @@ int multi_device(void);
 int multi_comm_mode(void);
 int multi_selftest(void);
 const char *multi_comm_id(void);
+/* exchange.c: the ONE exchange of a multi-rank job. exchange_comm_early (helper thread, once the HIP runtime is up) starts the RCCL
+ * communicator beside the scan; exchange_partials exports the engine's partial into its own buffers (*d_u64 / *d_u32), agrees
+ * with the other ranks on RCCL or files, sums partials and meta[] onto rank 0 and ends the ranks above 0 */
+void exchange_comm_early(void);
+void exchange_partials(itx_engine *eng, uint64_t *meta, size_t n_meta, int timing, void **d_u64, void **d_u32);
 /* stream.c: what the writers read — itx_engine_finish, or, after a multi-GPU stream, the same from the reduced partial */
 int stream_finish(itx_engine *eng, const itx_result *res);
 /* filter -r with the lists built on the device: after run_stream, the number of names per table row (NULL: the host built the

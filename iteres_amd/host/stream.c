@@ -1,9 +1,9 @@
-/* stream.c — the record loop of the reference (generic.c:700-1062 stat copy, 343-697 filter copy) as a host
- * pipeline around the GPU engine: decode a batch into one pinned staging slot while the other slot is in
- * flight (itx_engine_staging / submit_slot / wait_slot), keep what is order-dependent or text on the host
- * (progress banners, the "chromosome not in the size file" warnings, read names for filter -r, and — side.c —
- * the -R duplicate filter, the -B/-V bed lines and the XA veto for the batches the device cannot take: BAM windows the device
- * decoder parsed get all three where they lie, include/iteres_amd.h itx_dedup_* / itx_bed_* / itx_xaveto_*). */
+/* stream.c — the record loop of the reference (generic.c:700-1062 stat copy, 343-697 filter copy) as a host pipeline around the
+ * GPU engine. run_stream is the list of steps; record_loop is the dispatcher: a BAM window the device decoder parsed goes to the
+ * engine where it lies (device_window: per batch bed text, names, veto, progress, submit — the reference's order) when the file
+ * may hand off and window_goes_direct; everything else, and the rest of a window only the host can read (host_takes_over), goes
+ * through host_batch: one pinned staging slot decoded while the other is in flight, then warnings with progress, -R and bed lines
+ * in file order, the XA veto (side.c), submit. First in the file: the helper thread that starts the runtime and decodes ahead. */
 #define _GNU_SOURCE
 #include "itx_host.h"
 
@@ -16,13 +16,6 @@
 #include <time.h>
 
 #define BATCH_RECORDS (4u << 20)
-
-static double now_s(void)
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
 
 /* The first HIP call costs a few hundred milliseconds of runtime start-up; a helper thread pays them while the main
  * thread parses the rmsk file. */
@@ -103,73 +96,23 @@ static void use_device_reader(void)
 static int warm_splittable;
 static size_t warm_input_bytes;               /* size of all alignment files together (0: unknown) */
 
-/* The communicator of a multi-rank job is made while the stream is being read: ncclCommInitRank takes seconds (bootstrap
- * over the network interface, one ring per link) and needs nothing of the data — the exchange at the end only joins it. */
-static struct {
-    pthread_t th;
-    int on, rc, done;
-    itx_comm *comm;
-    char err[400];
-} early_comm;
 static char warm_err[400];                    /* the helper thread's last error (itx_last_error is per thread) */
-/* Which way the partials travel is agreed on by ALL ranks: every rank leaves a marker next to the communicator id when its
- * attempt at an RCCL communicator has ended — "ok" or "fail" — and the exchange is RCCL only when every marker says ok. A
- * rank that fails alone (its device, its copy of the library, the id file) would otherwise switch to files while the others
- * sit in ncclCommInitRank / ncclReduce, which have no timeout. */
-static void comm_marker_path(char *buf, size_t n, int rank) { snprintf(buf, n, "%s.st%d", multi_comm_id(), rank); }
-static void comm_marker_write(int ok)
+
+/* generic.c:781-791 (-C): NULL when the record is skipped ("GL*"), else the (possibly renamed) chromosome */
+static const char *rename_chr(const char *name, int add_chr, char *buf, size_t bufsz)
 {
-    if (multi_world() <= 1) return;
-    char path[700], tmp[720];
-    comm_marker_path(path, sizeof path, multi_rank());
-    snprintf(tmp, sizeof tmp, "%s.tmp", path);
-    FILE *f = fopen(tmp, "w");
-    if (!f) return;
-    fputs(ok ? "ok" : "fail", f);
-    if (fclose(f) == 0 && rename(tmp, path) != 0) unlink(tmp);
-}
-/* 1: every rank has a communicator; 0: some rank has none (all take the files); -1: a marker never came */
-static int comm_agree(double timeout_s)
-{
-    const double t0 = now_s();
-    for (unsigned spins = 0;; spins++) {
-        int n_ok = 0;
-        for (int r = 0; r < multi_world(); r++) {
-            char path[700], w[8] = {0};
-            comm_marker_path(path, sizeof path, r);
-            FILE *f = fopen(path, "r");
-            if (!f) continue;
-            const size_t k = fread(w, 1, 7, f);
-            fclose(f);
-            if (k >= 4 && memcmp(w, "fail", 4) == 0) return 0;
-            if (k >= 2 && memcmp(w, "ok", 2) == 0) n_ok++;
-        }
-        if (n_ok == multi_world()) return 1;
-        if (now_s() - t0 > timeout_s) return -1;
-        usleep(spins < 2000 ? 200 : 2000);
+    if (!add_chr) return name;
+    if (strncmp(name, "GL", 2) == 0) return NULL;
+    if (strcasecmp(name, "MT") == 0) return "chrM";
+    if (strncmp(name, "chr", 3) != 0) {
+        snprintf(buf, bufsz, "chr%s", name);
+        return buf;
     }
-}
-static void comm_markers_remove(void)
-{
-    for (int r = 0; r < multi_world(); r++) {
-        char path[700];
-        comm_marker_path(path, sizeof path, r);
-        unlink(path);
-    }
-}
-static void *early_comm_main(void *arg)
-{
-    (void)arg;
-    early_comm.rc = itx_comm_create(multi_rank(), multi_world(), multi_device(), multi_comm_id(), ITX_COMM_RCCL, &early_comm.comm);
-    if (early_comm.rc != ITX_OK) snprintf(early_comm.err, sizeof early_comm.err, "%s", itx_last_error());
-    comm_marker_write(early_comm.rc == ITX_OK);
-    __atomic_store_n(&early_comm.done, 1, __ATOMIC_RELEASE);
-    return NULL;
+    return name;
 }
 
 /* generic.c:781-801 for one reference name of a BAM header: its chromosome in the size file, -1 when it is not there (or its
  * size reads as "not found": generic.c:796-797), -2 when -C drops it */
-static const char *rename_chr(const char *name, int add_chr, char *buf, size_t bufsz);
 static int32_t chrom_of_target(const char *target, const run_opts *o, const sizes_t *chr_sizes)
 {
     char buf[4096];
@@ -204,6 +147,16 @@ void stream_prefetch_allow(const run_opts *o, int filter_mode, int allowed)
 }
 void stream_sizes_ready(const sizes_t *chr_sizes) { __atomic_store_n(&pre_sizes, chr_sizes, __ATOMIC_RELEASE); }
 
+/* May this window go to the engine where it lies? Not with XA tags while the veto is on, unless the veto may run on the device
+ * too (itx_xaveto_*); not with a mapped record on a chromosome the size file lacks (the warning is per record, in file order). */
+static int window_goes_direct(int wfl, const uint8_t *seen, const int32_t *t2c, int nt, int veto_on, int dev_veto)
+{
+    if (veto_on && (wfl & 2) && !dev_veto) return 0;
+    for (int t = 0; t < nt; t++)
+        if (seen[t] && t2c[t] == -1) return 0;
+    return 1;
+}
+
 static void prefetch_records(aln_reader *rd)
 {
     const double t0 = now_s();
@@ -226,13 +179,10 @@ static void prefetch_records(aln_reader *rd)
     }
     const int veto_on = o->xa_veto && !pre_filter_mode;
     while (!__atomic_load_n(&pre_stop, __ATOMIC_ACQUIRE)) {
-        int wfl = 0, ok = 1;
+        int wfl = 0;
         const uint8_t *seen = NULL;
         if (!aln_device_window(rd, &wfl, &seen)) break;                         /* end of input */
-        if (veto_on && (wfl & 2)) break;
-        for (int t = 0; t < nt && ok; t++)
-            if (seen[t] && t2c[t] == -1) ok = 0;
-        if (!ok || aln_device_left(rd) > itx_backlog_room(pre_bl)) break;
+        if (!window_goes_direct(wfl, seen, t2c, nt, veto_on, 0) || aln_device_left(rd) > itx_backlog_room(pre_bl)) break;
         itx_batch db;
         const size_t n = aln_read_batch_device(rd, SIZE_MAX, &db);
         if (n == 0) break;
@@ -282,9 +232,7 @@ static void *warm_main(void *arg)
     const double a = now_s();
     const int ndev = itx_device_count();
     const double b = now_s();
-    if (ndev > 0 && (multi_world() > 1 || multi_selftest()) && multi_comm_mode() == ITX_COMM_RCCL && !getenv("ITX_NO_EARLY_COMM") &&
-        pthread_create(&early_comm.th, NULL, early_comm_main, NULL) == 0)
-        early_comm.on = 1;
+    if (ndev > 0) exchange_comm_early();                                 /* a multi-rank job: the communicator is made beside the scan */
     double t_created = b, t_pinned = b;
     int inf_rc = ITX_OK;
     /* the compressed chunks the reader rotates through are page-locked, which takes its time (0.1 - 0.2 s for the first two): a
@@ -413,57 +361,89 @@ static void gpu_warmup_join(void)
     warm_on = 0;
 }
 
-static void chk(int rc, const char *what)
-{
-    if (rc != ITX_OK) die("%s: %s", what, itx_last_error());
-}
-
-/* -R on the device: every window, right after its records are parsed (aln_set_window_hook) */
-static double t_dedup;
-static void dedup_window(void *ctx, size_t n_rec)
-{
-    (void)n_rec;
-    const double t0 = now_s();
-    chk(itx_bamwin_dedup(g_inflater, (itx_dedup *)ctx), "itx_bamwin_dedup");
-    t_dedup += now_s() - t0;
-}
-
-/* -B / -V on the device (csrc/itx_bed.hip): the text of a batch is started right after the batch is taken and written to the
- * files one batch later, so that the copy and the fwrite run beside the next batch's kernels. Both routes write to the same
- * FILE: whatever is pending is written before the host route prints a line. */
-static int bed_pending;
-static void bed_write_out(itx_bed *bd, FILE *bed_f, FILE *bed_uniq_f, int discard)
-{
-    itx_bed_text tx;
-    chk(itx_bed_collect(bd, &tx), "itx_bed_collect");
-    bed_pending--;
-    if (discard) return;
-    if (bed_f && tx.all_bytes && fwrite(tx.all, 1, tx.all_bytes, bed_f) != tx.all_bytes) die("writing the bed file: %s", strerror(errno));
-    if (bed_uniq_f && tx.uniq_bytes && fwrite(tx.uniq, 1, tx.uniq_bytes, bed_uniq_f) != tx.uniq_bytes) die("writing the unique bed file: %s", strerror(errno));
-}
-
-/* generic.c:781-791 (-C): NULL when the record is skipped ("GL*"), else the (possibly renamed) chromosome */
-static const char *rename_chr(const char *name, int add_chr, char *buf, size_t bufsz)
-{
-    if (!add_chr) return name;
-    if (strncmp(name, "GL", 2) == 0) return NULL;
-    if (strcasecmp(name, "MT") == 0) return "chrM";
-    if (strncmp(name, "chr", 3) != 0) {
-        snprintf(buf, bufsz, "chr%s", name);
-        return buf;
-    }
-    return name;
-}
-
 typedef struct {
     uint32_t row;
     char *name;
 } hit_name;
 
+/* ---- one run of run_stream */
 typedef struct {
-    hit_name *v;
-    size_t n, cap;
-} hit_names;
+    const run_opts *o;
+    const rmsk_t *rm;
+    const sizes_t *chr_sizes;
+    int filter_mode, multi_file, timing;
+    int want_bed, want_qnames;
+    int veto_on;                                  /* filter.c:134 passes diffSubfam = 0 */
+    int dev_veto;                                 /* the veto may run on the device (not ITX_HOST_VETO) */
+    itx_table *tab;
+    itx_engine *eng;
+    itx_params p;
+    /* the four side objects, each with its host twin. -R: one set over all files */
+    itx_dedup *dd;
+    dup_set *dups;
+    names_t chr_names;                            /* identities of the chromosome strings inside -R keys */
+    double t_dedup;
+    itx_xaveto *xv;                               /* the veto on the device (windows that stay in HBM) */
+    xa_index *xi;
+    /* -B / -V on the device (csrc/itx_bed.hip): the text of a batch is started right after the batch is taken and written to
+     * the files one batch later, so that the copy and the fwrite run beside the next batch's kernels. Both routes write to the
+     * same FILE: whatever is pending is written before the host route prints a line. */
+    itx_bed *bd;
+    int bed_pending;
+    FILE *bed_f, *bed_uniq_f;
+    itx_names *nm;                                /* the read lists gathered on the device (filter -r) */
+    struct { hit_name *v; size_t n, cap; } hn;    /* ... and by the host */
+    struct { uint32_t *rows; uint64_t *off; char *bytes; size_t cap_n, cap_b; } nbuf;
+    /* the host route: two pinned slots, taken when a batch first goes that way; s is filled next, pend[] are in flight */
+    itx_staging st[2];
+    aln_side side[2];                             /* what the host keeps per record beside the SoA */
+    size_t pend[2];
+    int have_slots, any_side, s;
+    host_iv *iv;
+    uint8_t *live;                                /* the record reached the bed / veto stage */
+    names_t warned;
+    unsigned long long ends;
+    unsigned progress_every;
+    host_counts *hc;
+    unsigned long long veto_dev_batches, veto_host_batches, bed_host_batches, names_host_batches, boundary_missed;
+    /* the list of files and this rank's share of each (one rank: all of it) */
+    char *arg, *files[100];
+    int n_files, shared;
+    share_t share[100];
+} stream_run;
+
+/* ---- one file of it */
+typedef struct {
+    aln_reader *rd;
+    int nt;                                       /* the header's references: chromosome, -R identity, (renamed) name of each */
+    int32_t *t2c;
+    uint32_t *t2id;
+    char **t2name;
+    int dev_bed, dev_names, handoff_ok, any_paired;
+    double t_wait, t_read, t_host, t_submit;
+    double t_open0, t_opened, t_loop_done;
+} stream_file;
+
+/* -R on the device: every window, right after its records are parsed (aln_set_window_hook) */
+static void dedup_window(void *ctx, size_t n_rec)
+{
+    (void)n_rec;
+    stream_run *r = ctx;
+    const double t0 = now_s();
+    chk(itx_bamwin_dedup(g_inflater, r->dd), "itx_bamwin_dedup");
+    r->t_dedup += now_s() - t0;
+}
+
+static void bed_write_out(stream_run *r, int discard)
+{
+    itx_bed_text tx;
+    chk(itx_bed_collect(r->bd, &tx), "itx_bed_collect");
+    r->bed_pending--;
+    if (discard) return;
+    if (r->bed_f && tx.all_bytes && fwrite(tx.all, 1, tx.all_bytes, r->bed_f) != tx.all_bytes) die("writing the bed file: %s", strerror(errno));
+    if (r->bed_uniq_f && tx.uniq_bytes && fwrite(tx.uniq, 1, tx.uniq_bytes, r->bed_uniq_f) != tx.uniq_bytes)
+        die("writing the unique bed file: %s", strerror(errno));
+}
 
 /* filter -r on the device (csrc/itx_names.hip): the lists are gathered where the records lie; what the host route reads goes to
  * the same pool, in stream order (itx_names_append_host), so the end of the stream has one list to sort whatever route a window
@@ -478,13 +458,6 @@ static int names_by_host(void)
     const char *e = getenv("ITX_HOST_NAMES");
     return e && *e ? atoi(e) != 0 : NAMES_HOST_DEFAULT;
 }
-static unsigned long long names_host_batches;
-static struct {
-    uint32_t *rows;
-    uint64_t *off;
-    char *bytes;
-    size_t cap_n, cap_b;
-} nbuf;
 static const uint32_t *g_names_cnt;                                   /* after the stream: names per row (stream_names_counts) */
 
 const uint32_t *stream_names_counts(void) { return g_names_cnt; }
@@ -497,51 +470,55 @@ void stream_names_free(char **locus_names)
 }
 
 /* the batch's hits to the device pool: (row, name) in record order */
-static void names_to_device(const itx_staging *st, aln_side *side, size_t n)
+static void names_to_device(stream_run *r, int k)
 {
-    size_t m = 0, b = 0;
-    if (nbuf.cap_n < n + 1) {
-        nbuf.cap_n = n + n / 4 + 1;
-        nbuf.rows = xrealloc(nbuf.rows, sizeof(uint32_t) * nbuf.cap_n);
-        nbuf.off = xrealloc(nbuf.off, sizeof(uint64_t) * (nbuf.cap_n + 1));
+    const itx_staging *st = &r->st[k];
+    aln_side *side = &r->side[k];
+    size_t m = 0, b = 0, n = r->pend[k];
+    if (r->nbuf.cap_n < n + 1) {
+        r->nbuf.cap_n = n + n / 4 + 1;
+        r->nbuf.rows = xrealloc(r->nbuf.rows, sizeof(uint32_t) * r->nbuf.cap_n);
+        r->nbuf.off = xrealloc(r->nbuf.off, sizeof(uint64_t) * (r->nbuf.cap_n + 1));
     }
     for (size_t i = 0; i < n; i++) {
         if (st->hit_row[i] >= 0) {
-            const size_t k = strlen(side->qname[i]);
-            if (nbuf.cap_b < b + k + 1) {
-                nbuf.cap_b = (b + k + 1) * 2;
-                nbuf.bytes = xrealloc(nbuf.bytes, nbuf.cap_b);
+            const size_t len = strlen(side->qname[i]);
+            if (r->nbuf.cap_b < b + len + 1) {
+                r->nbuf.cap_b = (b + len + 1) * 2;
+                r->nbuf.bytes = xrealloc(r->nbuf.bytes, r->nbuf.cap_b);
             }
-            nbuf.rows[m] = (uint32_t)st->hit_row[i];
-            nbuf.off[m++] = b;
-            memcpy(nbuf.bytes + b, side->qname[i], k);
-            b += k;
+            r->nbuf.rows[m] = (uint32_t)st->hit_row[i];
+            r->nbuf.off[m++] = b;
+            memcpy(r->nbuf.bytes + b, side->qname[i], len);
+            b += len;
         }
         free(side->qname[i]);
         side->qname[i] = NULL;
     }
-    nbuf.off[m] = b;
-    chk(itx_names_append_host(g_names, nbuf.rows, nbuf.bytes, nbuf.off, m), "itx_names_append_host");
+    r->nbuf.off[m] = b;
+    chk(itx_names_append_host(r->nm, r->nbuf.rows, r->nbuf.bytes, r->nbuf.off, m), "itx_names_append_host");
 }
 
-/* filter -r: keep the names of the records that chose a row, free the others */
-static void collect_names(hit_names *hn, const itx_staging *st, aln_side *side, size_t n)
+/* filter -r: keep the names of the records of slot k that chose a row, free the others */
+static void collect_names(stream_run *r, int k)
 {
-    names_host_batches++;
-    if (g_names) {
-        names_to_device(st, side, n);
+    const itx_staging *st = &r->st[k];
+    aln_side *side = &r->side[k];
+    r->names_host_batches++;
+    if (r->nm) {
+        names_to_device(r, k);
         return;
     }
-    for (size_t i = 0; i < n; i++) {
+    for (size_t i = 0; i < r->pend[k]; i++) {
         const int32_t row = st->hit_row[i];
         if (row >= 0) {
-            if (hn->n == hn->cap) {
-                hn->cap = hn->cap ? hn->cap * 2 : 1 << 16;
-                hn->v = xrealloc(hn->v, sizeof *hn->v * hn->cap);
+            if (r->hn.n == r->hn.cap) {
+                r->hn.cap = r->hn.cap ? r->hn.cap * 2 : 1 << 16;
+                r->hn.v = xrealloc(r->hn.v, sizeof *r->hn.v * r->hn.cap);
             }
-            hn->v[hn->n].row = (uint32_t)row;
-            hn->v[hn->n].name = side->qname[i];
-            hn->n++;
+            r->hn.v[r->hn.n].row = (uint32_t)row;
+            r->hn.v[r->hn.n].name = side->qname[i];
+            r->hn.n++;
         } else {
             free(side->qname[i]);
         }
@@ -565,6 +542,33 @@ static void side_release(aln_side *side, size_t n, int keep_qnames)
     }
 }
 
+/* wait for host slot k and collect what its previous batch left behind; returns the seconds waited */
+static double drain_slot(stream_run *r, int k)
+{
+    const double t0 = now_s();
+    chk(itx_engine_wait_slot(r->eng, k), "itx_engine_wait_slot");
+    const double waited = now_s() - t0;
+    if (!r->pend[k]) return waited;
+    if (r->want_qnames) collect_names(r, k);
+    side_release(&r->side[k], r->pend[k], r->want_qnames);
+    r->pend[k] = 0;
+    return waited;
+}
+/* both (idle_too: or only those with a batch in flight), the older batch first: the read lists are in file order */
+static void drain_slots(stream_run *r, int idle_too)
+{
+    for (int kk = 0; kk < 2; kk++)
+        if (idle_too || r->pend[r->s ^ kk]) drain_slot(r, r->s ^ kk);
+}
+
+/* generic.c:760-761 for n records at once */
+static void progress_marks(stream_run *r, size_t n)
+{
+    for (unsigned long long m = (r->ends / r->progress_every + 1) * r->progress_every; m <= r->ends + n; m += r->progress_every)
+        fprintf(stderr, "\r* Processed read ends: %llu", m);
+    r->ends += n;
+}
+
 /* after a multi-GPU stream: the reduced partial (the engine's own buffers) the writers' arrays come from */
 static void *g_reduced_u64, *g_reduced_u32;
 
@@ -574,656 +578,617 @@ int stream_finish(itx_engine *eng, const itx_result *res)
     return itx_engine_finish(eng, res);
 }
 
-void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, int filter_mode, int multi_file,
-                unsigned progress_every, int want_qnames, itx_engine **eng_out, itx_table **tab_out, char ***locus_names,
-                host_counts *hc)
+/* ---- the steps of run_stream, in its order ------------------------------------------------------------------------------ */
+
+/* table: every chromosome of the size file is known to the engine (a read may land on one without repeats) */
+static void make_table_and_engine(stream_run *r)
 {
-    const int timing = getenv("ITX_TIMING") != NULL;
+    const rmsk_t *rm = r->rm;
+    const run_opts *o = r->o;
     struct timespec ts0, ts1;
     clock_gettime(CLOCK_MONOTONIC, &ts0);
     int ndev = itx_device_count();
     if (ndev <= 0) die("no usable MI355X (HIP) device: %s", ndev < 0 ? itx_last_error() : "none visible");
-    /* table: every chromosome of the size file is known to the engine (a read may land on one without repeats) */
-    const uint32_t n_chrom = chr_sizes->names.n;
-    itx_table *tab = NULL;
     size_t bad = 0;
-    int rc = itx_table_create(rm->rows, rm->n_rows, chr_sizes->value, (int)n_chrom, rm->rep_len, rm->reps.n, rm->fams.n, rm->clas.n, multi_device(),
-                              &tab, &bad);
+    int rc = itx_table_create(rm->rows, rm->n_rows, r->chr_sizes->value, (int)r->chr_sizes->names.n, rm->rep_len, rm->reps.n, rm->fams.n, rm->clas.n,
+                              multi_device(), &r->tab, &bad);
     if (rc == ITX_E_RANGE) {
-        const itx_row *r = &rm->rows[bad];
-        die("(%d %d) out of range (%d %d) in binKeeperAdd", (int)r->start, (int)r->end, 0, (int)chr_sizes->value[r->chrom]);
+        const itx_row *row = &rm->rows[bad];
+        die("(%d %d) out of range (%d %d) in binKeeperAdd", (int)row->start, (int)row->end, 0, (int)r->chr_sizes->value[row->chrom]);
     }
     chk(rc, "itx_table_create");
-    itx_params p;
-    memset(&p, 0, sizeof p);
-    p.mapq_min = o->mapq;
-    p.min_cov = o->min_cov;
-    p.extension = o->extension;
-    p.isize_max = o->isize;
-    p.treat_pe_as_se = o->treat;
-    p.discard_half_mapped = o->discard;
-    p.mode = filter_mode ? ITX_MODE_FILTER : ITX_MODE_STAT;
-    p.accum = ITX_ACCUM_DEFAULT;
-    itx_engine *eng = NULL;
-    chk(itx_engine_create(tab, &p, BATCH_RECORDS, &eng), "itx_engine_create");
+    r->p.mapq_min = o->mapq;
+    r->p.min_cov = o->min_cov;
+    r->p.extension = o->extension;
+    r->p.isize_max = o->isize;
+    r->p.treat_pe_as_se = o->treat;
+    r->p.discard_half_mapped = o->discard;
+    r->p.mode = r->filter_mode ? ITX_MODE_FILTER : ITX_MODE_STAT;
+    r->p.accum = ITX_ACCUM_DEFAULT;
+    chk(itx_engine_create(r->tab, &r->p, BATCH_RECORDS, &r->eng), "itx_engine_create");
     clock_gettime(CLOCK_MONOTONIC, &ts1);
-    if (timing) fprintf(stderr, "[itx timing] table build + engine %.3f s\n", (double)(ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double)(ts1.tv_nsec - ts0.tv_nsec));
-    itx_staging st[2];                            /* the pinned slots of the host route, taken when a batch first goes that way */
-    int have_slots = 0;
-    memset(st, 0, sizeof st);
+    if (r->timing) fprintf(stderr, "[itx timing] table build + engine %.3f s\n", (double)(ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double)(ts1.tv_nsec - ts0.tv_nsec));
+}
 
-    /* what the host keeps per record beside the SoA */
-    const int want_bed = o->bed_path || o->bed_uniq_path;
-    const int veto_on = o->xa_veto && !filter_mode;                    /* filter.c:134 passes diffSubfam = 0 */
-    aln_side side[2];
-    size_t pend[2] = {0, 0};
+static void open_outputs_and_side_buffers(stream_run *r)
+{
+    const run_opts *o = r->o;
     for (int k = 0; k < 2; k++) {
-        memset(&side[k], 0, sizeof side[k]);
-        side[k].want_qnames = want_qnames || want_bed;
-        side[k].want_aux = veto_on || o->bed_path != NULL;
-        if (side[k].want_qnames) side[k].qname = xcalloc(BATCH_RECORDS, sizeof(char *));
-        if (side[k].want_aux) {
-            side[k].xa = xcalloc(BATCH_RECORDS, sizeof(char *));
-            side[k].nm = xcalloc(BATCH_RECORDS, sizeof(int32_t));
+        r->side[k].want_qnames = r->want_qnames || r->want_bed;
+        r->side[k].want_aux = r->veto_on || o->bed_path != NULL;
+        if (r->side[k].want_qnames) r->side[k].qname = xcalloc(BATCH_RECORDS, sizeof(char *));
+        if (r->side[k].want_aux) {
+            r->side[k].xa = xcalloc(BATCH_RECORDS, sizeof(char *));
+            r->side[k].nm = xcalloc(BATCH_RECORDS, sizeof(int32_t));
         }
     }
-    const int any_side = side[0].want_qnames || side[0].want_aux;
-    hit_names hn = {NULL, 0, 0};
-    host_iv *iv = NULL;
-    uint8_t *live = NULL;                                              /* the record reached the bed / veto stage */
-    if (o->dedup || want_bed || veto_on) {
-        iv = xcalloc(BATCH_RECORDS, sizeof *iv);
-        live = xcalloc(BATCH_RECORDS, 1);
+    r->any_side = r->side[0].want_qnames || r->side[0].want_aux;
+    if (o->dedup || r->want_bed || r->veto_on) {
+        r->iv = xcalloc(BATCH_RECORDS, sizeof *r->iv);
+        r->live = xcalloc(BATCH_RECORDS, 1);
     }
-    itx_dedup *dd = NULL;
-    dup_set *dups = NULL;
-    names_t chr_names;                                                 /* identities of the chromosome strings inside -R keys */
-    names_init(&chr_names);
-    xa_index *xi = NULL;
-    itx_xaveto *xv = NULL;                                             /* the veto on the device (windows that stay in HBM) */
-    const int dev_veto = !getenv("ITX_HOST_VETO");
-    unsigned long long veto_dev_batches = 0, veto_host_batches = 0;
-    itx_bed *bd = NULL;                                                /* the bed text built on the device (windows that stay in HBM) */
-    unsigned long long bed_host_batches = 0;
-    itx_names *nm = NULL;                                              /* the read lists gathered on the device (filter -r) */
-    names_host_batches = 0;
-    FILE *bed_f = NULL, *bed_uniq_f = NULL;
+    names_init(&r->chr_names);
+    names_init(&r->warned);
     /* mustOpen, cuskent/common.c:2543-2568 */
-    if (o->bed_path && !(bed_f = fopen(o->bed_path, "w"))) die("mustOpen: Can't open %s to write: %s", o->bed_path, strerror(errno));
-    if (o->bed_uniq_path && !(bed_uniq_f = fopen(o->bed_uniq_path, "w")))
+    if (o->bed_path && !(r->bed_f = fopen(o->bed_path, "w"))) die("mustOpen: Can't open %s to write: %s", o->bed_path, strerror(errno));
+    if (o->bed_uniq_path && !(r->bed_uniq_f = fopen(o->bed_uniq_path, "w")))
         die("mustOpen: Can't open %s to write: %s", o->bed_uniq_path, strerror(errno));
-    unsigned long long ends = 0;
+}
 
-    /* the list of files (stat: comma separated, generic.c:725; filter: one file) */
-    char *arg = xstrdup(o->aln_arg);
-    char *files[100];
-    int n_files = 0;
-    if (multi_file) {
-        for (char *s = arg; n_files < 100;) {
-            files[n_files++] = s;
+/* the list of files (stat: comma separated, generic.c:725; filter: one file) and this rank's share of every one */
+static void list_files_and_shares(stream_run *r)
+{
+    r->arg = xstrdup(r->o->aln_arg);
+    if (r->multi_file) {
+        for (char *s = r->arg; r->n_files < 100;) {
+            r->files[r->n_files++] = s;
             char *c = strchr(s, ',');
             if (!c) break;
             *c = 0;
             s = c + 1;
         }
     } else {
-        files[n_files++] = arg;
+        r->files[r->n_files++] = r->arg;
     }
-    names_t warned;
-    names_init(&warned);
-    /* this rank's share of every file (one rank: all of it) */
-    share_t share[100];
-    const int world = multi_world(), rank = multi_rank();
-    int shared = plan_shares(files, n_files, warm_splittable && !getenv("ITX_HOST_INFLATE"), rank, world, multi_min_share(), share) && world > 1;
-    unsigned long long boundary_missed = 0;
-    /* the helper thread (HIP start-up, device decoder, first file opened and decoding ahead) has had the rmsk parse and the
-     * table build to finish */
+    r->shared = plan_shares(r->files, r->n_files, warm_splittable && !getenv("ITX_HOST_INFLATE"), multi_rank(), multi_world(), multi_min_share(), r->share) &&
+                multi_world() > 1;
+}
+
+/* the helper thread (HIP start-up, device decoder, first file opened and decoding ahead) has had the rmsk parse and the table
+ * build to finish */
+static void join_helper_thread(stream_run *r)
+{
     const double t_join = now_s();
     if (getenv("ITX_PREFETCH_HOLD_MS")) usleep((useconds_t)atol(getenv("ITX_PREFETCH_HOLD_MS")) * 1000u);     /* tests: a table that takes its time */
     __atomic_store_n(&pre_stop, 1, __ATOMIC_RELEASE);                  /* table and engine are there: the helper thread finishes the window it is at */
     gpu_warmup_join();
-    if (timing) fprintf(stderr, "[itx timing] waited %.3f s for the helper thread\n", now_s() - t_join);
+    if (r->timing) fprintf(stderr, "[itx timing] waited %.3f s for the helper thread\n", now_s() - t_join);
     if (g_inflater) use_device_reader();
-    /* -R: one set over all files, like `dup` (generic.c:721). BAM decoded on the device: the set lives there too
-     * (csrc/itx_dedup.hip) and marks a window's duplicates where the window lies, right after it is parsed; SAM text, the host
-     * decoder and ITX_HOST_DEDUP=1: the host's hash set, record by record */
+}
+
+/* -R: one set over all files, like `dup` (generic.c:721). BAM decoded on the device: the set lives there too
+ * (csrc/itx_dedup.hip) and marks a window's duplicates where the window lies, right after it is parsed; SAM text, the host
+ * decoder and ITX_HOST_DEDUP=1: the host's hash set, record by record */
+static void choose_dedup_set(stream_run *r)
+{
+    const run_opts *o = r->o;
     if (o->dedup && g_inflater && !o->is_sam && !getenv("ITX_HOST_DEDUP")) {
         size_t cells = warm_input_bytes / 24;                          /* a first guess at the keys to come; the table grows */
         if (cells < ((size_t)1 << 20)) cells = (size_t)1 << 20;
         if (cells > ((size_t)1 << 28)) cells = (size_t)1 << 28;
-        chk(itx_dedup_create(multi_device(), chr_sizes->value, (int)n_chrom, &p, cells, &dd), "itx_dedup_create");
+        chk(itx_dedup_create(multi_device(), r->chr_sizes->value, (int)r->chr_sizes->names.n, &r->p, cells, &r->dd), "itx_dedup_create");
     }
-    dups = o->dedup && !dd ? dup_set_new() : NULL;
-    if (shared && !g_inflater) die("rank %d: the device decoder did not come up: %s", rank, warm_err[0] ? warm_err : itx_last_error());
-    /* pass 0: this rank's shares, then the exchange. pass 1 (rank 0 only, and only when a share boundary did not hold —
-     * the split points are guesses that the rank before verifies): the whole job again by this rank alone */
-    for (int pass = 0; pass < 2; pass++) {
-    if (pass == 1) {
-        if (!boundary_missed) break;
-        fprintf(stderr, "[iteres] note: a share boundary was not a record start; scanning the input again with one GPU\n");
-        chk(itx_engine_reset(eng), "itx_engine_reset");
-        if (hc) hc->diff_subfam = hc->dup_unique = 0;
-        ends = 0;
-        for (int i = 0; i < n_files; i++) share[i].lo = 0, share[i].hi = SIZE_MAX;
-        shared = 0;
-    }
-    for (int fi = 0; fi < n_files; fi++) {
-        if (multi_file) fprintf(stderr, "\n* Processing %s\n", files[fi]);
-        if (share[fi].lo == share[fi].hi) continue;                      /* nothing of this file is this rank's */
-        const double t_open0 = now_s();
-        aln_reader *rd = NULL;
-        int drain_backlog = 0;
-        if (fi == 0 && pass == 0 && warm_reader && warm_first && strcmp(files[0], warm_first) == 0 && warm_lo == share[0].lo && warm_hi == share[0].hi) {
-            rd = warm_reader;                                            /* opened and decoding since the helper thread came up */
-            warm_reader = NULL;
-            drain_backlog = pre_bl != NULL;
-        } else {
-            if (warm_reader && fi == 0 && pass == 0) {                   /* opened for another share than this plan's: not used */
-                aln_close(warm_reader);
-                warm_reader = NULL;
-            }
-            rd = (share[fi].lo == 0 && share[fi].hi == SIZE_MAX) ? aln_open(files[fi], o->is_sam) : aln_open_range(files[fi], share[fi].lo, share[fi].hi);
-        }
-        const double t_opened = now_s();
-        if (!rd) {
-            fprintf(stderr, "Fail to open %s file %s\n", o->is_sam ? "SAM" : "BAM", o->aln_arg);
-            die("Error\n");
-        }
-        const int nt = aln_n_targets(rd);
-        int32_t *t2c = xmalloc(sizeof(int32_t) * (size_t)(nt + 1));
-        uint32_t *t2id = xcalloc((size_t)nt + 1, sizeof(uint32_t));
-        char **t2name = xcalloc((size_t)nt + 1, sizeof(char *));
-        for (int t = 0; t < nt; t++) {
-            char buf[4096];
-            const char *nm = rename_chr(aln_target_name(rd, t), o->add_chr, buf, sizeof buf);
-            t2name[t] = nm ? xstrdup(nm) : NULL;
-            if (!nm) {
-                t2c[t] = -2;
-            } else {
-                /* generic.c:796-797: cend = size-1 with 2 as the "not found" default; a listed size of 2 reads the same */
-                t2c[t] = chrom_of_target(aln_target_name(rd, t), o, chr_sizes);
-                if (dups || dd) t2id[t] = names_intern(&chr_names, nm);
-            }
-        }
-        chk(itx_engine_set_tidmap(eng, t2c, nt > 0 ? nt : 0), "itx_engine_set_tidmap");
-        if (xv) chk(itx_xaveto_set_tidmap(xv, t2c, nt > 0 ? nt : 0), "itx_xaveto_set_tidmap");
-        if (bd) chk(itx_bed_set_tidmap(bd, t2c, (const char *const *)t2name, nt > 0 ? nt : 0), "itx_bed_set_tidmap");
-        if (dd) {
-            chk(itx_dedup_set_tidmap(dd, t2c, t2id, nt > 0 ? nt : 0), "itx_dedup_set_tidmap");
-            aln_set_window_hook(rd, dedup_window, dd);
-        }
-        if (nt == 0) {
-            /* no references: nothing can map; still count the read ends */
-            int32_t none = -1;
-            chk(itx_engine_set_tidmap(eng, &none, 1), "itx_engine_set_tidmap");
-        }
-        int s = 0, any_paired = 0, aux_xa = 0;
-        double t_wait = 0, t_read = 0, t_host = 0, t_submit = 0, tq;
-        /* Nothing per record is the host's business when no option asks for names, -R or bed lines: a window of records the
-         * device decoder parsed then goes to the engine where it lies, in HBM. What is left for the host to look at comes with
-         * the window — does a record carry an XA tag (the veto needs its strings: host route for that window), is a mapped
-         * record on a chromosome the size file lacks (the warning is per record, in file order: host route). */
-        /* The bed lines no longer keep a window on the host: the device decoder's windows get their text built where they lie
-         * (ITX_HOST_BED=1: by the host, as before). */
-        const int dev_bed = want_bed && g_inflater && !o->is_sam && !getenv("ITX_HOST_BED");
-        /* Nor do the read lists of filter -r on the device route (ITX_HOST_NAMES=0): the names are gathered from the window where
-         * it lies. */
-        const int dev_names = want_qnames && g_inflater && !o->is_sam && !names_by_host();
-        const int handoff_ok = !dups && (!want_bed || dev_bed) && (!want_qnames || dev_names);
-        if (dev_names && !nm) {
-            chk(itx_names_create(multi_device(), BATCH_RECORDS, 0, &nm), "itx_names_create");
-            g_names = nm;
-        }
-        if (dev_bed && !bd) {
-            chk(itx_bed_create(multi_device(), chr_sizes->value, (int)n_chrom, &p, (bed_f ? ITX_BED_ALL : 0) | (bed_uniq_f ? ITX_BED_UNIQ : 0), BATCH_RECORDS, &bd),
-                "itx_bed_create");
-            chk(itx_bed_set_tidmap(bd, t2c, (const char *const *)t2name, nt > 0 ? nt : 0), "itx_bed_set_tidmap");
-        }
-        if (drain_backlog) {
-            /* the records the helper thread parsed while the table was being built: first, in file order */
-            const double td = now_s();
-            unsigned long long got = 0;
-            for (size_t k = 0; k < pre_n; k++)
-                for (size_t off = 0; off < pre_v[k].n; off += BATCH_RECORDS) {
-                    const size_t m = pre_v[k].n - off < BATCH_RECORDS ? pre_v[k].n - off : BATCH_RECORDS;
-                    itx_batch db;
-                    chk(itx_backlog_batch(pre_bl, pre_v[k].at + off, pre_v[k].paired, &db), "itx_backlog_batch");
-                    for (unsigned long long mk = (ends / progress_every + 1) * progress_every; mk <= ends + m; mk += progress_every)
-                        fprintf(stderr, "\r* Processed read ends: %llu", mk);
-                    ends += m;
-                    got += m;
-                    chk(itx_engine_submit_device_own(eng, &db, m, NULL), "itx_engine_submit_device_own");
-                }
-            chk(itx_engine_wait_own(eng), "itx_engine_wait_own");
-            if (timing)
-                fprintf(stderr, "\n[itx timing] parsed ahead of the table by the helper thread: %llu records of %zu windows (%.3f s there), submitted in %.3f s\n", got, pre_n,
-                        pre_seconds, now_s() - td);
-        }
-        if (pre_bl && fi == 0 && pass == 0) {                            /* used or not (another share than the plan's): gone */
-            itx_backlog_destroy(pre_bl);
-            pre_bl = NULL;
-            free(pre_v);
-            pre_v = NULL;
-            pre_n = pre_cap = 0;
-        }
-        for (;;) {
-            if (handoff_ok) {
-                int wfl = 0, direct = 1;
-                const uint8_t *seen = NULL;
-                tq = now_s();
-                if (aln_device_window(rd, &wfl, &seen)) {
-                    /* a window with XA tags while the veto is on: the veto runs on the device too (itx_xaveto_*), batch by batch
-                     * (a window of records without sequence holds several batches); when a record needs the host's reading, the
-                     * host route takes over from that batch on */
-                    const int xa_window = veto_on && (wfl & 2);
-                    if (xa_window && !dev_veto) direct = 0;
-                    for (int t = 0; t < nt && direct; t++)
-                        if (seen[t] && t2c[t] == -1) direct = 0;
-                    if (direct && xa_window && !xv) {
-                        uint32_t *row_rep = xmalloc(sizeof(uint32_t) * (rm->n_rows + 1)), *words = xa_rep_words(rm);
-                        for (size_t i = 0; i < rm->n_rows; i++) row_rep[i] = rm->rows[i].rep;
-                        chk(itx_xaveto_create(tab, &p, row_rep, words, (const char *const *)chr_sizes->names.name, (int)n_chrom, BATCH_RECORDS, &xv), "itx_xaveto_create");
-                        chk(itx_xaveto_set_tidmap(xv, t2c, nt > 0 ? nt : 0), "itx_xaveto_set_tidmap");
-                        free(row_rep);
-                        free(words);
-                    }
-                    if (direct) {
-                        int wfl2;
-                        do {
-                            itx_batch db;
-                            const size_t n = aln_read_batch_device(rd, BATCH_RECORDS, &db);
-                            t_read += now_s() - tq;
-                            if (n == 0) break;
-                            if (bd) {
-                                /* the bed lines come before the veto (generic.c:925 vs 972): built from the window as -R left it.
-                                 * The batch before this one is written out while this one's kernels run. */
-                                const double tb = now_s();
-                                uint64_t bhard = 0;
-                                if (aln_device_bed(rd, bd, n, &bhard) != 0) die("device bed: %s", itx_last_error());
-                                if (!bhard) bed_pending++;
-                                while (bed_pending > (bhard ? 0 : 1)) bed_write_out(bd, bed_f, bed_uniq_f, 0);
-                                t_host += now_s() - tb;
-                                if (bhard) {                                      /* a record only the host can print: this batch and the rest of the window */
-                                    aln_device_rewind(rd, n);
-                                    direct = 0;
-                                    tq = now_s();
-                                    break;
-                                }
-                            }
-                            if (nm) {
-                                /* Classify into the lists' buffer first, gather, and only then submit: a batch whose names
-                                 * only the host can read (*n_hard) has then not been counted yet, and the host route counts
-                                 * it once. (filter runs no veto: the rows are final.) What the host route still holds of
-                                 * earlier batches goes to the pool first — the lists are in file order. */
-                                const double tn = now_s();
-                                for (int k = 0; k < 2; k++) {
-                                    const int sk = s ^ k;                             /* the older of the two slots first */
-                                    if (!pend[sk]) continue;
-                                    chk(itx_engine_wait_slot(eng, sk), "itx_engine_wait_slot");
-                                    collect_names(&hn, &st[sk], &side[sk], pend[sk]);
-                                    side_release(&side[sk], pend[sk], want_qnames);
-                                    pend[sk] = 0;
-                                }
-                                uint64_t nhard = 0;
-                                chk(itx_engine_classify_device(eng, &db, n, itx_names_hits(nm), itx_names_stream(nm)), "itx_engine_classify_device");
-                                if (aln_device_names(rd, nm, n, itx_names_hits(nm), itx_names_stream(nm), &nhard) != 0) die("device read lists: %s", itx_last_error());
-                                t_host += now_s() - tn;
-                                if (nhard) {                                      /* this batch and the rest of the window: the host route */
-                                    aln_device_rewind(rd, n);
-                                    direct = 0;
-                                    tq = now_s();
-                                    break;
-                                }
-                            }
-                            if (xa_window) {
-                                /* classify, let the device read the tags of the classified records, mark the vetoed ones */
-                                const double tv = now_s();
-                                uint64_t vetoed = 0, hard = 0;
-                                chk(itx_engine_classify_device(eng, &db, n, itx_xaveto_hits(xv), itx_xaveto_stream(xv)), "itx_engine_classify_device");
-                                if (aln_device_xa_veto(rd, xv, n, &vetoed, &hard) != 0) die("device veto: %s", itx_last_error());
-                                t_host += now_s() - tv;
-                                if (hard) {                                       /* an alternative only strtol / the reference's assert can judge: this batch
-                                                                                   * and the rest of the window take the host route (the batches before are through) */
-                                    if (bd) bed_write_out(bd, bed_f, bed_uniq_f, 1);              /* the host prints this batch's lines */
-                                    aln_device_rewind(rd, n);
-                                    direct = 0;
-                                    tq = now_s();
-                                    break;
-                                }
-                                if (hc) hc->diff_subfam += vetoed;
-                                veto_dev_batches++;
-                            }
-                            for (unsigned long long m = (ends / progress_every + 1) * progress_every; m <= ends + n; m += progress_every)
-                                fprintf(stderr, "\r* Processed read ends: %llu", m);
-                            ends += n;
-                            tq = now_s();
-                            chk(itx_engine_submit_device_own(eng, &db, n, NULL), "itx_engine_submit_device_own");
-                            /* the window's arrays are the decoder's again once its last batch is through: the next parse
-                             * overwrites them */
-                            if (aln_device_left(rd) == 0) {
-                                chk(itx_engine_wait_own(eng), "itx_engine_wait_own");
-                                if (bd) chk(itx_bed_wait_kernels(bd), "itx_bed_wait_kernels");
-                                if (nm) chk(itx_names_wait_kernels(nm), "itx_names_wait_kernels");
-                            }
-                            t_submit += now_s() - tq;
-                            tq = now_s();
-                        } while (!aln_device_window(rd, &wfl2, &seen));                        /* until the next window's start (or the end) */
-                        if (direct) continue;
-                    }
-                }
-                t_read += now_s() - tq;
-                if (aln_device_exhausted(rd)) break;
-            }
-            while (bd && bed_pending) bed_write_out(bd, bed_f, bed_uniq_f, 0);        /* before the host prints a line of its own */
-            if (nm) chk(itx_names_wait_kernels(nm), "itx_names_wait_kernels");
-            if (!have_slots) {
-                chk(itx_engine_staging(eng, 0, &st[0]), "itx_engine_staging");
-                chk(itx_engine_staging(eng, 1, &st[1]), "itx_engine_staging");
-                have_slots = 1;
-            }
-            /* slot s: collect what its previous batch left behind, then refill */
-            tq = now_s();
-            chk(itx_engine_wait_slot(eng, s), "itx_engine_wait_slot");
-            t_wait += now_s() - tq;
-            if (pend[s]) {
-                if (want_qnames) collect_names(&hn, &st[s], &side[s], pend[s]);
-                side_release(&side[s], pend[s], want_qnames);
-                pend[s] = 0;
-            }
-            aux_xa = 0;                                                        /* per batch */
-            tq = now_s();
-            const size_t n = aln_read_batch(rd, &st[s], BATCH_RECORDS, any_side ? &side[s] : NULL, &any_paired, &aux_xa);
-            t_read += now_s() - tq;
-            if (n == 0) break;
-            tq = now_s();
-            /* generic.c:760-761 progress; generic.c:793-801 one warning per unknown chromosome, in file order. Batches
-             * without a mapped record on an unknown chromosome (all of them, for most files) only print the progress marks. */
-            int unknown = 0;
-            {
-                const int32_t *tidv = st[s].tid;
-                const uint8_t *f5 = st[s].flag5;
-#pragma omp parallel for schedule(static) reduction(| : unknown)
-                for (long i = 0; i < (long)n; i++) {
-                    const int32_t t = tidv[i];
-                    if (!(f5[i] & 2) && t >= 0 && t < nt && t2c[t] == -1) unknown |= 1;
-                }
-            }
-            if (!unknown) {
-                for (unsigned long long m = (ends / progress_every + 1) * progress_every; m <= ends + n; m += progress_every)
-                    fprintf(stderr, "\r* Processed read ends: %llu", m);
-                ends += n;
-            } else {
-                for (size_t i = 0; i < n; i++) {
-                    if (++ends % progress_every == 0) fprintf(stderr, "\r* Processed read ends: %llu", ends);
-                    const int32_t t = st[s].tid[i];
-                    if (!(st[s].flag5[i] & 2) && t >= 0 && t < nt && t2c[t] == -1 && names_find(&warned, t2name[t]) < 0) {
-                        names_intern(&warned, t2name[t]);
-                        warnf("* Warning: read ends mapped to chromosome %s will be discarded as %s not existed in the chromosome size file",
-                              t2name[t], t2name[t]);
-                    }
-                }
-            }
-            /* ---- in file order: -R and the bed lines (generic.c:907-936) */
-            int batch_xa = 0;
-            if (dups || dd || bed_f || bed_uniq_f) {
-                if (want_bed) bed_host_batches++;
-                for (size_t i = 0; i < n; i++) {
-                    const int32_t t = st[s].tid[i];
-                    const int32_t chrom = (t >= 0 && t < nt) ? t2c[t] : -1;
-                    live[i] = 0;
-                    if (!host_derive(o, chrom, chrom >= 0 ? chr_sizes->value[chrom] : 0, st[s].flag5[i], st[s].pos[i], st[s].tmpend[i],
-                                     st[s].mpos[i], st[s].isize[i], &iv[i]))
-                        continue;
-                    const int uniq = st[s].mapq[i] >= o->mapq;
-                    if (dd && (st[s].flag5[i] & ITX_F5_NOLOOKUP)) continue;          /* a duplicate, marked on the device */
-                    if (dups && dup_set_seen(dups, t2id[t], &iv[i], uniq)) {
-                        st[s].flag5[i] |= ITX_F5_NOLOOKUP;
-                        if (uniq && hc) hc->dup_unique++;
-                        continue;
-                    }
-                    live[i] = 1;
-                    const char *xa = side[s].want_aux ? side[s].xa[i] : NULL;
-                    if (xa) batch_xa = 1;
-                    if (bed_f) {
-                        fprintf(bed_f, "%s\t%u\t%u\t%s\t%i\t%c", t2name[t], iv[i].start, iv[i].end, side[s].qname[i], (int)st[s].mapq[i], iv[i].strand);
-                        if (xa) fprintf(bed_f, "\t%i\t%s", (int)side[s].nm[i], xa);
-                        fprintf(bed_f, "\n");
-                    }
-                    if (bed_uniq_f && uniq)
-                        fprintf(bed_uniq_f, "%s\t%u\t%u\t%s\t%i\t%c\n", t2name[t], iv[i].start, iv[i].end, side[s].qname[i], (int)st[s].mapq[i],
-                                iv[i].strand);
-                }
-            } else if (veto_on && aux_xa) {
-                /* only the veto needs the intervals, and only of the records that carry XA: no order involved */
-                batch_xa = 1;
-#pragma omp parallel for schedule(static)
-                for (long i = 0; i < (long)n; i++) {
-                    live[i] = 0;
-                    if (!side[s].xa[i] || (st[s].flag5[i] & ITX_F5_NOLOOKUP)) continue;
-                    const int32_t t = st[s].tid[i];
-                    const int32_t chrom = (t >= 0 && t < nt) ? t2c[t] : -1;
-                    live[i] = (uint8_t)host_derive(o, chrom, chrom >= 0 ? chr_sizes->value[chrom] : 0, st[s].flag5[i], st[s].pos[i],
-                                                   st[s].tmpend[i], st[s].mpos[i], st[s].isize[i], &iv[i]);
-                }
-            }
-            /* ---- the XA veto needs the chosen row first: classify the slot, look, mark, then count (generic.c:972-982) */
-            if (veto_on && batch_xa) {
-                veto_host_batches++;
-                if (!xi) xi = xa_index_new(rm);
-                chk(itx_engine_classify_slot(eng, s, n, any_paired), "itx_engine_classify_slot");
-                chk(itx_engine_wait_slot(eng, s), "itx_engine_wait_slot");
-                unsigned long long vetoed = 0;
-#pragma omp parallel for schedule(dynamic, 4096) reduction(+ : vetoed)
-                for (long i = 0; i < (long)n; i++) {
-                    if (!live[i] || !side[s].xa[i] || st[s].hit_row[i] < 0) continue;
-                    const uint32_t rep = rm->rows[st[s].hit_row[i]].rep;
-                    if (xa_veto(xi, rep, side[s].nm[i], side[s].xa[i], (int)(iv[i].end - iv[i].start))) {
-                        st[s].flag5[i] |= ITX_F5_NOLOOKUP;
-                        vetoed++;
-                    }
-                }
-                if (hc) hc->diff_subfam += vetoed;
-            }
-            t_host += now_s() - tq;
-            tq = now_s();
-            chk(itx_engine_submit_slot(eng, s, n, any_paired, want_qnames), "itx_engine_submit_slot");
-            t_submit += now_s() - tq;
-            pend[s] = n;
-            s ^= 1;
-        }
-        while (bd && bed_pending) bed_write_out(bd, bed_f, bed_uniq_f, 0);
-        const double t_loop_done = now_s();
-        /* drain both slots before the tid map of the next file replaces this one */
-        for (int kk = 0; kk < 2; kk++) {
-            const int k = s ^ kk;                                        /* the older batch first: the read lists are in file order */
-            chk(itx_engine_wait_slot(eng, k), "itx_engine_wait_slot");
-            if (pend[k]) {
-                if (want_qnames) collect_names(&hn, &st[k], &side[k], pend[k]);
-                side_release(&side[k], pend[k], want_qnames);
-            }
-            pend[k] = 0;
-        }
-        /* a share of a multi-rank job: the line with the whole job's count comes after the exchange (rank 0's share alone
-         * would differ from what the reference prints) */
-        if (!(shared && pass == 0)) fprintf(stderr, "\r* Processed read ends: %llu\n", ends);
-        if (timing)
-            fprintf(stderr, "[itx timing] stream of %s: decode %.3f s, host passes %.3f s, submit %.3f s, waiting for the device %.3f s\n", files[fi],
-                    t_read, t_host, t_submit, t_wait);
-        for (int t = 0; t < nt; t++) free(t2name[t]);
-        free(t2name);
-        free(t2id);
-        free(t2c);
-        const double t_drained = now_s();
-        if (!aln_range_verified(rd)) boundary_missed++;
-        aln_close(rd);
-        if (timing)
-            fprintf(stderr, "[itx timing] open %.3f s, record loop %.3f s, drain %.3f s, close %.3f s\n", t_opened - t_open0, t_loop_done - t_opened,
-                    t_drained - t_loop_done, now_s() - t_drained);
-    }
-    if (pass == 1 || (world <= 1 && !multi_selftest())) break;
-    {
-        /* ---- the ONE exchange: every rank's partial, summed onto rank 0 (RCCL over xGMI) */
-        const double tx = now_s();
-        void *p64 = NULL, *p32 = NULL;
-        uint64_t n64 = 0, n32 = 0;
-        chk(itx_engine_partial_buffers(eng, &p64, &p32), "itx_engine_partial_buffers");
-        chk(itx_engine_partial_size(eng, &n64, &n32), "itx_engine_partial_size");
-        chk(itx_engine_sync(eng), "itx_engine_sync");
-        chk(itx_engine_export_partial(eng, p64, p32, NULL), "itx_engine_export_partial");
-        uint64_t meta[4] = {hc ? hc->diff_subfam : 0, hc ? hc->dup_unique : 0, boundary_missed, ends};
-        itx_comm *comm = NULL;
-        const double tc = now_s();
-        int comm_mode = multi_comm_mode();
-        int crc = ITX_OK;
-        if (comm_mode == ITX_COMM_RCCL) {
-            if (!early_comm.on) {                                    /* not under way since the start of the run: make it now, same thread function */
-                if (pthread_create(&early_comm.th, NULL, early_comm_main, NULL) == 0) {
-                    early_comm.on = 1;
-                } else {
-                    early_comm.rc = ITX_E_STATE;
-                    snprintf(early_comm.err, sizeof early_comm.err, "no thread for the communicator");
-                    comm_marker_write(0);
-                    early_comm.done = 1;
-                }
-            }
-            const char *te = getenv("ITX_COMM_TIMEOUT");
-            int agreed;
-            if (world > 1) {
-                agreed = comm_agree(te && atof(te) > 0 ? atof(te) : 900.0);
-            } else {                                                 /* ITX_COMM_SELFTEST: a job of one rank agrees with itself */
-                if (early_comm.on) pthread_join(early_comm.th, NULL);
-                early_comm.on = 0;
-                agreed = early_comm.rc == ITX_OK;
-            }
-            if (agreed < 0) die("rank %d: the other ranks never said whether they have a communicator (a rank of the job has died?)", rank);
-            if (agreed == 1 || __atomic_load_n(&early_comm.done, __ATOMIC_ACQUIRE)) {
-                if (early_comm.on) pthread_join(early_comm.th, NULL);
-                early_comm.on = 0;
-                crc = early_comm.rc;
-                comm = early_comm.comm;
-            } else {
-                early_comm.on = 0;                                   /* still inside ncclCommInitRank, waiting for a rank that will not come: left behind */
-                crc = ITX_E_STATE;
-            }
-            if (agreed == 0) {
-                /* some rank has no RCCL communicator (no usable network interface for its bootstrap, its device, its library):
-                 * every rank has seen the same markers and hands its partial over through files — slower, same sums */
-                if (early_comm.err[0]) warnf("[iteres] note: no RCCL communicator (%s); the ranks exchange through files instead", early_comm.err);
-                else warnf("[iteres] note: another rank has no RCCL communicator; the ranks exchange through files instead");
-                if (crc == ITX_OK && comm) itx_comm_destroy(comm);
-                comm = NULL;
-                comm_mode = ITX_COMM_FILE;
-                crc = itx_comm_create(rank, world, multi_device(), multi_comm_id(), comm_mode, &comm);
-            }
-        } else {
-            crc = itx_comm_create(rank, world, multi_device(), multi_comm_id(), comm_mode, &comm);
-        }
-        chk(crc, "itx_comm_create");
-        const double ty = now_s();
-        chk(itx_comm_reduce_sum(comm, p64, n64, p32, n32, meta, 4, NULL), "itx_comm_reduce_sum");
-        if (timing && rank == 0)
-            fprintf(stderr, "[itx timing] exchange (%s): export %.3f s, communicator %.3f s, reduce of %.1f MB per rank (waits for the slowest rank) %.3f s\n",
-                    comm_mode == ITX_COMM_FILE ? "files" : "RCCL", tc - tx, ty - tc, (double)(n64 * 8 + n32 * 4) / 1e6, now_s() - ty);
-        itx_comm_destroy(comm);
-        if (rank == 0 && world > 1) {
-            comm_markers_remove();                                   /* every rank has read them: its partial is here */
-            /* RCCL was given up for the files: the communicator id this rank may have written for it (its thread still sits in
-             * ncclCommInitRank, waiting for a rank that will not come) goes too */
-            if (comm_mode == ITX_COMM_FILE && multi_comm_mode() == ITX_COMM_RCCL) unlink(multi_comm_id());
-        }
-        if (rank > 0) {                                              /* handed over: rank 0 writes the files */
-            fflush(NULL);
-            _exit(0);
-        }
-        if (hc) {
-            hc->diff_subfam = meta[0];
-            hc->dup_unique = meta[1];
-        }
-        boundary_missed = meta[2];
-        if (shared && !boundary_missed) fprintf(stderr, "\r* Processed read ends: %llu\n", (unsigned long long)meta[3]);
-        if (!boundary_missed) {
-            g_reduced_u64 = p64;
-            g_reduced_u32 = p32;
-        }
-    }
-    }
-    if (timing && veto_on)
-        fprintf(stderr, "[itx timing] XA veto: %llu batches judged on the device, %llu by the host\n", veto_dev_batches, veto_host_batches);
-    if (timing && want_bed) {
-        itx_bed_stats bs;
-        memset(&bs, 0, sizeof bs);
-        if (bd) chk(itx_bed_get_stats(bd, &bs), "itx_bed_get_stats");
-        fprintf(stderr, "[itx timing] bed: %llu batches built on the device (%llu bytes, %.3f ms in its kernels, host waited %.3f s), %llu by the host\n",
-                (unsigned long long)bs.batches, (unsigned long long)bs.bytes, bs.kernel_ms, bs.wait_s, bed_host_batches);
-    }
-    itx_bed_destroy(bd);
-    names_free(&warned);
-    names_free(&chr_names);
-    free(arg);
-    if (bed_f) fclose(bed_f);
-    if (bed_uniq_f) fclose(bed_uniq_f);
-    dup_set_free(dups);
-    if (dd) {
-        uint64_t du = 0, dropped = 0, keys = 0;
-        chk(itx_dedup_counts(dd, &du, &dropped, &keys), "itx_dedup_counts");
-        if (hc) hc->dup_unique = du;
-        if (timing) fprintf(stderr, "[itx timing] -R on the device: %llu records dropped (%llu of them MAPQ >= -Q), %llu keys, %.3f s in its kernels\n",
-                            (unsigned long long)dropped, (unsigned long long)du, (unsigned long long)keys, t_dedup);
-        itx_dedup_destroy(dd);
-    }
-    xa_index_free(xi);
-    itx_xaveto_destroy(xv);
-    free(iv);
-    free(live);
+    r->dups = o->dedup && !r->dd ? dup_set_new() : NULL;
+    if (r->shared && !g_inflater) die("rank %d: the device decoder did not come up: %s", multi_rank(), warm_err[0] ? warm_err : itx_last_error());
+}
 
-    if (want_qnames && locus_names && nm) {
+/* ---- per file: open, tid maps, backlog ------------------------------------------------------------------------------------ */
+
+/* 1: the reader is the helper thread's, with records parsed ahead of the table to submit first */
+static int open_file(stream_run *r, stream_file *f, int fi, int pass)
+{
+    const run_opts *o = r->o;
+    const share_t *sh = &r->share[fi];
+    int backlog = 0;
+    f->t_open0 = now_s();
+    if (fi == 0 && pass == 0 && warm_reader && warm_first && strcmp(r->files[0], warm_first) == 0 && warm_lo == sh->lo && warm_hi == sh->hi) {
+        f->rd = warm_reader;                                             /* opened and decoding since the helper thread came up */
+        warm_reader = NULL;
+        backlog = pre_bl != NULL;
+    } else {
+        if (warm_reader && fi == 0 && pass == 0) {                       /* opened for another share than this plan's: not used */
+            aln_close(warm_reader);
+            warm_reader = NULL;
+        }
+        f->rd = (sh->lo == 0 && sh->hi == SIZE_MAX) ? aln_open(r->files[fi], o->is_sam) : aln_open_range(r->files[fi], sh->lo, sh->hi);
+    }
+    f->t_opened = now_s();
+    if (!f->rd) {
+        fprintf(stderr, "Fail to open %s file %s\n", o->is_sam ? "SAM" : "BAM", o->aln_arg);
+        die("Error\n");
+    }
+    return backlog;
+}
+
+/* The engine and the side objects learn the current file's header: at the top of a file all that exist (only == NULL), after a
+ * late creation the new one. */
+static void attach_tidmaps(stream_run *r, stream_file *f, const void *only)
+{
+    const int nt = f->nt > 0 ? f->nt : 0;
+    if (!only) chk(itx_engine_set_tidmap(r->eng, f->t2c, nt), "itx_engine_set_tidmap");
+    if (r->xv && (!only || only == r->xv)) chk(itx_xaveto_set_tidmap(r->xv, f->t2c, nt), "itx_xaveto_set_tidmap");
+    if (r->bd && (!only || only == r->bd)) chk(itx_bed_set_tidmap(r->bd, f->t2c, (const char *const *)f->t2name, nt), "itx_bed_set_tidmap");
+    if (r->dd && !only) {
+        chk(itx_dedup_set_tidmap(r->dd, f->t2c, f->t2id, nt), "itx_dedup_set_tidmap");
+        aln_set_window_hook(f->rd, dedup_window, r);
+    }
+    if (!only && f->nt == 0) {
+        /* no references: nothing can map; still count the read ends */
+        int32_t none = -1;
+        chk(itx_engine_set_tidmap(r->eng, &none, 1), "itx_engine_set_tidmap");
+    }
+}
+
+/* The side objects of the device route are made when first needed: the veto object must not be built for inputs without XA tags. */
+static void create_bed(stream_run *r, stream_file *f)
+{
+    chk(itx_bed_create(multi_device(), r->chr_sizes->value, (int)r->chr_sizes->names.n, &r->p, (r->bed_f ? ITX_BED_ALL : 0) | (r->bed_uniq_f ? ITX_BED_UNIQ : 0),
+                       BATCH_RECORDS, &r->bd),
+        "itx_bed_create");
+    attach_tidmaps(r, f, r->bd);
+}
+static void create_xaveto(stream_run *r, stream_file *f)
+{
+    const rmsk_t *rm = r->rm;
+    uint32_t *row_rep = xmalloc(sizeof(uint32_t) * (rm->n_rows + 1)), *words = xa_rep_words(rm);
+    for (size_t i = 0; i < rm->n_rows; i++) row_rep[i] = rm->rows[i].rep;
+    chk(itx_xaveto_create(r->tab, &r->p, row_rep, words, (const char *const *)r->chr_sizes->names.name, (int)r->chr_sizes->names.n, BATCH_RECORDS, &r->xv),
+        "itx_xaveto_create");
+    attach_tidmaps(r, f, r->xv);
+    free(row_rep);
+    free(words);
+}
+
+/* the header's references against the size file, and which routes this file may take */
+static void map_targets(stream_run *r, stream_file *f)
+{
+    const run_opts *o = r->o;
+    const int nt = f->nt = aln_n_targets(f->rd);
+    f->t2c = xmalloc(sizeof(int32_t) * (size_t)(nt + 1));
+    f->t2id = xcalloc((size_t)nt + 1, sizeof(uint32_t));
+    f->t2name = xcalloc((size_t)nt + 1, sizeof(char *));
+    for (int t = 0; t < nt; t++) {
+        char buf[4096];
+        const char *nm = rename_chr(aln_target_name(f->rd, t), o->add_chr, buf, sizeof buf);
+        f->t2name[t] = nm ? xstrdup(nm) : NULL;
+        if (!nm) {
+            f->t2c[t] = -2;
+        } else {
+            /* generic.c:796-797: cend = size-1 with 2 as the "not found" default; a listed size of 2 reads the same */
+            f->t2c[t] = chrom_of_target(aln_target_name(f->rd, t), o, r->chr_sizes);
+            if (r->dups || r->dd) f->t2id[t] = names_intern(&r->chr_names, nm);
+        }
+    }
+    attach_tidmaps(r, f, NULL);
+    /* Nothing per record is the host's business when no option asks for names, -R or bed lines: a window of records the
+     * device decoder parsed then goes to the engine where it lies, in HBM (window_goes_direct says which). The bed lines do
+     * not keep a window on the host: the device decoder's windows get their text built where they lie (ITX_HOST_BED=1: by the
+     * host). Nor do the read lists of filter -r on the device route (ITX_HOST_NAMES=0). */
+    f->dev_bed = r->want_bed && g_inflater && !o->is_sam && !getenv("ITX_HOST_BED");
+    f->dev_names = r->want_qnames && g_inflater && !o->is_sam && !names_by_host();
+    f->handoff_ok = !r->dups && (!r->want_bed || f->dev_bed) && (!r->want_qnames || f->dev_names);
+    if (f->dev_names && !r->nm) {
+        chk(itx_names_create(multi_device(), BATCH_RECORDS, 0, &r->nm), "itx_names_create");
+        g_names = r->nm;
+    }
+    if (f->dev_bed && !r->bd) create_bed(r, f);
+}
+
+/* the records the helper thread parsed while the table was being built: first, in file order */
+static void submit_backlog(stream_run *r)
+{
+    const double td = now_s();
+    unsigned long long got = 0;
+    for (size_t k = 0; k < pre_n; k++)
+        for (size_t off = 0; off < pre_v[k].n; off += BATCH_RECORDS) {
+            const size_t m = pre_v[k].n - off < BATCH_RECORDS ? pre_v[k].n - off : BATCH_RECORDS;
+            itx_batch db;
+            chk(itx_backlog_batch(pre_bl, pre_v[k].at + off, pre_v[k].paired, &db), "itx_backlog_batch");
+            progress_marks(r, m);
+            got += m;
+            chk(itx_engine_submit_device_own(r->eng, &db, m, NULL), "itx_engine_submit_device_own");
+        }
+    chk(itx_engine_wait_own(r->eng), "itx_engine_wait_own");
+    if (r->timing)
+        fprintf(stderr, "\n[itx timing] parsed ahead of the table by the helper thread: %llu records of %zu windows (%.3f s there), submitted in %.3f s\n", got, pre_n,
+                pre_seconds, now_s() - td);
+}
+
+/* ---- the record loop: the device route window by window, the host route batch by batch ----------------------------------- */
+
+/* Only the host can read this batch: it and the rest of its window take the host route (the batches before are through).
+ * drop_bed: the bed text this batch already started is the host's to print. */
+static int host_takes_over(stream_run *r, stream_file *f, size_t n, int drop_bed, double since)
+{
+    if (drop_bed && r->bd) bed_write_out(r, 1);
+    aln_device_rewind(f->rd, n);
+    f->t_host += now_s() - since;
+    return 0;
+}
+
+/* The device route for the window the reader stands at: its batches go to the engine where they lie. Per batch, in the
+ * reference's order (generic.c:925 before 972): bed text, names, veto, progress, submit. 1: the window went through; 0: the
+ * host route takes over from the current batch. */
+static int device_window(stream_run *r, stream_file *f, int xa_window)
+{
+    int wfl;
+    const uint8_t *seen;
+    double tq = now_s();
+    do {
+        itx_batch db;
+        const size_t n = aln_read_batch_device(f->rd, BATCH_RECORDS, &db);
+        f->t_read += now_s() - tq;
+        if (n == 0) break;
+        tq = now_s();
+        if (r->bd) {
+            /* built from the window as -R left it. The batch before this one is written out while this one's kernels run. */
+            uint64_t hard = 0;
+            if (aln_device_bed(f->rd, r->bd, n, &hard) != 0) die("device bed: %s", itx_last_error());
+            if (!hard) r->bed_pending++;
+            while (r->bed_pending > (hard ? 0 : 1)) bed_write_out(r, 0);
+            if (hard) return host_takes_over(r, f, n, 0, tq);        /* a record only the host can print */
+        }
+        if (r->nm) {
+            /* Classify into the lists' buffer first, gather, and only then submit: a batch whose names only the host can read
+             * has then not been counted yet, and the host route counts it once. (filter runs no veto: the rows are final.)
+             * What the host route still holds of earlier batches goes to the pool first — the lists are in file order. */
+            drain_slots(r, 0);
+            uint64_t hard = 0;
+            chk(itx_engine_classify_device(r->eng, &db, n, itx_names_hits(r->nm), itx_names_stream(r->nm)), "itx_engine_classify_device");
+            if (aln_device_names(f->rd, r->nm, n, itx_names_hits(r->nm), itx_names_stream(r->nm), &hard) != 0) die("device read lists: %s", itx_last_error());
+            if (hard) return host_takes_over(r, f, n, 0, tq);
+        }
+        if (xa_window) {
+            /* classify, let the device read the tags of the classified records, mark the vetoed ones */
+            uint64_t vetoed = 0, hard = 0;
+            chk(itx_engine_classify_device(r->eng, &db, n, itx_xaveto_hits(r->xv), itx_xaveto_stream(r->xv)), "itx_engine_classify_device");
+            if (aln_device_xa_veto(f->rd, r->xv, n, &vetoed, &hard) != 0) die("device veto: %s", itx_last_error());
+            if (hard) return host_takes_over(r, f, n, 1, tq);        /* an alternative only strtol / the reference's assert can judge */
+            if (r->hc) r->hc->diff_subfam += vetoed;
+            r->veto_dev_batches++;
+        }
+        f->t_host += now_s() - tq;
+        progress_marks(r, n);
+        tq = now_s();
+        chk(itx_engine_submit_device_own(r->eng, &db, n, NULL), "itx_engine_submit_device_own");
+        /* the window's arrays are the decoder's again once its last batch is through: the next parse overwrites them */
+        if (aln_device_left(f->rd) == 0) {
+            chk(itx_engine_wait_own(r->eng), "itx_engine_wait_own");
+            if (r->bd) chk(itx_bed_wait_kernels(r->bd), "itx_bed_wait_kernels");
+            if (r->nm) chk(itx_names_wait_kernels(r->nm), "itx_names_wait_kernels");
+        }
+        f->t_submit += now_s() - tq;
+        tq = now_s();
+    } while (!aln_device_window(f->rd, &wfl, &seen));                  /* until the next window's start (or the end) */
+    return 1;
+}
+
+/* generic.c:760-761 progress; generic.c:793-801 one warning per unknown chromosome, in file order. Batches without a mapped
+ * record on an unknown chromosome (all of them, for most files) only print the progress marks. */
+static void warn_unknown_chromosomes(stream_run *r, const stream_file *f, size_t n)
+{
+    const int32_t *tidv = r->st[r->s].tid, *t2c = f->t2c;
+    const uint8_t *f5 = r->st[r->s].flag5;
+    const int nt = f->nt;
+    int unknown = 0;
+#pragma omp parallel for schedule(static) reduction(| : unknown)
+    for (long i = 0; i < (long)n; i++) {
+        const int32_t t = tidv[i];
+        if (!(f5[i] & 2) && t >= 0 && t < nt && t2c[t] == -1) unknown |= 1;
+    }
+    if (!unknown) {
+        progress_marks(r, n);
+        return;
+    }
+    for (size_t i = 0; i < n; i++) {
+        if (++r->ends % r->progress_every == 0) fprintf(stderr, "\r* Processed read ends: %llu", r->ends);
+        const int32_t t = tidv[i];
+        if (!(f5[i] & 2) && t >= 0 && t < nt && t2c[t] == -1 && names_find(&r->warned, f->t2name[t]) < 0) {
+            names_intern(&r->warned, f->t2name[t]);
+            warnf("* Warning: read ends mapped to chromosome %s will be discarded as %s not existed in the chromosome size file", f->t2name[t],
+                  f->t2name[t]);
+        }
+    }
+}
+
+/* in file order: -R and the bed lines (generic.c:907-936). 1: a live record carries an XA tag */
+static int ordered_pass(stream_run *r, const stream_file *f, size_t n)
+{
+    const run_opts *o = r->o;
+    itx_staging *st = &r->st[r->s];
+    const aln_side *side = &r->side[r->s];
+    host_iv *iv = r->iv;
+    int batch_xa = 0;
+    if (r->want_bed) r->bed_host_batches++;
+    for (size_t i = 0; i < n; i++) {
+        const int32_t t = st->tid[i];
+        const int32_t chrom = (t >= 0 && t < f->nt) ? f->t2c[t] : -1;
+        r->live[i] = 0;
+        if (!host_derive(o, chrom, chrom >= 0 ? r->chr_sizes->value[chrom] : 0, st->flag5[i], st->pos[i], st->tmpend[i], st->mpos[i], st->isize[i], &iv[i]))
+            continue;
+        const int uniq = st->mapq[i] >= o->mapq;
+        if (r->dd && (st->flag5[i] & ITX_F5_NOLOOKUP)) continue;          /* a duplicate, marked on the device */
+        if (r->dups && dup_set_seen(r->dups, f->t2id[t], &iv[i], uniq)) {
+            st->flag5[i] |= ITX_F5_NOLOOKUP;
+            if (uniq && r->hc) r->hc->dup_unique++;
+            continue;
+        }
+        r->live[i] = 1;
+        const char *xa = side->want_aux ? side->xa[i] : NULL;
+        if (xa) batch_xa = 1;
+        if (r->bed_f) {
+            fprintf(r->bed_f, "%s\t%u\t%u\t%s\t%i\t%c", f->t2name[t], iv[i].start, iv[i].end, side->qname[i], (int)st->mapq[i], iv[i].strand);
+            if (xa) fprintf(r->bed_f, "\t%i\t%s", (int)side->nm[i], xa);
+            fprintf(r->bed_f, "\n");
+        }
+        if (r->bed_uniq_f && uniq)
+            fprintf(r->bed_uniq_f, "%s\t%u\t%u\t%s\t%i\t%c\n", f->t2name[t], iv[i].start, iv[i].end, side->qname[i], (int)st->mapq[i], iv[i].strand);
+    }
+    return batch_xa;
+}
+
+/* the XA veto needs the chosen row first: classify the slot, look, mark, then count (generic.c:972-982) */
+static void veto_pass(stream_run *r, const stream_file *f, size_t n)
+{
+    itx_staging *st = &r->st[r->s];
+    const aln_side *side = &r->side[r->s];
+    r->veto_host_batches++;
+    if (!r->xi) r->xi = xa_index_new(r->rm);
+    chk(itx_engine_classify_slot(r->eng, r->s, n, f->any_paired), "itx_engine_classify_slot");
+    chk(itx_engine_wait_slot(r->eng, r->s), "itx_engine_wait_slot");
+    unsigned long long vetoed = 0;
+#pragma omp parallel for schedule(dynamic, 4096) reduction(+ : vetoed)
+    for (long i = 0; i < (long)n; i++) {
+        if (!r->live[i] || !side->xa[i] || st->hit_row[i] < 0) continue;
+        const uint32_t rep = r->rm->rows[st->hit_row[i]].rep;
+        if (xa_veto(r->xi, rep, side->nm[i], side->xa[i], (int)(r->iv[i].end - r->iv[i].start))) {
+            st->flag5[i] |= ITX_F5_NOLOOKUP;
+            vetoed++;
+        }
+    }
+    if (r->hc) r->hc->diff_subfam += vetoed;
+}
+
+/* The host route for one batch: slot s is collected and refilled by the reader, the host's passes run over it in the
+ * reference's order (warnings with progress, -R and bed lines, veto), then it is submitted. Returns the records read (0: end). */
+static size_t host_batch(stream_run *r, stream_file *f)
+{
+    const int s = r->s;
+    if (!r->have_slots) {
+        chk(itx_engine_staging(r->eng, 0, &r->st[0]), "itx_engine_staging");
+        chk(itx_engine_staging(r->eng, 1, &r->st[1]), "itx_engine_staging");
+        r->have_slots = 1;
+    }
+    itx_staging *st = &r->st[s];
+    aln_side *side = &r->side[s];
+    f->t_wait += drain_slot(r, s);
+    int aux_xa = 0;                                                    /* per batch */
+    double tq = now_s();
+    const size_t n = aln_read_batch(f->rd, st, BATCH_RECORDS, r->any_side ? side : NULL, &f->any_paired, &aux_xa);
+    f->t_read += now_s() - tq;
+    if (n == 0) return 0;
+    tq = now_s();
+    warn_unknown_chromosomes(r, f, n);
+    int batch_xa = 0;
+    if (r->dups || r->dd || r->bed_f || r->bed_uniq_f) {
+        batch_xa = ordered_pass(r, f, n);
+    } else if (r->veto_on && aux_xa) {
+        /* only the veto needs the intervals, and only of the records that carry XA: no order involved */
+        batch_xa = 1;
+#pragma omp parallel for schedule(static)
+        for (long i = 0; i < (long)n; i++) {
+            r->live[i] = 0;
+            if (!side->xa[i] || (st->flag5[i] & ITX_F5_NOLOOKUP)) continue;
+            const int32_t t = st->tid[i];
+            const int32_t chrom = (t >= 0 && t < f->nt) ? f->t2c[t] : -1;
+            r->live[i] = (uint8_t)host_derive(r->o, chrom, chrom >= 0 ? r->chr_sizes->value[chrom] : 0, st->flag5[i], st->pos[i], st->tmpend[i], st->mpos[i],
+                                              st->isize[i], &r->iv[i]);
+        }
+    }
+    if (r->veto_on && batch_xa) veto_pass(r, f, n);
+    f->t_host += now_s() - tq;
+    tq = now_s();
+    chk(itx_engine_submit_slot(r->eng, s, n, f->any_paired, r->want_qnames), "itx_engine_submit_slot");
+    f->t_submit += now_s() - tq;
+    r->pend[s] = n;
+    r->s ^= 1;
+    return n;
+}
+
+/* The dispatcher: the device route when this file may take it and the reader stands at the start of a window that qualifies;
+ * else one batch by the host route — which prints and reads only after the pending bed text is written and the names kernels
+ * are through. A window the device route gave up continues here, batch by batch, to its end. */
+static void record_loop(stream_run *r, stream_file *f)
+{
+    for (;;) {
+        if (f->handoff_ok) {
+            int wfl = 0;
+            const uint8_t *seen = NULL;
+            const double tq = now_s();
+            const int direct = aln_device_window(f->rd, &wfl, &seen) && window_goes_direct(wfl, seen, f->t2c, f->nt, r->veto_on, r->dev_veto);
+            const int xa_window = r->veto_on && (wfl & 2);
+            if (direct && xa_window && !r->xv) create_xaveto(r, f);
+            f->t_read += now_s() - tq;
+            if (direct && device_window(r, f, xa_window)) continue;
+            if (aln_device_exhausted(f->rd)) break;
+        }
+        while (r->bd && r->bed_pending) bed_write_out(r, 0);
+        if (r->nm) chk(itx_names_wait_kernels(r->nm), "itx_names_wait_kernels");
+        if (host_batch(r, f) == 0) break;
+    }
+}
+
+static void scan_file(stream_run *r, int fi, int pass)
+{
+    stream_file f;
+    memset(&f, 0, sizeof f);
+    if (r->multi_file) fprintf(stderr, "\n* Processing %s\n", r->files[fi]);
+    if (r->share[fi].lo == r->share[fi].hi) return;                    /* nothing of this file is this rank's */
+    const int backlog = open_file(r, &f, fi, pass);
+    r->s = 0;
+    map_targets(r, &f);
+    if (backlog) submit_backlog(r);
+    if (pre_bl && fi == 0 && pass == 0) {                              /* used or not (another share than the plan's): gone */
+        itx_backlog_destroy(pre_bl);
+        pre_bl = NULL;
+        free(pre_v);
+        pre_v = NULL;
+        pre_n = pre_cap = 0;
+    }
+    record_loop(r, &f);
+    while (r->bd && r->bed_pending) bed_write_out(r, 0);
+    f.t_loop_done = now_s();
+    drain_slots(r, 1);                                                 /* before the tid map of the next file replaces this one */
+    /* a share of a multi-rank job: the line with the whole job's count comes after the exchange (rank 0's share alone
+     * would differ from what the reference prints) */
+    if (!r->shared) fprintf(stderr, "\r* Processed read ends: %llu\n", r->ends);
+    if (r->timing)
+        fprintf(stderr, "[itx timing] stream of %s: decode %.3f s, host passes %.3f s, submit %.3f s, waiting for the device %.3f s\n", r->files[fi], f.t_read,
+                f.t_host, f.t_submit, f.t_wait);
+    for (int t = 0; t < f.nt; t++) free(f.t2name[t]);
+    free(f.t2name);
+    free(f.t2id);
+    free(f.t2c);
+    const double t_drained = now_s();
+    if (!aln_range_verified(f.rd)) r->boundary_missed++;
+    aln_close(f.rd);
+    if (r->timing)
+        fprintf(stderr, "[itx timing] open %.3f s, record loop %.3f s, drain %.3f s, close %.3f s\n", f.t_opened - f.t_open0, f.t_loop_done - f.t_opened,
+                t_drained - f.t_loop_done, now_s() - t_drained);
+}
+
+/* the ONE exchange (exchange.c): every rank's partial, summed onto rank 0, which goes on alone */
+static void exchange(stream_run *r)
+{
+    host_counts *hc = r->hc;
+    uint64_t meta[4] = {hc ? hc->diff_subfam : 0, hc ? hc->dup_unique : 0, r->boundary_missed, r->ends};
+    void *p64 = NULL, *p32 = NULL;
+    exchange_partials(r->eng, meta, 4, r->timing, &p64, &p32);
+    if (hc) {
+        hc->diff_subfam = meta[0];
+        hc->dup_unique = meta[1];
+    }
+    r->boundary_missed = meta[2];
+    if (r->shared && !r->boundary_missed) fprintf(stderr, "\r* Processed read ends: %llu\n", (unsigned long long)meta[3]);
+    if (!r->boundary_missed) {
+        g_reduced_u64 = p64;
+        g_reduced_u32 = p32;
+    }
+}
+
+/* A share boundary did not hold (the split points are guesses that the rank before verifies): rank 0 scans the whole job again,
+ * alone. */
+static void scan_again_alone(stream_run *r)
+{
+    fprintf(stderr, "[iteres] note: a share boundary was not a record start; scanning the input again with one GPU\n");
+    chk(itx_engine_reset(r->eng), "itx_engine_reset");
+    if (r->hc) r->hc->diff_subfam = r->hc->dup_unique = 0;
+    r->ends = 0;
+    for (int i = 0; i < r->n_files; i++) r->share[i].lo = 0, r->share[i].hi = SIZE_MAX;
+    r->shared = 0;
+    for (int fi = 0; fi < r->n_files; fi++) scan_file(r, fi, 1);
+}
+
+static void finish_names(stream_run *r, char ***locus_names)
+{
+    const rmsk_t *rm = r->rm;
+    if (!r->want_qnames || !locus_names) return;
+    char **out = xcalloc(rm->n_rows ? rm->n_rows : 1, sizeof(char *));
+    *locus_names = out;
+    if (r->nm) {
         /* one sort by row, stable in append order, and one text: every list is a NUL-terminated piece of it */
         itx_names_result nr;
-        chk(itx_names_finish(nm, rm->n_rows ? rm->n_rows : 1, &nr), "itx_names_finish");
-        char **out = xcalloc(rm->n_rows ? rm->n_rows : 1, sizeof(char *));
-        for (size_t r = 0; r < rm->n_rows; r++)
-            if (nr.row_off[r] != UINT64_MAX) out[r] = (char *)nr.text + nr.row_off[r];
+        chk(itx_names_finish(r->nm, rm->n_rows ? rm->n_rows : 1, &nr), "itx_names_finish");
+        for (size_t row = 0; row < rm->n_rows; row++)
+            if (nr.row_off[row] != UINT64_MAX) out[row] = (char *)nr.text + nr.row_off[row];
         g_names_cnt = nr.row_cnt;
-        *locus_names = out;
-    } else if (want_qnames && locus_names) {
-        /* names per locus in BAM order (generic.c:1729 reverses the head-inserted list back to file order) */
-        char **out = xcalloc(rm->n_rows ? rm->n_rows : 1, sizeof(char *));
-        size_t *len = xcalloc(rm->n_rows ? rm->n_rows : 1, sizeof(size_t));
-        for (size_t i = 0; i < hn.n; i++) len[hn.v[i].row] += strlen(hn.v[i].name) + 1;
-        for (size_t r = 0; r < rm->n_rows; r++)
-            if (len[r]) {
-                out[r] = xmalloc(len[r] + 1);
-                out[r][0] = 0;
-                len[r] = 0;
-            }
-        for (size_t i = 0; i < hn.n; i++) {
-            char *dst = out[hn.v[i].row] + len[hn.v[i].row];
-            const size_t k = strlen(hn.v[i].name);
-            if (len[hn.v[i].row]) *dst++ = ',', len[hn.v[i].row]++;
-            memcpy(dst, hn.v[i].name, k + 1);
-            len[hn.v[i].row] += k;
-            free(hn.v[i].name);
-        }
-        free(len);
-        *locus_names = out;
+        return;
     }
-    free(hn.v);
-    if (timing && want_qnames) {
+    /* names per locus in BAM order (generic.c:1729 reverses the head-inserted list back to file order) */
+    const hit_name *v = r->hn.v;
+    size_t *len = xcalloc(rm->n_rows ? rm->n_rows : 1, sizeof(size_t));
+    for (size_t i = 0; i < r->hn.n; i++) len[v[i].row] += strlen(v[i].name) + 1;
+    for (size_t row = 0; row < rm->n_rows; row++)
+        if (len[row]) {
+            out[row] = xmalloc(len[row] + 1);
+            out[row][0] = 0;
+            len[row] = 0;
+        }
+    for (size_t i = 0; i < r->hn.n; i++) {
+        char *dst = out[v[i].row] + len[v[i].row];
+        const size_t k = strlen(v[i].name);
+        if (len[v[i].row]) *dst++ = ',', len[v[i].row]++;
+        memcpy(dst, v[i].name, k + 1);
+        len[v[i].row] += k;
+        free(v[i].name);
+    }
+    free(len);
+}
+
+/* the counters of bed, -R and veto for ITX_TIMING; their objects and what the host route kept go */
+static void release_side_objects(stream_run *r)
+{
+    const int timing = r->timing;
+    if (timing && r->veto_on)
+        fprintf(stderr, "[itx timing] XA veto: %llu batches judged on the device, %llu by the host\n", r->veto_dev_batches, r->veto_host_batches);
+    if (timing && r->want_bed) {
+        itx_bed_stats bs;
+        memset(&bs, 0, sizeof bs);
+        if (r->bd) chk(itx_bed_get_stats(r->bd, &bs), "itx_bed_get_stats");
+        fprintf(stderr, "[itx timing] bed: %llu batches built on the device (%llu bytes, %.3f ms in its kernels, host waited %.3f s), %llu by the host\n",
+                (unsigned long long)bs.batches, (unsigned long long)bs.bytes, bs.kernel_ms, bs.wait_s, r->bed_host_batches);
+    }
+    itx_bed_destroy(r->bd);
+    names_free(&r->warned);
+    names_free(&r->chr_names);
+    free(r->arg);
+    if (r->bed_f) fclose(r->bed_f);
+    if (r->bed_uniq_f) fclose(r->bed_uniq_f);
+    dup_set_free(r->dups);
+    if (r->dd) {
+        uint64_t du = 0, dropped = 0, keys = 0;
+        chk(itx_dedup_counts(r->dd, &du, &dropped, &keys), "itx_dedup_counts");
+        if (r->hc) r->hc->dup_unique = du;
+        if (timing) fprintf(stderr, "[itx timing] -R on the device: %llu records dropped (%llu of them MAPQ >= -Q), %llu keys, %.3f s in its kernels\n",
+                            (unsigned long long)dropped, (unsigned long long)du, (unsigned long long)keys, r->t_dedup);
+        itx_dedup_destroy(r->dd);
+    }
+    xa_index_free(r->xi);
+    itx_xaveto_destroy(r->xv);
+    free(r->iv);
+    free(r->live);
+}
+
+/* the names' counters, the buffers of the lists (unless the caller took them) and the decoder */
+static void teardown(stream_run *r, int lists_taken)
+{
+    const int timing = r->timing;
+    free(r->hn.v);
+    if (timing && r->want_qnames) {
         itx_names_stats ns;
         memset(&ns, 0, sizeof ns);
-        if (nm) chk(itx_names_get_stats(nm, &ns), "itx_names_get_stats");
+        if (r->nm) chk(itx_names_get_stats(r->nm, &ns), "itx_names_get_stats");
         fprintf(stderr, "[itx timing] names: %llu batches gathered on the device (%llu names, %llu bytes, %.3f ms in the gather kernels, %.3f ms sort + text), %llu batches by the host\n",
-                (unsigned long long)ns.batches, (unsigned long long)ns.entries, (unsigned long long)ns.bytes, ns.gather_ms, ns.finish_ms, names_host_batches);
+                (unsigned long long)ns.batches, (unsigned long long)ns.entries, (unsigned long long)ns.bytes, ns.gather_ms, ns.finish_ms, r->names_host_batches);
     }
-    if (nm && !(want_qnames && locus_names)) stream_names_free(NULL);
-    free(nbuf.rows);
-    free(nbuf.off);
-    free(nbuf.bytes);
-    memset(&nbuf, 0, sizeof nbuf);
+    if (r->nm && !lists_taken) stream_names_free(NULL);
+    free(r->nbuf.rows);
+    free(r->nbuf.off);
+    free(r->nbuf.bytes);
     for (int k = 0; k < 2; k++) {
-        free(side[k].qname);
-        free(side[k].xa);
-        free(side[k].nm);
+        free(r->side[k].qname);
+        free(r->side[k].xa);
+        free(r->side[k].nm);
     }
     /* The decoder's device memory (17 GB for a big input) goes back NOW, not when the process ends: the driver clears released
      * memory in the background, and the next command's reservation of the same 17 GB waits for whatever is still uncleared —
@@ -1237,6 +1202,31 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
         aln_use_device(NULL);
         if (timing) fprintf(stderr, "[itx timing] decoder released %.3f s\n", now_s() - tr);
     }
-    *eng_out = eng;
-    *tab_out = tab;
+}
+
+void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, int filter_mode, int multi_file,
+                unsigned progress_every, int want_qnames, itx_engine **eng_out, itx_table **tab_out, char ***locus_names,
+                host_counts *hc)
+{
+    const int want_bed = o->bed_path || o->bed_uniq_path;
+    stream_run run = {.o = o, .rm = rm, .chr_sizes = chr_sizes, .filter_mode = filter_mode, .multi_file = multi_file, .progress_every = progress_every,
+                      .hc = hc, .timing = getenv("ITX_TIMING") != NULL, .want_qnames = want_qnames, .want_bed = want_bed,
+                      .veto_on = o->xa_veto && !filter_mode, .dev_veto = !getenv("ITX_HOST_VETO")}, *r = &run;
+
+    make_table_and_engine(r);
+    open_outputs_and_side_buffers(r);
+    list_files_and_shares(r);
+    join_helper_thread(r);
+    choose_dedup_set(r);
+    /* this rank's shares, then (a job of several ranks) the exchange — after which rank 0 is alone */
+    for (int fi = 0; fi < r->n_files; fi++) scan_file(r, fi, 0);
+    if (multi_world() > 1 || multi_selftest()) {
+        exchange(r);
+        if (r->boundary_missed) scan_again_alone(r);
+    }
+    release_side_objects(r);
+    finish_names(r, locus_names);
+    teardown(r, want_qnames && locus_names);
+    *eng_out = r->eng;
+    *tab_out = r->tab;
 }
