@@ -42,6 +42,8 @@ static __device__ inline uint32_t itxi_pksign16(uint32_t a, uint32_t b)
 // once, so no cached copy can be stale. (An agent-scope fence here writes the L2 back: measured 4 500 cycles per token.)
 #define ITXI_FENCE() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup")
 #include "itx_inflate_core.h"
+#define ITXG_FN static __host__ __device__ inline
+#include "itx_inflate_group.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -52,9 +54,25 @@ static __device__ inline uint32_t itxi_pksign16(uint32_t a, uint32_t b)
 #define BGZF_TRAILER 8u      /* CRC32 + ISIZE */
 #define SCR_STRIDE ITXI_REGION                    /* bytes of scratch per block: literals from its bottom, tokens from its top (itx_inflate_core.h) */
 
-// pass 1: lane = block. meta[3b] = status, [3b+1] = literals, [3b+2] = tokens
-__global__ __launch_bounds__(64) void k_tokens(const uint32_t *__restrict__ comp, const itx_bgzf_block *__restrict__ blk, uint32_t n, uint8_t *__restrict__ scr,
-                                               uint32_t *__restrict__ meta)
+// One launch covers a GROUP of up to ITXG_SLOTS pushes (itx_inflate_group.h): each slot brings its own compressed bytes, block
+// list, output base and status bytes; the scratch regions and meta are indexed by the group-wide block index.
+struct GroupArgs {
+    itxg_index x;
+    const uint32_t *comp[ITXG_SLOTS];
+    const itx_bgzf_block *blk[ITXG_SLOTS];
+    uint8_t *out[ITXG_SLOTS], *status[ITXG_SLOTS];
+};
+template <typename T> static __host__ __device__ inline T itxg_pick(T const (&a)[ITXG_SLOTS], uint32_t k)
+{
+    T v = a[0];
+#pragma unroll
+    for (uint32_t j = 1; j < ITXG_SLOTS; j++)
+        if (k == j) v = a[j];
+    return v;
+}
+
+// pass 1: lane = block. meta[3g] = status, [3g+1] = literals, [3g+2] = tokens (g: the group-wide index)
+__global__ __launch_bounds__(64) void k_tokens(const GroupArgs G, uint8_t *__restrict__ scr, uint32_t *__restrict__ meta)
 {
 #ifndef ITXI_SYM16
     __shared__ uint32_t s_lhi[9 * 64];                                   // 26 880 bytes in all: six of these workgroups to a CU
@@ -64,39 +82,46 @@ __global__ __launch_bounds__(64) void k_tokens(const uint32_t *__restrict__ comp
     __shared__ uint16_t s_lsym16[288 * 64], s_loffs[16 * 64], s_doffs[16 * 64];      // 43 008 bytes: three to a CU (experiment builds)
     __shared__ uint8_t s_dsym[32 * 64];
 #endif
-    const uint32_t ln = threadIdx.x, b = blockIdx.x * 64u + ln;
-    if (b >= n) return;
+    const uint32_t ln = threadIdx.x, g = blockIdx.x * 64u + ln;
+    uint32_t slot, wb;
+    (void)itxg_locate(G.x, blockIdx.x * 64u, &slot, &wb);               // a slot starts at a multiple of 64: the whole wave is in one
+    const uint32_t b = wb + ln;
+    if (b >= itxg_pick(G.x.n, slot)) return;
+    const itx_bgzf_block *__restrict__ blk = itxg_pick(G.blk, slot);
+    const uint32_t *__restrict__ comp = itxg_pick(G.comp, slot);
     const uint32_t coff = blk[b].coff, csize = blk[b].csize, usize = blk[b].usize;
 #ifndef ITXI_SYM16
     ItxiTab T{s_lsym8, s_lhi, s_dsym, s_loffs, s_doffs};
 #else
     ItxiTab T{s_lsym16, s_dsym, s_loffs, s_doffs};
 #endif
-    uint8_t *region = scr + (size_t)b * SCR_STRIDE;
+    uint8_t *region = scr + (size_t)g * SCR_STRIDE;
     ItxiTokens K{region, reinterpret_cast<uint32_t *>(region + SCR_STRIDE), 0, 0};
     int rc = ITXI_E_INPUT;
     if (csize >= BGZF_HEADER + BGZF_TRAILER + 2u && usize <= ITXI_MAX_BLOCK)
         rc = itxi_tokens(T, ln, comp, coff + BGZF_HEADER, coff + csize - BGZF_TRAILER, usize, K);
-    meta[3 * b] = (uint32_t)rc;
-    meta[3 * b + 1] = K.n_lit;
-    meta[3 * b + 2] = K.n_tok;
+    meta[3 * g] = (uint32_t)rc;
+    meta[3 * g + 1] = K.n_lit;
+    meta[3 * g + 2] = K.n_tok;
 }
 
-// pass 2: wave = block
-__global__ __launch_bounds__(64) void k_resolve(const itx_bgzf_block *__restrict__ blk, uint32_t first, uint32_t n, const uint8_t *__restrict__ scr,
-                                                const uint32_t *__restrict__ meta, uint8_t *__restrict__ out, uint8_t *__restrict__ status)
+// pass 2: wave = block, the group-wide indices [first, first + n)
+__global__ __launch_bounds__(64) void k_resolve(const GroupArgs G, uint32_t first, uint32_t n, const uint8_t *__restrict__ scr, const uint32_t *__restrict__ meta)
 {
     __shared__ uint32_t s_mem[(ITXI_RING + ITXI_LSTAGE + ITXI_BMAP / 8u + 8u) / 4];       // the ring, right behind it the literal stage, then the bitmap of token starts
     uint32_t *s_ring = s_mem, *s_stage = s_mem + ITXI_RING / 4, *s_bmap = s_mem + (ITXI_RING + ITXI_LSTAGE) / 4;
     if (blockIdx.x >= n) return;
-    const uint32_t b = first + blockIdx.x;
-    int rc = (int)meta[3 * b];
+    const uint32_t g = first + blockIdx.x;
+    uint32_t slot, b;
+    if (!itxg_locate(G.x, g, &slot, &b)) return;                         // padding between two slots
+    const itx_bgzf_block *__restrict__ blk = itxg_pick(G.blk, slot);
+    int rc = (int)meta[3 * g];
     if (rc == ITXI_OK) {
-        const uint8_t *region = scr + (size_t)b * SCR_STRIDE;
-        rc = itxi_resolve(s_ring, s_stage, s_bmap, region, reinterpret_cast<const uint32_t *>(region + SCR_STRIDE), meta[3 * b + 1], meta[3 * b + 2], out, blk[b].uoff,
-                          blk[b].usize, threadIdx.x);
+        const uint8_t *region = scr + (size_t)g * SCR_STRIDE;
+        rc = itxi_resolve(s_ring, s_stage, s_bmap, region, reinterpret_cast<const uint32_t *>(region + SCR_STRIDE), meta[3 * g + 1], meta[3 * g + 2], itxg_pick(G.out, slot),
+                          blk[b].uoff, blk[b].usize, threadIdx.x);
     }
-    if (threadIdx.x == 0) status[b] = (uint8_t)rc;
+    if (threadIdx.x == 0) itxg_pick(G.status, slot)[b] = (uint8_t)rc;
 }
 
 // =====================================================================================================================
@@ -340,7 +365,9 @@ static int lanes_in_use()
 // = 46 ms per push of which the kernels are 34 — on average 2.6 of 4 pass-1 kernels were running (profiles/r03_cli_500M_trace_*).
 // With more slots than lanes the next push's bytes cross PCIe while the lane still computes; more LANES instead cost a gigabyte
 // of scratch each and their kernels crowd the engine's out of the CUs (k_hist 0.67 -> 3.1 ms with 8).
-#define ITX_COMPUTE_LANES_DEFAULT 4
+// (Since the launches are grouped — below — one lane is the default: four pushes a launch on one stream, 2.50 s per run at the runtime's four
+// hardware queues against 2.44 s with two lanes of two and 3.01 s with four lanes of one, profiles/r10_grouped_launches_parent_vs_branch.json.)
+#define ITX_COMPUTE_LANES_DEFAULT 1
 static int compute_lanes()
 {
     static int v;
@@ -348,6 +375,23 @@ static int compute_lanes()
         const char *e = getenv("ITX_LANES");
         const int x = e ? atoi(e) : 0;
         v = x >= 1 && x <= ITX_BAMWIN_LANES ? x : ITX_COMPUTE_LANES_DEFAULT;
+        if (v > lanes_in_use()) v = lanes_in_use();
+    }
+    return v;
+}
+
+// ... and the pushes one launch covers (ITX_GROUP, 1 .. ITXG_SLOTS). Pass 1 is a lane per block: its time is the length of a
+// block's decode chain, hardly the number of blocks, until waves share a CU. Four pushes' pass 1 therefore had to overlap, on
+// four streams that need a hardware queue each — and the runtime has four in all by default, shared with the copy stream, the
+// parse stream and the engine. One launch over G pushes' blocks keeps as many blocks in flight from 1 / G of the streams.
+#define ITX_GROUP_DEFAULT 4
+static int group_size()
+{
+    static int v;
+    if (!v) {
+        const char *e = getenv("ITX_GROUP");
+        const int x = e ? atoi(e) : 0;
+        v = x >= 1 && x <= (int)ITXG_SLOTS ? x : ITX_GROUP_DEFAULT;
         if (v > lanes_in_use()) v = lanes_in_use();
     }
     return v;
@@ -376,17 +420,27 @@ struct itx_inflater {
     hipStream_t copy_st;
     struct {
         hipEvent_t copied;                 // the compressed bytes have left the caller's buffer
-        hipEvent_t ev[3];                  // ITX_TIMING: before pass 1, between the passes, after pass 2
-        hipEvent_t p1_done, done;          // pass 1 through (the shared pass-2 stream waits for it); the whole push through
+        int grp;                           // the group the push belongs to (-1: none, a push without blocks)
+        uint8_t *win_buf;                  // where its blocks' bytes go: the window's buffer
         uint8_t *d_comp, *d_status, *h_status;
         itx_bgzf_block *d_blk, *h_blk;     // h_blk (page-locked): the block list shifted to the window's offsets
         size_t comp_cap, status_cap, blk_cap, h_cap;
         size_t n_blk, total;
         int busy;
     } lane[ITX_BAMWIN_LANES];
-    // a compute lane: the stream the two passes of its slots' pushes run on, one after the other, and their scratch
+    // a group of consecutive pushes that one launch of each pass covers (group_size() of them, fewer when a push_end comes first)
     struct {
-        hipStream_t cst;
+        int n, slot[ITXG_SLOTS];           // its members, in push order
+        int live;                          // members whose push_end is still to come (0: the entry is free)
+        bool launched, timed;
+        hipEvent_t ev[3];                  // ITX_TIMING: before pass 1, between the passes, after pass 2
+        hipEvent_t done;                   // both passes and the status copies of every member through
+    } grp[ITX_BAMWIN_LANES];
+    int open_grp;                          // the group that still takes members (-1: none)
+    unsigned long grp_seq;                 // groups launched so far: group q runs on compute lane q % compute_lanes()
+    // a compute lane: the stream the two passes of its groups run on, one group after the other, and their scratch
+    struct {
+        hipStream_t cst;                   // (created when the first group is launched on it)
         uint8_t *d_lit;
         uint32_t *d_meta;
         size_t lit_cap, meta_cap;
@@ -423,21 +477,23 @@ extern "C" int itx_inflater_create(int device, itx_inflater **out)
     itx_inflater *h = (itx_inflater *)calloc(1, sizeof *h);
     if (!h) return ITX_E_NOMEM;
     h->device = device;
-    for (int k = 0; k < 2; k++) ITX_HIP(hipStreamCreateWithFlags(&h->st[k], hipStreamNonBlocking));
-    SETUP_TICK("first two streams");
+    // st[1] carries the carry-over, locate and parse of every window; st[0] only itx_inflate_bgzf's calls: made when one comes
+    // (a stream that is never launched on still shares a hardware queue with one that is)
+    ITX_HIP(hipStreamCreateWithFlags(&h->st[1], hipStreamNonBlocking));
+    SETUP_TICK("first stream");
     for (int k = 0; k < 4; k++) ITX_HIP(hipEventCreate(&h->ev[k]));
     for (int k = 0; k < 2; k++) ITX_HIP(hipEventCreate(&h->ev_res_end[k]));
     for (int k = 0; k < lanes_in_use(); k++) {
         ITX_HIP(hipEventCreateWithFlags(&h->lane[k].copied, hipEventDisableTiming));
-        for (int q = 0; q < 3; q++) ITX_HIP(hipEventCreate(&h->lane[k].ev[q]));
-        ITX_HIP(hipEventCreateWithFlags(&h->lane[k].p1_done, hipEventDisableTiming));
-        ITX_HIP(hipEventCreateWithFlags(&h->lane[k].done, hipEventDisableTiming));
+        h->lane[k].grp = -1;
+        for (int q = 0; q < 3; q++) ITX_HIP(hipEventCreate(&h->grp[k].ev[q]));
+        ITX_HIP(hipEventCreateWithFlags(&h->grp[k].done, hipEventDisableTiming));
     }
+    h->open_grp = -1;
     // ONE stream carries every push's bytes across PCIe, in push order (the link is one: copies side by side only finish later,
     // all of them); a stream per slot also meant more streams than hardware queues, and streams that share a queue run one
     // after the other — two compute lanes on one queue halved pass 1's overlap (1.8 kernels in flight instead of 3)
     ITX_HIP(hipStreamCreateWithFlags(&h->copy_st, hipStreamNonBlocking));
-    for (int k = 0; k < compute_lanes(); k++) ITX_HIP(hipStreamCreateWithFlags(&h->clane[k].cst, hipStreamNonBlocking));
     SETUP_TICK("lane streams, events, counters");
     h->n_cu = 256;
     if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->n_cu <= 0) h->n_cu = 256;
@@ -448,9 +504,9 @@ extern "C" int itx_inflater_create(int device, itx_inflater **out)
             atexit(report_at_exit);
         }
     }
-    hipLaunchKernelGGL(k_warm, dim3(1), dim3(1), 0, h->st[0], (uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_warm, dim3(1), dim3(1), 0, h->st[1], (uint32_t *)nullptr);
     ITX_HIP(hipGetLastError());
-    ITX_HIP(hipStreamSynchronize(h->st[0]));
+    ITX_HIP(hipStreamSynchronize(h->st[1]));
     SETUP_TICK("first kernel (code object load)");
 #undef SETUP_TICK
     *out = h;
@@ -476,9 +532,8 @@ extern "C" void itx_inflater_destroy(itx_inflater *h)
     for (int k = 0; k < ITX_BAMWIN_LANES; k++) {
         if (h->lane[k].copied) (void)hipEventDestroy(h->lane[k].copied);
         for (int q = 0; q < 3; q++)
-            if (h->lane[k].ev[q]) (void)hipEventDestroy(h->lane[k].ev[q]);
-        if (h->lane[k].p1_done) (void)hipEventDestroy(h->lane[k].p1_done);
-        if (h->lane[k].done) (void)hipEventDestroy(h->lane[k].done);
+            if (h->grp[k].ev[q]) (void)hipEventDestroy(h->grp[k].ev[q]);
+        if (h->grp[k].done) (void)hipEventDestroy(h->grp[k].done);
         if (h->clane[k].cst) {
             (void)hipStreamSynchronize(h->clane[k].cst);
             (void)hipStreamDestroy(h->clane[k].cst);
@@ -618,7 +673,7 @@ extern "C" int itx_backlog_create(int device, size_t max_records, itx_backlog **
     b->cap = (max_records + 15) & ~(size_t)15;
     const size_t n = b->cap + 64;
     if (hipMalloc((void **)&b->tid, n * 4) != hipSuccess || hipMalloc((void **)&b->pos, n * 4) != hipSuccess || hipMalloc((void **)&b->end, n * 4) != hipSuccess ||
-        hipMalloc((void **)&b->mapq, n) != hipSuccess || hipMalloc((void **)&b->f5, n) != hipSuccess || hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking) != hipSuccess) {
+        hipMalloc((void **)&b->mapq, n) != hipSuccess || hipMalloc((void **)&b->f5, n) != hipSuccess) {
         itx_set_error("itx_backlog_create: no device memory for %zu records", max_records);
         (void)hipGetLastError();
         (void)hipFree(b->tid); (void)hipFree(b->pos); (void)hipFree(b->end); (void)hipFree(b->mapq); (void)hipFree(b->f5);
@@ -658,6 +713,7 @@ extern "C" int itx_backlog_append(itx_backlog *b, const itx_batch *src, size_t n
         ITX_HIP(hipMalloc((void **)&b->mpos, m * 4));
         ITX_HIP(hipMalloc((void **)&b->isize, m * 4));
     }
+    if (!b->st) ITX_HIP(hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));       // (a run that appends nothing has no such stream)
     ITX_HIP(hipMemcpyAsync(b->tid + o, src->tid, n * 4, hipMemcpyDeviceToDevice, b->st));
     ITX_HIP(hipMemcpyAsync(b->pos + o, src->pos, n * 4, hipMemcpyDeviceToDevice, b->st));
     ITX_HIP(hipMemcpyAsync(b->end + o, src->tmpend, n * 4, hipMemcpyDeviceToDevice, b->st));
@@ -689,14 +745,15 @@ extern "C" int itx_backlog_batch(const itx_backlog *b, size_t at, int with_mates
 
 // ITX_TIMING: where the decoder's device-side time goes (printed when the process ends)
 static double g_alloc_s, g_tok_ms, g_res_ms;
-static unsigned long g_allocs, g_pushes;
+static unsigned long g_allocs, g_pushes, g_launches, g_blocks;
 static bool g_reported;
 static void report_at_exit()
 {
     if (g_reported || !g_pushes) return;
     g_reported = true;
-    fprintf(stderr, "[itx timing] device decoder: %lu pushes, pass 1 %.1f ms and pass 2 %.1f ms per push (HIP events, pushes overlap), %lu device allocations %.3f s\n", g_pushes,
-            g_pushes ? g_tok_ms / (double)g_pushes : 0.0, g_pushes ? g_res_ms / (double)g_pushes : 0.0, g_allocs, g_alloc_s);
+    const double nl = g_launches ? (double)g_launches : 1.0;
+    fprintf(stderr, "[itx timing] device decoder: %lu pushes in %lu launches of %.0f blocks, pass 1 %.1f ms and pass 2 %.1f ms per launch (HIP events, launches overlap), "
+                    "%lu device allocations %.3f s\n", g_pushes, g_launches, (double)g_blocks / nl, g_tok_ms / nl, g_res_ms / nl, g_allocs, g_alloc_s);
 }
 
 extern "C" void itx_timing_report(void) { report_at_exit(); }
@@ -749,12 +806,20 @@ extern "C" int itx_inflate_bgzf(itx_inflater *h, const void *comp, size_t comp_l
     if ((rc = grow(&h->d_blk, &h->blk_cap, n_blk)) != ITX_OK) return rc;
     if ((rc = grow(&h->d_lit, &h->lit_cap, n_blk * (size_t)SCR_STRIDE)) != ITX_OK) return rc;
     if ((rc = grow(&h->d_meta, &h->meta_cap, 3 * n_blk)) != ITX_OK) return rc;
+    if (!h->st[0]) ITX_HIP(hipStreamCreateWithFlags(&h->st[0], hipStreamNonBlocking));
+    GroupArgs G;                                                   // a group of one
+    memset(&G, 0, sizeof G);
+    const uint32_t one = (uint32_t)n_blk;
+    (void)itxg_layout(&G.x, &one, 1);
+    G.comp[0] = (const uint32_t *)h->d_comp;
+    G.blk[0] = h->d_blk;
+    G.out[0] = h->d_out;
+    G.status[0] = h->d_status;
     // pass 1 over all blocks at once (a lane per block: it takes many blocks to fill the chip)
     ITX_HIP(hipMemcpyAsync(h->d_blk, blk, n_blk * sizeof *blk, hipMemcpyHostToDevice, h->st[0]));
     ITX_HIP(hipMemcpyAsync(h->d_comp, comp, comp_len, hipMemcpyHostToDevice, h->st[0]));
     ITX_HIP(hipEventRecord(h->ev[0], h->st[0]));
-    hipLaunchKernelGGL(k_tokens, dim3((unsigned)((n_blk + 63) / 64)), dim3(64), 0, h->st[0], (const uint32_t *)h->d_comp, h->d_blk, (uint32_t)n_blk, h->d_lit,
-                       h->d_meta);
+    hipLaunchKernelGGL(k_tokens, dim3((unsigned)((n_blk + 63) / 64)), dim3(64), 0, h->st[0], G, h->d_lit, h->d_meta);
     ITX_HIP(hipGetLastError());
     ITX_HIP(hipEventRecord(h->ev[1], h->st[0]));
     ITX_HIP(hipStreamSynchronize(h->st[0]));
@@ -764,8 +829,7 @@ extern "C" int itx_inflate_bgzf(itx_inflater *h, const void *comp, size_t comp_l
     ITX_HIP(hipEventRecord(h->ev[2], h->st[0]));
     for (size_t b0 = 0; b0 < n_blk; b0 += per, s ^= 1) {
         const size_t b1 = b0 + per < n_blk ? b0 + per : n_blk;
-        hipLaunchKernelGGL(k_resolve, dim3((unsigned)(b1 - b0)), dim3(64), 0, h->st[s], h->d_blk, (uint32_t)b0, (uint32_t)(b1 - b0), h->d_lit, h->d_meta,
-                           h->d_out, h->d_status);
+        hipLaunchKernelGGL(k_resolve, dim3((unsigned)(b1 - b0)), dim3(64), 0, h->st[s], G, (uint32_t)b0, (uint32_t)(b1 - b0), h->d_lit, h->d_meta);
         ITX_HIP(hipGetLastError());
         if (b0 == 0) ITX_HIP(hipEventRecord(h->ev[3], h->st[0]));
         const size_t u0 = blk[b0].uoff, u1 = (size_t)blk[b1 - 1].uoff + blk[b1 - 1].usize;
@@ -823,7 +887,56 @@ static int check_blocks(const itx_bgzf_block *blk, size_t n_blk, size_t comp_len
 #define BAD_W(w) ((w) < 0 || (w) >= ITX_BAMWIN_WINDOWS)
 #define BAD_S(s) ((s) < 0 || (s) >= lanes_in_use())
 
-/* push, first half: everything is enqueued on lane s's stream and the call returns; the caller's buffers are in use until
+/* one launch of each pass over the open group's blocks, on the next compute lane in turn: behind every member's copy, and
+ * behind the group that had the lane (and its scratch) before */
+static int launch_group(itx_inflater *h)
+{
+    const int gi = h->open_grp;
+    if (gi < 0) return ITX_OK;
+    auto &Gr = h->grp[gi];
+    h->open_grp = -1;
+    auto &CL = h->clane[h->grp_seq % (unsigned long)compute_lanes()];
+    h->grp_seq++;
+    GroupArgs G;
+    memset(&G, 0, sizeof G);
+    uint32_t counts[ITXG_SLOTS] = {0};
+    for (int m = 0; m < Gr.n; m++) counts[m] = (uint32_t)h->lane[Gr.slot[m]].n_blk;
+    const uint32_t span = itxg_layout(&G.x, counts, (uint32_t)Gr.n);
+    for (int m = 0; m < Gr.n; m++) {
+        auto &Ln = h->lane[Gr.slot[m]];
+        G.comp[m] = (const uint32_t *)Ln.d_comp;
+        G.blk[m] = Ln.d_blk;
+        G.out[m] = Ln.win_buf;
+        G.status[m] = Ln.d_status;
+    }
+    int rc;
+    if ((rc = grow(&CL.d_lit, &CL.lit_cap, (size_t)span * SCR_STRIDE)) != ITX_OK) return rc;      // (growing frees: that waits for whatever still runs)
+    if ((rc = grow(&CL.d_meta, &CL.meta_cap, 3 * (size_t)span)) != ITX_OK) return rc;
+    if (!CL.cst) ITX_HIP(hipStreamCreateWithFlags(&CL.cst, hipStreamNonBlocking));
+    hipStream_t st = CL.cst;
+    for (int m = 0; m < Gr.n; m++) ITX_HIP(hipStreamWaitEvent(st, h->lane[Gr.slot[m]].copied, 0));
+    ITX_HIP(hipEventRecord(Gr.ev[0], st));
+    hipLaunchKernelGGL(k_tokens, dim3((span + 63u) / 64u), dim3(64), 0, st, G, CL.d_lit, CL.d_meta);
+    ITX_HIP(hipGetLastError());
+    // pass 2 on the same stream, one wave per block (every push's pass 2 on one shared stream, or a fixed set of waves
+    // that take blocks in turn, were measured slower: DESIGN.md)
+    ITX_HIP(hipEventRecord(Gr.ev[1], st));
+    hipLaunchKernelGGL(k_resolve, dim3(span), dim3(64), 0, st, G, 0u, span, CL.d_lit, CL.d_meta);
+    ITX_HIP(hipGetLastError());
+    ITX_HIP(hipEventRecord(Gr.ev[2], st));
+    for (int m = 0; m < Gr.n; m++) {
+        auto &Ln = h->lane[Gr.slot[m]];
+        ITX_HIP(hipMemcpyAsync(Ln.h_status, Ln.d_status, Ln.n_blk, hipMemcpyDeviceToHost, st));
+    }
+    ITX_HIP(hipEventRecord(Gr.done, st));
+    Gr.launched = true;
+    g_launches++;
+    for (int m = 0; m < Gr.n; m++) g_blocks += counts[m];
+    return ITX_OK;
+}
+
+/* push, first half: the copies are enqueued on the copy stream, the push joins the open group, and the group_size()-th member
+ * launches the group (itx_bamwin_push_end launches a group that is still open); the caller's buffers are in use until
  * itx_bamwin_push_copied (comp) / this call's return (blk) */
 extern "C" int itx_bamwin_push_begin(itx_inflater *h, int w, int s, const void *comp, size_t comp_len, const itx_bgzf_block *blk, size_t n_blk)
 {
@@ -833,7 +946,7 @@ extern "C" int itx_bamwin_push_begin(itx_inflater *h, int w, int s, const void *
     size_t total = 0;
     int rc = check_blocks(blk, n_blk, comp_len, &total);
     if (rc != ITX_OK) return rc;
-    if (comp_len > 0xfffffff0u || total + WIN_HEAD > 0xfffffff0u || n_blk > 0x7fffffffu) return ITX_E_LIMIT;
+    if (comp_len > 0xfffffff0u || total + WIN_HEAD > 0xfffffff0u || n_blk > 0x7fffffffu / ITXG_SLOTS) return ITX_E_LIMIT;
     ITX_HIP(hipSetDevice(h->device));
     if (h->arena && (w >= h->n_reserved_win || WIN_HEAD + total + 64 > h->win[w].cap || comp_len + 64 > Ln.comp_cap || n_blk > Ln.status_cap)) {
         itx_set_error("push of %zu blocks / %zu bytes into window %d exceeds what itx_inflater_reserve set up", n_blk, total, w);
@@ -844,6 +957,7 @@ extern "C" int itx_bamwin_push_begin(itx_inflater *h, int w, int s, const void *
     h->win[w].len = WIN_HEAD + (uint32_t)total;
     Ln.n_blk = n_blk;
     Ln.total = total;
+    Ln.grp = -1;
     Ln.busy = 1;
     if (n_blk == 0) return ITX_OK;
     if (Ln.h_cap < n_blk) {
@@ -861,35 +975,33 @@ extern "C" int itx_bamwin_push_begin(itx_inflater *h, int w, int s, const void *
         Ln.h_blk[i] = blk[i];
         Ln.h_blk[i].uoff += WIN_HEAD;
     }
-    auto &CL = h->clane[s % compute_lanes()];
     if ((rc = grow(&Ln.d_comp, &Ln.comp_cap, comp_len + 64)) != ITX_OK) return rc;
     if ((rc = grow(&Ln.d_status, &Ln.status_cap, n_blk)) != ITX_OK) return rc;
     if ((rc = grow(&Ln.d_blk, &Ln.blk_cap, n_blk)) != ITX_OK) return rc;
-    if ((rc = grow(&CL.d_lit, &CL.lit_cap, n_blk * (size_t)SCR_STRIDE)) != ITX_OK) return rc;      // (growing frees: that waits for whatever still runs)
-    if ((rc = grow(&CL.d_meta, &CL.meta_cap, 3 * n_blk)) != ITX_OK) return rc;
     // the bytes cross PCIe on the copy stream ...
     ITX_HIP(hipMemcpyAsync(Ln.d_blk, Ln.h_blk, n_blk * sizeof *blk, hipMemcpyHostToDevice, h->copy_st));
     ITX_HIP(hipMemcpyAsync(Ln.d_comp, comp, comp_len, hipMemcpyHostToDevice, h->copy_st));
     ITX_HIP(hipEventRecord(Ln.copied, h->copy_st));
-    // ... and both passes run on the compute lane, behind the push that had the lane (and its scratch) before
-    hipStream_t st = CL.cst;
-    ITX_HIP(hipStreamWaitEvent(st, Ln.copied, 0));
-    ITX_HIP(hipEventRecord(Ln.ev[0], st));
-    hipLaunchKernelGGL(k_tokens, dim3((unsigned)((n_blk + 63) / 64)), dim3(64), 0, st, (const uint32_t *)Ln.d_comp, Ln.d_blk, (uint32_t)n_blk, CL.d_lit, CL.d_meta);
-    ITX_HIP(hipGetLastError());
-    // pass 2 on the same stream, one wave per block (every push's pass 2 on one shared stream, or a fixed set of waves
-    // that take blocks in turn, were measured slower: DESIGN.md)
-    hipStream_t sr = st;
-    ITX_HIP(hipEventRecord(Ln.ev[1], sr));
-    hipLaunchKernelGGL(k_resolve, dim3((unsigned)n_blk), dim3(64), 0, sr, Ln.d_blk, 0u, (uint32_t)n_blk, CL.d_lit, CL.d_meta, h->win[w].buf, Ln.d_status);
-    ITX_HIP(hipGetLastError());
-    ITX_HIP(hipEventRecord(Ln.ev[2], sr));
-    ITX_HIP(hipMemcpyAsync(Ln.h_status, Ln.d_status, n_blk, hipMemcpyDeviceToHost, sr));
-    ITX_HIP(hipEventRecord(Ln.done, sr));
+    // ... and both passes run with the group's, on a compute lane
+    if (h->open_grp < 0) {
+        int gi = 0;
+        while (gi < lanes_in_use() && h->grp[gi].live) gi++;       // every live group has a busy slot, and this slot was not: one is free
+        if (gi == lanes_in_use()) return ITX_E_STATE;
+        h->grp[gi].n = h->grp[gi].live = 0;
+        h->grp[gi].launched = h->grp[gi].timed = false;
+        h->open_grp = gi;
+    }
+    auto &Gr = h->grp[h->open_grp];
+    Gr.slot[Gr.n++] = s;
+    Gr.live++;
+    Ln.grp = h->open_grp;
+    Ln.win_buf = h->win[w].buf;
+    if (Gr.n == group_size()) return launch_group(h);
     return ITX_OK;
 }
 
-/* the compressed bytes of lane s's push have been copied: the caller may reuse that buffer */
+/* the compressed bytes of lane s's push have been copied: the caller may reuse that buffer. (Never launches a group: the
+ * reader's io thread calls this, and the copies do not wait for the group.) */
 extern "C" int itx_bamwin_push_copied(itx_inflater *h, int s)
 {
     if (!h || BAD_S(s)) return ITX_E_ARG;
@@ -899,23 +1011,35 @@ extern "C" int itx_bamwin_push_copied(itx_inflater *h, int s)
     return ITX_OK;
 }
 
-/* push, second half: waits for lane s's push; status[n_blk] as for itx_inflate_bgzf, *n_new = bytes the window gained */
+/* push, second half: waits for lane s's push — launching its group first if that is still open; status[n_blk] as for
+ * itx_inflate_bgzf, *n_new = bytes the window gained */
 extern "C" int itx_bamwin_push_end(itx_inflater *h, int s, uint8_t *status, size_t *n_new)
 {
     if (!h || BAD_S(s) || !status || !n_new) return ITX_E_ARG;
     auto &Ln = h->lane[s];
     if (!Ln.busy) return ITX_E_STATE;
     ITX_HIP(hipSetDevice(h->device));
-    if (Ln.n_blk) ITX_HIP(hipEventSynchronize(Ln.done));
     if (Ln.n_blk) {
-        float a = 0, b = 0;
-        if (hipEventElapsedTime(&a, Ln.ev[0], Ln.ev[1]) == hipSuccess && hipEventElapsedTime(&b, Ln.ev[1], Ln.ev[2]) == hipSuccess) {
-            g_tok_ms += a;
-            g_res_ms += b;
-            g_pushes++;
+        if (Ln.grp < 0) return ITX_E_STATE;                         // its push_begin failed half way
+        auto &Gr = h->grp[Ln.grp];
+        if (!Gr.launched) {
+            if (h->open_grp != Ln.grp) return ITX_E_STATE;          // (an unlaunched group is the open one, unless its launch failed)
+            const int rc = launch_group(h);
+            if (rc != ITX_OK) return rc;
         }
+        ITX_HIP(hipEventSynchronize(Gr.done));
+        if (!Gr.timed) {
+            Gr.timed = true;
+            float a = 0, b = 0;
+            if (hipEventElapsedTime(&a, Gr.ev[0], Gr.ev[1]) == hipSuccess && hipEventElapsedTime(&b, Gr.ev[1], Gr.ev[2]) == hipSuccess) {
+                g_tok_ms += a;
+                g_res_ms += b;
+            }
+        }
+        g_pushes++;
+        Gr.live--;
+        memcpy(status, Ln.h_status, Ln.n_blk);
     }
-    if (Ln.n_blk) memcpy(status, Ln.h_status, Ln.n_blk);
     *n_new = Ln.total;
     Ln.busy = 0;
     return ITX_OK;
@@ -946,8 +1070,10 @@ extern "C" int itx_inflater_reserve(itx_inflater *h, size_t comp_bytes, size_t m
     // ONE allocation for all of it: on some hosts every hipMalloc costs ~15 ms whatever its size (and holds up the other
     // threads' HIP calls meanwhile) — seventy of them were 1.2 s of a 4 s run
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t sz_comp = al(comp_bytes + 64), sz_status = al(max_blocks), sz_blk = al(max_blocks * sizeof(itx_bgzf_block)), sz_lit = al(max_blocks * (size_t)SCR_STRIDE),
-                 sz_meta = al(3 * max_blocks * 4);
+    const size_t sz_comp = al(comp_bytes + 64), sz_status = al(max_blocks), sz_blk = al(max_blocks * sizeof(itx_bgzf_block));
+    // a compute lane's scratch holds a whole group: each member's blocks start at a multiple of ITXG_ALIGN
+    const size_t grp_blocks = (size_t)group_size() * ((max_blocks + ITXG_ALIGN - 1) / ITXG_ALIGN * ITXG_ALIGN);
+    const size_t sz_lit = al(grp_blocks * (size_t)SCR_STRIDE), sz_meta = al(3 * grp_blocks * 4);
     const int n_comp = compute_lanes();
     const size_t total = (sz_comp + sz_status + sz_blk) * (size_t)n_lanes + (sz_lit + sz_meta) * (size_t)n_comp + per * n;
     uint8_t *base = nullptr;
@@ -980,8 +1106,8 @@ extern "C" int itx_inflater_reserve(itx_inflater *h, size_t comp_bytes, size_t m
     }
     for (int k = 0; k < n_comp; k++) {
         auto &CL = h->clane[k];
-        CL.d_lit = p; p += sz_lit; CL.lit_cap = max_blocks * (size_t)SCR_STRIDE;
-        CL.d_meta = (uint32_t *)p; p += sz_meta; CL.meta_cap = 3 * max_blocks;
+        CL.d_lit = p; p += sz_lit; CL.lit_cap = grp_blocks * (size_t)SCR_STRIDE;
+        CL.d_meta = (uint32_t *)p; p += sz_meta; CL.meta_cap = 3 * grp_blocks;
     }
     for (size_t w = 0; w < n; w++) {
         if (h->win[w].buf) (void)hipFree(h->win[w].buf);

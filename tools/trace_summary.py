@@ -90,6 +90,21 @@ if tk and rs:
     d1 = sum(b - a for a, b, n in iv if n.startswith("k_tokens"))
     d2 = sum(b - a for a, b, n in iv if n.startswith("k_resolve"))
     print(f"mean pass-1 kernels in flight while any runs: {d1 / max(length(tk), 1):.2f}; pass-2: {d2 / max(length(rs), 1):.2f}")
+# which hardware queue (and stream) each of the decoder's and the consumer's kernels ran on: streams that share a queue id run
+# their kernels one after the other
+for name in ("k_tokens", "k_resolve", "k_guess", "k_parse", "k_stream"):
+    ids = defaultdict(int)
+    for r in k:
+        if r["Kernel_Name"].replace("void ", "", 1).startswith(name):
+            ids[(r.get("Queue_Id", "?"), r.get("Stream_Id", "?"))] += 1
+    if ids:
+        print(f"{name}: (queue id, stream id): launches " + ", ".join(f"({q}, {s}): {c}" for (q, s), c in sorted(ids.items())))
+ids = defaultdict(int)
+for r in m:
+    if "HOST_TO_DEVICE" in r.get("Direction", "") and int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) > 2_000_000:
+        ids[(r.get("Queue_Id", "?"), r.get("Stream_Id", "?"))] += 1
+if ids:
+    print("big H2D copies: (queue id, stream id): copies " + ", ".join(f"({q}, {s}): {c}" for (q, s), c in sorted(ids.items())))
 cp = defaultdict(lambda: [0, 0, 0])
 for r in m:
     a, b = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
