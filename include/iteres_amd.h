@@ -459,6 +459,44 @@ int itx_names_append_host(itx_names *nm, const uint32_t *rows, const char *name_
 int itx_names_finish(itx_names *nm, size_t n_rows, itx_names_result *out);
 int itx_names_get_stats(const itx_names *nm, itx_names_stats *out);
 
+/* ---- the .loci file of filter / cpgfilter on the device ----------------------------------------------------------------------
+ * Replaces the row walk and the fprintf of writeFilterOut (generic.c:1709-1746) and writeFilterOutMRE (generic.c:1748-1772): the
+ * order of the lines is a function of the table alone — hashRmsk's chromosomes in hash order, a chromosome's rows by bin
+ * ascending, newest insertion first (cuskent/binRange.c:365-392) — so it is sorted when the table is known, beside the scan of
+ * the alignments; the lines are formatted where the sorted table lies and come back as one text (csrc/itx_loci.hip, the line
+ * rule: csrc/itx_lociline.h).
+ *   create      kind: ITX_LOCI_FILTER / ITX_LOCI_CPG. rows[n_rows] in file order with row_chrom[i] = row i's index into the
+ *               chromosome names (itx_row.chrom is not read); chrom_rank[c] = chromosome c's place in the file's chromosome order;
+ *               four name tables, name i = bytes[off[i] .. off[i + 1]) (off has n + 1 elements): chromosomes, then what
+ *               itx_row.rep / .cla / .fam index. Uploads (the caller's arrays are its own again on return), starts the sort on a
+ *               stream of its own and returns without waiting for it. n_chrom >= 2^19, n_rows >= 2^32 - 1, or a row whose bin does
+ *               not fit 13 bits (a coordinate of 460 M and above): ITX_E_RANGE, before anything is allocated. ITX_E_NOMEM: the
+ *               device cannot hold the table.
+ *   order       waits for the sort; order[k] = the row at place k of the file (n_rows elements); *sort_ms (optional): its device time
+ *   filter_text the lines of writeFilterOut without the read lists (generic.c:1719-1728): locus_cnt[n_rows], the -t threshold, the
+ *               normalising read number. cpg_text: those of writeFilterOutMRE (generic.c:1760-1766): cpg_count[n_rows],
+ *               cpg_total[n_rows], the -t threshold. out->lines: lines printed; out->hard: printed lines with a double the device
+ *               does not model (not finite: a read number of 0, a row of length 0; 2^63 and above) — then text is NULL and the
+ *               caller writes the whole file itself. Else text[0 .. bytes) is the file behind its header line, host memory owned by
+ *               the object (capacity bytes, the ones behind the text filled with 0xA5 on the device), valid until the next call.
+ *               The text call of the other kind: ITX_E_ARG. ITX_E_NOMEM: no room for the text. */
+typedef struct itx_loci itx_loci;
+#define ITX_LOCI_FILTER 0
+#define ITX_LOCI_CPG 1
+typedef struct itx_loci_text {
+    const char *text;
+    uint64_t bytes, capacity, lines, hard;
+    double sort_ms, text_ms;                   /* device time: key + sort kernels; measure + scan + write kernels of this call */
+} itx_loci_text;
+int itx_loci_create(int device, int kind, const itx_row *rows, const uint32_t *row_chrom, size_t n_rows, const uint32_t *chrom_rank, uint32_t n_chrom,
+                    const char *chrom_bytes, const uint64_t *chrom_off, const char *rep_bytes, const uint64_t *rep_off, uint32_t n_rep,
+                    const char *cla_bytes, const uint64_t *cla_off, uint32_t n_cla, const char *fam_bytes, const uint64_t *fam_off, uint32_t n_fam,
+                    itx_loci **out);
+void itx_loci_destroy(itx_loci *lo);
+int itx_loci_order(itx_loci *lo, uint32_t *order, double *sort_ms);
+int itx_loci_filter_text(itx_loci *lo, const uint32_t *locus_cnt, int threshold, unsigned long long reads_num, itx_loci_text *out);
+int itx_loci_cpg_text(itx_loci *lo, const int *cpg_count, const double *cpg_total, double threshold, itx_loci_text *out);
+
 /* ITX_TIMING: what the device decoder measured about itself (pushes, mean duration of the two passes, device allocations),
  * one line on stderr; also printed when the process exits normally. */
 void itx_timing_report(void);

@@ -22,6 +22,7 @@
 //
 // Byte and integer work; the sort's scatter moves the most bytes. No kernel uses scratch (DESIGN.md has the figures).
 #include "itx_textpack.h"
+#include "itx_radixsort.h"
 #include "itx_bedline.h"
 
 #include <stdlib.h>
@@ -34,7 +35,6 @@ typedef unsigned long long ull;
 #define NM_TILE 256u                 // records (gather) / sorted entries (write) per workgroup
 #define NM_LDS 16384u                // bytes staged at a time: a tile of ordinary names (256 x 20-40 bytes) in one window
 #define NM_NOHIT 0xffffffffu
-#define SORT_CHUNK 8192u             // keys per workgroup and pass
 #define NM_MAX_ENTRIES 0xfffffffeull
 #define NM_COPY_CHUNK ((size_t)8 << 20)
 
@@ -109,72 +109,7 @@ __global__ __launch_bounds__(256) void k_sort_init(const NameEnt *__restrict__ e
     keys[j] = make_uint2(row, j);
 }
 
-__global__ __launch_bounds__(256) void k_sort_hist(const uint2 *__restrict__ keys, uint32_t n, uint32_t shift, uint32_t *__restrict__ hist, uint32_t nwg)
-{
-    __shared__ uint32_t s_h[256];
-    s_h[threadIdx.x] = 0;
-    __syncthreads();
-    const ull base = (ull)blockIdx.x * SORT_CHUNK;
-    for (uint32_t k = threadIdx.x; k < SORT_CHUNK && base + k < n; k += 256u) atomicAdd(&s_h[(keys[base + k].x >> shift) & 255u], 1u);
-    __syncthreads();
-    hist[(size_t)threadIdx.x * nwg + blockIdx.x] = s_h[threadIdx.x];
-}
-
-// exclusive scan in place, one workgroup; digit-major counts: the scanned value is where (digit, workgroup) starts
-__global__ __launch_bounds__(ITX_SCAN_WG) void k_sort_scan(uint32_t *__restrict__ v, uint32_t n)
-{
-    __shared__ uint32_t s[ITX_SCAN_WG];
-    uint64_t lo, hi;
-    itx_scan_chunk(n, &lo, &hi);
-    uint32_t a = 0, total;
-    for (uint64_t k = lo; k < hi; k++) a += v[k];
-    uint32_t e = itx_scan_wg(a, s, &total);
-    for (uint64_t k = lo; k < hi; k++) {
-        const uint32_t c = v[k];
-        v[k] = e;
-        e += c;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_sort_scatter(const uint2 *__restrict__ in, uint2 *__restrict__ out, uint32_t n, uint32_t shift, const uint32_t *__restrict__ hist,
-                                                       uint32_t nwg)
-{
-    __shared__ uint32_t s_base[256];
-    __shared__ uint32_t s_wc[4][256];
-    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-    s_base[t] = hist[(size_t)t * nwg + blockIdx.x];
-    for (uint32_t k = 0; k < 4u; k++) s_wc[k][t] = 0;
-    __syncthreads();
-    const ull base = (ull)blockIdx.x * SORT_CHUNK;
-    for (uint32_t r = 0; r < SORT_CHUNK && base + r < n; r += 256u) {
-        const ull j = base + r + t;
-        const bool valid = j < n;
-        const uint2 key = valid ? in[j] : make_uint2(0u, 0u);
-        const uint32_t d = (key.x >> shift) & 255u;
-        ull m = __ballot(valid);                                        // the lanes of this wave with the same digit
-        for (uint32_t bit = 0; bit < 8u; bit++) {
-            const bool one = (d >> bit) & 1u;
-            const ull bm = __ballot(one);
-            m &= one ? bm : ~bm;
-        }
-        const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        if (valid && rank == 0) s_wc[w][d] = (uint32_t)__popcll(m);
-        __syncthreads();
-        if (valid) {
-            uint32_t off = s_base[d] + rank;
-            for (uint32_t k = 0; k < w; k++) off += s_wc[k][d];
-            out[off] = key;
-        }
-        __syncthreads();
-        uint32_t sum = 0;
-        for (uint32_t k = 0; k < 4u; k++) {
-            sum += s_wc[k][t];
-            s_wc[k][t] = 0;
-        }
-        s_base[t] += sum;
-        __syncthreads();
-    }
-}
+// (k_sort_hist, k_sort_scan, k_sort_scatter: itx_radixsort.h)
 
 // ---- the text
 __global__ __launch_bounds__(NM_TILE) void k_text_measure(const uint2 *__restrict__ keys, const NameEnt *__restrict__ ent, uint32_t n, ull *__restrict__ tile_sum)

@@ -33,6 +33,7 @@ EXPORTS = [
     "itx_bed_create", "itx_bed_destroy", "itx_bed_set_tidmap", "itx_bamwin_bed", "itx_bed_run", "itx_bed_wait_kernels", "itx_bed_collect", "itx_bed_get_stats",
     "itx_names_create", "itx_names_destroy", "itx_names_hits", "itx_names_stream", "itx_bamwin_names", "itx_names_run", "itx_names_wait_kernels", "itx_names_append_host",
     "itx_names_finish", "itx_names_get_stats",
+    "itx_loci_create", "itx_loci_destroy", "itx_loci_order", "itx_loci_filter_text", "itx_loci_cpg_text",
 ]
 
 
@@ -111,6 +112,14 @@ class NamesResult(C.Structure):
 class NamesStats(C.Structure):
     _fields_ = [("batches", C.c_uint64), ("hard_batches", C.c_uint64), ("host_batches", C.c_uint64), ("entries", C.c_uint64), ("bytes", C.c_uint64),
                 ("grows", C.c_uint64), ("gather_ms", C.c_double), ("finish_ms", C.c_double)]
+
+
+class LociText(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("bytes", C.c_uint64), ("capacity", C.c_uint64), ("lines", C.c_uint64), ("hard", C.c_uint64), ("sort_ms", C.c_double),
+                ("text_ms", C.c_double)]
+
+
+LOCI_FILTER, LOCI_CPG = 0, 1
 
 _lib = None
 
@@ -202,6 +211,13 @@ def load():
     L.itx_names_append_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.itx_names_finish.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(NamesResult)]
     L.itx_names_get_stats.argtypes = [C.c_void_p, C.POINTER(NamesStats)]
+    L.itx_loci_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                  C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.itx_loci_destroy.argtypes = [C.c_void_p]
+    L.itx_loci_destroy.restype = None
+    L.itx_loci_order.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+    L.itx_loci_filter_text.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_ulonglong, C.POINTER(LociText)]
+    L.itx_loci_cpg_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(LociText)]
     L.itx_pinned_alloc.argtypes = [C.c_size_t]
     L.itx_pinned_alloc.restype = C.c_void_p
     L.itx_pinned_free.argtypes = [C.c_void_p]

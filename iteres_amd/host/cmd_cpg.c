@@ -429,6 +429,7 @@ int main_cpgfilter(int argc, char **argv)
     rmsk_t rm;
     rmsk_load(rmsk_file, &chr_sizes, &rep_sizes, filter_field, subfam, &rm);
     fprintf(stderr, "* Total %d repeats found.\n", rm.repeat_num);
+    loci_dev *ldev = loci_dev_begin(&rm, ITX_LOCI_CPG, 0, 0);          /* the order of the lines: sorted on the device from here on */
 
     fprintf(stderr, "* Start to parse the bedGraph file\n");
     cpg_sites sites;
@@ -449,7 +450,8 @@ int main_cpgfilter(int argc, char **argv)
     fprintf(stderr, "* Preparing the output file\n");
     char *out = NULL;
     if (asprintf(&out, "%s_%s.CpG.loci", output, subfam) < 0) die("Preparing output wrong");
-    write_cpg_loci(&rm, cnt, tot, out, subfam, threshold);
+    write_cpg_loci(&rm, cnt, tot, out, subfam, threshold, ldev);
+    loci_dev_free(ldev);
     fprintf(stderr, "* Done, time used %.0f seconds.\n", difftime(time(NULL), start_time));
     return 0;
 }

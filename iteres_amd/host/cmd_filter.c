@@ -118,6 +118,8 @@ int main_filter(int argc, char **argv)
         if (rm.repeat_num <= 0) die("* No repeats found related to [%s], typo? or specify wrong repName/Class/Family filter?", subfam);
         fprintf(stderr, "* Total %d repeats for [%s].\n", rm.repeat_num, subfam);
     }
+    /* the .loci order depends on the table alone: its sort runs on the device beside the scan (rank 0 writes the files) */
+    loci_dev *ldev = multi_rank() == 0 ? loci_dev_begin(&rm, ITX_LOCI_FILTER, optreadlist, multi_device()) : NULL;
     fprintf(stderr, "* Start to parse the SAM/BAM file\n");
     itx_engine *eng = NULL;
     itx_table *tab = NULL;
@@ -141,7 +143,8 @@ int main_filter(int argc, char **argv)
         for (size_t r = 0; r < rm.n_rows; r++)
             if (names_cnt[r] != res.locus_cnt[r])
                 die("read lists: row %zu has %u names but %u counted reads (ITX_HOST_NAMES=1 builds the lists on the host)", r, names_cnt[r], res.locus_cnt[r]);
-    write_filter_out(&rm, res.locus_cnt, locus_names, out, optreadlist, optthreshold, subfam, cnt[nindex]);
+    write_filter_out(&rm, res.locus_cnt, locus_names, out, optreadlist, optthreshold, subfam, cnt[nindex], ldev);
+    loci_dev_free(ldev);
     if (names_cnt) {
         stream_names_free(locus_names);
     } else if (locus_names) {

@@ -222,8 +222,16 @@ void write_report(const char *path, const uint64_t *cnt, unsigned mapq, const ch
 void write_wig_and_stat(const rmsk_t *rm, const itx_result *res, const uint64_t *cov_off, const char *f_stat, const char *f_wig,
                         const char *f_fam, const char *f_cla, const char *f_wig_uniq, unsigned long long reads_num,
                         unsigned long long reads_num_unique);
+/* The .loci file's order sorted and its lines formatted on the device (include/iteres_amd.h: itx_loci_*). loci_dev_begin, right
+ * after the table is loaded: decides the route (ITX_HOST_LOCI; filter -r stays with the host) and starts the device's sort, which
+ * runs beside whatever the command does next; the writer takes the device's text, or writes the file itself when the route is the
+ * host's, the device cannot hold the table, or a line holds a number the device does not print. ITX_TIMING: one line says which.
+ * kind: ITX_LOCI_FILTER / ITX_LOCI_CPG; device: the HIP device. dev may be NULL: the host writes, no timing line. */
+typedef struct loci_dev loci_dev;
+loci_dev *loci_dev_begin(const rmsk_t *rm, int kind, int readlist, int device);
+void loci_dev_free(loci_dev *d);
 void write_filter_out(const rmsk_t *rm, const uint32_t *locus_cnt, char **locus_names, const char *path, int readlist, int threshold,
-                      const char *subfam, unsigned long long reads_num);
+                      const char *subfam, unsigned long long reads_num, loci_dev *dev);
 
 /* bigwig.c: the bigWig of one set of wig blocks (stat.c:156-158); only names with a consensus length belong here */
 void write_bigwig(const char *path, const char *wig_name, const char *const *names, const uint32_t *len, const float *const *val,
@@ -279,7 +287,7 @@ void stream_names_free(char **locus_names);
 int main_cpgstat(int argc, char **argv);
 int main_cpgfilter(int argc, char **argv);
 
-void write_cpg_loci(const rmsk_t *rm, const int *cpg_count, const double *cpg_total, const char *path, const char *subfam, double threshold);
+void write_cpg_loci(const rmsk_t *rm, const int *cpg_count, const double *cpg_total, const char *path, const char *subfam, double threshold, loci_dev *dev);
 
 int main_stat(int argc, char **argv);
 int main_filter(int argc, char **argv);

@@ -4,6 +4,7 @@
  * binKeeperNext's order: bins ascending, newest insertion first (cuskent/binRange.c:365-392). */
 #define _GNU_SOURCE
 #include "itx_host.h"
+#include "../csrc/itx_lociline.h"
 
 #include <errno.h>
 #include <stdlib.h>
@@ -11,12 +12,12 @@
 
 double cal_rpkm(unsigned long long reads_count, unsigned long long total_length, unsigned long long mapped_reads_num)
 {
-    return reads_count / (mapped_reads_num * 1e-9 * total_length);
+    return itx_loci_rpkm(reads_count, total_length, mapped_reads_num);
 }
 
 double cal_rpm(unsigned long long reads_count, unsigned long long mapped_reads_num)
 {
-    return reads_count / (mapped_reads_num * 1e-6);
+    return itx_loci_rpm(reads_count, mapped_reads_num);
 }
 
 static FILE *must_open(const char *path, const char *mode)
@@ -134,19 +135,6 @@ void write_wig_and_stat(const rmsk_t *rm, const itx_result *res, const uint64_t 
     free(order);
 }
 
-/* cuskent/binRange.c:119-138 */
-static int bin_of_range(int start, int end)
-{
-    static const int off[6] = {4096 + 512 + 64 + 8 + 1, 512 + 64 + 8 + 1, 64 + 8 + 1, 8 + 1, 1, 0};
-    int sb = start >> 17, eb = (end - 1) >> 17;
-    for (int i = 0; i < 6; ++i) {
-        if (sb == eb) return off[i] + sb;
-        sb >>= 3;
-        eb >>= 3;
-    }
-    return -1;
-}
-
 struct lo {
     int bin;
     uint32_t row;
@@ -158,13 +146,22 @@ static int lo_cmp(const void *a, const void *b)
     return x->row > y->row ? -1 : (x->row < y->row ? 1 : 0);      /* list head = newest insertion (binRange.c:185) */
 }
 
-/* The loci of a table in binKeeper order: hashRmsk's chromosome order (names_kent_order), and for every chromosome its
- * rows with their bin numbers, to be sorted by lo_cmp (cuskent/binRange.c:365-392). */
+/* hashRmsk's chromosome order, for the host's walk and for the device's sort key alike: corder[k] = the chromosome at place k
+ * (NC + 1 elements), rank[c] = the place of chromosome c (NULL: not wanted) */
+static void loci_chrom_order(const rmsk_t *rm, uint32_t *corder, uint32_t *rank)
+{
+    names_kent_order(&rm->chroms, 12, corder);                  /* hashRmsk = newHash(0): 2^12 buckets */
+    if (rank)
+        for (uint32_t k = 0; k < rm->chroms.n; k++) rank[corder[k]] = k;
+}
+
+/* The loci of a table in binKeeper order: hashRmsk's chromosome order, and for every chromosome its rows with their bin numbers
+ * (itx_loci_bin of ../csrc/itx_lociline.h), to be sorted by lo_cmp (cuskent/binRange.c:365-392). */
 static struct lo *loci_prepare(const rmsk_t *rm, uint32_t **corder_out, size_t **cnt_out, size_t **beg_out)
 {
     const uint32_t NC = rm->chroms.n;
     uint32_t *corder = xmalloc(sizeof(uint32_t) * (NC + 1));
-    names_kent_order(&rm->chroms, 12, corder);                  /* hashRmsk = newHash(0): 2^12 buckets */
+    loci_chrom_order(rm, corder, NULL);
     /* rows per chromosome */
     size_t *cnt = xcalloc(NC + 1, sizeof(size_t)), *beg = xcalloc(NC + 2, sizeof(size_t));
     for (size_t r = 0; r < rm->n_rows; r++) cnt[rm->row_chrom_name[r]]++;
@@ -174,7 +171,7 @@ static struct lo *loci_prepare(const rmsk_t *rm, uint32_t **corder_out, size_t *
     memcpy(fill, beg, sizeof(size_t) * (NC + 1));
     for (size_t r = 0; r < rm->n_rows; r++) {
         struct lo *e = &lo[fill[rm->row_chrom_name[r]]++];
-        e->bin = bin_of_range((int)rm->rows[r].start, (int)rm->rows[r].end);
+        e->bin = itx_loci_bin((int)rm->rows[r].start, (int)rm->rows[r].end);
         e->row = (uint32_t)r;
     }
     free(fill);
@@ -184,8 +181,91 @@ static struct lo *loci_prepare(const rmsk_t *rm, uint32_t **corder_out, size_t *
     return lo;
 }
 
+/* ---- the device route (include/iteres_amd.h itx_loci_*): the order is sorted on the device from the moment the table is known, the
+ * lines are formatted there from the counts. Which route writes the file when ITX_HOST_LOCI is not set: the device route becomes the
+ * default only on a measurement of the whole command ("The .loci file on the device"); until one exists the host writes
+ * it, as before. ITX_HOST_LOCI=0 asks for the device route, ITX_HOST_LOCI=1 for the host's. filter -r stays with the host: its
+ * lists are in host memory. */
+struct loci_dev {
+    itx_loci *obj;
+    int timing;
+    char why[160];               /* why the host writes the file ("": the device does) */
+};
+
+static void loci_name_table(const names_t *t, char **bytes, uint64_t **off)
+{
+    uint64_t *o = xmalloc(sizeof(uint64_t) * ((size_t)t->n + 1));
+    o[0] = 0;
+    for (uint32_t i = 0; i < t->n; i++) o[i + 1] = o[i] + strlen(t->name[i]);
+    char *b = xmalloc(o[t->n] + 1);
+    for (uint32_t i = 0; i < t->n; i++) memcpy(b + o[i], t->name[i], o[i + 1] - o[i]);
+    *bytes = b;
+    *off = o;
+}
+
+loci_dev *loci_dev_begin(const rmsk_t *rm, int kind, int readlist, int device)
+{
+    loci_dev *d = xcalloc(1, sizeof *d);
+    const char *e = getenv("ITX_HOST_LOCI");
+    d->timing = getenv("ITX_TIMING") != NULL;
+    if (readlist) snprintf(d->why, sizeof d->why, "-r: the read lists are in host memory");
+    else if (!e || !*e) snprintf(d->why, sizeof d->why, "ITX_HOST_LOCI is not set: the host is the default");
+    else if (atoi(e) != 0) snprintf(d->why, sizeof d->why, "ITX_HOST_LOCI=%s", e);
+    if (d->why[0]) return d;
+    const uint32_t NC = rm->chroms.n;
+    uint32_t *corder = xmalloc(sizeof(uint32_t) * (NC + 1)), *rank = xmalloc(sizeof(uint32_t) * (NC + 1));
+    loci_chrom_order(rm, corder, rank);
+    const names_t *tabs[4] = {&rm->chroms, &rm->reps, &rm->clas, &rm->fams};
+    char *nb[4];
+    uint64_t *no[4];
+    for (int t = 0; t < 4; t++) loci_name_table(tabs[t], &nb[t], &no[t]);
+    /* writeFilterOut generic.c:1709-1746 / writeFilterOutMRE generic.c:1748-1772: the walk over hashRmsk and its binKeepers */
+    const int rc = itx_loci_create(device, kind, rm->rows, rm->row_chrom_name, rm->n_rows, rank, NC, nb[0], no[0], nb[1], no[1], rm->reps.n, nb[2], no[2], rm->clas.n,
+                                   nb[3], no[3], rm->fams.n, &d->obj);
+    if (rc == ITX_E_RANGE) snprintf(d->why, sizeof d->why, "ITX_E_RANGE: the table does not fit the device's sort key");
+    else if (rc == ITX_E_NOMEM) snprintf(d->why, sizeof d->why, "ITX_E_NOMEM: the device cannot hold the table");
+    else chk(rc, "itx_loci_create");
+    for (int t = 0; t < 4; t++) {
+        free(nb[t]);
+        free(no[t]);
+    }
+    free(corder);
+    free(rank);
+    return d;
+}
+
+void loci_dev_free(loci_dev *d)
+{
+    if (!d) return;
+    itx_loci_destroy(d->obj);
+    free(d);
+}
+
+/* after a text call: 1 when the device's text is the file's body (then the timing line is printed here) */
+static int loci_dev_took(loci_dev *d, int rc, const itx_loci_text *tx, double waited)
+{
+    if (rc == ITX_E_NOMEM) {
+        snprintf(d->why, sizeof d->why, "ITX_E_NOMEM: no room for the text");
+        return 0;
+    }
+    chk(rc, "itx_loci text");
+    if (tx->hard) {
+        snprintf(d->why, sizeof d->why, "%llu lines hold a number the device does not print: not finite, or 2^63 and above", (unsigned long long)tx->hard);
+        return 0;
+    }
+    if (d->timing)
+        fprintf(stderr, "[itx timing] loci: %llu lines built on the device (%llu bytes, sort %.3f ms, text %.3f ms, host waited %.3f s)\n",
+                (unsigned long long)tx->lines, (unsigned long long)tx->bytes, tx->sort_ms, tx->text_ms, waited);
+    return 1;
+}
+
+static void loci_dev_host_wrote(const loci_dev *d, int lines)
+{
+    if (d && d->timing) fprintf(stderr, "[itx timing] loci: %d lines written by the host (%s)\n", lines, d->why);
+}
+
 void write_filter_out(const rmsk_t *rm, const uint32_t *locus_cnt, char **locus_names, const char *path, int readlist, int threshold,
-                      const char *subfam, unsigned long long reads_num)
+                      const char *subfam, unsigned long long reads_num, loci_dev *dev)
 {
     FILE *out = must_open(path, "w");
     int j = 0;
@@ -195,6 +275,17 @@ void write_filter_out(const rmsk_t *rm, const uint32_t *locus_cnt, char **locus_
     else
         fprintf(out, "%s\t%s\t%s\t%s\t%s\t%s\t%s\t%s\t%s\t%s\n", "#chr", "start", "end", "length", "repName", "repClass", "repFamily",
                 "readsCount", "RPKM", "RPM");
+    if (dev && dev->obj && !readlist) {
+        itx_loci_text tx;
+        const double t0 = now_s();
+        const int rc = itx_loci_filter_text(dev->obj, locus_cnt, threshold, reads_num, &tx);
+        if (loci_dev_took(dev, rc, &tx, now_s() - t0)) {
+            if (tx.bytes && fwrite(tx.text, 1, tx.bytes, out) != tx.bytes) die("%s: %s", path, strerror(errno));
+            fclose(out);
+            fprintf(stderr, "* Total %d [%s] TEs have at least %d reads mapped.\n", (int)tx.lines, subfam, threshold);
+            return;
+        }
+    }
     const uint32_t NC = rm->chroms.n;
     uint32_t *corder;
     size_t *cnt, *beg;
@@ -219,6 +310,7 @@ void write_filter_out(const rmsk_t *rm, const uint32_t *locus_cnt, char **locus_
     }
     fclose(out);
     fprintf(stderr, "* Total %d [%s] TEs have at least %d reads mapped.\n", j, subfam, threshold);
+    loci_dev_host_wrote(dev, j);
     free(lo);
     free(cnt);
     free(beg);
@@ -226,12 +318,23 @@ void write_filter_out(const rmsk_t *rm, const uint32_t *locus_cnt, char **locus_
 }
 
 /* writeFilterOutMRE, generic.c:1748-1772 */
-void write_cpg_loci(const rmsk_t *rm, const int *cpg_count, const double *cpg_total, const char *path, const char *subfam, double threshold)
+void write_cpg_loci(const rmsk_t *rm, const int *cpg_count, const double *cpg_total, const char *path, const char *subfam, double threshold, loci_dev *dev)
 {
     FILE *out = must_open(path, "w");
     int j = 0;
     fprintf(out, "%s\t%s\t%s\t%s\t%s\t%s\t%s\t%s\t%s\n", "#chr", "start", "end", "length", "repName", "repClass", "repFamily", "covered_CpG_site",
             "total_CpG_score");
+    if (dev && dev->obj) {
+        itx_loci_text tx;
+        const double t0 = now_s();
+        const int rc = itx_loci_cpg_text(dev->obj, cpg_count, cpg_total, threshold, &tx);
+        if (loci_dev_took(dev, rc, &tx, now_s() - t0)) {
+            if (tx.bytes && fwrite(tx.text, 1, tx.bytes, out) != tx.bytes) die("%s: %s", path, strerror(errno));
+            fclose(out);
+            fprintf(stderr, "* Total %d [%s] TEs have CpG score larger than %.3f.\n", (int)tx.lines, subfam, threshold);
+            return;
+        }
+    }
     const uint32_t NC = rm->chroms.n;
     uint32_t *corder;
     size_t *cnt, *beg;
@@ -250,6 +353,7 @@ void write_cpg_loci(const rmsk_t *rm, const int *cpg_count, const double *cpg_to
     }
     fclose(out);
     fprintf(stderr, "* Total %d [%s] TEs have CpG score larger than %.3f.\n", j, subfam, threshold);
+    loci_dev_host_wrote(dev, j);
     free(lo);
     free(cnt);
     free(beg);

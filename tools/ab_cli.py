@@ -3,7 +3,7 @@
 Generates the bench inputs once (bench.py's generator), then runs `iteres stat -w` <reps> times per setting, interleaved.
 LD_LIBRARY_PATH in a setting selects another build of libiteres_amd.so (the program's RUNPATH comes after it).
 ITX_AB_FILTER=1 runs `iteres filter -c <the table's biggest class>` instead (ITX_AB_OPTS="-r": with the read lists) and compares
-the .loci / .reportloci files."""
+the .loci / .reportloci files; ITX_AB_FILTER=all runs `iteres filter` without a name filter (every row of the table is a line)."""
 import json
 import os
 import subprocess
@@ -45,7 +45,8 @@ def main():
             extra = os.environ.get("ITX_AB_OPTS", "").split()              # e.g. ITX_AB_OPTS="-R": options behind `stat -w`
             args = args[:2] + extra + args[2:]
             if os.environ.get("ITX_AB_FILTER"):
-                args = ["filter", "-c", info["filter_class"]["name"]] + extra + args[2:]
+                select = [] if os.environ["ITX_AB_FILTER"] == "all" else ["-c", info["filter_class"]["name"]]
+                args = ["filter"] + select + extra + args[2:]
             wall, rc, err, seen = bench.run_timed(bench.OURS, args + [os.path.join(wd, "reads.bam")], out, env, (bench.SCAN_BEGIN, bench.SCAN_END))
             assert rc == 0, err[-800:]
             walls[name].append(round(wall, 3))
