@@ -497,6 +497,45 @@ int itx_loci_order(itx_loci *lo, uint32_t *order, double *sort_ms);
 int itx_loci_filter_text(itx_loci *lo, const uint32_t *locus_cnt, int threshold, unsigned long long reads_num, itx_loci_text *out);
 int itx_loci_cpg_text(itx_loci *lo, const int *cpg_count, const double *cpg_total, double threshold, itx_loci_text *out);
 
+/* ---- SAM text split and parsed on the device (iteres stat|filter -S) --------------------------------------------------------
+ * A chunk of SAM body text, cut by the caller behind a newline, becomes the per-record arrays the host reader fills otherwise
+ * (itx_batch's layout) plus, per record, byte offsets into the text: the caller cuts a read name or an XA value out of its own
+ * copy of the text only when it wants one (csrc/itx_samtext.hip; the line rule, stated once: csrc/itx_samline.h). The device
+ * models the plain spelling of every field; a line spelt otherwise is HARD: the chunk's records are then not handed out
+ * (n_rec = 0) and the caller parses the chunk itself, whole and in order.
+ *   create       the @SQ names, name t = name_bytes[name_off[t] .. name_off[t + 1]) (the first of equal names wins a lookup);
+ *                max_chunk_bytes: the largest text one parse may carry (at most 256 MiB: ITX_E_LIMIT), which sizes the buffers of
+ *                both slots. ITX_E_NO_DEVICE when there is no such device.
+ *   parse_begin  slot 0 or 1: copies text[0 .. len) to the device on the object's copy stream and enqueues the kernels; returns
+ *                without waiting (the text must stay as it is until parse_end). final: the input ends with this text, a last line
+ *                without a newline is a line; otherwise the bytes behind the last newline are not consumed. len > max_chunk_bytes:
+ *                ITX_E_LIMIT. Two slots, so that one chunk crosses the link and is parsed while the other's records are fetched;
+ *                the two slots may be driven from two threads.
+ *   parse_end    waits for the slot's parse. n_lines: lines in the consumed bytes; consumed: through the last '\n', all of len
+ *                when final; n_hard: lines the device does not model, first_hard_line: the 0-based index of the first of them
+ *                (more lines than len / 20 + 2 prove a line too short for 11 fields: counted as one more hard line);
+ *                n_rec: n_lines, or 0 when n_hard > 0; flags: ITX_SAMTEXT_PAIRED / _XA some record has the PAIRED flag / an XA
+ *                field, ITX_SAMTEXT_NUL the text holds a NUL byte; kernel_ms: device time of the four kernels.
+ *   fetch        records [first, first + n) of the slot's parsed chunk into the staging arrays at dst_at, and their side values
+ *                into whichever of the other arrays is not NULL: line_off (the line's first byte in the text), qname_len (the
+ *                read name is the line's first bytes), xa_off / xa_len (the XA value; xa_mark[i] != 0: the record carries XA),
+ *                nm. Waits for the copies. */
+typedef struct itx_samtext itx_samtext;
+#define ITX_SAMTEXT_PAIRED 1
+#define ITX_SAMTEXT_XA 2
+#define ITX_SAMTEXT_NUL 4
+typedef struct itx_samtext_result {
+    uint64_t n_lines, n_rec, consumed, n_hard, first_hard_line;
+    int flags;
+    double kernel_ms;
+} itx_samtext_result;
+int itx_samtext_create(int device, const char *name_bytes, const uint64_t *name_off, int n_targets, size_t max_chunk_bytes, itx_samtext **out);
+int itx_samtext_parse_begin(itx_samtext *x, int slot, const void *text, size_t len, int final);
+int itx_samtext_parse_end(itx_samtext *x, int slot, itx_samtext_result *res);
+int itx_samtext_fetch(itx_samtext *x, int slot, size_t first, size_t n, const itx_staging *dst_staging, size_t dst_at, uint32_t *line_off,
+                      uint32_t *qname_len, uint32_t *xa_off, uint32_t *xa_len, int32_t *nm, uint8_t *xa_mark);
+void itx_samtext_destroy(itx_samtext *x);
+
 /* ITX_TIMING: what the device decoder measured about itself (pushes, mean duration of the two passes, device allocations),
  * one line on stderr; also printed when the process exits normally. */
 void itx_timing_report(void);

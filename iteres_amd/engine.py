@@ -34,6 +34,7 @@ EXPORTS = [
     "itx_names_create", "itx_names_destroy", "itx_names_hits", "itx_names_stream", "itx_bamwin_names", "itx_names_run", "itx_names_wait_kernels", "itx_names_append_host",
     "itx_names_finish", "itx_names_get_stats",
     "itx_loci_create", "itx_loci_destroy", "itx_loci_order", "itx_loci_filter_text", "itx_loci_cpg_text",
+    "itx_samtext_create", "itx_samtext_destroy", "itx_samtext_parse_begin", "itx_samtext_parse_end", "itx_samtext_fetch",
 ]
 
 
@@ -120,6 +121,14 @@ class LociText(C.Structure):
 
 
 LOCI_FILTER, LOCI_CPG = 0, 1
+
+
+class SamTextResult(C.Structure):
+    _fields_ = [("n_lines", C.c_uint64), ("n_rec", C.c_uint64), ("consumed", C.c_uint64), ("n_hard", C.c_uint64), ("first_hard_line", C.c_uint64),
+                ("flags", C.c_int), ("kernel_ms", C.c_double)]
+
+
+SAMTEXT_PAIRED, SAMTEXT_XA, SAMTEXT_NUL = 1, 2, 4
 
 _lib = None
 
@@ -218,6 +227,12 @@ def load():
     L.itx_loci_order.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
     L.itx_loci_filter_text.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_ulonglong, C.POINTER(LociText)]
     L.itx_loci_cpg_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(LociText)]
+    L.itx_samtext_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
+    L.itx_samtext_destroy.argtypes = [C.c_void_p]
+    L.itx_samtext_destroy.restype = None
+    L.itx_samtext_parse_begin.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int]
+    L.itx_samtext_parse_end.argtypes = [C.c_void_p, C.c_int, C.POINTER(SamTextResult)]
+    L.itx_samtext_fetch.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(Staging), C.c_size_t] + [C.c_void_p] * 6
     L.itx_pinned_alloc.argtypes = [C.c_size_t]
     L.itx_pinned_alloc.restype = C.c_void_p
     L.itx_pinned_free.argtypes = [C.c_void_p]
@@ -671,6 +686,56 @@ class Names:
     def close(self):
         if self._h:
             load().itx_names_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SamText:
+    """SAM text split and parsed on the device (include/iteres_amd.h itx_samtext_*, the line rule: csrc/itx_samline.h). `names`: the
+    @SQ names as bytes, in header order. `parse(text, final, slot)` returns the result fields as a dict; `fetch(slot, first, n)` the
+    records' arrays and side values as numpy arrays. A chunk with a hard line has n_rec == 0: the caller parses it itself."""
+
+    def __init__(self, names, max_chunk_bytes: int = 1 << 20, device: int = 0):
+        off = np.zeros(len(names) + 1, np.uint64)
+        off[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(names) + b"\0", np.uint8).copy()
+        self._h = C.c_void_p()
+        self._text = {}
+        _chk(load().itx_samtext_create(device, _p(blob), _p(off), len(names), max_chunk_bytes, C.byref(self._h)), "itx_samtext_create")
+
+    def begin(self, text: bytes, final: bool, slot: int = 0):
+        buf = np.frombuffer(text + b"\0", np.uint8).copy()           # stays alive until the parse has ended
+        self._text[slot] = buf
+        _chk(load().itx_samtext_parse_begin(self._h, slot, _p(buf), len(text), int(final)), "itx_samtext_parse_begin")
+
+    def end(self, slot: int = 0):
+        res = SamTextResult()
+        _chk(load().itx_samtext_parse_end(self._h, slot, C.byref(res)), "itx_samtext_parse_end")
+        return {k: getattr(res, k) for k, _ in SamTextResult._fields_}
+
+    def parse(self, text: bytes, final: bool, slot: int = 0):
+        self.begin(text, final, slot)
+        return self.end(slot)
+
+    def fetch(self, slot, first, n, side=True):
+        a = {k: np.full(n + 1, 7, dt) for k, dt in (("tid", np.int32), ("pos", np.int32), ("tmpend", np.int32), ("mapq", np.uint8), ("flag5", np.uint8),
+                                                      ("mpos", np.int32), ("isize", np.int32))}
+        st = Staging(*[_p(a[k]) for k in ("tid", "pos", "tmpend", "mapq", "flag5", "mpos", "isize")], None, n)
+        s = {k: np.full(n + 1, 7, dt) for k, dt in (("line_off", np.uint32), ("qname_len", np.uint32), ("xa_off", np.uint32), ("xa_len", np.uint32),
+                                                        ("nm", np.int32), ("xa_mark", np.uint8))} if side else {}
+        ptrs = [_p(s[k]) if side else None for k in ("line_off", "qname_len", "xa_off", "xa_len", "nm", "xa_mark")]
+        _chk(load().itx_samtext_fetch(self._h, slot, first, n, C.byref(st), 0, *ptrs), "itx_samtext_fetch")
+        a.update(s)
+        return {k: v[:n] for k, v in a.items()}
+
+    def close(self):
+        if self._h:
+            load().itx_samtext_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -7,6 +7,7 @@
 #include "itx_host.h"
 
 #include <ctype.h>
+#include <stdarg.h>
 #include <dlfcn.h>
 #include <omp.h>
 #include <pthread.h>
@@ -114,6 +115,35 @@ struct aln_reader {
     size_t line_cap;
     ssize_t pending_len;     /* first alignment line read while scanning the header, -1 none */
     long long n_lines;
+    /* SAM in chunks (sam_chunks_start): a read-ahead thread fills two text buffers, each cut behind its last newline; with a
+     * device object attached it also begins the chunk's parse there, so chunk k + 1 crosses the link while chunk k is consumed */
+    int sc_on, sc_done;
+    size_t sc_chunk;
+    int sdev_on;
+    aln_sam_device sdev;
+    struct sam_chunk {
+        uint8_t *buf;
+        size_t cap, len;
+        int final, begun, begin_rc, from_alloc;
+    } sc[2];
+    uint8_t *sc_tail;         /* the bytes behind the last newline of the chunk before */
+    size_t sc_tail_len, sc_tail_cap;
+    long sc_fill, sc_take;    /* chunks filled / consumed so far (chunk k lives in buffer k % 2) */
+    int sc_stop;
+    pthread_t sc_thread;
+    pthread_mutex_t sc_mu;
+    pthread_cond_t sc_cv;
+    int sc_open, sc_host;     /* a chunk is being consumed; by the host's line parser */
+    size_t sc_pos;            /* host: the next line's first byte */
+    uint64_t sc_nrec, sc_next, sc_lines;   /* device: records of the chunk, the next one to hand out, its lines */
+    int sc_flags;
+    uint32_t *s_off, *s_qlen, *s_xoff, *s_xlen;   /* a batch's side values from the device */
+    int32_t *s_nm;
+    uint8_t *s_mark;
+    size_t s_cap;
+    unsigned long long st_dev_chunks, st_dev_bytes, st_host_chunks;   /* ITX_TIMING */
+    double st_ms, st_wait;
+    char st_reason[96];
 };
 
 /* ---- BGZF ------------------------------------------------------------------------------------------------ */
@@ -1311,6 +1341,7 @@ int aln_range_verified(const aln_reader *r)
     return r->rg_verified == 1;
 }
 
+static void sam_chunks_stop(aln_reader *r);
 void aln_close(aln_reader *r)
 {
     if (!r) return;
@@ -1337,6 +1368,7 @@ void aln_close(aln_reader *r)
         pthread_mutex_unlock(&r->io_mu);
         pthread_join(r->io_thread, NULL);
     }
+    sam_chunks_stop(r);
     if (r->f) fclose(r->f);
     for (int k = 0; k < N_RAW_DEVICE; k++) buf_free(r->craw[k]);
     buf_free(r->nbuf);
@@ -1850,9 +1882,386 @@ static unsigned flag_from_chars(const char *s)
     return f;
 }
 
+/* One line of SAM text (NUL-terminated at line[len], terminator excluded or not) into record *n of the staging slot:
+ * 0 a record was taken (*n advanced), 1 the line is empty and skipped, 2 a truncated line: the parser gives up on this batch.
+ * The line is cut up in place. r->n_lines is the line's number (the warning prints it). */
+static int sam_take_line(aln_reader *r, char *line, ssize_t len, itx_staging *st, size_t *np, aln_side *side, int *any_paired, int *aux_xa)
+{
+    const size_t n = *np;
+    while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = 0;
+    if (len == 0) return 1;                                          /* empty lines are skipped */
+    char *fld[12];
+    int nf = 0;
+    char *p = line;
+    while (nf < 12) {
+        fld[nf++] = p;
+        if (nf == 12) break;                                         /* the 12th "field" keeps all optional fields */
+        char *t = strchr(p, '\t');
+        if (!t) break;
+        *t = 0;
+        p = t + 1;
+    }
+    if (nf < 11) return 2;                                           /* truncated line: the parser gives up */
+    char *endp;
+    long flag = strtol(fld[1], &endp, 0);
+    if (*endp) flag = (long)flag_from_chars(fld[1]);
+    int32_t tid = -1;
+    if (strcmp(fld[2], "*") != 0) {
+        const int64_t t = names_find(&r->tnames, fld[2]);
+        if (t < 0) {
+            if (r->n_targets == 0) {
+                fprintf(stderr, "[sam_read1] missing header? Abort!\n");
+                exit(1);
+            }
+            fprintf(stderr, "[sam_read1] reference '%s' is recognized as '*'.\n", fld[2]);
+        }
+        tid = (int32_t)t;
+    }
+    const int32_t pos = isdigit((unsigned char)fld[3][0]) ? atoi(fld[3]) - 1 : -1;
+    const int qual = isdigit((unsigned char)fld[4][0]) ? atoi(fld[4]) : 0;
+    uint32_t e = (uint32_t)pos;
+    int n_cigar = 0;
+    if (fld[5][0] != '*') {
+        const char *s = fld[5];
+        while (*s) {
+            char *t;
+            const long x = strtol(s, &t, 10);
+            const int op = toupper((unsigned char)*t);
+            if (!*t) break;
+            if (op == 'M' || op == 'D' || op == 'N') e += (uint32_t)x;
+            n_cigar++;
+            s = t + 1;
+        }
+    } else if (!(flag & 0x4)) {
+        fprintf(stderr, "Parse warning at line %lld: mapped sequence without CIGAR\n", r->n_lines);
+        flag |= 0x4;
+    }
+    const int32_t mpos = isdigit((unsigned char)fld[7][0]) ? atoi(fld[7]) - 1 : -1;
+    const int32_t isize = (fld[8][0] == '-' || isdigit((unsigned char)fld[8][0])) ? atoi(fld[8]) : 0;
+    const int32_t l_qseq = strcmp(fld[9], "*") == 0 ? 0 : (int32_t)strlen(fld[9]);
+    st->tid[n] = tid;
+    st->pos[n] = pos;
+    st->tmpend[n] = n_cigar ? (int32_t)e : (int32_t)((uint32_t)pos + (uint32_t)l_qseq);
+    st->mapq[n] = (uint8_t)qual;
+    st->flag5[n] = ITX_FLAG5((unsigned)flag);
+    st->mpos[n] = mpos;
+    st->isize[n] = isize;
+    if (flag & 1) *any_paired = 1;
+    if (side && side->want_qnames) side->qname[n] = xstrdup(fld[0]);
+    if (side && side->want_aux) {
+        side->xa[n] = NULL;
+        side->nm[n] = 0;
+    }
+    if (nf == 12) {
+        /* optional fields TAG:TYPE:VALUE (bam_import.c:402-470); the first XA and the first NM count (bam_aux_get) */
+        const char *xa = NULL, *nm = NULL;
+        for (char *a = fld[11]; a; a = strchr(a, '\t') ? strchr(a, '\t') + 1 : NULL) {
+            if (!xa && strncmp(a, "XA:", 3) == 0) xa = a;
+            if (!nm && strncmp(a, "NM:", 3) == 0) nm = a;
+        }
+        if (xa) *aux_xa = 1;
+        if (xa && side && side->want_aux) {
+            const int is_z = strlen(xa) >= 5 && (xa[3] == 'Z' || xa[3] == 'H') && xa[4] == ':';
+            const char *v = is_z ? xa + 5 : "";
+            side->xa[n] = xstrndup_bound(v, strcspn(v, "\t"));
+            if (nm && strlen(nm) >= 5 && nm[3] == 'i' && nm[4] == ':') side->nm[n] = (int32_t)strtol(nm + 5, NULL, 10);
+        }
+    }
+    *np = n + 1;
+    return 0;
+}
+
+/* ---- SAM in chunks ------------------------------------------------------------------------------------------------------ */
+size_t aln_sam_chunk_bytes(void)
+{
+    const char *e = getenv("ITX_SAM_CHUNK");
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (size_t)v : ALN_SAM_CHUNK;
+}
+
+void aln_set_sam_device(aln_reader *r, const aln_sam_device *d)
+{
+    if (!r->is_sam || r->sc_on) return;                              /* before the first batch only */
+    r->sdev_on = d && d->obj && d->parse_begin;
+    if (r->sdev_on) r->sdev = *d;
+}
+
+/* room for n bytes in the chunk's buffer, the first `keep` ones preserved: from the device's `alloc` (page-locked) when it gives */
+static void sam_buf_need(aln_reader *r, struct sam_chunk *c, size_t n, size_t keep)
+{
+    if (c->cap >= n) return;
+    const size_t cap = n + n / 8 + 4096;
+    uint8_t *p = r->sdev_on && r->sdev.alloc ? r->sdev.alloc(cap) : NULL;
+    const int fa = p != NULL;
+    if (!p) p = xmalloc(cap);
+    if (keep) memcpy(p, c->buf, keep);
+    if (c->buf) {
+        if (c->from_alloc) r->sdev.release(c->buf);
+        else free(c->buf);
+    }
+    c->buf = p;
+    c->cap = cap;
+    c->from_alloc = fa;
+}
+
+static void *sam_chunk_thread(void *arg)
+{
+    aln_reader *r = arg;
+    for (;;) {
+        pthread_mutex_lock(&r->sc_mu);
+        while (!r->sc_stop && r->sc_fill - r->sc_take >= 2) pthread_cond_wait(&r->sc_cv, &r->sc_mu);
+        const int stop = r->sc_stop;
+        pthread_mutex_unlock(&r->sc_mu);
+        if (stop) break;
+        const int k = (int)(r->sc_fill & 1);
+        struct sam_chunk *c = &r->sc[k];
+        size_t have = r->sc_tail_len, cut = 0, seen = 0;
+        int eof = 0;
+        sam_buf_need(r, c, have + r->sc_chunk + 1, 0);
+        if (have) memcpy(c->buf, r->sc_tail, have);
+        r->sc_tail_len = 0;
+        for (;;) {
+            /* up to a chunk in all; a line longer than that grows the buffer a chunk at a time */
+            const size_t want = have < r->sc_chunk ? r->sc_chunk - have : r->sc_chunk;
+            sam_buf_need(r, c, have + want + 1, have);
+            const double t0 = now_s();
+            const size_t got = fread(c->buf + have, 1, want, r->f);
+            t_io += now_s() - t0;
+            have += got;
+            if (got < want) eof = 1;
+            if (eof) {
+                cut = have;
+                break;
+            }
+            const uint8_t *nl = memrchr(c->buf + seen, '\n', have - seen);
+            if (nl) {
+                cut = (size_t)(nl - c->buf) + 1;
+                break;
+            }
+            seen = have;
+        }
+        if (have > cut) {
+            if (r->sc_tail_cap < have - cut) {
+                r->sc_tail_cap = (have - cut) + (have - cut) / 4 + 256;
+                r->sc_tail = xrealloc(r->sc_tail, r->sc_tail_cap);
+            }
+            memcpy(r->sc_tail, c->buf + cut, have - cut);
+            r->sc_tail_len = have - cut;
+        }
+        c->len = cut;
+        c->final = eof;
+        c->begun = 0;
+        c->begin_rc = 0;
+        if (r->sdev_on && cut) {
+            c->begin_rc = r->sdev.parse_begin(r->sdev.obj, k, c->buf, cut, eof);
+            c->begun = c->begin_rc == 0;
+        }
+        pthread_mutex_lock(&r->sc_mu);
+        r->sc_fill++;
+        pthread_cond_broadcast(&r->sc_cv);
+        pthread_mutex_unlock(&r->sc_mu);
+        if (eof) break;
+    }
+    return NULL;
+}
+
+static void sam_chunks_start(aln_reader *r)
+{
+    r->sc_on = 1;
+    r->sc_chunk = aln_sam_chunk_bytes();
+    if (r->pending_len >= 0) {                                       /* the first body line goes in front of the first chunk */
+        r->sc_tail_cap = (size_t)r->pending_len + 256;
+        r->sc_tail = xmalloc(r->sc_tail_cap);
+        memcpy(r->sc_tail, r->line, (size_t)r->pending_len);
+        r->sc_tail_len = (size_t)r->pending_len;
+        r->pending_len = -1;
+        r->n_lines--;                                                /* counted again when its chunk is taken */
+    }
+    pthread_mutex_init(&r->sc_mu, NULL);
+    pthread_cond_init(&r->sc_cv, NULL);
+    if (pthread_create(&r->sc_thread, NULL, sam_chunk_thread, r) != 0) die("cannot start the SAM read-ahead thread");
+}
+
+static void sam_host_reason(aln_reader *r, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+static void sam_host_reason(aln_reader *r, const char *fmt, ...)
+{
+    if (r->st_host_chunks++ || !fmt) return;                         /* the reason of the first one is reported */
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(r->st_reason, sizeof r->st_reason, fmt, ap);
+    va_end(ap);
+}
+
+static void sam_chunk_close(aln_reader *r)
+{
+    if (r->sc[r->sc_take & 1].final) r->sc_done = 1;
+    r->sc_open = 0;
+    pthread_mutex_lock(&r->sc_mu);
+    r->sc_take++;
+    pthread_cond_broadcast(&r->sc_cv);
+    pthread_mutex_unlock(&r->sc_mu);
+}
+
+/* the next chunk becomes the one being consumed: 0 at the end of the input */
+static int sam_chunk_open(aln_reader *r)
+{
+    for (;;) {
+        if (r->sc_done) return 0;
+        pthread_mutex_lock(&r->sc_mu);
+        while (r->sc_fill == r->sc_take) pthread_cond_wait(&r->sc_cv, &r->sc_mu);
+        pthread_mutex_unlock(&r->sc_mu);
+        const int k = (int)(r->sc_take & 1);
+        struct sam_chunk *c = &r->sc[k];
+        r->sc_open = 1;
+        r->sc_host = 1;
+        r->sc_pos = 0;
+        if (c->len == 0) {                                           /* nothing but the end of the file */
+            sam_chunk_close(r);
+            continue;
+        }
+        if (c->begun) {
+            itx_samtext_result res;
+            const double t0 = now_s();
+            if (r->sdev.parse_end(r->sdev.obj, k, &res) != 0) die("SAM text on the device: parse failed: %s", r->sdev.last_error ? r->sdev.last_error() : "?");
+            r->st_wait += now_s() - t0;
+            c->begun = 0;
+            if (res.n_hard == 0) {
+                if (res.consumed != c->len) die("SAM text on the device: %llu of %zu bytes consumed", (unsigned long long)res.consumed, c->len);
+                r->sc_host = 0;
+                r->sc_nrec = res.n_rec;
+                r->sc_next = 0;
+                r->sc_lines = res.n_lines;
+                r->sc_flags = res.flags;
+                r->st_dev_chunks++;
+                r->st_dev_bytes += c->len;
+                r->st_ms += res.kernel_ms;
+                if (res.n_rec == 0) {
+                    sam_chunk_close(r);
+                    continue;
+                }
+            } else {
+                sam_host_reason(r, "line %lld is spelt in a way the device does not model", r->n_lines + (long long)res.first_hard_line + 1);
+            }
+        } else if (!r->sdev_on) {
+            sam_host_reason(r, "no device object attached");
+        } else {
+            sam_host_reason(r, "a chunk of %zu bytes, more than the device object holds", c->len);
+        }
+        return 1;
+    }
+}
+
+static size_t sam_read_chunked(aln_reader *r, itx_staging *st, size_t cap, aln_side *side, int *any_paired, int *aux_xa)
+{
+    size_t n = 0;
+    while (n < cap) {
+        if (!r->sc_open && !sam_chunk_open(r)) break;
+        const int k = (int)(r->sc_take & 1);
+        struct sam_chunk *c = &r->sc[k];
+        if (r->sc_host) {
+            while (n < cap && r->sc_pos < c->len) {
+                uint8_t *s = c->buf + r->sc_pos;
+                const uint8_t *nl = memchr(s, '\n', c->len - r->sc_pos);
+                const size_t ll = nl ? (size_t)(nl - s) : c->len - r->sc_pos;
+                r->sc_pos += ll + (nl ? 1 : 0);
+                r->n_lines++;
+                s[ll] = 0;                                           /* the newline, or the spare byte behind the last line */
+                if (sam_take_line(r, (char *)s, (ssize_t)ll, st, &n, side, any_paired, aux_xa) == 2) {
+                    if (r->sc_pos >= c->len) sam_chunk_close(r);
+                    return n;
+                }
+            }
+            if (r->sc_pos >= c->len) sam_chunk_close(r);
+            continue;
+        }
+        size_t m = (size_t)(r->sc_nrec - r->sc_next);
+        if (m > cap - n) m = cap - n;
+        const int want_q = side && side->want_qnames, want_a = side && side->want_aux, has_xa = (r->sc_flags & ITX_SAMTEXT_XA) != 0;
+        if (r->s_cap < m) {
+            r->s_cap = m + m / 4 + 64;
+            r->s_off = xrealloc(r->s_off, 4 * r->s_cap);
+            r->s_qlen = xrealloc(r->s_qlen, 4 * r->s_cap);
+            r->s_xoff = xrealloc(r->s_xoff, 4 * r->s_cap);
+            r->s_xlen = xrealloc(r->s_xlen, 4 * r->s_cap);
+            r->s_nm = xrealloc(r->s_nm, 4 * r->s_cap);
+            r->s_mark = xrealloc(r->s_mark, r->s_cap);
+        }
+        const int aux = want_a && has_xa;
+        const double tp = now_s();
+        if (r->sdev.fetch(r->sdev.obj, k, (size_t)r->sc_next, m, st, n, want_q ? r->s_off : NULL, want_q ? r->s_qlen : NULL, aux ? r->s_xoff : NULL,
+                          aux ? r->s_xlen : NULL, aux ? r->s_nm : NULL, has_xa ? r->s_mark : NULL) != 0)
+            die("SAM text on the device: fetch failed: %s", r->sdev.last_error ? r->sdev.last_error() : "?");
+        int ap = 0, xa = 0;
+        const uint8_t *f5 = st->flag5 + n;
+        for (size_t i = 0; i < m; i++) ap |= f5[i] & 1;
+        if (has_xa)
+            for (size_t i = 0; i < m; i++) xa |= r->s_mark[i];
+        if (ap) *any_paired = 1;
+        if (xa) *aux_xa = 1;
+        if (want_q || want_a) {
+            const char *text = (const char *)c->buf;
+#pragma omp parallel for schedule(static)
+            for (long i = 0; i < (long)m; i++) {
+                if (want_q) side->qname[n + (size_t)i] = xstrndup_bound(text + r->s_off[i], r->s_qlen[i]);
+                if (want_a) {
+                    side->xa[n + (size_t)i] = NULL;
+                    side->nm[n + (size_t)i] = 0;
+                    if (aux && r->s_mark[i]) {
+                        side->xa[n + (size_t)i] = xstrndup_bound(text + r->s_xoff[i], r->s_xlen[i]);
+                        side->nm[n + (size_t)i] = r->s_nm[i];
+                    }
+                }
+            }
+        }
+        t_parse += now_s() - tp;
+        r->sc_next += m;
+        n += m;
+        if (r->sc_next == r->sc_nrec) {
+            r->n_lines += (long long)r->sc_lines;
+            sam_chunk_close(r);
+        }
+    }
+    return n;
+}
+
+static void sam_chunks_stop(aln_reader *r)
+{
+    if (!r->sc_on) return;
+    pthread_mutex_lock(&r->sc_mu);
+    r->sc_stop = 1;
+    pthread_cond_broadcast(&r->sc_cv);
+    pthread_mutex_unlock(&r->sc_mu);
+    pthread_join(r->sc_thread, NULL);
+    for (int k = 0; k < 2; k++) {
+        struct sam_chunk *c = &r->sc[k];
+        if (c->begun) {                                              /* a parse nobody took: the object must be idle when it is destroyed */
+            itx_samtext_result res;
+            (void)r->sdev.parse_end(r->sdev.obj, k, &res);
+        }
+        if (c->buf) {
+            if (c->from_alloc) r->sdev.release(c->buf);
+            else free(c->buf);
+        }
+    }
+    if (getenv("ITX_TIMING"))
+        fprintf(stderr, "[itx timing] sam: %llu chunks parsed on the device (%llu bytes, %.3f ms in its kernels, host waited %.3f s), %llu by the host (%s)\n", r->st_dev_chunks,
+                r->st_dev_bytes, r->st_ms, r->st_wait, r->st_host_chunks, r->st_host_chunks ? r->st_reason : "none");
+    free(r->sc_tail);
+    free(r->s_off);
+    free(r->s_qlen);
+    free(r->s_xoff);
+    free(r->s_xlen);
+    free(r->s_nm);
+    free(r->s_mark);
+    pthread_mutex_destroy(&r->sc_mu);
+    pthread_cond_destroy(&r->sc_cv);
+}
+
 static size_t sam_read_batch(aln_reader *r, itx_staging *st, size_t cap, aln_side *side, int *any_paired, int *aux_xa)
 {
     if (side) side->has_strings = 1;
+    if (!r->sc_on && (r->sdev_on || getenv("ITX_SAM_CHUNK"))) sam_chunks_start(r);
+    if (r->sc_on) return sam_read_chunked(r, st, cap, side, any_paired, aux_xa);
     size_t n = 0;
     while (n < cap) {
         ssize_t len;
@@ -1864,86 +2273,7 @@ static size_t sam_read_batch(aln_reader *r, itx_staging *st, size_t cap, aln_sid
             if (len < 0) break;
             r->n_lines++;
         }
-        while (len > 0 && (r->line[len - 1] == '\n' || r->line[len - 1] == '\r')) r->line[--len] = 0;
-        if (len == 0) continue;                                          /* empty lines are skipped */
-        char *fld[12];
-        int nf = 0;
-        char *p = r->line;
-        while (nf < 12) {
-            fld[nf++] = p;
-            if (nf == 12) break;                                         /* the 12th "field" keeps all optional fields */
-            char *t = strchr(p, '\t');
-            if (!t) break;
-            *t = 0;
-            p = t + 1;
-        }
-        if (nf < 11) break;                                              /* truncated line: the parser gives up */
-        char *endp;
-        long flag = strtol(fld[1], &endp, 0);
-        if (*endp) flag = (long)flag_from_chars(fld[1]);
-        int32_t tid = -1;
-        if (strcmp(fld[2], "*") != 0) {
-            const int64_t t = names_find(&r->tnames, fld[2]);
-            if (t < 0) {
-                if (r->n_targets == 0) {
-                    fprintf(stderr, "[sam_read1] missing header? Abort!\n");
-                    exit(1);
-                }
-                fprintf(stderr, "[sam_read1] reference '%s' is recognized as '*'.\n", fld[2]);
-            }
-            tid = (int32_t)t;
-        }
-        const int32_t pos = isdigit((unsigned char)fld[3][0]) ? atoi(fld[3]) - 1 : -1;
-        const int qual = isdigit((unsigned char)fld[4][0]) ? atoi(fld[4]) : 0;
-        uint32_t e = (uint32_t)pos;
-        int n_cigar = 0;
-        if (fld[5][0] != '*') {
-            const char *s = fld[5];
-            while (*s) {
-                char *t;
-                const long x = strtol(s, &t, 10);
-                const int op = toupper((unsigned char)*t);
-                if (!*t) break;
-                if (op == 'M' || op == 'D' || op == 'N') e += (uint32_t)x;
-                n_cigar++;
-                s = t + 1;
-            }
-        } else if (!(flag & 0x4)) {
-            fprintf(stderr, "Parse warning at line %lld: mapped sequence without CIGAR\n", r->n_lines);
-            flag |= 0x4;
-        }
-        const int32_t mpos = isdigit((unsigned char)fld[7][0]) ? atoi(fld[7]) - 1 : -1;
-        const int32_t isize = (fld[8][0] == '-' || isdigit((unsigned char)fld[8][0])) ? atoi(fld[8]) : 0;
-        const int32_t l_qseq = strcmp(fld[9], "*") == 0 ? 0 : (int32_t)strlen(fld[9]);
-        st->tid[n] = tid;
-        st->pos[n] = pos;
-        st->tmpend[n] = n_cigar ? (int32_t)e : (int32_t)((uint32_t)pos + (uint32_t)l_qseq);
-        st->mapq[n] = (uint8_t)qual;
-        st->flag5[n] = ITX_FLAG5((unsigned)flag);
-        st->mpos[n] = mpos;
-        st->isize[n] = isize;
-        if (flag & 1) *any_paired = 1;
-        if (side && side->want_qnames) side->qname[n] = xstrdup(fld[0]);
-        if (side && side->want_aux) {
-            side->xa[n] = NULL;
-            side->nm[n] = 0;
-        }
-        if (nf == 12) {
-            /* optional fields TAG:TYPE:VALUE (bam_import.c:402-470); the first XA and the first NM count (bam_aux_get) */
-            const char *xa = NULL, *nm = NULL;
-            for (char *a = fld[11]; a; a = strchr(a, '\t') ? strchr(a, '\t') + 1 : NULL) {
-                if (!xa && strncmp(a, "XA:", 3) == 0) xa = a;
-                if (!nm && strncmp(a, "NM:", 3) == 0) nm = a;
-            }
-            if (xa) *aux_xa = 1;
-            if (xa && side && side->want_aux) {
-                const int is_z = strlen(xa) >= 5 && (xa[3] == 'Z' || xa[3] == 'H') && xa[4] == ':';
-                const char *v = is_z ? xa + 5 : "";
-                side->xa[n] = xstrndup_bound(v, strcspn(v, "\t"));
-                if (nm && strlen(nm) >= 5 && nm[3] == 'i' && nm[4] == ':') side->nm[n] = (int32_t)strtol(nm + 5, NULL, 10);
-            }
-        }
-        n++;
+        if (sam_take_line(r, r->line, len, st, &n, side, any_paired, aux_xa) == 2) break;
     }
     return n;
 }

@@ -145,6 +145,25 @@ size_t aln_device_left(const aln_reader *r);  /* device decoder: records of the 
 int aln_device_exhausted(aln_reader *r);
 void aln_readahead(aln_reader *r);            /* BAM: start decoding ahead of the first aln_read_batch */     /* device decoder: 1 when no record is left */
 aln_reader *aln_open(const char *path, int is_sam);          /* NULL when the file cannot be opened / has no header */
+/* SAM text split and parsed on the device (include/iteres_amd.h: itx_samtext_*). aln_open never touches the GPU: the driver,
+ * which knows the device, makes the object from the reader's reference names and attaches it before the first batch is read;
+ * entry points instead of a link-time dependency, as for aln_device_ops. The body of the file is then read in chunks of
+ * ITX_SAM_CHUNK bytes (default ALN_SAM_CHUNK) cut behind a newline, by a read-ahead thread into two buffers from `alloc`; a
+ * chunk's records come from the device's arrays, its read names and XA strings from the host's copy of the text by offset. A
+ * chunk with a line the device does not model (csrc/itx_samline.h) is parsed by the host, whole and in order. Without an
+ * attached object the reader takes line after line with getline, or — ITX_SAM_CHUNK set — the same chunks all by the host. */
+typedef struct aln_sam_device {
+    itx_samtext *obj;
+    int (*parse_begin)(itx_samtext *, int, const void *, size_t, int);
+    int (*parse_end)(itx_samtext *, int, itx_samtext_result *);
+    int (*fetch)(itx_samtext *, int, size_t, size_t, const itx_staging *, size_t, uint32_t *, uint32_t *, uint32_t *, uint32_t *, int32_t *, uint8_t *);
+    void *(*alloc)(size_t bytes);
+    void (*release)(void *p);
+    const char *(*last_error)(void);
+} aln_sam_device;
+#define ALN_SAM_CHUNK ((size_t)64 << 20)
+size_t aln_sam_chunk_bytes(void);           /* ITX_SAM_CHUNK, or the default */
+void aln_set_sam_device(aln_reader *r, const aln_sam_device *d);
 /* One rank's share of a BAM file (multi-GPU; device decoder): the records that start between the split points of the
  * compressed byte offsets lo and hi (hi = SIZE_MAX: to the end; (0, SIZE_MAX) is aln_open). aln_range_verified, after the
  * last batch: 1 when the share's end boundary proved to be a true record start (or the share runs to the end of the file). */

@@ -684,6 +684,39 @@ static void choose_dedup_set(stream_run *r)
 
 /* ---- per file: open, tid maps, backlog ------------------------------------------------------------------------------------ */
 
+/* SAM text: the route. ITX_HOST_SAM=1 the host's line parser, =0 the device's kernels (csrc/itx_samtext.hip); unset: the host,
+ * until a measurement at size says otherwise (DESIGN.md "SAM text on the device"). */
+static int sam_by_device(void)
+{
+    const char *e = getenv("ITX_HOST_SAM");
+    return e && atoi(e) == 0;
+}
+
+/* the device object for one SAM file, made from the reader's reference names and attached before the first batch is read */
+static itx_samtext *sam_device_attach(aln_reader *rd)
+{
+    const int nt = aln_n_targets(rd);
+    size_t bytes = 0;
+    for (int t = 0; t < nt; t++) bytes += strlen(aln_target_name(rd, t));
+    char *pool = xmalloc(bytes + 1);
+    uint64_t *off = xmalloc(sizeof(uint64_t) * ((size_t)nt + 1));
+    size_t at = 0;
+    for (int t = 0; t < nt; t++) {
+        const size_t k = strlen(aln_target_name(rd, t));
+        off[t] = at;
+        memcpy(pool + at, aln_target_name(rd, t), k);
+        at += k;
+    }
+    off[nt] = at;
+    itx_samtext *x = NULL;
+    chk(itx_samtext_create(multi_device(), pool, off, nt, aln_sam_chunk_bytes(), &x), "itx_samtext_create");
+    free(pool);
+    free(off);
+    const aln_sam_device d = {x, itx_samtext_parse_begin, itx_samtext_parse_end, itx_samtext_fetch, itx_pinned_alloc, itx_pinned_free, itx_last_error};
+    aln_set_sam_device(rd, &d);
+    return x;
+}
+
 /* 1: the reader is the helper thread's, with records parsed ahead of the table to submit first */
 static int open_file(stream_run *r, stream_file *f, int fi, int pass)
 {
@@ -1035,6 +1068,7 @@ static void scan_file(stream_run *r, int fi, int pass)
     if (r->multi_file) fprintf(stderr, "\n* Processing %s\n", r->files[fi]);
     if (r->share[fi].lo == r->share[fi].hi) return;                    /* nothing of this file is this rank's */
     const int backlog = open_file(r, &f, fi, pass);
+    itx_samtext *sam_dev = r->o->is_sam && sam_by_device() ? sam_device_attach(f.rd) : NULL;
     r->s = 0;
     map_targets(r, &f);
     if (backlog) submit_backlog(r);
@@ -1062,6 +1096,7 @@ static void scan_file(stream_run *r, int fi, int pass)
     const double t_drained = now_s();
     if (!aln_range_verified(f.rd)) r->boundary_missed++;
     aln_close(f.rd);
+    itx_samtext_destroy(sam_dev);                                      /* after the reader, which ends whatever parse is still in flight */
     if (r->timing)
         fprintf(stderr, "[itx timing] open %.3f s, record loop %.3f s, drain %.3f s, close %.3f s\n", f.t_opened - f.t_open0, f.t_loop_done - f.t_opened,
                 t_drained - f.t_loop_done, now_s() - t_drained);
