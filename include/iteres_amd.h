@@ -535,6 +535,42 @@ int itx_samtext_parse_end(itx_samtext *x, int slot, itx_samtext_result *res);
 int itx_samtext_fetch(itx_samtext *x, int slot, size_t first, size_t n, const itx_staging *dst_staging, size_t dst_at, uint32_t *line_off,
                       uint32_t *qname_len, uint32_t *xa_off, uint32_t *xa_len, int32_t *nm, uint8_t *xa_mark);
 void itx_samtext_destroy(itx_samtext *x);
+/* The same for a SAM text that arrives as BGZF (bgzip's output: a chain of gzip members of at most 64 KiB each): the members are
+ * inflated on the device by the decoder of itx_inflate_bgzf and parsed where they land, so only the compressed bytes cross the link.
+ * The chunks of a file form a STREAM: the bytes behind the last newline of a chunk begun with final = 0 (its tail) are the first
+ * bytes (the carry) of the next chunk's text, copied on the device.
+ *   parse_begin_bgzf  the members blk[0 .. n_blk) of comp (offsets as for itx_inflate_bgzf, checked the same way: ITX_E_ARG for a
+ *                list that does not fit) are copied and inflated into a buffer of the slot; the slot's text is the carry, then the
+ *                inflated bytes from offset `skip` on (the file's header, which the caller has read itself; skip beyond the
+ *                inflated bytes leaves none); the four kernels of parse_begin run over that text. Waits for the parse of the
+ *                stream's previous chunk (its tail length is needed), for nothing of this one; comp and blk are the caller's again
+ *                when parse_end returns. The previous chunk must lie in the OTHER slot (ITX_E_STATE). A chunk begun with final != 0,
+ *                a chunk with a member the decoder did not take, and itx_samtext_parse_begin into the previous chunk's slot end
+ *                the stream: the next chunk has no carry. ITX_E_LIMIT, nothing begun, when the members inflate to more than
+ *                max_chunk_bytes + 64 KiB or the text would exceed max_chunk_bytes.
+ *   parse_end    as above, over the slot's text; n_rec = 0 also when a member's status is not 0 (bgzf_info: n_bad).
+ *   bgzf_info    after parse_end of a chunk begun by parse_begin_bgzf: text_len, carry_len (the text's first bytes, from the chunk
+ *                before), tail_len (text_len - consumed), n_bad / first_bad: members whose status is not 0 (itx_inflate_bgzf) and
+ *                the index of the first; inflate_ms: device time of the decoder's two passes.
+ *   text         bytes [off, off + len) of the text of a slot whose parse has ended (begun either way), to the host.
+ *   strings      the read names (want & 1) of records [first, first + n) of the slot's parsed chunk and the XA values (want & 2) of
+ *                those with xa_mark != 0, gathered on the device: each followed by a NUL, packed in record order (name, then XA)
+ *                into a page-locked buffer the object owns (valid until the next strings call or destroy); qname_at[i] / xa_at[i]:
+ *                where record first + i's string starts in it, UINT32_MAX for none. */
+typedef struct itx_samtext_bgzf_info_t {
+    uint64_t text_len, carry_len, tail_len, n_bad, first_bad;
+    double inflate_ms;
+} itx_samtext_bgzf_info_t;
+typedef struct itx_samtext_strings_out {
+    const char *text;
+    uint64_t text_len;
+    const uint32_t *qname_at, *xa_at;
+    double kernel_ms;
+} itx_samtext_strings_out;
+int itx_samtext_parse_begin_bgzf(itx_samtext *x, int slot, const void *comp, size_t comp_len, const itx_bgzf_block *blk, size_t n_blk, size_t skip, int final);
+int itx_samtext_bgzf_info(itx_samtext *x, int slot, itx_samtext_bgzf_info_t *out);
+int itx_samtext_text(itx_samtext *x, int slot, size_t off, void *dst, size_t len);
+int itx_samtext_strings(itx_samtext *x, int slot, size_t first, size_t n, int want, itx_samtext_strings_out *out);
 
 /* ITX_TIMING: what the device decoder measured about itself (pushes, mean duration of the two passes, device allocations),
  * one line on stderr; also printed when the process exits normally. */

@@ -100,6 +100,10 @@ struct itx_table {
 void itx_set_error(const char *fmt, ...);
 // internal: the engine's finished per-base coverage in HBM (all reads, or unique reads), for csrc/itx_bigwig.hip
 int itxe_cov_device(itx_engine *e, int uniq, const uint32_t **cov, uint64_t *cov_len, int *device);
+// internal: the BGZF decoder's two passes enqueued on a stream, everything on the device already (csrc/itx_inflate.hip)
+size_t itx_inflate_scratch_bytes(size_t n_blk);
+int itx_inflate_enqueue(hipStream_t st, const void *d_comp, const itx_bgzf_block *d_blk, uint32_t n_blk, uint8_t *d_out, uint8_t *d_status, uint8_t *d_scr,
+                        uint32_t *d_meta);
 #define ITX_HIP(call)                                                                         \
     do {                                                                                      \
         hipError_t err__ = (call);                                                            \

@@ -850,6 +850,30 @@ extern "C" int itx_inflate_bgzf(itx_inflater *h, const void *comp, size_t comp_l
     return ITX_OK;
 }
 
+// internal (itx_common.h): both passes over one block list whose blocks, compressed bytes, output, status bytes and scratch all
+// lie on the device already, enqueued on `st` one behind the other and not waited for (the synchronisation between the passes in
+// itx_inflate_bgzf is there for its timers). The caller has checked the list as itx_inflate_bgzf does; d_out takes 64 bytes more
+// than the blocks inflate to, d_comp 64 more than comp_len, d_scr itx_inflate_scratch_bytes(n_blk), d_meta 3 words a block.
+size_t itx_inflate_scratch_bytes(size_t n_blk) { return n_blk * (size_t)SCR_STRIDE; }
+
+int itx_inflate_enqueue(hipStream_t st, const void *d_comp, const itx_bgzf_block *d_blk, uint32_t n_blk, uint8_t *d_out, uint8_t *d_status, uint8_t *d_scr,
+                        uint32_t *d_meta)
+{
+    if (!n_blk) return ITX_OK;
+    GroupArgs G;                                                   // a group of one
+    memset(&G, 0, sizeof G);
+    (void)itxg_layout(&G.x, &n_blk, 1);
+    G.comp[0] = (const uint32_t *)d_comp;
+    G.blk[0] = d_blk;
+    G.out[0] = d_out;
+    G.status[0] = d_status;
+    hipLaunchKernelGGL(k_tokens, dim3((n_blk + 63u) / 64u), dim3(64), 0, st, G, d_scr, d_meta);
+    ITX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_resolve, dim3(n_blk), dim3(64), 0, st, G, 0u, n_blk, d_scr, d_meta);
+    ITX_HIP(hipGetLastError());
+    return ITX_OK;
+}
+
 /* device time of the two passes of the last itx_inflate_bgzf call (pass 2: its first group), milliseconds */
 extern "C" int itx_inflater_last_ms(const itx_inflater *h, float *tokens_ms, float *resolve_ms)
 {

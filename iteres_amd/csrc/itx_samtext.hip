@@ -10,6 +10,15 @@
 //                  from ballots and popcounts
 //   k_sam_parse    a lane per line: a wave stages the contiguous bytes of its 64 lines in its own LDS window with 16-byte loads
 //                  and the lanes parse out of LDS; a wave whose lines do not fit parses the same way out of global memory
+//
+// A text that arrives as BGZF (itx_samtext_parse_begin_bgzf) is inflated on the device by the decoder's two passes
+// (itx_inflate_enqueue, csrc/itx_inflate.hip) into a buffer of the slot; the slot's text is put together from the previous
+// chunk's tail and those bytes with device-to-device copies, so the four kernels above see a 16-byte-aligned start whatever
+// the tail's length is. The host then has no copy of the text to cut strings out of: itx_samtext_strings gathers them,
+//   k_sam_str_measure  a lane per record: the bytes its strings take (name + NUL, XA value + NUL), summed per tile of 256
+//   k_tile_scan2       the tiles' places in the packed text
+//   k_sam_str_write    a workgroup per tile: the tile's strings are one contiguous range of the output, staged in LDS and stored
+//                      with 16-byte vectors (itx_textpack.h)
 #include <string.h>
 
 #include <string>
@@ -258,6 +267,64 @@ static __global__ __launch_bounds__(SAM_WAVES * 64u) void k_sam_parse(const uint
     }
 }
 
+// ---- the string gather ----------------------------------------------------------------------------------------------------------
+#define SAM_STR_TILE 256u               // records per workgroup
+#define SAM_STR_LDS 16384u              // bytes staged at a time: a tile of names (256 x 20-40 bytes) and its few XA values in one window
+#define SAM_STR_NONE 0xffffffffu
+#define SAM_STR_GUARD 16u               // bytes behind the packed text that travel with it (set before the write, nothing writes them)
+
+// the piece of record i: its name and a NUL (want & 1), then its XA value and a NUL (want & 2, a record that carries XA).
+// The strings are disjoint slices of a text of at most SAM_MAX_CHUNK bytes: a tile's sum, and every offset, fits 32 bits.
+__device__ __forceinline__ uint32_t sam_str_len(const SamOut &O, uint32_t i, int want, uint32_t *ql1, uint32_t *xl1)
+{
+    *ql1 = (want & 1) ? O.qname_len[i] + 1u : 0u;
+    *xl1 = ((want & 2) && O.xa_mark[i]) ? O.xa_len[i] + 1u : 0u;
+    return *ql1 + *xl1;
+}
+
+static __global__ __launch_bounds__(SAM_STR_TILE) void k_sam_str_measure(SamOut O, uint32_t first, uint32_t n, int want, unsigned long long *__restrict__ tile_sum)
+{
+    __shared__ uint32_t s_w[SAM_STR_TILE / 64u];
+    const uint32_t j = blockIdx.x * SAM_STR_TILE + threadIdx.x;
+    uint32_t ql1 = 0, xl1 = 0, total = 0;
+    const uint32_t len = j < n ? sam_str_len(O, first + j, want, &ql1, &xl1) : 0u;
+    (void)itx_tile_offsets<SAM_STR_TILE>(len, s_w, &total);
+    if (threadIdx.x == 0) {
+        tile_sum[2u * blockIdx.x] = total;
+        tile_sum[2u * blockIdx.x + 1u] = 0;
+    }
+}
+
+static __global__ __launch_bounds__(SAM_STR_TILE) void k_sam_str_write(const uint8_t *__restrict__ text, SamOut O, uint32_t first, uint32_t n, int want,
+                                                                        const unsigned long long *__restrict__ tile_base, uint8_t *__restrict__ out,
+                                                                        uint32_t *__restrict__ qname_at, uint32_t *__restrict__ xa_at)
+{
+    __shared__ uint4 s_buf[SAM_STR_LDS / 16u];
+    __shared__ uint32_t s_w[SAM_STR_TILE / 64u];
+    const uint32_t j = blockIdx.x * SAM_STR_TILE + threadIdx.x;
+    const bool valid = j < n;
+    uint32_t ql1 = 0, xl1 = 0, total = 0;
+    const uint32_t len = valid ? sam_str_len(O, first + j, want, &ql1, &xl1) : 0u;
+    const uint32_t moff = itx_tile_offsets<SAM_STR_TILE>(len, s_w, &total);
+    const unsigned long long tb = tile_base[2u * blockIdx.x], te = tb + total;
+    const unsigned long long mb = tb + moff, me = mb + len;
+    if (valid) {
+        qname_at[j] = ql1 ? (uint32_t)mb : SAM_STR_NONE;
+        xa_at[j] = xl1 ? (uint32_t)mb + ql1 : SAM_STR_NONE;
+    }
+    const uint8_t *qs = text + (ql1 ? O.line_off[first + j] : 0u), *xs = text + (xl1 ? O.xa_off[first + j] : 0u);
+    itx_pack_tile<SAM_STR_TILE, SAM_STR_LDS>(s_buf, out, tb, te, mb, me, [=](uint8_t *dst, uint32_t from, uint32_t to) {
+        // 20-60 bytes at any alignment: a byte loop, as in itx_names.hip
+#pragma clang loop vectorize(disable)
+        for (uint32_t k = from; k < to; k++) {
+            uint8_t c;
+            if (k < ql1) c = k + 1u < ql1 ? qs[k] : (uint8_t)0;
+            else c = k - ql1 + 1u < xl1 ? xs[k - ql1] : (uint8_t)0;
+            dst[k - from] = c;
+        }
+    });
+}
+
 // ---- the C ABI ----------------------------------------------------------------------------------------------------------------
 struct SamSlot {
     uint8_t *d_text = nullptr;
@@ -271,6 +338,14 @@ struct SamSlot {
     int state = 0;                         // 0 idle, 1 begun, 2 ended: its records can be fetched
     size_t len = 0;
     uint64_t n_rec = 0;
+    // a chunk begun by parse_begin_bgzf: its compressed bytes, block list and status bytes, and what they inflate to
+    int bgzf = 0;
+    uint8_t *d_comp = nullptr, *d_infl = nullptr, *d_status = nullptr, *h_status = nullptr;
+    itx_bgzf_block *d_blk = nullptr, *h_blk = nullptr;
+    size_t comp_cap = 0, infl_cap = 0, blk_cap = 0;
+    size_t n_blk = 0, carry_len = 0;
+    hipEvent_t ev_d0 = nullptr, ev_d1 = nullptr;
+    double inflate_ms = 0;
 };
 
 struct itx_samtext {
@@ -283,7 +358,36 @@ struct itx_samtext {
     unsigned long long *d_tile_sum = nullptr, *d_tile_base = nullptr;
     hipStream_t st = nullptr, st_copy = nullptr;
     SamSlot slot[2];
+    // BGZF: the decoder's scratch (one chunk's passes at a time: they all run on st), the slot of the stream's previous chunk (-1:
+    // the next chunk has no carry), the last text put together on st (a copy into a slot's text on st_copy waits for it)
+    uint8_t *d_scr = nullptr;
+    uint32_t *d_meta = nullptr;
+    size_t scr_cap = 0, meta_cap = 0;
+    int bgzf_prev = -1;
+    hipEvent_t ev_asm = nullptr;
+    bool asm_recorded = false;
+    // the string gather: a stream and buffers of its own, so that it does not queue behind the other slot's parse
+    hipStream_t st_str = nullptr;
+    hipEvent_t ev_s[4] = {};
+    unsigned long long *d_str_sum = nullptr, *d_str_base = nullptr, *d_str_tot = nullptr, *h_str_tot = nullptr;
+    uint32_t *d_at = nullptr, *h_at = nullptr;       // qname_at[n], then xa_at[n]
+    uint8_t *d_str = nullptr, *h_str = nullptr;
+    size_t str_tiles_cap = 0, at_cap = 0, h_at_cap = 0, str_cap = 0, h_str_cap = 0;
 };
+
+// room for `need` elements at *p, nothing kept (hipFree waits for whatever still uses the old one)
+template <typename T> static int sam_grow(T **p, size_t *cap, size_t need, bool pinned = false)
+{
+    if (need <= *cap) return ITX_OK;
+    if (*p) ITX_HIP(pinned ? hipHostFree(*p) : hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    const size_t want = need + need / 4 + 64;
+    if (pinned) ITX_HIP(hipHostMalloc((void **)p, want * sizeof(T), hipHostMallocDefault));
+    else ITX_HIP(hipMalloc((void **)p, want * sizeof(T)));
+    *cap = want;
+    return ITX_OK;
+}
 
 extern "C" void itx_samtext_destroy(itx_samtext *x)
 {
@@ -298,10 +402,31 @@ extern "C" void itx_samtext_destroy(itx_samtext *x)
         (void)hipFree(s.d_tot);
         (void)hipFree(s.d_res);
         if (s.h_res) (void)hipHostFree(s.h_res);
-        hipEvent_t *ev[4] = {&s.ev_copy, &s.ev_k0, &s.ev_k1, &s.ev_done};
+        (void)hipFree(s.d_comp);
+        (void)hipFree(s.d_infl);
+        (void)hipFree(s.d_status);
+        (void)hipFree(s.d_blk);
+        if (s.h_status) (void)hipHostFree(s.h_status);
+        if (s.h_blk) (void)hipHostFree(s.h_blk);
+        hipEvent_t *ev[6] = {&s.ev_copy, &s.ev_k0, &s.ev_k1, &s.ev_done, &s.ev_d0, &s.ev_d1};
         for (auto e : ev)
             if (*e) (void)hipEventDestroy(*e);
     }
+    if (x->st_str) (void)hipStreamSynchronize(x->st_str);
+    (void)hipFree(x->d_scr);
+    (void)hipFree(x->d_meta);
+    (void)hipFree(x->d_str_sum);
+    (void)hipFree(x->d_str_base);
+    (void)hipFree(x->d_str_tot);
+    (void)hipFree(x->d_at);
+    (void)hipFree(x->d_str);
+    if (x->h_str_tot) (void)hipHostFree(x->h_str_tot);
+    if (x->h_at) (void)hipHostFree(x->h_at);
+    if (x->h_str) (void)hipHostFree(x->h_str);
+    if (x->ev_asm) (void)hipEventDestroy(x->ev_asm);
+    for (auto e : x->ev_s)
+        if (e) (void)hipEventDestroy(e);
+    if (x->st_str) (void)hipStreamDestroy(x->st_str);
     (void)hipFree(x->d_tab);
     (void)hipFree(x->d_off);
     (void)hipFree(x->d_pool);
@@ -385,9 +510,14 @@ static int samtext_create(itx_samtext *x, int device, const char *name_bytes, co
         ITX_HIP(hipMalloc((void **)&s.d_tot, 16));
         ITX_HIP(hipMalloc((void **)&s.d_res, 4 * SAM_R_WORDS));
         ITX_HIP(hipHostMalloc((void **)&s.h_res, 4 * SAM_R_WORDS + 16, hipHostMallocDefault));
-        hipEvent_t *ev[4] = {&s.ev_copy, &s.ev_k0, &s.ev_k1, &s.ev_done};
+        hipEvent_t *ev[6] = {&s.ev_copy, &s.ev_k0, &s.ev_k1, &s.ev_done, &s.ev_d0, &s.ev_d1};
         for (auto e : ev) ITX_HIP(hipEventCreate(e));
     }
+    ITX_HIP(hipStreamCreateWithFlags(&x->st_str, hipStreamNonBlocking));
+    ITX_HIP(hipEventCreate(&x->ev_asm));
+    for (auto &e : x->ev_s) ITX_HIP(hipEventCreate(&e));
+    ITX_HIP(hipMalloc((void **)&x->d_str_tot, 16));
+    ITX_HIP(hipHostMalloc((void **)&x->h_str_tot, 16, hipHostMallocDefault));
     return ITX_OK;
 }
 
@@ -422,6 +552,8 @@ extern "C" int itx_samtext_create(int device, const char *name_bytes, const uint
     return ITX_OK;
 }
 
+static int sam_enqueue_parse(itx_samtext *x, SamSlot &s, size_t len, int final);
+
 extern "C" int itx_samtext_parse_begin(itx_samtext *x, int slot, const void *text, size_t len, int final)
 {
     if (!x || slot < 0 || slot > 1 || (len && !text)) {
@@ -440,9 +572,20 @@ extern "C" int itx_samtext_parse_begin(itx_samtext *x, int slot, const void *tex
     ITX_HIP(hipSetDevice(x->device));
     s.state = 0;
     s.len = len;
+    s.bgzf = 0;
+    if (x->bgzf_prev == slot) x->bgzf_prev = -1;                           // the tail a BGZF chunk left here is overwritten
+    if (x->asm_recorded) ITX_HIP(hipStreamWaitEvent(x->st_copy, x->ev_asm, 0));       // ... but not before the chunk that took it has it
     if (len) ITX_HIP(hipMemcpyAsync(s.d_text, text, len, hipMemcpyHostToDevice, x->st_copy));
     ITX_HIP(hipEventRecord(s.ev_copy, x->st_copy));
     ITX_HIP(hipStreamWaitEvent(x->st, s.ev_copy, 0));
+    const int rc = sam_enqueue_parse(x, s, len, final);
+    if (rc == ITX_OK) s.state = 1;
+    return rc;
+}
+
+// the four kernels over the slot's text[0 .. len) and the copies of what they leave, on x->st
+static int sam_enqueue_parse(itx_samtext *x, SamSlot &s, size_t len, int final)
+{
     ITX_HIP(hipEventRecord(s.ev_k0, x->st));
     ITX_HIP(hipMemsetAsync(s.d_res, 0, 4 * SAM_R_WORDS, x->st));
     ITX_HIP(hipMemsetAsync(s.d_res + SAM_R_FIRST, 0xff, 4, x->st));
@@ -463,7 +606,112 @@ extern "C" int itx_samtext_parse_begin(itx_samtext *x, int slot, const void *tex
     ITX_HIP(hipMemcpyAsync(s.h_res, s.d_res, 4 * SAM_R_WORDS, hipMemcpyDeviceToHost, x->st));
     ITX_HIP(hipMemcpyAsync(s.h_res + SAM_R_WORDS, s.d_tot, 16, hipMemcpyDeviceToHost, x->st));
     ITX_HIP(hipEventRecord(s.ev_done, x->st));
+    return ITX_OK;
+}
+
+// members of the slot's chunk whose status is not 0 (valid once ev_done has passed)
+static size_t sam_count_bad(const SamSlot &s, size_t *first)
+{
+    size_t n = 0;
+    for (size_t i = 0; i < s.n_blk; i++)
+        if (s.h_status[i]) {
+            if (!n) *first = i;
+            n++;
+        }
+    return n;
+}
+
+extern "C" int itx_samtext_parse_begin_bgzf(itx_samtext *x, int slot, const void *comp, size_t comp_len, const itx_bgzf_block *blk, size_t n_blk, size_t skip,
+                                            int final)
+{
+    if (!x || slot < 0 || slot > 1 || !comp || !blk) {
+        itx_set_error("itx_samtext_parse_begin_bgzf: bad argument");
+        return ITX_E_ARG;
+    }
+    if (comp_len > 0xfffffff0u || n_blk > 0x7fffffffu) {
+        itx_set_error("itx_samtext_parse_begin_bgzf: %zu bytes in %zu members are more than the decoder encodes", comp_len, n_blk);
+        return ITX_E_LIMIT;
+    }
+    size_t total = 0;                                                      // what the decoder assumes about every member (itx_inflate_bgzf)
+    for (size_t i = 0; i < n_blk; i++) {
+        const itx_bgzf_block &b = blk[i];
+        if ((size_t)b.coff + b.csize > comp_len || b.csize < 26u || b.uoff != total || b.usize > 65536u) {
+            itx_set_error("itx_samtext_parse_begin_bgzf: block %zu does not fit its buffers", i);
+            return ITX_E_ARG;
+        }
+        total += b.usize;
+    }
+    if (total > x->max_chunk + 65536u) {
+        itx_set_error("itx_samtext_parse_begin_bgzf: the members inflate to %zu bytes, the object was made for %zu + 64 KiB", total, x->max_chunk);
+        return ITX_E_LIMIT;
+    }
+    SamSlot &s = x->slot[slot];
+    if (s.state == 1) {
+        itx_set_error("itx_samtext_parse_begin_bgzf: the slot's parse has not been ended");
+        return ITX_E_STATE;
+    }
+    size_t unused = 0;
+    int prev = x->bgzf_prev;
+    if (prev == slot) {                                                    // (ended: its status bytes are here)
+        if (sam_count_bad(s, &unused) == 0) {
+            itx_set_error("itx_samtext_parse_begin_bgzf: the stream's previous chunk lies in this slot");
+            return ITX_E_STATE;
+        }
+        prev = x->bgzf_prev = -1;
+    }
+    ITX_HIP(hipSetDevice(x->device));
+    int rc;
+    size_t st_cap = s.blk_cap, hb_cap = s.blk_cap, hs_cap = s.blk_cap;
+    if ((rc = sam_grow(&s.d_comp, &s.comp_cap, comp_len + 64)) != ITX_OK) return rc;
+    if ((rc = sam_grow(&s.d_infl, &s.infl_cap, x->max_chunk + 65536u + 64)) != ITX_OK) return rc;
+    if ((rc = sam_grow(&s.d_status, &st_cap, n_blk + 1)) != ITX_OK) return rc;
+    if ((rc = sam_grow(&s.h_blk, &hb_cap, n_blk + 1, true)) != ITX_OK) return rc;
+    if ((rc = sam_grow(&s.h_status, &hs_cap, n_blk + 1, true)) != ITX_OK) return rc;
+    if ((rc = sam_grow(&s.d_blk, &s.blk_cap, n_blk + 1)) != ITX_OK) return rc;
+    if ((rc = sam_grow(&x->d_scr, &x->scr_cap, itx_inflate_scratch_bytes(n_blk))) != ITX_OK) return rc;
+    if ((rc = sam_grow(&x->d_meta, &x->meta_cap, 3 * n_blk)) != ITX_OK) return rc;
+    s.state = 0;
+    s.n_blk = 0;
+    // 1. the compressed bytes cross the link on the copy stream, both passes of the decoder run behind them
+    memcpy(s.h_blk, blk, n_blk * sizeof *blk);
+    memset(s.h_status, 0xff, n_blk);
+    if (n_blk) ITX_HIP(hipMemcpyAsync(s.d_blk, s.h_blk, n_blk * sizeof *blk, hipMemcpyHostToDevice, x->st_copy));
+    if (comp_len) ITX_HIP(hipMemcpyAsync(s.d_comp, comp, comp_len, hipMemcpyHostToDevice, x->st_copy));
+    ITX_HIP(hipEventRecord(s.ev_copy, x->st_copy));
+    ITX_HIP(hipStreamWaitEvent(x->st, s.ev_copy, 0));
+    ITX_HIP(hipEventRecord(s.ev_d0, x->st));
+    if ((rc = itx_inflate_enqueue(x->st, s.d_comp, s.d_blk, (uint32_t)n_blk, s.d_infl, s.d_status, x->d_scr, x->d_meta)) != ITX_OK) return rc;
+    ITX_HIP(hipEventRecord(s.ev_d1, x->st));
+    if (n_blk) ITX_HIP(hipMemcpyAsync(s.h_status, s.d_status, n_blk, hipMemcpyDeviceToHost, x->st));
+    // 2. where the previous chunk's parse stopped: its tail is this text's front
+    size_t carry = 0, carry_at = 0;
+    if (prev >= 0) {
+        const SamSlot &p = x->slot[prev];
+        ITX_HIP(hipEventSynchronize(p.ev_done));
+        carry_at = p.len ? p.h_res[SAM_R_CONSUMED] : 0;
+        carry = sam_count_bad(p, &unused) || carry_at > p.len ? 0 : p.len - carry_at;
+    }
+    x->bgzf_prev = -1;
+    const size_t from = skip < total ? skip : total, len = carry + (total - from);
+    if (len > x->max_chunk) {
+        ITX_HIP(hipStreamSynchronize(x->st_copy));                         // comp is the caller's again
+        itx_set_error("itx_samtext_parse_begin_bgzf: a text of %zu bytes (%zu of them the chunk before's tail) exceeds the chunk size the object was made for (%zu)",
+                      len, carry, x->max_chunk);
+        return ITX_E_LIMIT;
+    }
+    // 3. the text, put together on the device
+    if (carry) ITX_HIP(hipMemcpyAsync(s.d_text, x->slot[prev].d_text + carry_at, carry, hipMemcpyDeviceToDevice, x->st));
+    if (total > from) ITX_HIP(hipMemcpyAsync(s.d_text + carry, s.d_infl + from, total - from, hipMemcpyDeviceToDevice, x->st));
+    ITX_HIP(hipEventRecord(x->ev_asm, x->st));
+    x->asm_recorded = true;
+    // 4. the parse
+    s.len = len;
+    s.bgzf = 1;
+    s.n_blk = n_blk;
+    s.carry_len = carry;
+    if ((rc = sam_enqueue_parse(x, s, len, final)) != ITX_OK) return rc;
     s.state = 1;
+    if (!final) x->bgzf_prev = slot;
     return ITX_OK;
 }
 
@@ -496,8 +744,121 @@ extern "C" int itx_samtext_parse_end(itx_samtext *x, int slot, itx_samtext_resul
     res->flags = (int)(s.h_res[SAM_R_FLAGS] | (tot[1] ? ITX_SAMTEXT_NUL : 0));
     res->n_rec = res->n_hard ? 0 : res->n_lines;
     res->kernel_ms = ms;
+    if (s.bgzf) {
+        size_t first = 0;
+        if (sam_count_bad(s, &first)) res->n_rec = 0;                      // the text is not the file's: nothing of it is handed out
+        float dms = 0;
+        ITX_HIP(hipEventElapsedTime(&dms, s.ev_d0, s.ev_d1));
+        s.inflate_ms = dms;
+    }
     s.n_rec = res->n_rec;
     s.state = 2;
+    return ITX_OK;
+}
+
+extern "C" int itx_samtext_bgzf_info(itx_samtext *x, int slot, itx_samtext_bgzf_info_t *out)
+{
+    if (!x || slot < 0 || slot > 1 || !out) {
+        itx_set_error("itx_samtext_bgzf_info: bad argument");
+        return ITX_E_ARG;
+    }
+    const SamSlot &s = x->slot[slot];
+    if (s.state != 2 || !s.bgzf) {
+        itx_set_error("itx_samtext_bgzf_info: the slot holds no parsed BGZF chunk");
+        return ITX_E_STATE;
+    }
+    memset(out, 0, sizeof *out);
+    size_t first = 0;
+    const size_t consumed = s.len ? s.h_res[SAM_R_CONSUMED] : 0;
+    out->text_len = s.len;
+    out->carry_len = s.carry_len;
+    out->tail_len = s.len - consumed;
+    out->n_bad = sam_count_bad(s, &first);
+    out->first_bad = first;
+    out->inflate_ms = s.inflate_ms;
+    return ITX_OK;
+}
+
+extern "C" int itx_samtext_text(itx_samtext *x, int slot, size_t off, void *dst, size_t len)
+{
+    if (!x || slot < 0 || slot > 1 || (len && !dst)) {
+        itx_set_error("itx_samtext_text: bad argument");
+        return ITX_E_ARG;
+    }
+    const SamSlot &s = x->slot[slot];
+    if (s.state != 2) {
+        itx_set_error("itx_samtext_text: the slot holds no parsed chunk");
+        return ITX_E_STATE;
+    }
+    if (off > s.len || len > s.len - off) {
+        itx_set_error("itx_samtext_text: bytes %zu + %zu of %zu", off, len, s.len);
+        return ITX_E_ARG;
+    }
+    if (!len) return ITX_OK;
+    ITX_HIP(hipSetDevice(x->device));
+    ITX_HIP(hipMemcpyAsync(dst, s.d_text + off, len, hipMemcpyDeviceToHost, x->st_str));
+    ITX_HIP(hipStreamSynchronize(x->st_str));
+    return ITX_OK;
+}
+
+extern "C" int itx_samtext_strings(itx_samtext *x, int slot, size_t first, size_t n, int want, itx_samtext_strings_out *out)
+{
+    if (!x || slot < 0 || slot > 1 || !out || want < 1 || want > 3) {
+        itx_set_error("itx_samtext_strings: bad argument");
+        return ITX_E_ARG;
+    }
+    const SamSlot &s = x->slot[slot];
+    if (s.state != 2) {
+        itx_set_error("itx_samtext_strings: the slot holds no parsed chunk");
+        return ITX_E_STATE;
+    }
+    if (first > s.n_rec || n > s.n_rec - first) {
+        itx_set_error("itx_samtext_strings: records %zu + %zu of %llu", first, n, (unsigned long long)s.n_rec);
+        return ITX_E_ARG;
+    }
+    memset(out, 0, sizeof *out);
+    if (!n) return ITX_OK;
+    ITX_HIP(hipSetDevice(x->device));
+    const uint32_t nt = (uint32_t)((n + SAM_STR_TILE - 1) / SAM_STR_TILE);
+    int rc;
+    size_t cap2 = x->str_tiles_cap;
+    if ((rc = sam_grow(&x->d_str_sum, &cap2, 2 * (size_t)nt)) != ITX_OK) return rc;
+    if ((rc = sam_grow(&x->d_str_base, &x->str_tiles_cap, 2 * (size_t)nt)) != ITX_OK) return rc;
+    if ((rc = sam_grow(&x->d_at, &x->at_cap, 2 * n)) != ITX_OK) return rc;
+    if ((rc = sam_grow(&x->h_at, &x->h_at_cap, 2 * n, true)) != ITX_OK) return rc;
+    hipStream_t st = x->st_str;
+    ITX_HIP(hipEventRecord(x->ev_s[0], st));
+    hipLaunchKernelGGL(k_sam_str_measure, dim3(nt), dim3(SAM_STR_TILE), 0, st, s.out, (uint32_t)first, (uint32_t)n, want, x->d_str_sum);
+    ITX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, st, x->d_str_sum, nt, x->d_str_base, x->d_str_tot);
+    ITX_HIP(hipGetLastError());
+    ITX_HIP(hipEventRecord(x->ev_s[1], st));
+    ITX_HIP(hipMemcpyAsync(x->h_str_tot, x->d_str_tot, 16, hipMemcpyDeviceToHost, st));
+    ITX_HIP(hipStreamSynchronize(st));                                     // the total is all the host waits for before the write
+    const size_t total = (size_t)x->h_str_tot[0];
+    if (total > s.len + n) {                                               // disjoint slices of the text and a NUL each: cannot be more
+        itx_set_error("itx_samtext_strings: %zu bytes of strings out of a text of %zu", total, s.len);
+        return ITX_E_STATE;
+    }
+    if ((rc = sam_grow(&x->d_str, &x->str_cap, total + SAM_STR_GUARD + 16)) != ITX_OK) return rc;
+    if ((rc = sam_grow(&x->h_str, &x->h_str_cap, total + SAM_STR_GUARD, true)) != ITX_OK) return rc;
+    ITX_HIP(hipMemsetAsync(x->d_str + total, 0xa5, SAM_STR_GUARD, st));
+    ITX_HIP(hipEventRecord(x->ev_s[2], st));
+    hipLaunchKernelGGL(k_sam_str_write, dim3(nt), dim3(SAM_STR_TILE), 0, st, s.d_text, s.out, (uint32_t)first, (uint32_t)n, want, x->d_str_base, x->d_str, x->d_at,
+                       x->d_at + n);
+    ITX_HIP(hipGetLastError());
+    ITX_HIP(hipEventRecord(x->ev_s[3], st));
+    ITX_HIP(hipMemcpyAsync(x->h_str, x->d_str, total + SAM_STR_GUARD, hipMemcpyDeviceToHost, st));
+    ITX_HIP(hipMemcpyAsync(x->h_at, x->d_at, 8 * n, hipMemcpyDeviceToHost, st));
+    ITX_HIP(hipStreamSynchronize(st));
+    float a = 0, b = 0;
+    ITX_HIP(hipEventElapsedTime(&a, x->ev_s[0], x->ev_s[1]));
+    ITX_HIP(hipEventElapsedTime(&b, x->ev_s[2], x->ev_s[3]));
+    out->text = (const char *)x->h_str;
+    out->text_len = total;
+    out->qname_at = x->h_at;
+    out->xa_at = x->h_at + n;
+    out->kernel_ms = (double)a + (double)b;
     return ITX_OK;
 }
 

@@ -35,6 +35,7 @@ EXPORTS = [
     "itx_names_finish", "itx_names_get_stats",
     "itx_loci_create", "itx_loci_destroy", "itx_loci_order", "itx_loci_filter_text", "itx_loci_cpg_text",
     "itx_samtext_create", "itx_samtext_destroy", "itx_samtext_parse_begin", "itx_samtext_parse_end", "itx_samtext_fetch",
+    "itx_samtext_parse_begin_bgzf", "itx_samtext_bgzf_info", "itx_samtext_text", "itx_samtext_strings",
 ]
 
 
@@ -128,7 +129,17 @@ class SamTextResult(C.Structure):
                 ("flags", C.c_int), ("kernel_ms", C.c_double)]
 
 
+class SamTextBgzfInfo(C.Structure):
+    _fields_ = [("text_len", C.c_uint64), ("carry_len", C.c_uint64), ("tail_len", C.c_uint64), ("n_bad", C.c_uint64), ("first_bad", C.c_uint64),
+                ("inflate_ms", C.c_double)]
+
+
+class SamTextStrings(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("text_len", C.c_uint64), ("qname_at", C.c_void_p), ("xa_at", C.c_void_p), ("kernel_ms", C.c_double)]
+
+
 SAMTEXT_PAIRED, SAMTEXT_XA, SAMTEXT_NUL = 1, 2, 4
+SAMTEXT_NO_STRING = 0xFFFFFFFF
 
 _lib = None
 
@@ -233,6 +244,10 @@ def load():
     L.itx_samtext_parse_begin.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int]
     L.itx_samtext_parse_end.argtypes = [C.c_void_p, C.c_int, C.POINTER(SamTextResult)]
     L.itx_samtext_fetch.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(Staging), C.c_size_t] + [C.c_void_p] * 6
+    L.itx_samtext_parse_begin_bgzf.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]
+    L.itx_samtext_bgzf_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(SamTextBgzfInfo)]
+    L.itx_samtext_text.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t]
+    L.itx_samtext_strings.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(SamTextStrings)]
     L.itx_pinned_alloc.argtypes = [C.c_size_t]
     L.itx_pinned_alloc.restype = C.c_void_p
     L.itx_pinned_free.argtypes = [C.c_void_p]
@@ -721,6 +736,45 @@ class SamText:
     def parse(self, text: bytes, final: bool, slot: int = 0):
         self.begin(text, final, slot)
         return self.end(slot)
+
+    def begin_bgzf(self, comp: bytes, final: bool, slot: int = 0, skip: int = 0, blocks: np.ndarray | None = None):
+        """the members of `comp` (all complete ones, or `blocks`) inflated on the device; the slot's text is the tail the stream's
+        previous chunk left, then the inflated bytes from `skip` on"""
+        blocks = index_bgzf(comp) if blocks is None else np.ascontiguousarray(blocks, BGZF_BLOCK)
+        buf = np.frombuffer(comp + b"\0", np.uint8).copy()           # stays alive until the parse has ended
+        self._text[slot] = (buf, blocks)
+        _chk(load().itx_samtext_parse_begin_bgzf(self._h, slot, _p(buf), len(comp), _p(blocks) if len(blocks) else _p(np.zeros(1, BGZF_BLOCK)),
+                                                 len(blocks), skip, int(final)), "itx_samtext_parse_begin_bgzf")
+
+    def parse_bgzf(self, comp: bytes, final: bool, slot: int = 0, skip: int = 0, blocks: np.ndarray | None = None):
+        """-> (the result fields, the BGZF fields: text_len, carry_len, tail_len, n_bad, first_bad, inflate_ms)"""
+        self.begin_bgzf(comp, final, slot, skip, blocks)
+        res = self.end(slot)
+        return res, self.bgzf_info(slot)
+
+    def bgzf_info(self, slot: int = 0):
+        info = SamTextBgzfInfo()
+        _chk(load().itx_samtext_bgzf_info(self._h, slot, C.byref(info)), "itx_samtext_bgzf_info")
+        return {k: getattr(info, k) for k, _ in SamTextBgzfInfo._fields_}
+
+    def text(self, slot: int = 0, off: int = 0, n: int | None = None) -> bytes:
+        """bytes [off, off + n) of the slot's text (all of it by default: its length is known for a BGZF chunk only)"""
+        if n is None:
+            n = self.bgzf_info(slot)["text_len"] - off
+        out = np.zeros(n + 1, np.uint8)
+        _chk(load().itx_samtext_text(self._h, slot, off, _p(out), n), "itx_samtext_text")
+        return out[:n].tobytes()
+
+    def strings(self, slot, first, n, want=3):
+        """-> (the packed text, qname_at, xa_at, the 16 bytes the object keeps behind the text): read names (want & 1) and XA values
+        (want & 2) of records [first, first + n), each followed by a NUL; SAMTEXT_NO_STRING where a record has none"""
+        o = SamTextStrings()
+        _chk(load().itx_samtext_strings(self._h, slot, first, n, want, C.byref(o)), "itx_samtext_strings")
+        if not n:
+            return b"", np.zeros(0, np.uint32), np.zeros(0, np.uint32), b""
+        raw = C.string_at(o.text, o.text_len + 16)
+        at = lambda p: np.frombuffer(C.string_at(p, 4 * n), np.uint32).copy()
+        return raw[:o.text_len], at(o.qname_at), at(o.xa_at), raw[o.text_len:]
 
     def fetch(self, slot, first, n, side=True):
         a = {k: np.full(n + 1, 7, dt) for k, dt in (("tid", np.int32), ("pos", np.int32), ("tmpend", np.int32), ("mapq", np.uint8), ("flag5", np.uint8),

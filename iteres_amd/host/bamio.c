@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <zlib.h>
+#include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -125,6 +126,14 @@ struct aln_reader {
         uint8_t *buf;
         size_t cap, len;
         int final, begun, begin_rc, from_alloc;
+        /* a chunk of BGZF members for the device to inflate (sam_bgzf_thread): the host has no copy of its text */
+        int bgzf, handover;   /* handover: the decoder cannot take it, nothing was begun; `why` says what is wrong */
+        uint8_t *cbuf;        /* the members' bytes */
+        size_t ccap, clen, coff, utot, skip_before;     /* coff: the first member's file offset; skip_before: header bytes not yet skipped there */
+        int c_from_alloc;
+        itx_bgzf_block *zb;
+        size_t zb_cap;
+        char why[128];
     } sc[2];
     uint8_t *sc_tail;         /* the bytes behind the last newline of the chunk before */
     size_t sc_tail_len, sc_tail_cap;
@@ -144,6 +153,17 @@ struct aln_reader {
     unsigned long long st_dev_chunks, st_dev_bytes, st_host_chunks;   /* ITX_TIMING */
     double st_ms, st_wait;
     char st_reason[96];
+    /* -S input through zlib; BGZF inflated on the device */
+    int sam_fd;               /* the file's own descriptor (-1 none): the compressed bytes are read from it with pread   */
+    int sz_gz, sz_bgzf;       /* the file starts with the gzip magic / its first member is BGZF                          */
+    size_t sz_hdr;            /* inflated bytes of the header lines                                                      */
+    int sz_on;                /* the device inflates: until a hand-over, which is for good                               */
+    size_t sz_off, sz_skip;   /* the next member's file offset; header bytes the device stream has still to skip        */
+    int sz_prev_slot;         /* where the last device chunk left its tail (-1: there is none): a hand-over's carry      */
+    size_t sz_prev_at, sz_prev_tail;
+    unsigned long long sz_dev_chunks, sz_comp_bytes, sz_infl_bytes, sz_host_chunks;   /* ITX_TIMING */
+    double sz_inflate_ms, sz_gather_ms;
+    char sz_reason[200];
 };
 
 /* ---- BGZF ------------------------------------------------------------------------------------------------ */
@@ -1146,6 +1166,7 @@ static int sam_read_header(aln_reader *r)
             r->pending_len = len;
             break;
         }
+        r->sz_hdr += (size_t)len;
         if (strncmp(r->line, "@SQ", 3) == 0) {
             char *sn = strstr(r->line, "\tSN:");
             if (sn) {
@@ -1162,14 +1183,52 @@ static int sam_read_header(aln_reader *r)
     return 0;
 }
 
+/* ---- SAM input through zlib ------------------------------------------------------------------------------------------- */
+/* The reference opens -S input with gzopen (bam_import.c:17,76,126), so plain gzip, bgzip's output and a mix of both are SAM
+ * text to it, what lies behind the last member is ignored, and a file cut short gives what a streaming inflater gets out of it.
+ * The same calls behind the FILE the reader already uses: a file without the gzip magic is passed through as it is. */
+static ssize_t samz_read(void *c, char *buf, size_t n)
+{
+    const int got = gzread((gzFile)c, buf, n > (1u << 30) ? 1u << 30 : (unsigned)n);
+    return got < 0 ? 0 : got;                                        /* a damaged stream ends the input, as it does there */
+}
+
+static int samz_close(void *c)
+{
+    return gzclose((gzFile)c) == Z_OK ? 0 : -1;
+}
+
+static FILE *samz_fopen(gzFile g)
+{
+    if (!g) return NULL;
+    gzbuffer(g, 1u << 17);
+    FILE *f = fopencookie(g, "r", (cookie_io_functions_t){.read = samz_read, .close = samz_close});
+    if (!f) gzclose(g);
+    return f;
+}
+
 aln_reader *aln_open(const char *path, int is_sam)
 {
-    FILE *f = fopen(path, is_sam ? "r" : "rb");
-    if (!f) return NULL;
+    const int fd = is_sam ? open(path, O_RDONLY) : -1;
+    if (is_sam && fd < 0) return NULL;
+    const int fd_own = is_sam ? dup(fd) : -1;
+    FILE *f = is_sam ? samz_fopen(gzdopen(fd, "rb")) : fopen(path, "rb");
+    if (!f) {
+        if (fd_own >= 0) close(fd_own);
+        return NULL;
+    }
     ld_probe();
     aln_reader *r = xcalloc(1, sizeof *r);
     r->f = f;
     r->is_sam = is_sam;
+    r->sam_fd = fd_own;
+    r->sz_prev_slot = -1;
+    if (fd_own >= 0) {
+        uint8_t h[18];
+        const ssize_t got = pread(fd_own, h, sizeof h, 0);
+        r->sz_gz = got >= 2 && h[0] == 0x1f && h[1] == 0x8b;
+        r->sz_bgzf = got == (ssize_t)sizeof h && bgzf_header_ok(h);
+    }
     r->pending_len = -1;
     names_init(&r->tnames);
     int rc;
@@ -1369,7 +1428,16 @@ void aln_close(aln_reader *r)
         pthread_join(r->io_thread, NULL);
     }
     sam_chunks_stop(r);
+    if (r->is_sam && getenv("ITX_TIMING")) {
+        if (!r->sz_gz)
+            fprintf(stderr, "[itx timing] sam gz: not compressed\n");
+        else
+            fprintf(stderr, "[itx timing] sam gz: %llu chunks inflated on the device (%llu -> %llu bytes, %.3f ms in the decoder, %.3f ms gathering strings), %llu by the host (%s)\n",
+                    r->sz_dev_chunks, r->sz_comp_bytes, r->sz_infl_bytes, r->sz_inflate_ms, r->sz_gather_ms, r->sz_host_chunks,
+                    r->sz_reason[0] ? r->sz_reason : r->sc_on ? "none" : "read line by line");
+    }
     if (r->f) fclose(r->f);
+    if (r->is_sam && r->sam_fd >= 0) close(r->sam_fd);
     for (int k = 0; k < N_RAW_DEVICE; k++) buf_free(r->craw[k]);
     buf_free(r->nbuf);
     free(r->blk);
@@ -1986,23 +2054,26 @@ void aln_set_sam_device(aln_reader *r, const aln_sam_device *d)
     if (r->sdev_on) r->sdev = *d;
 }
 
-/* room for n bytes in the chunk's buffer, the first `keep` ones preserved: from the device's `alloc` (page-locked) when it gives */
-static void sam_buf_need(aln_reader *r, struct sam_chunk *c, size_t n, size_t keep)
+/* room for n bytes in a buffer, the first `keep` ones preserved: from the device's `alloc` (page-locked) when it gives */
+static void sam_room(aln_reader *r, uint8_t **buf, size_t *pcap, int *from_alloc, size_t n, size_t keep)
 {
-    if (c->cap >= n) return;
+    if (*pcap >= n) return;
     const size_t cap = n + n / 8 + 4096;
     uint8_t *p = r->sdev_on && r->sdev.alloc ? r->sdev.alloc(cap) : NULL;
     const int fa = p != NULL;
     if (!p) p = xmalloc(cap);
-    if (keep) memcpy(p, c->buf, keep);
-    if (c->buf) {
-        if (c->from_alloc) r->sdev.release(c->buf);
-        else free(c->buf);
+    if (keep) memcpy(p, *buf, keep);
+    if (*buf) {
+        if (*from_alloc) r->sdev.release(*buf);
+        else free(*buf);
     }
-    c->buf = p;
-    c->cap = cap;
-    c->from_alloc = fa;
+    *buf = p;
+    *pcap = cap;
+    *from_alloc = fa;
 }
+
+/* ... in the chunk's text buffer */
+static void sam_buf_need(aln_reader *r, struct sam_chunk *c, size_t n, size_t keep) { sam_room(r, &c->buf, &c->cap, &c->from_alloc, n, keep); }
 
 static void *sam_chunk_thread(void *arg)
 {
@@ -2052,6 +2123,8 @@ static void *sam_chunk_thread(void *arg)
         c->final = eof;
         c->begun = 0;
         c->begin_rc = 0;
+        c->bgzf = c->handover = 0;
+        if (r->sz_gz && cut) r->sz_host_chunks++;                        /* inflated by gzread behind r->f */
         if (r->sdev_on && cut) {
             c->begin_rc = r->sdev.parse_begin(r->sdev.obj, k, c->buf, cut, eof);
             c->begun = c->begin_rc == 0;
@@ -2065,10 +2138,119 @@ static void *sam_chunk_thread(void *arg)
     return NULL;
 }
 
+/* BGZF for the device to inflate: whole members, read from the file's own descriptor, until they inflate to a chunk (the last one
+ * may take it up to 64 KiB - 1 further); the chunk's parse is begun here, so that it runs while the chunk before is consumed. Ends
+ * with the chunk behind which the file ends, or with a chunk the decoder cannot take: what lies at its first byte is not a BGZF
+ * member, or the file ends inside it (sam_hand_over). */
+static void *sam_bgzf_thread(void *arg)
+{
+    aln_reader *r = arg;
+    const size_t step = r->sc_chunk / 2 < 65536 ? 65536 : r->sc_chunk / 2 > ((size_t)4 << 20) ? (size_t)4 << 20 : r->sc_chunk / 2;
+    for (;;) {
+        pthread_mutex_lock(&r->sc_mu);
+        while (!r->sc_stop && r->sc_fill - r->sc_take >= 2) pthread_cond_wait(&r->sc_cv, &r->sc_mu);
+        const int stop = r->sc_stop;
+        pthread_mutex_unlock(&r->sc_mu);
+        if (stop) break;
+        const int k = (int)(r->sc_fill & 1);
+        struct sam_chunk *c = &r->sc[k];
+        c->bgzf = 1;
+        c->handover = c->begun = c->begin_rc = c->final = 0;
+        c->len = 0;
+        c->coff = r->sz_off;
+        c->skip_before = r->sz_skip;
+        c->why[0] = 0;
+        size_t have = 0, off = 0, utot = 0, nb = 0;
+        int damaged = 0, capped = 0, at_end = 0;
+        for (;;) {                                                   /* more bytes until a chunk's worth of whole members is at hand */
+            sam_room(r, &c->cbuf, &c->ccap, &c->c_from_alloc, have + step + 64, have);
+            const double t0 = now_s();
+            ssize_t got = pread(r->sam_fd, c->cbuf + have, step, (off_t)(r->sz_off + have));
+            t_io += now_s() - t0;
+            if (got < 0) got = 0;                                    /* a read error ends the file, as it does for gzread */
+            have += (size_t)got;
+            at_end = (size_t)got < step;
+            r->cbuf = c->cbuf;                                       /* (the BGZF reader's index state: nobody else's in a SAM reader) */
+            r->clen = have;
+            nb = index_blocks(r, SIZE_MAX, r->sc_chunk + BGZF_MAX - 1, &off, &utot, &damaged, &capped);
+            if (capped || damaged || at_end) break;
+        }
+        for (size_t i = 0; i < nb; i++)                              /* the chunk ends with the member that takes the sum to a chunk */
+            if (r->blk[i].uoff + r->blk[i].usize >= r->sc_chunk) {
+                nb = i + 1;
+                off = r->blk[i].coff + r->blk[i].csize;
+                utot = r->blk[i].uoff + r->blk[i].usize;
+                break;
+            }
+        int last = 0;
+        if (nb == 0) {
+            c->handover = last = 1;
+            snprintf(c->why, sizeof c->why, damaged ? "what lies there is not a BGZF member" : "the file ends inside that member");
+        } else {
+            if (c->zb_cap < nb) {
+                c->zb_cap = nb + nb / 4 + 64;
+                c->zb = xrealloc(c->zb, sizeof *c->zb * c->zb_cap);
+            }
+            for (size_t i = 0; i < nb; i++)
+                c->zb[i] = (itx_bgzf_block){(uint32_t)r->blk[i].coff, (uint32_t)r->blk[i].csize, (uint32_t)r->blk[i].uoff, (uint32_t)r->blk[i].usize};
+            const size_t skip = r->sz_skip < utot ? r->sz_skip : utot;
+            r->sz_skip -= skip;
+            c->clen = off;
+            c->utot = utot;
+            c->final = at_end && off == have && !damaged;            /* the file ends behind the chunk's last member */
+            c->begin_rc = r->sdev.parse_begin_bgzf(r->sdev.obj, k, c->cbuf, off, c->zb, nb, skip, c->final);
+            if (c->begin_rc == 0) {
+                c->begun = 1;
+                r->sz_off += off;
+                last = c->final;
+            } else {                                                 /* (a text that does not fit the object, for one) */
+                c->handover = last = 1;
+                c->final = 0;
+                snprintf(c->why, sizeof c->why, "%s", r->sdev.last_error ? r->sdev.last_error() : "the device declined the chunk");
+            }
+        }
+        pthread_mutex_lock(&r->sc_mu);
+        r->sc_fill++;
+        pthread_cond_broadcast(&r->sc_cv);
+        pthread_mutex_unlock(&r->sc_mu);
+        if (last) break;
+    }
+    return NULL;
+}
+
+/* whether the device inflates this file, and if not, who does and why (ITX_TIMING) */
+static int sam_device_inflates(aln_reader *r)
+{
+    const char *e = getenv("ITX_HOST_SAM_INFLATE");
+    struct stat sb;
+    const char *why = NULL;
+    if (!r->sz_gz) return 0;
+    if (!r->sdev_on) why = "no device object attached";
+    else if (e && atoi(e) == 1) why = "ITX_HOST_SAM_INFLATE=1";
+    else if (!r->sz_bgzf) why = "plain gzip is one stream";
+    else if (!r->sdev.parse_begin_bgzf || !r->sdev.bgzf_info || !r->sdev.text || !r->sdev.strings) why = "the device object has no BGZF entries";
+    else if (r->sam_fd < 0 || fstat(r->sam_fd, &sb) != 0 || !S_ISREG(sb.st_mode)) why = "not a regular file";
+    if (why) snprintf(r->sz_reason, sizeof r->sz_reason, "%s", why);
+    return why == NULL;
+}
+
 static void sam_chunks_start(aln_reader *r)
 {
     r->sc_on = 1;
     r->sc_chunk = aln_sam_chunk_bytes();
+    r->sz_on = sam_device_inflates(r);
+    if (r->sz_on) {
+        /* the device's stream starts again at the file's first byte and skips the header; the first body line, which the header
+         * scan has read already, is in that stream too */
+        if (r->pending_len >= 0) r->n_lines--;
+        r->pending_len = -1;
+        r->sz_off = 0;
+        r->sz_skip = r->sz_hdr;
+        pthread_mutex_init(&r->sc_mu, NULL);
+        pthread_cond_init(&r->sc_cv, NULL);
+        if (pthread_create(&r->sc_thread, NULL, sam_bgzf_thread, r) != 0) die("cannot start the SAM read-ahead thread");
+        return;
+    }
     if (r->pending_len >= 0) {                                       /* the first body line goes in front of the first chunk */
         r->sc_tail_cap = (size_t)r->pending_len + 256;
         r->sc_tail = xmalloc(r->sc_tail_cap);
@@ -2102,6 +2284,99 @@ static void sam_chunk_close(aln_reader *r)
     pthread_mutex_unlock(&r->sc_mu);
 }
 
+/* The decoder cannot take chunk c whole: nothing of it is used. The host's zlib reader takes the file from the chunk's first member
+ * on, with the carry (bytes [at, at + len) of the text in `slot`: the tail of the last chunk that was used) in front; what it
+ * makes of odd and damaged input is then the reference's, whose reader it is. For the rest of the file. */
+static void sam_hand_over(aln_reader *r, struct sam_chunk *c, int slot, size_t at, size_t len)
+{
+    pthread_mutex_lock(&r->sc_mu);
+    r->sc_stop = 1;
+    pthread_cond_broadcast(&r->sc_cv);
+    pthread_mutex_unlock(&r->sc_mu);
+    pthread_join(r->sc_thread, NULL);
+    for (int k = 0; k < 2; k++)
+        if (r->sc[k].begun) {                                        /* a chunk begun behind this one */
+            itx_samtext_result res;
+            (void)r->sdev.parse_end(r->sdev.obj, k, &res);
+            r->sc[k].begun = 0;
+        }
+    if (r->sc_tail_cap < len + 1) {
+        r->sc_tail_cap = len + len / 4 + 256;
+        r->sc_tail = xrealloc(r->sc_tail, r->sc_tail_cap);
+    }
+    if (len && r->sdev.text(r->sdev.obj, slot, at, r->sc_tail, len) != 0)
+        die("SAM text on the device: the carry could not be fetched: %s", r->sdev.last_error ? r->sdev.last_error() : "?");
+    r->sc_tail_len = len;
+    if (!r->sz_reason[0]) snprintf(r->sz_reason, sizeof r->sz_reason, "handed over at byte %zu of the file: %s", c->coff, c->why);
+    if (r->f) fclose(r->f);
+    const int fd = dup(r->sam_fd);
+    if (fd < 0 || lseek(fd, (off_t)c->coff, SEEK_SET) < 0 || !(r->f = samz_fopen(gzdopen(fd, "rb")))) die("SAM input: cannot read on from byte %zu", c->coff);
+    for (size_t left = c->skip_before; left;) {                      /* what is left of the header */
+        uint8_t junk[4096];
+        const size_t got = fread(junk, 1, left < sizeof junk ? left : sizeof junk, r->f);
+        if (!got) break;
+        left -= got;
+    }
+    r->sz_on = 0;
+    r->sz_prev_slot = -1;
+    r->sc[0].bgzf = r->sc[1].bgzf = r->sc[0].handover = r->sc[1].handover = 0;
+    r->sc_stop = r->sc_open = 0;
+    r->sc_fill = r->sc_take = 0;
+    if (pthread_create(&r->sc_thread, NULL, sam_chunk_thread, r) != 0) die("cannot start the SAM read-ahead thread");
+}
+
+/* a chunk the device has inflated becomes the one being consumed. 1: it is open; 0: it held nothing, or the file was handed over:
+ * the caller looks for the next chunk */
+static int sam_bgzf_open(aln_reader *r, int k, struct sam_chunk *c)
+{
+    if (c->handover) {                                               /* nothing begun: the carry lies where the chunk before left it */
+        sam_hand_over(r, c, r->sz_prev_slot, r->sz_prev_at, r->sz_prev_slot >= 0 ? r->sz_prev_tail : 0);
+        return 0;
+    }
+    itx_samtext_result res;
+    itx_samtext_bgzf_info_t zi;
+    const double t0 = now_s();
+    if (r->sdev.parse_end(r->sdev.obj, k, &res) != 0) die("SAM text on the device: parse failed: %s", r->sdev.last_error ? r->sdev.last_error() : "?");
+    r->st_wait += now_s() - t0;
+    c->begun = 0;
+    if (r->sdev.bgzf_info(r->sdev.obj, k, &zi) != 0) die("SAM text on the device: %s", r->sdev.last_error ? r->sdev.last_error() : "?");
+    if (zi.n_bad) {                                                  /* its text begins with the carry, whatever the members gave */
+        snprintf(c->why, sizeof c->why, "member %llu from there on does not inflate on the device", (unsigned long long)zi.first_bad);
+        sam_hand_over(r, c, k, 0, (size_t)zi.carry_len);
+        return 0;
+    }
+    if (res.consumed + zi.tail_len != zi.text_len || (c->final && zi.tail_len))
+        die("SAM text on the device: %llu of %llu bytes consumed", (unsigned long long)res.consumed, (unsigned long long)zi.text_len);
+    r->sz_prev_slot = k;
+    r->sz_prev_at = (size_t)res.consumed;
+    r->sz_prev_tail = (size_t)zi.tail_len;
+    r->sz_dev_chunks++;
+    r->sz_comp_bytes += c->clen;
+    r->sz_infl_bytes += c->utot;
+    r->sz_inflate_ms += zi.inflate_ms;
+    if (res.n_hard == 0) {
+        r->sc_host = 0;
+        r->sc_nrec = res.n_rec;
+        r->sc_next = 0;
+        r->sc_lines = res.n_lines;
+        r->sc_flags = res.flags;
+        r->st_dev_chunks++;
+        r->st_dev_bytes += res.consumed;
+        r->st_ms += res.kernel_ms;
+    } else {                                                         /* the host takes the consumed text line by line: it fetches it */
+        sam_host_reason(r, "line %lld is spelt in a way the device does not model", r->n_lines + (long long)res.first_hard_line + 1);
+        sam_buf_need(r, c, (size_t)res.consumed + 1, 0);
+        if (res.consumed && r->sdev.text(r->sdev.obj, k, 0, c->buf, (size_t)res.consumed) != 0)
+            die("SAM text on the device: the text could not be fetched: %s", r->sdev.last_error ? r->sdev.last_error() : "?");
+        c->len = (size_t)res.consumed;
+    }
+    if (r->sc_host ? c->len == 0 : res.n_rec == 0) {                 /* (a chunk inside the header, a chunk that ends before its first newline) */
+        sam_chunk_close(r);
+        return 0;
+    }
+    return 1;
+}
+
 /* the next chunk becomes the one being consumed: 0 at the end of the input */
 static int sam_chunk_open(aln_reader *r)
 {
@@ -2115,6 +2390,10 @@ static int sam_chunk_open(aln_reader *r)
         r->sc_open = 1;
         r->sc_host = 1;
         r->sc_pos = 0;
+        if (c->bgzf) {
+            if (sam_bgzf_open(r, k, c)) return 1;
+            continue;
+        }
         if (c->len == 0) {                                           /* nothing but the end of the file */
             sam_chunk_close(r);
             continue;
@@ -2188,9 +2467,17 @@ static size_t sam_read_chunked(aln_reader *r, itx_staging *st, size_t cap, aln_s
         }
         const int aux = want_a && has_xa;
         const double tp = now_s();
-        if (r->sdev.fetch(r->sdev.obj, k, (size_t)r->sc_next, m, st, n, want_q ? r->s_off : NULL, want_q ? r->s_qlen : NULL, aux ? r->s_xoff : NULL,
-                          aux ? r->s_xlen : NULL, aux ? r->s_nm : NULL, has_xa ? r->s_mark : NULL) != 0)
+        const int on_dev = c->bgzf;                                  /* the text lies on the device only: the strings are gathered there */
+        if (r->sdev.fetch(r->sdev.obj, k, (size_t)r->sc_next, m, st, n, want_q && !on_dev ? r->s_off : NULL, want_q ? r->s_qlen : NULL,
+                          aux && !on_dev ? r->s_xoff : NULL, aux ? r->s_xlen : NULL, aux ? r->s_nm : NULL, has_xa ? r->s_mark : NULL) != 0)
             die("SAM text on the device: fetch failed: %s", r->sdev.last_error ? r->sdev.last_error() : "?");
+        itx_samtext_strings_out so;
+        memset(&so, 0, sizeof so);
+        if (on_dev && (want_q || aux)) {
+            if (r->sdev.strings(r->sdev.obj, k, (size_t)r->sc_next, m, (want_q ? 1 : 0) | (aux ? 2 : 0), &so) != 0)
+                die("SAM text on the device: the strings could not be gathered: %s", r->sdev.last_error ? r->sdev.last_error() : "?");
+            r->sz_gather_ms += so.kernel_ms;
+        }
         int ap = 0, xa = 0;
         const uint8_t *f5 = st->flag5 + n;
         for (size_t i = 0; i < m; i++) ap |= f5[i] & 1;
@@ -2199,15 +2486,16 @@ static size_t sam_read_chunked(aln_reader *r, itx_staging *st, size_t cap, aln_s
         if (ap) *any_paired = 1;
         if (xa) *aux_xa = 1;
         if (want_q || want_a) {
-            const char *text = (const char *)c->buf;
+            const char *text = on_dev ? so.text : (const char *)c->buf;
+            const uint32_t *q_at = on_dev ? so.qname_at : r->s_off, *x_at = on_dev ? so.xa_at : r->s_xoff;
 #pragma omp parallel for schedule(static)
             for (long i = 0; i < (long)m; i++) {
-                if (want_q) side->qname[n + (size_t)i] = xstrndup_bound(text + r->s_off[i], r->s_qlen[i]);
+                if (want_q) side->qname[n + (size_t)i] = xstrndup_bound(text + q_at[i], r->s_qlen[i]);
                 if (want_a) {
                     side->xa[n + (size_t)i] = NULL;
                     side->nm[n + (size_t)i] = 0;
                     if (aux && r->s_mark[i]) {
-                        side->xa[n + (size_t)i] = xstrndup_bound(text + r->s_xoff[i], r->s_xlen[i]);
+                        side->xa[n + (size_t)i] = xstrndup_bound(text + x_at[i], r->s_xlen[i]);
                         side->nm[n + (size_t)i] = r->s_nm[i];
                     }
                 }
@@ -2242,6 +2530,11 @@ static void sam_chunks_stop(aln_reader *r)
             if (c->from_alloc) r->sdev.release(c->buf);
             else free(c->buf);
         }
+        if (c->cbuf) {
+            if (c->c_from_alloc) r->sdev.release(c->cbuf);
+            else free(c->cbuf);
+        }
+        free(c->zb);
     }
     if (getenv("ITX_TIMING"))
         fprintf(stderr, "[itx timing] sam: %llu chunks parsed on the device (%llu bytes, %.3f ms in its kernels, host waited %.3f s), %llu by the host (%s)\n", r->st_dev_chunks,

@@ -151,7 +151,13 @@ aln_reader *aln_open(const char *path, int is_sam);          /* NULL when the fi
  * ITX_SAM_CHUNK bytes (default ALN_SAM_CHUNK) cut behind a newline, by a read-ahead thread into two buffers from `alloc`; a
  * chunk's records come from the device's arrays, its read names and XA strings from the host's copy of the text by offset. A
  * chunk with a line the device does not model (csrc/itx_samline.h) is parsed by the host, whole and in order. Without an
- * attached object the reader takes line after line with getline, or — ITX_SAM_CHUNK set — the same chunks all by the host. */
+ * attached object the reader takes line after line with getline, or — ITX_SAM_CHUNK set — the same chunks all by the host.
+ * -S input is read through zlib, as the reference reads it: gzip, BGZF and a mix of both are SAM text too. With an object attached
+ * and its BGZF entries set, a file whose first member is BGZF is inflated on the device as well (ITX_HOST_SAM_INFLATE=1: by the
+ * host): the read-ahead thread reads whole members from the file's own descriptor until they inflate to ITX_SAM_CHUNK bytes, the
+ * device inflates them, carries the unconsumed tail from chunk to chunk and gathers the strings a side channel wants. A chunk the
+ * decoder cannot take whole (a member that does not inflate, a member that is not BGZF, a member the file's end cuts short) hands
+ * the rest of the file over to the host's zlib reader, from that chunk's first member on and for good. */
 typedef struct aln_sam_device {
     itx_samtext *obj;
     int (*parse_begin)(itx_samtext *, int, const void *, size_t, int);
@@ -160,7 +166,13 @@ typedef struct aln_sam_device {
     void *(*alloc)(size_t bytes);
     void (*release)(void *p);
     const char *(*last_error)(void);
+    /* BGZF inflated on the device (all four, or none) */
+    int (*parse_begin_bgzf)(itx_samtext *, int, const void *, size_t, const itx_bgzf_block *, size_t, size_t, int);
+    int (*bgzf_info)(itx_samtext *, int, itx_samtext_bgzf_info_t *);
+    int (*text)(itx_samtext *, int, size_t, void *, size_t);
+    int (*strings)(itx_samtext *, int, size_t, size_t, int, itx_samtext_strings_out *);
 } aln_sam_device;
+#define ALN_SAM_CARRY ((size_t)1 << 20)     /* room the device object gets for the tail one chunk leaves to the next */
 #define ALN_SAM_CHUNK ((size_t)64 << 20)
 size_t aln_sam_chunk_bytes(void);           /* ITX_SAM_CHUNK, or the default */
 void aln_set_sam_device(aln_reader *r, const aln_sam_device *d);

@@ -709,10 +709,14 @@ static itx_samtext *sam_device_attach(aln_reader *rd)
     }
     off[nt] = at;
     itx_samtext *x = NULL;
-    chk(itx_samtext_create(multi_device(), pool, off, nt, aln_sam_chunk_bytes(), &x), "itx_samtext_create");
+    /* room for a chunk of text; for BGZF, whose chunks end with a whole member, 64 KiB more and the tail of the chunk before */
+    size_t room = aln_sam_chunk_bytes() + 65536 + ALN_SAM_CARRY;
+    if (room > (size_t)256 << 20) room = (size_t)256 << 20;              /* the most an object takes: a longer text is the host's */
+    chk(itx_samtext_create(multi_device(), pool, off, nt, room, &x), "itx_samtext_create");
     free(pool);
     free(off);
-    const aln_sam_device d = {x, itx_samtext_parse_begin, itx_samtext_parse_end, itx_samtext_fetch, itx_pinned_alloc, itx_pinned_free, itx_last_error};
+    const aln_sam_device d = {x, itx_samtext_parse_begin, itx_samtext_parse_end, itx_samtext_fetch, itx_pinned_alloc, itx_pinned_free, itx_last_error,
+                              itx_samtext_parse_begin_bgzf, itx_samtext_bgzf_info, itx_samtext_text, itx_samtext_strings};
     aln_set_sam_device(rd, &d);
     return x;
 }
