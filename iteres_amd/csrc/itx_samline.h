@@ -1,7 +1,7 @@
 /* itx_samline.h — one line of SAM text turned into one record of the engine's arrays: the rule of `iteres stat|filter -S`
  * (bam_import.c:237-470 of samtools 0.1.18 as far as the record loop reads the result), stated once for the device
  * (csrc/itx_samtext.hip, over LDS and over global memory) and for the host build the tests hold against the host reader's own
- * parser, host/bamio.c sam_take_line (tests/samline_host.cpp). Valid C and C++.
+ * parser, host/samio.c sam_take_line (tests/samline_host.cpp). Valid C and C++.
  *
  * The function models only the PLAIN spelling of every field; whatever else the host parser accepts — through strtol's
  * prefixes, signs and blanks, the flag letters of samtools 0.1.x, a warning or an abort it prints — is called HARD and the

@@ -2,6 +2,7 @@
  * with the product's aln_reader into plain malloc'd staging arrays and prints one line per record:
  *   tid pos tmpend mapq flag5 mpos isize qname        (plus a header line per reference sequence)
  * usage: reader_dump <file> <is_sam 0|1> [batch=4096] */
+#include "reader_units.h"
 #include "../itx_host.h"
 
 #include <stdlib.h>

@@ -1,9 +1,10 @@
 /* share_dump.c — CPU-only check tool (tests/test_distributed_gloo.py): what every rank of a job of <world> ranks would take
- * of a list of BAM files — the product's own share planning (shares.c: plan_shares) and split points (bamio.c: find_split).
+ * of a list of BAM files — the product's own share planning (shares.c: plan_shares) and split points (bgzf.c: find_split).
  * One line per (rank, file):   rank file lo hi | lo_found lo_block lo_off | hi_found hi_block hi_off
  * (found: 1 a record start was found at/after the offset, 0 none up to the end of the file, -1 given up; lo = 0 and
  * hi = SIZE_MAX need no search: found = 2). A first line "shared 0|1" says whether the job can be shared at all.
  * usage: share_dump <world> <min_share_bytes> <file.bam>[,<file.bam>...] */
+#include "reader_units.h"
 #include "../itx_host.h"
 
 #include <stdlib.h>

@@ -1,6 +1,7 @@
 /* split_dump.c — CPU-only check tool (tests/test_host_reader.py): where would a share of this BAM begin for each of the
  * given compressed byte offsets? One line per offset: at found block off csize.
  * usage: split_dump <file.bam> <at> [<at> ...] */
+#include "reader_units.h"
 #include "../itx_host.h"
 
 #include <stdlib.h>

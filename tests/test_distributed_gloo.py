@@ -1,6 +1,6 @@
 """The N > 1 path on CPU (gloo, world size 2) with the PRODUCT's share arithmetic: the compressed bytes of the alignment
 files are cut into per-rank ranges by iteres_amd/host/shares.c (plan_shares) and turned into record boundaries by
-iteres_amd/host/bamio.c (find_split) — both reached through the CPU-only tool iteres_amd/host/test/share_dump.c. Every rank
+iteres_amd/host/bgzf.c (find_split) — both reached through the CPU-only tool iteres_amd/host/test/share_dump.c. Every rank
 decodes what lies between ITS two split points (an independent Python walk of the BGZF blocks), produces its partial with
 the oracle (no GPU in this container), ONE sum-all-reduce merges the partials (unsigned sums carried in signed tensors:
 mod 2^64 / 2^32 like the reference's counters and like ncclSum on the device, csrc/itx_comm.hip) and rank 0 compares
@@ -21,11 +21,11 @@ import torch.multiprocessing as mp
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-HOST = os.path.join(ROOT, "iteres_amd", "host")
 for p in (ROOT, HERE):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+import hosttool  # noqa: E402
 from iteres_amd import engine as eng, synth  # noqa: E402
 
 SIZE_MAX = (1 << 64) - 1
@@ -42,9 +42,7 @@ def _free_port():
 
 def build_share_dump(dst_dir):
     exe = os.path.join(dst_dir, "share_dump")
-    subprocess.check_call(["gcc", "-O2", "-g", "-fopenmp", "-std=gnu11", "-o", exe, os.path.join(HOST, "test", "share_dump.c"), os.path.join(HOST, "shares.c"),
-                           os.path.join(HOST, "bamio.c"), os.path.join(HOST, "tables.c"), "-lz", "-ldl"])
-    return exe
+    return hosttool.build(exe, "share_dump.c", extra=("shares.c",))
 
 
 @pytest.fixture(scope="module")

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import goldencase as gc
+import hosttool
 import refio
 from iteres_amd import build, engine as eng, synth
 from test_samline import HEADER, XA1, expect_aux, make_line, named_cases, pick_plain
@@ -21,7 +22,6 @@ from test_samline import HEADER, XA1, expect_aux, make_line, named_cases, pick_p
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "iteres_amd", "host")
 REF = os.path.join(ROOT, "oracle", "_ref", "iteres")
 NAMES = [b"chr1", b"chr2", b"chrX", b"chr2"]           # HEADER's @SQ lines: the second chr2 never wins a lookup
 TILE, WIN = 16384, 24576                                # bytes per tile of the line search; LDS bytes a wave stages its 64 lines in
@@ -31,9 +31,7 @@ MAX_CHUNK = 8 << 20
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("bin") / "reader_dump")
-    subprocess.check_call(["gcc", "-O2", "-g", "-fopenmp", "-std=gnu11", "-o", exe, os.path.join(HOST, "test", "reader_dump.c"),
-                           os.path.join(HOST, "bamio.c"), os.path.join(HOST, "tables.c"), "-lz", "-ldl"])
-    return exe
+    return hosttool.build(exe, "reader_dump.c")
 
 
 @pytest.fixture(scope="module")

@@ -8,19 +8,17 @@ import numpy as np
 import pytest
 
 import goldencase as gc
+import hosttool
 import refio
 from iteres_amd import engine as eng, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "iteres_amd", "host")
 
 
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("bin") / "reader_dump")
-    subprocess.check_call(["gcc", "-O2", "-g", "-fopenmp", "-std=gnu11", "-o", exe, os.path.join(HOST, "test", "reader_dump.c"),
-                           os.path.join(HOST, "bamio.c"), os.path.join(HOST, "tables.c"), "-lz", "-ldl"])
-    return exe
+    return hosttool.build(exe, "reader_dump.c")
 
 
 def run_dump(exe, path, is_sam, batch=4096, threads=4, chunk=None, piece=None):
@@ -135,13 +133,11 @@ def test_many_small_blocks_and_truncation(dump, tmp_path):
     assert pr.returncode == 1
 
 
-# ---- split points of the multi-GPU shares (bamio.c: find_split) --------------------------------------------------------
+# ---- split points of the multi-GPU shares (bgzf.c: find_split) ---------------------------------------------------------
 @pytest.fixture(scope="module")
 def split_dump(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("bin") / "split_dump")
-    subprocess.check_call(["gcc", "-O2", "-g", "-fopenmp", "-std=gnu11", "-o", exe, os.path.join(HOST, "test", "split_dump.c"),
-                           os.path.join(HOST, "bamio.c"), os.path.join(HOST, "tables.c"), "-lz", "-ldl"])
-    return exe
+    return hosttool.build(exe, "split_dump.c")
 
 
 def _record_starts(path):

@@ -1,4 +1,4 @@
-"""Host logic on CPU: -S input read through zlib (iteres_amd/host/bamio.c aln_open), as the reference reads it (gzopen,
+"""Host logic on CPU: -S input read through zlib (iteres_amd/host/samio.c sam_open), as the reference reads it (gzopen,
 cussamtools/bam_import.c:17,76,126). The host reader (iteres_amd/host/test/reader_dump) must print the same records, byte for byte,
 for a SAM text and for every compressed form of it: plain gzip, BGZF (a chain of gzip members), a mix of both, garbage behind the last
 member; and, for a file cut short, what a streaming inflater gets out of the bytes that are left."""
@@ -12,20 +12,18 @@ import numpy as np
 import pytest
 
 import goldencase as gc
+import hosttool
 import refio
 from iteres_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "iteres_amd", "host")
 REF = os.path.join(ROOT, "oracle", "_ref", "iteres")
 
 
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("bin") / "reader_dump")
-    subprocess.check_call(["gcc", "-O2", "-g", "-fopenmp", "-std=gnu11", "-o", exe, os.path.join(HOST, "test", "reader_dump.c"),
-                           os.path.join(HOST, "bamio.c"), os.path.join(HOST, "tables.c"), "-lz", "-ldl"])
-    return exe
+    return hosttool.build(exe, "reader_dump.c")
 
 
 def bgzf(text: bytes, payload: int, eof: bool = True, level: int = 6) -> bytes:

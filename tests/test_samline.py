@@ -1,5 +1,5 @@
 """The SAM line rule stated once (iteres_amd/csrc/itx_samline.h, built for the host by tests/samline_host.cpp) against the
-product's own SAM parser (iteres_amd/host/bamio.c through iteres_amd/host/test/reader_dump) on the same file: every line the
+product's own SAM parser (iteres_amd/host/samio.c through iteres_amd/host/test/reader_dump) on the same file: every line the
 rule does not call hard gives the same tid pos tmpend mapq flag5 mpos isize qname, every line written in a spelling only the
 host models is called hard, and the rule cannot pass by calling everything hard. Then the reader's two line iterators — getline,
 and lines taken out of chunks in memory — against each other."""
@@ -11,10 +11,10 @@ import numpy as np
 import pytest
 
 import goldencase as gc
+import hosttool
 import refio
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "iteres_amd", "host")
 HEADER = "@HD\tVN:1.0\n@SQ\tSN:chr1\tLN:1000000\n@SQ\tSN:chr2\tLN:500000\n@SQ\tSN:chrX\tLN:200000\n@SQ\tSN:chr2\tLN:7\n@PG\tID:x\n"
 
 
@@ -22,8 +22,7 @@ HEADER = "@HD\tVN:1.0\n@SQ\tSN:chr1\tLN:1000000\n@SQ\tSN:chr2\tLN:500000\n@SQ\tS
 def tools(tmp_path_factory):
     d = tmp_path_factory.mktemp("bin")
     dump, rule = str(d / "reader_dump"), str(d / "samline_host")
-    subprocess.check_call(["gcc", "-O2", "-g", "-fopenmp", "-std=gnu11", "-o", dump, os.path.join(HOST, "test", "reader_dump.c"),
-                           os.path.join(HOST, "bamio.c"), os.path.join(HOST, "tables.c"), "-lz", "-ldl"])
+    hosttool.build(dump, "reader_dump.c")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", rule, os.path.join(ROOT, "tests", "samline_host.cpp")])
     return dump, rule
 
@@ -120,7 +119,7 @@ def random_lines(n, seed):
 
 
 def expect_aux(line):
-    """(has_xa, nm, xa) as bamio.c reads a plain line's optional fields"""
+    """(has_xa, nm, xa) as samio.c reads a plain line's optional fields"""
     body = line.rstrip("\r\n")
     f = body.split("\t", 11)
     if len(f) < 12:
