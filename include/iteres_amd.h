@@ -459,6 +459,50 @@ int itx_names_append_host(itx_names *nm, const uint32_t *rows, const char *name_
 int itx_names_finish(itx_names *nm, size_t n_rows, itx_names_result *out);
 int itx_names_get_stats(const itx_names *nm, itx_names_stats *out);
 
+/* ---- the BAM of filter -b on the device (an extension: the reference writes no such file) -------------------------------------
+ * Every record that chose a row, block_size and bytes unchanged and in file order, becomes part of one stream of bytes in device
+ * memory; every ITX_BAMOUT_PAYLOAD bytes of it (csrc/itx_bgzfmember.h: 8192) are made one BGZF member there, and the members
+ * are handed out packed one behind the other (csrc/itx_bamout.hip). The header's members and the EOF marker are the caller's.
+ *   create      batch_capacity: the most records a batch may carry; stream_bytes: a first size for the stream's buffer
+ *               (at least four payloads are taken). Every buffer grows on demand.
+ *   hits/stream as for itx_names_*
+ *   itx_bamwin_bamout  records [first, first + n) of the inflater's last parsed window; `stream`: where d_hit_row was written.
+ *               Waits for the batch's totals, enqueues gather, members and pack, returns.
+ *   run         the same over plain DEVICE arrays: the records' bytes and rec_off[i] = where record i (its block_size field) starts
+ *   wait_kernels  returns when every gather is through: the window's bytes may then be overwritten by the decoder
+ *   append_host whole records (block_size field and bytes, one behind the other) the caller counted itself, in stream order
+ *               between the device batches; bytes that are not whole records: ITX_E_ARG, nothing appended
+ *   finish      once: what is left of the stream, less than one payload, becomes the last member (none when nothing is left)
+ *   collect     the members of the oldest batch (run, append_host or finish) not yet handed out: waits for that batch's kernels,
+ *               copies the packed members into one of two page-locked buffers of the object; `bytes` stays valid until the
+ *               next-but-one collect. len 0: that batch completed no payload, or nothing is pending. At most two batches may
+ *               wait to be collected: a third that completes a payload is refused with ITX_E_STATE, nothing appended.
+ *   pending     batches that wait to be collected
+ * A record of 1 GiB or more, or more than 2^31 members in a batch: ITX_E_LIMIT; no memory: ITX_E_NOMEM; both before anything
+ * is written, the object stays as it was. */
+typedef struct itx_bamout itx_bamout;
+typedef struct itx_bamout_members {
+    const void *bytes;
+    uint64_t len, room;                      /* packed bytes; the size of the buffer they lie in */
+    uint64_t n_members;
+} itx_bamout_members;
+typedef struct itx_bamout_stats {
+    uint64_t batches, host_batches, records, payload_bytes, members, out_bytes, grows, carry;   /* carry: stream bytes not yet in a member */
+    double gather_ms, member_ms, wait_ms;    /* device time: measure + gather; member + scan + pack. Host time spent waiting in these calls */
+} itx_bamout_stats;
+int itx_bamout_create(int device, size_t batch_capacity, size_t stream_bytes, itx_bamout **out);
+void itx_bamout_destroy(itx_bamout *bo);
+int32_t *itx_bamout_hits(itx_bamout *bo);
+void *itx_bamout_stream(itx_bamout *bo);
+int itx_bamwin_bamout(itx_inflater *h, itx_bamout *bo, size_t first, size_t n, const int32_t *d_hit_row, void *stream);
+int itx_bamout_run(itx_bamout *bo, const void *d_bytes, const uint32_t *d_rec_off, const int32_t *d_hit_row, size_t n, void *stream);
+int itx_bamout_wait_kernels(itx_bamout *bo);
+int itx_bamout_append_host(itx_bamout *bo, const void *bytes, size_t len);
+int itx_bamout_finish(itx_bamout *bo);
+int itx_bamout_collect(itx_bamout *bo, itx_bamout_members *out);
+int itx_bamout_pending(const itx_bamout *bo);
+int itx_bamout_get_stats(const itx_bamout *bo, itx_bamout_stats *out);
+
 /* ---- the .loci file of filter / cpgfilter on the device ----------------------------------------------------------------------
  * Replaces the row walk and the fprintf of writeFilterOut (generic.c:1709-1746) and writeFilterOutMRE (generic.c:1748-1772): the
  * order of the lines is a function of the table alone — hashRmsk's chromosomes in hash order, a chromosome's rows by bin

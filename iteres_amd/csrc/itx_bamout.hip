@@ -1,0 +1,588 @@
+// itx_bamout.hip — the BAM of `iteres filter -b` (an extension: the reference has no such output) built where the records lie:
+// every record of a batch that chose a table row goes, block_size and bytes unchanged and in file order, into one stream of
+// payload bytes in HBM; every ITX_BAMOUT_PAYLOAD bytes of that stream become one BGZF member (itx_bgzfmember.h), and only the
+// members, compressed and packed, cross the link back. The header's members and the EOF marker are the host's (bamout.c).
+//
+// per batch (records in device memory, the chosen rows in d_hit_row):
+//   k_bo_measure   one lane per record: 4 + block_size for a record with hit_row >= 0, else 0. A tile of BO_TILE records adds up
+//                  its bytes (64 bit) and its records.
+//   k_tile_scan2   (itx_textpack.h) exclusive sums over the tiles, one workgroup; the totals are all the host waits for: they
+//                  say how many whole payloads the stream now holds, and every buffer is sized before anything is written.
+//   k_bo_gather    one workgroup per tile: the tile's records are ONE contiguous range of the stream, behind what the call before
+//                  left over; staged in LDS a window at a time and stored with 16-byte vectors (itx_textpack.h says why and how).
+//   k_bo_member    one wave per whole payload: the payload into LDS, itx_bgzf_member into the member's slot (a fixed stride)
+//   k_bo_scan      exclusive sums of the member sizes, one workgroup     } written as k_bw_scan / k_bw_gather of itx_bigwig.hip
+//   k_bo_pack      the members one behind the other                       }
+//   then the stream's rest, less than one payload, moves to its front (device to device), and the packed total to the host.
+// itx_bamout_collect hands a batch's members out: it waits for that batch's kernels only (the next batch's are queued behind them
+// and go on), copies the packed bytes on the copy stream into one of two page-locked buffers, and the host writes them to the file
+// while the next batch's kernels run — the bed route's arrangement.
+// What the host route counted joins the same stream in stream order (itx_bamout_append_host), so the file is one ordered stream
+// whatever route a window took. itx_bamout_finish makes the last, short payload a member.
+//
+// Byte and integer work. k_bo_member is bound by the encoder's serial parse (one lane per member); ITX_BAMOUT_PAYLOAD is chosen
+// for that (itx_bgzfmember.h). No kernel uses scratch (DESIGN.md has the figures).
+#include "itx_textpack.h"
+
+#include <stdlib.h>
+#include <string.h>
+
+#define ITXD_FN __device__ static inline
+#define ITXD_SYNC() __syncthreads()
+#define ITXD_AMAX(p, v) atomicMax((p), (v))
+#define ITXD_CTZ(x) ((uint32_t)__builtin_ctz(x))
+#include "itx_bgzfmember.h"
+
+typedef unsigned long long ull;
+
+#define BO_TILE 256u                 // records per workgroup (measure, gather)
+#define BO_LDS 32768u                // bytes staged at a time: a tile of short reads (256 x ~120 bytes) in one window
+#define BO_P ITX_BAMOUT_PAYLOAD
+#define BO_STRIDE ITX_BGZF_MEMBER_CAP(BO_P)      // bytes between two members' slots (a multiple of 4)
+#define BO_MAX_RECORD 0x40000000u    // a record of a gibibyte is nobody's: the decoder's windows hold less
+
+static_assert(BO_P % 16u == 0 && BO_P <= ITXD_MAX_IN, "the payload: at most one DEFLATE window, whole 16-byte vectors");
+
+__global__ __launch_bounds__(BO_TILE) void k_bo_measure(const uint8_t *__restrict__ u, const uint32_t *__restrict__ rec_off, const int32_t *__restrict__ hit_row,
+                                                         uint32_t n, uint32_t *__restrict__ len_out, ull *__restrict__ tile_sum, ull *__restrict__ tot)
+{
+    __shared__ ull s_sum[2];
+    if (threadIdx.x < 2) s_sum[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * BO_TILE + threadIdx.x;
+    bool bad = false;
+    if (i < n) {
+        uint32_t len = 0;
+        if (hit_row[i] >= 0) {
+            const uint8_t *p = u + rec_off[i];
+            const uint32_t bs = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+            bad = bs >= BO_MAX_RECORD;
+            if (!bad) {
+                len = 4u + bs;
+                atomicAdd(&s_sum[0], (ull)len);
+                atomicAdd(&s_sum[1], 1ull);
+            }
+        }
+        len_out[i] = len;
+    }
+    const ull badm = __ballot(bad);
+    if ((threadIdx.x & 63u) == 0 && badm) atomicAdd(&tot[2], (ull)__popcll(badm));
+    __syncthreads();
+    if (threadIdx.x < 2) tile_sum[2u * blockIdx.x + threadIdx.x] = s_sum[threadIdx.x];
+}
+
+__global__ __launch_bounds__(BO_TILE) void k_bo_gather(const uint8_t *__restrict__ u, const uint32_t *__restrict__ rec_off, uint32_t n,
+                                                        const uint32_t *__restrict__ len_in, const ull *__restrict__ tile_base, ull base, uint8_t *__restrict__ pay)
+{
+    __shared__ uint4 s_buf[BO_LDS / 16u];
+    __shared__ uint32_t s_w[BO_TILE / 64u];
+    const uint32_t i = blockIdx.x * BO_TILE + threadIdx.x;
+    const uint32_t len = i < n ? len_in[i] : 0u;
+    uint32_t total = 0;
+    const uint32_t moff = itx_tile_offsets<BO_TILE>(len, s_w, &total);
+    const ull tb = base + tile_base[2u * blockIdx.x], te = tb + total;
+    const ull mb = tb + moff, me = mb + len;
+    const uint8_t *src = len ? u + rec_off[i] : u;
+    itx_pack_tile<BO_TILE, BO_LDS>(s_buf, pay, tb, te, mb, me, [=](uint8_t *dst, uint32_t from, uint32_t to) {
+        // a record starts wherever the one before it ended: kept a byte loop (names' gather says why)
+#pragma clang loop vectorize(disable)
+        for (uint32_t k = from; k < to; k++) dst[k - from] = src[k];
+    });
+}
+
+// LDS of one member's encoder (itxd_ws), for payloads of up to BO_P bytes
+struct BoLds {
+    uint32_t in[BO_P / 4 + 4];
+    uint32_t head[1u << ITXD_HBITS];
+    uint16_t md[BO_P];
+    uint8_t ml[BO_P];
+    uint32_t fq[ITXD_NSYM], key[ITXD_NSYM];
+    uint16_t srt[ITXD_NSYM], code[ITXD_NSYM];
+    uint8_t len[ITXD_NSYM];
+    uint32_t clfq[20];
+    uint16_t clcode[20];
+    uint8_t cllen[20];
+    uint64_t red[128];
+    uint32_t misc[16];
+};
+
+// one wave per member: payload m is pay[m * BO_P, min((m + 1) * BO_P, total)); pay is 16-byte aligned and BO_P a multiple of 16
+__global__ __launch_bounds__(64) void k_bo_member(const uint8_t *__restrict__ pay, ull total, uint8_t *__restrict__ mem, uint32_t *__restrict__ msize)
+{
+    __shared__ BoLds s;
+    const ull at = (ull)blockIdx.x * BO_P;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t n = total - at < BO_P ? (uint32_t)(total - at) : BO_P;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(pay + at);
+    for (uint32_t i = lane; i < BO_P / 4 + 4; i += 64) {
+        uint32_t v = 0;
+        if (4u * i + 4u <= n) {
+            v = src[i];
+        } else {
+            for (uint32_t k = 0; k < 4u && 4u * i + k < n; k++) v |= (uint32_t)pay[at + 4u * i + k] << (8u * k);      // (the last payload's ragged word)
+        }
+        s.in[i] = v;
+    }
+    __syncthreads();
+    const itxd_ws w = {s.in, s.head, s.ml, s.md, s.fq, s.key, s.srt, s.len, s.code, s.clfq, s.cllen, s.clcode, s.red, s.misc};
+    const uint32_t z = itx_bgzf_member(w, n, mem + (ull)blockIdx.x * BO_STRIDE, lane, 64);
+    if (lane == 0) msize[blockIdx.x] = z;
+}
+
+// exclusive prefix sum of the member sizes: moff[0 .. n] (one workgroup, itx_device.h)
+__global__ __launch_bounds__(ITX_SCAN_WG) void k_bo_scan(const uint32_t *__restrict__ msize, uint64_t n, uint64_t *__restrict__ moff)
+{
+    __shared__ uint64_t s[ITX_SCAN_WG];
+    uint64_t lo, hi;
+    itx_scan_chunk(n, &lo, &hi);
+    uint64_t a = 0, total;
+    for (uint64_t i = lo; i < hi; i++) a += msize[i];
+    uint64_t e = itx_scan_wg(a, s, &total);
+    for (uint64_t i = lo; i < hi; i++) {
+        moff[i] = e;
+        e += msize[i];
+    }
+    if (threadIdx.x == 0) moff[n] = total;
+}
+
+__global__ __launch_bounds__(256) void k_bo_pack(const uint8_t *__restrict__ mem, const uint32_t *__restrict__ msize, const uint64_t *__restrict__ moff,
+                                                 uint8_t *__restrict__ packed)
+{
+    const uint64_t b = blockIdx.x;
+    const uint8_t *src = mem + b * BO_STRIDE;
+    uint8_t *dst = packed + moff[b];
+    const uint32_t z = msize[b] < BO_STRIDE ? msize[b] : BO_STRIDE;
+    for (uint32_t i = threadIdx.x; i < z; i += 256) dst[i] = src[i];
+}
+
+// ---- host side
+struct bo_slot {                     // one batch's members on their way out
+    uint8_t *d_packed, *h_pin;
+    size_t cap;                      // bytes of both
+    ull *h_total;                    // page-locked: the packed size
+    hipEvent_t e0, e1;               // around member + scan + pack; e1 is the batch's "done"
+    uint32_t n_mem;
+    int busy;
+};
+
+struct itx_bamout {
+    int device;
+    size_t cap;                      // records per batch
+    hipStream_t st, cst;             // kernels; the copies to the host
+    hipEvent_t ev[5];                // measure: 0 .. 1, gather: 2 .. 3 (3: the batch's records are read); 4: the caller's stream
+    int gather_timed;
+    int32_t *d_hits;
+    uint32_t *d_len;
+    ull *d_tile_sum, *d_tile_base, *d_tot, *h_tot;
+    uint8_t *d_pay;                  // the payload stream: carry bytes, then the batch's
+    size_t pay_cap, carry;
+    uint8_t *d_mem;                  // member slots of BO_STRIDE bytes
+    uint32_t *d_msize;
+    uint64_t *d_moff;
+    size_t mem_cap;                  // members
+    bo_slot slot[2];
+    int head, pending;               // the oldest batch not yet collected; batches not yet collected
+    int finished;
+    itx_bamout_stats stats;
+};
+
+static int bo_hip(hipError_t e, const char *what, int line)
+{
+    if (e == hipSuccess) return ITX_OK;
+    itx_set_error("%s failed: %s (%s:%d)", what, hipGetErrorString(e), __FILE__, line);
+    return ITX_E_NO_DEVICE;
+}
+#define BO_TRY(call)                                       \
+    do {                                                   \
+        if ((rc = bo_hip((call), #call, __LINE__)) != 0) goto out; \
+    } while (0)
+
+extern "C" void itx_bamout_destroy(itx_bamout *bo)
+{
+    if (!bo) return;
+    (void)hipSetDevice(bo->device);
+    if (bo->st) (void)hipStreamSynchronize(bo->st);
+    if (bo->cst) (void)hipStreamSynchronize(bo->cst);
+    for (auto &e : bo->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &s : bo->slot) {
+        if (s.e0) (void)hipEventDestroy(s.e0);
+        if (s.e1) (void)hipEventDestroy(s.e1);
+        (void)hipFree(s.d_packed);
+        if (s.h_pin) (void)hipHostFree(s.h_pin);
+        if (s.h_total) (void)hipHostFree(s.h_total);
+    }
+    if (bo->st) (void)hipStreamDestroy(bo->st);
+    if (bo->cst) (void)hipStreamDestroy(bo->cst);
+    (void)hipFree(bo->d_hits);
+    (void)hipFree(bo->d_len);
+    (void)hipFree(bo->d_tile_sum);
+    (void)hipFree(bo->d_tile_base);
+    (void)hipFree(bo->d_tot);
+    (void)hipFree(bo->d_pay);
+    (void)hipFree(bo->d_mem);
+    (void)hipFree(bo->d_msize);
+    (void)hipFree(bo->d_moff);
+    if (bo->h_tot) (void)hipHostFree(bo->h_tot);
+    delete bo;
+}
+
+extern "C" int itx_bamout_create(int device, size_t batch_capacity, size_t stream_bytes, itx_bamout **out)
+{
+    if (!out || batch_capacity == 0 || batch_capacity > 0xffffff00u) {
+        itx_set_error("itx_bamout_create: bad argument");
+        return ITX_E_ARG;
+    }
+    *out = nullptr;
+    int rc = ITX_OK;
+    itx_bamout *bo = new itx_bamout();
+    bo->device = device;
+    bo->cap = batch_capacity;
+    const size_t n = batch_capacity + 64, nt = (batch_capacity + BO_TILE - 1) / BO_TILE + 1;
+    if (stream_bytes < 4 * (size_t)BO_P) stream_bytes = 4 * (size_t)BO_P;
+    bo->pay_cap = stream_bytes;
+    BO_TRY(hipSetDevice(device));
+    if (hipMalloc((void **)&bo->d_hits, 4 * n) != hipSuccess || hipMalloc((void **)&bo->d_len, 4 * n) != hipSuccess ||
+        hipMalloc((void **)&bo->d_tile_sum, 16 * nt) != hipSuccess || hipMalloc((void **)&bo->d_tile_base, 16 * nt) != hipSuccess ||
+        hipMalloc((void **)&bo->d_tot, 32) != hipSuccess || hipMalloc((void **)&bo->d_pay, bo->pay_cap + 16) != hipSuccess) {
+        (void)hipGetLastError();
+        itx_set_error("itx_bamout_create: no device memory for batches of %zu records and a stream of %zu bytes", batch_capacity, stream_bytes);
+        rc = ITX_E_NOMEM;
+        goto out;
+    }
+    BO_TRY(hipHostMalloc((void **)&bo->h_tot, 32, hipHostMallocDefault));
+    BO_TRY(hipStreamCreateWithFlags(&bo->st, hipStreamNonBlocking));
+    BO_TRY(hipStreamCreateWithFlags(&bo->cst, hipStreamNonBlocking));
+    for (auto &e : bo->ev) BO_TRY(hipEventCreate(&e));
+    for (auto &s : bo->slot) {
+        BO_TRY(hipEventCreate(&s.e0));
+        BO_TRY(hipEventCreate(&s.e1));
+        BO_TRY(hipHostMalloc((void **)&s.h_total, 16, hipHostMallocDefault));
+    }
+out:
+    if (rc != ITX_OK) {
+        itx_bamout_destroy(bo);
+        return rc;
+    }
+    *out = bo;
+    return ITX_OK;
+}
+
+extern "C" int32_t *itx_bamout_hits(itx_bamout *bo) { return bo ? bo->d_hits : nullptr; }
+extern "C" void *itx_bamout_stream(itx_bamout *bo) { return bo ? (void *)bo->st : nullptr; }
+
+static void bo_read_gather_time(itx_bamout *bo)
+{
+    if (!bo->gather_timed) return;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, bo->ev[2], bo->ev[3]) == hipSuccess) bo->stats.gather_ms += (double)ms;
+    bo->gather_timed = 0;
+}
+
+// Room for a stream of `total` bytes and for the n_mem members made of it next; bo->st is idle when this is called. Every limit is
+// checked and every buffer allocated here, before anything is written: what does not fit leaves the object as it was.
+static int bo_reserve(itx_bamout *bo, ull total, ull n_mem)
+{
+    int rc = ITX_OK;
+    bo_slot *s = &bo->slot[(bo->head + bo->pending) & 1];
+    uint8_t *npay = nullptr, *nmem = nullptr, *npk = nullptr, *npin = nullptr;
+    uint32_t *nms = nullptr;
+    uint64_t *nmo = nullptr;
+    size_t want_pay = 0, want_mem = 0, want_pk = 0;
+    if (n_mem > 0x7fffff00ull) {
+        itx_set_error("itx_bamout: %llu members in one batch", n_mem);
+        return ITX_E_LIMIT;
+    }
+    if (n_mem && bo->pending == 2) {
+        itx_set_error("itx_bamout: two batches wait to be collected (itx_bamout_collect)");
+        return ITX_E_STATE;
+    }
+    if (total > bo->pay_cap) want_pay = (size_t)(total + (total > 2 * (ull)bo->pay_cap ? total / 4 : total));
+    if (n_mem > bo->mem_cap) want_mem = (size_t)(n_mem + n_mem / 4 + 16);
+    if (n_mem && n_mem * BO_STRIDE > s->cap) want_pk = (size_t)((n_mem + n_mem / 4 + 16) * BO_STRIDE);
+    if ((want_pay && hipMalloc((void **)&npay, want_pay + 16) != hipSuccess) ||
+        (want_mem && (hipMalloc((void **)&nmem, want_mem * BO_STRIDE) != hipSuccess || hipMalloc((void **)&nms, 4 * want_mem) != hipSuccess ||
+                      hipMalloc((void **)&nmo, 8 * (want_mem + 1)) != hipSuccess)) ||
+        (want_pk && (hipMalloc((void **)&npk, want_pk) != hipSuccess || hipHostMalloc((void **)&npin, want_pk, hipHostMallocDefault) != hipSuccess))) {
+        (void)hipGetLastError();
+        itx_set_error("itx_bamout: no memory for a stream of %llu bytes in %llu members", total, n_mem);
+        rc = ITX_E_NOMEM;
+        goto out;
+    }
+    if (npay && bo->carry) {
+        BO_TRY(hipMemcpyAsync(npay, bo->d_pay, bo->carry, hipMemcpyDeviceToDevice, bo->st));
+        BO_TRY(hipStreamSynchronize(bo->st));                              // before the old buffer goes
+    }
+    if (npay) {
+        uint8_t *old = bo->d_pay;
+        bo->d_pay = npay;
+        bo->pay_cap = want_pay;
+        npay = old;
+        bo->stats.grows++;
+    }
+    if (nmem) {
+        uint8_t *o1 = bo->d_mem;
+        uint32_t *o2 = bo->d_msize;
+        uint64_t *o3 = bo->d_moff;
+        bo->d_mem = nmem;
+        bo->d_msize = nms;
+        bo->d_moff = nmo;
+        bo->mem_cap = want_mem;
+        nmem = o1;
+        nms = o2;
+        nmo = o3;
+    }
+    if (npk) {                                                             // (the slot is not busy: nothing reads its buffers)
+        uint8_t *o1 = s->d_packed, *o2 = s->h_pin;
+        s->d_packed = npk;
+        s->h_pin = npin;
+        s->cap = want_pk;
+        npk = o1;
+        npin = o2;
+    }
+out:
+    (void)hipFree(npay);                                                   // the old buffers, or the new ones that were not taken
+    (void)hipFree(nmem);
+    (void)hipFree(nms);
+    (void)hipFree(nmo);
+    (void)hipFree(npk);
+    if (npin) (void)hipHostFree(npin);
+    return rc;
+}
+
+// d_pay holds `total` bytes: its whole payloads (with_tail: and the short rest) become members in the next slot, the rest moves
+// to the front. bo_reserve(total, that many members) has succeeded.
+static int bo_emit(itx_bamout *bo, ull total, int with_tail)
+{
+    int rc = ITX_OK;
+    const ull n_full = total / BO_P, rest = total - n_full * BO_P;
+    const uint32_t n_mem = (uint32_t)(n_full + (with_tail && rest ? 1 : 0));
+    if (n_mem) {
+        bo_slot *s = &bo->slot[(bo->head + bo->pending) & 1];
+        BO_TRY(hipEventRecord(s->e0, bo->st));
+        hipLaunchKernelGGL(k_bo_member, dim3(n_mem), dim3(64), 0, bo->st, bo->d_pay, with_tail ? total : n_full * BO_P, bo->d_mem, bo->d_msize);
+        BO_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_bo_scan, dim3(1), dim3(ITX_SCAN_WG), 0, bo->st, bo->d_msize, (uint64_t)n_mem, bo->d_moff);
+        BO_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_bo_pack, dim3(n_mem), dim3(256), 0, bo->st, bo->d_mem, bo->d_msize, bo->d_moff, s->d_packed);
+        BO_TRY(hipGetLastError());
+        BO_TRY(hipMemcpyAsync(s->h_total, bo->d_moff + n_mem, 8, hipMemcpyDeviceToHost, bo->st));
+        BO_TRY(hipEventRecord(s->e1, bo->st));
+        s->n_mem = n_mem;
+        s->busy = 1;
+        bo->pending++;
+        bo->stats.members += n_mem;
+    }
+    if (with_tail) {
+        bo->carry = 0;
+    } else {
+        if (n_full && rest) BO_TRY(hipMemcpyAsync(bo->d_pay, bo->d_pay + n_full * BO_P, (size_t)rest, hipMemcpyDeviceToDevice, bo->st));   // (rest < BO_P: no overlap)
+        bo->carry = (size_t)rest;
+    }
+out:
+    return rc;
+}
+
+// measure + scan (waited for: the totals size every buffer), then gather, members and pack are enqueued
+int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, const int32_t *d_hit_row, size_t n, void *stream)
+{
+    if (!bo || (n && (!u || !rec_off || !d_hit_row))) {
+        itx_set_error("itx_bamout: bad argument");
+        return ITX_E_ARG;
+    }
+    if (n > bo->cap) {
+        itx_set_error("itx_bamout: batch exceeds the capacity");
+        return ITX_E_ARG;
+    }
+    if (bo->finished) {
+        itx_set_error("itx_bamout: the stream is finished");
+        return ITX_E_STATE;
+    }
+    if (!n) return ITX_OK;
+    int rc = ITX_OK;
+    float ms = 0;
+    ull total = 0;
+    const uint32_t nt = (uint32_t)((n + BO_TILE - 1) / BO_TILE);
+    BO_TRY(hipSetDevice(bo->device));
+    if ((hipStream_t)stream != bo->st) {                                   // the chosen rows were left on another stream
+        BO_TRY(hipEventRecord(bo->ev[4], (hipStream_t)stream));
+        BO_TRY(hipStreamWaitEvent(bo->st, bo->ev[4], 0));
+    }
+    BO_TRY(hipEventRecord(bo->ev[0], bo->st));
+    BO_TRY(hipMemsetAsync(bo->d_tot, 0, 32, bo->st));
+    hipLaunchKernelGGL(k_bo_measure, dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, d_hit_row, (uint32_t)n, bo->d_len, bo->d_tile_sum, bo->d_tot);
+    BO_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, bo->st, bo->d_tile_sum, nt, bo->d_tile_base, bo->d_tot);
+    BO_TRY(hipGetLastError());
+    BO_TRY(hipEventRecord(bo->ev[1], bo->st));
+    BO_TRY(hipMemcpyAsync(bo->h_tot, bo->d_tot, 32, hipMemcpyDeviceToHost, bo->st));
+    {
+        const double t0 = itx_wall_now();
+        BO_TRY(hipStreamSynchronize(bo->st));
+        bo->stats.wait_ms += 1e3 * (itx_wall_now() - t0);
+    }
+    bo_read_gather_time(bo);                                               // (the batch before this one)
+    BO_TRY(hipEventElapsedTime(&ms, bo->ev[0], bo->ev[1]));
+    bo->stats.gather_ms += (double)ms;
+    if (bo->h_tot[2]) {
+        itx_set_error("itx_bamout: %llu records of a gibibyte or more", bo->h_tot[2]);
+        rc = ITX_E_LIMIT;
+        goto out;
+    }
+    total = (ull)bo->carry + bo->h_tot[0];
+    if ((rc = bo_reserve(bo, total, total / BO_P)) != ITX_OK) goto out;
+    BO_TRY(hipEventRecord(bo->ev[2], bo->st));
+    if (bo->h_tot[0]) {
+        hipLaunchKernelGGL(k_bo_gather, dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, (uint32_t)n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->d_pay);
+        BO_TRY(hipGetLastError());
+    }
+    BO_TRY(hipEventRecord(bo->ev[3], bo->st));
+    bo->gather_timed = 1;
+    bo->stats.batches++;
+    bo->stats.records += bo->h_tot[1];
+    bo->stats.payload_bytes += bo->h_tot[0];
+    rc = bo_emit(bo, total, 0);
+out:
+    return rc;
+}
+
+extern "C" int itx_bamout_run(itx_bamout *bo, const void *d_bytes, const uint32_t *d_rec_off, const int32_t *d_hit_row, size_t n, void *stream)
+{
+    return itx_bamout_start(bo, (const uint8_t *)d_bytes, d_rec_off, d_hit_row, n, stream);
+}
+
+// the batch's records have been read (its members may still be in the making): the window's arrays are the decoder's again
+extern "C" int itx_bamout_wait_kernels(itx_bamout *bo)
+{
+    if (!bo) {
+        itx_set_error("itx_bamout_wait_kernels: bad argument");
+        return ITX_E_ARG;
+    }
+    int rc = ITX_OK;
+    BO_TRY(hipSetDevice(bo->device));
+    if (bo->gather_timed) {
+        const double t0 = itx_wall_now();
+        BO_TRY(hipEventSynchronize(bo->ev[3]));
+        bo->stats.wait_ms += 1e3 * (itx_wall_now() - t0);
+        bo_read_gather_time(bo);
+    }
+out:
+    return rc;
+}
+
+extern "C" int itx_bamout_append_host(itx_bamout *bo, const void *bytes, size_t len)
+{
+    if (!bo || (len && !bytes)) {
+        itx_set_error("itx_bamout_append_host: bad argument");
+        return ITX_E_ARG;
+    }
+    if (bo->finished) {
+        itx_set_error("itx_bamout_append_host: the stream is finished");
+        return ITX_E_STATE;
+    }
+    size_t at = 0, n_rec = 0;
+    while (at < len) {                                                     // whole records, or nothing is appended
+        uint32_t bs = 0;
+        if (len - at >= 4) memcpy(&bs, (const uint8_t *)bytes + at, 4);
+        if (len - at < 4 || bs >= BO_MAX_RECORD || (size_t)bs > len - at - 4) {
+            itx_set_error("itx_bamout_append_host: the bytes are not whole records (record %zu at byte %zu of %zu)", n_rec, at, len);
+            return ITX_E_ARG;
+        }
+        at += 4 + (size_t)bs;
+        n_rec++;
+    }
+    if (!len) return ITX_OK;
+    int rc = ITX_OK;
+    const ull total = (ull)bo->carry + len;
+    BO_TRY(hipSetDevice(bo->device));
+    {
+        const double t0 = itx_wall_now();
+        BO_TRY(hipStreamSynchronize(bo->st));                              // device batches before this one have their place
+        bo->stats.wait_ms += 1e3 * (itx_wall_now() - t0);
+    }
+    bo_read_gather_time(bo);
+    if ((rc = bo_reserve(bo, total, total / BO_P)) != ITX_OK) goto out;
+    BO_TRY(hipMemcpyAsync(bo->d_pay + bo->carry, bytes, len, hipMemcpyHostToDevice, bo->st));
+    BO_TRY(hipStreamSynchronize(bo->st));                                  // the caller's bytes are its own again
+    bo->stats.host_batches++;
+    bo->stats.records += n_rec;
+    bo->stats.payload_bytes += len;
+    rc = bo_emit(bo, total, 0);
+out:
+    return rc;
+}
+
+extern "C" int itx_bamout_finish(itx_bamout *bo)
+{
+    if (!bo) {
+        itx_set_error("itx_bamout_finish: bad argument");
+        return ITX_E_ARG;
+    }
+    if (bo->finished) {
+        itx_set_error("itx_bamout_finish: called twice");
+        return ITX_E_STATE;
+    }
+    int rc = ITX_OK;
+    BO_TRY(hipSetDevice(bo->device));
+    BO_TRY(hipStreamSynchronize(bo->st));
+    bo_read_gather_time(bo);
+    if (bo->carry) {
+        if ((rc = bo_reserve(bo, bo->carry, 1)) != ITX_OK) goto out;
+        if ((rc = bo_emit(bo, bo->carry, 1)) != ITX_OK) goto out;
+    }
+    bo->finished = 1;
+out:
+    return rc;
+}
+
+extern "C" int itx_bamout_collect(itx_bamout *bo, itx_bamout_members *out)
+{
+    if (!bo || !out) {
+        itx_set_error("itx_bamout_collect: bad argument");
+        return ITX_E_ARG;
+    }
+    memset(out, 0, sizeof *out);
+    if (!bo->pending) return ITX_OK;
+    int rc = ITX_OK;
+    float ms = 0;
+    bo_slot *s = &bo->slot[bo->head];
+    BO_TRY(hipSetDevice(bo->device));
+    {
+        const double t0 = itx_wall_now();
+        BO_TRY(hipEventSynchronize(s->e1));
+        bo->stats.wait_ms += 1e3 * (itx_wall_now() - t0);
+    }
+    if (hipEventElapsedTime(&ms, s->e0, s->e1) == hipSuccess) bo->stats.member_ms += (double)ms;
+    if (*s->h_total > s->cap) {
+        itx_set_error("itx_bamout_collect: %llu packed bytes in a buffer of %zu", *s->h_total, s->cap);
+        rc = ITX_E_LIMIT;
+        goto out;
+    }
+    if (*s->h_total) {
+        BO_TRY(hipMemcpyAsync(s->h_pin, s->d_packed, (size_t)*s->h_total, hipMemcpyDeviceToHost, bo->cst));
+        BO_TRY(hipStreamSynchronize(bo->cst));
+    }
+    out->bytes = s->h_pin;
+    out->len = *s->h_total;
+    out->room = s->cap;
+    out->n_members = s->n_mem;
+    bo->stats.out_bytes += *s->h_total;
+    s->busy = 0;
+    bo->head ^= 1;
+    bo->pending--;
+out:
+    return rc;
+}
+
+extern "C" int itx_bamout_pending(const itx_bamout *bo) { return bo ? bo->pending : 0; }
+
+extern "C" int itx_bamout_get_stats(const itx_bamout *bo, itx_bamout_stats *out)
+{
+    if (!bo || !out) {
+        itx_set_error("itx_bamout_get_stats: bad argument");
+        return ITX_E_ARG;
+    }
+    *out = bo->stats;
+    out->carry = bo->carry;
+    return ITX_OK;
+}

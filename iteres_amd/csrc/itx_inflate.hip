@@ -1427,6 +1427,16 @@ extern "C" int itx_bamwin_names(itx_inflater *h, itx_names *nm, size_t first, si
     return itx_names_start(nm, h->win[w].buf, h->d_recoff + first, d_hit_row, n, stream, n_hard);
 }
 
+int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, const int32_t *d_hit_row, size_t n, void *stream);   // itx_bamout.hip
+
+/* records [first, first + n) of the last parsed window that chose a row, appended to the BAM of filter -b (csrc/itx_bamout.hip) */
+extern "C" int itx_bamwin_bamout(itx_inflater *h, itx_bamout *bo, size_t first, size_t n, const int32_t *d_hit_row, void *stream)
+{
+    if (!h || !bo || first + n > h->n_rec) return ITX_E_ARG;
+    const int w = h->parsed_w;
+    return itx_bamout_start(bo, h->win[w].buf, h->d_recoff + first, d_hit_row, n, stream);
+}
+
 extern "C" int itx_bamwin_device_batch(itx_inflater *h, size_t first, int with_mates, itx_batch *out)
 {
     if (!h || !out || first > h->n_rec || (first & 15u)) return ITX_E_ARG;

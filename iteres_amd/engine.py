@@ -33,6 +33,8 @@ EXPORTS = [
     "itx_bed_create", "itx_bed_destroy", "itx_bed_set_tidmap", "itx_bamwin_bed", "itx_bed_run", "itx_bed_wait_kernels", "itx_bed_collect", "itx_bed_get_stats",
     "itx_names_create", "itx_names_destroy", "itx_names_hits", "itx_names_stream", "itx_bamwin_names", "itx_names_run", "itx_names_wait_kernels", "itx_names_append_host",
     "itx_names_finish", "itx_names_get_stats",
+    "itx_bamout_create", "itx_bamout_destroy", "itx_bamout_hits", "itx_bamout_stream", "itx_bamwin_bamout", "itx_bamout_run", "itx_bamout_wait_kernels",
+    "itx_bamout_append_host", "itx_bamout_finish", "itx_bamout_collect", "itx_bamout_pending", "itx_bamout_get_stats",
     "itx_loci_create", "itx_loci_destroy", "itx_loci_order", "itx_loci_filter_text", "itx_loci_cpg_text",
     "itx_samtext_create", "itx_samtext_destroy", "itx_samtext_parse_begin", "itx_samtext_parse_end", "itx_samtext_fetch",
     "itx_samtext_parse_begin_bgzf", "itx_samtext_bgzf_info", "itx_samtext_text", "itx_samtext_strings",
@@ -114,6 +116,16 @@ class NamesResult(C.Structure):
 class NamesStats(C.Structure):
     _fields_ = [("batches", C.c_uint64), ("hard_batches", C.c_uint64), ("host_batches", C.c_uint64), ("entries", C.c_uint64), ("bytes", C.c_uint64),
                 ("grows", C.c_uint64), ("gather_ms", C.c_double), ("finish_ms", C.c_double)]
+
+
+class BamoutMembers(C.Structure):
+    _fields_ = [("bytes", C.c_void_p), ("len", C.c_uint64), ("room", C.c_uint64), ("n_members", C.c_uint64)]
+
+
+class BamoutStats(C.Structure):
+    _fields_ = [("batches", C.c_uint64), ("host_batches", C.c_uint64), ("records", C.c_uint64), ("payload_bytes", C.c_uint64), ("members", C.c_uint64),
+                ("out_bytes", C.c_uint64), ("grows", C.c_uint64), ("carry", C.c_uint64), ("gather_ms", C.c_double), ("member_ms", C.c_double),
+                ("wait_ms", C.c_double)]
 
 
 class LociText(C.Structure):
@@ -231,6 +243,21 @@ def load():
     L.itx_names_append_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.itx_names_finish.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(NamesResult)]
     L.itx_names_get_stats.argtypes = [C.c_void_p, C.POINTER(NamesStats)]
+    L.itx_bamout_create.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]
+    L.itx_bamout_destroy.argtypes = [C.c_void_p]
+    L.itx_bamout_destroy.restype = None
+    L.itx_bamout_hits.argtypes = [C.c_void_p]
+    L.itx_bamout_hits.restype = C.c_void_p
+    L.itx_bamout_stream.argtypes = [C.c_void_p]
+    L.itx_bamout_stream.restype = C.c_void_p
+    L.itx_bamwin_bamout.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.itx_bamout_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.itx_bamout_wait_kernels.argtypes = [C.c_void_p]
+    L.itx_bamout_append_host.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.itx_bamout_finish.argtypes = [C.c_void_p]
+    L.itx_bamout_collect.argtypes = [C.c_void_p, C.POINTER(BamoutMembers)]
+    L.itx_bamout_pending.argtypes = [C.c_void_p]
+    L.itx_bamout_get_stats.argtypes = [C.c_void_p, C.POINTER(BamoutStats)]
     L.itx_loci_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                   C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
     L.itx_loci_destroy.argtypes = [C.c_void_p]
@@ -701,6 +728,77 @@ class Names:
     def close(self):
         if self._h:
             load().itx_names_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Bamout:
+    """The BAM of filter -b built on the device (include/iteres_amd.h itx_bamout_*): the records that chose a row, gathered into one
+    stream of bytes and cut into BGZF members there. `append_window` takes records of an Inflater's last parsed window and a torch
+    DEVICE int32 tensor of their chosen rows (-1: none), `run` plain torch DEVICE tensors (uint8 record bytes, uint32-as-int32
+    offsets, int32 rows), `append_host` whole records as bytes. Every call collects what is pending, so the members made so far are
+    in `self.out` (a bytearray) in stream order; `finish()` adds the last, short member and returns all of them."""
+
+    def __init__(self, batch_capacity: int = 1 << 20, stream_bytes: int = 0, device: int = 0):
+        self._h = C.c_void_p()
+        self.out = bytearray()
+        self.last = None                                                   # the last collect's (address, len, room)
+        _chk(load().itx_bamout_create(device, batch_capacity, stream_bytes, C.byref(self._h)), "itx_bamout_create")
+
+    _stream = staticmethod(Names._stream)
+
+    def collect(self):
+        """the oldest pending batch's members -> self.out; returns their bytes (b"" when nothing was pending or no payload was completed)"""
+        m = BamoutMembers()
+        _chk(load().itx_bamout_collect(self._h, C.byref(m)), "itx_bamout_collect")
+        got = C.string_at(m.bytes, m.len) if m.len else b""
+        if m.bytes:
+            self.last = (m.bytes, int(m.len), int(m.room))
+        self.out += got
+        return got
+
+    def _drain(self):
+        while load().itx_bamout_pending(self._h):
+            self.collect()
+
+    def append_window(self, inflater, first, n, hit_row, collect=True):
+        _chk(load().itx_bamwin_bamout(inflater._h, self._h, first, n, C.c_void_p(hit_row.data_ptr()), self._stream()), "itx_bamwin_bamout")
+        if collect:
+            self._drain()
+
+    def run(self, rec_bytes, rec_off, hit_row, collect=True):
+        _chk(load().itx_bamout_run(self._h, C.c_void_p(rec_bytes.data_ptr()), C.c_void_p(rec_off.data_ptr()), C.c_void_p(hit_row.data_ptr()), int(hit_row.numel()),
+                                   self._stream()), "itx_bamout_run")
+        if collect:
+            self._drain()
+
+    def append_host(self, records: bytes, collect=True):
+        _chk(load().itx_bamout_append_host(self._h, records, len(records)), "itx_bamout_append_host")
+        if collect:
+            self._drain()
+
+    def wait_kernels(self):
+        _chk(load().itx_bamout_wait_kernels(self._h), "itx_bamout_wait_kernels")
+
+    def finish(self):
+        self._drain()                                                      # (the last member needs a place of its own)
+        _chk(load().itx_bamout_finish(self._h), "itx_bamout_finish")
+        self._drain()
+        return bytes(self.out)
+
+    def stats(self):
+        s = BamoutStats()
+        _chk(load().itx_bamout_get_stats(self._h, C.byref(s)), "itx_bamout_get_stats")
+        return {k: getattr(s, k) for k, _ in BamoutStats._fields_}
+
+    def close(self):
+        if self._h:
+            load().itx_bamout_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -89,6 +89,8 @@ struct aln_reader {
         int n_targets;
         char **tname;
         names_t tnames;
+        uint8_t *hdr_raw;         /* aln_keep_header: the BAM header's bytes as they were read                     */
+        size_t hdr_raw_len, hdr_raw_cap;
         int eof;                  /* no more compressed input (end of file or a damaged block)                     */
         int pf_on, pf_stop;
         pthread_t pf_thread;

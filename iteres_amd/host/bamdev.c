@@ -433,6 +433,13 @@ int aln_device_names(aln_reader *r, itx_names *nm, size_t n, const int32_t *d_hi
     return 0;
 }
 
+int aln_device_bamout(aln_reader *r, itx_bamout *bo, size_t n, const int32_t *d_hit_row, void *stream)
+{
+    if (!r->dv.dev || !dev.bamout || n > r->dv.drec_next) return -1;
+    DEV_CHK(dev.bamout(dev.ctx, bo, r->dv.drec_next - n, n, d_hit_row, stream), "bamout");
+    return 0;
+}
+
 void aln_device_rewind(aln_reader *r, size_t n)
 {
     if (r->dv.dev && r->dv.dparsed) r->dv.drec_next = n <= r->dv.drec_next ? r->dv.drec_next - n : 0;
@@ -462,7 +469,9 @@ size_t dev_read_batch(aln_reader *r, itx_staging *st, size_t cap, aln_side *side
         if (m > cap - n) m = cap - n;
         const double tp = now_s();
         const int want_q = side && side->want_qnames, want_a = side && side->want_aux && (r->dv.dflags & 2);
-        if (want_q || want_a) {
+        const int want_r = side && side->want_raw;                     /* filter -b: the records' bytes themselves */
+        if (want_r && n == 0) side->raw_len = 0;
+        if (want_q || want_a || want_r) {
             if (r->dv.d_side_cap < m + 1) {
                 r->dv.d_side_cap = m + m / 4 + 1;
                 r->dv.d_off = xrealloc(r->dv.d_off, sizeof(uint32_t) * r->dv.d_side_cap);
@@ -471,7 +480,7 @@ size_t dev_read_batch(aln_reader *r, itx_staging *st, size_t cap, aln_side *side
             DEV_CHK(dev.fetch(dev.ctx, r->dv.drec_next, m, st, n, r->dv.d_off, r->dv.d_xa), "fetch");
             /* the raw bytes from the first wanted record to the end of the last one */
             size_t i0 = 0, i1 = m;
-            if (!want_q) {
+            if (!want_q && !want_r) {
                 while (i0 < m && !r->dv.d_xa[i0]) i0++;
                 while (i1 > i0 && !r->dv.d_xa[i1 - 1]) i1--;
             }
@@ -488,16 +497,25 @@ size_t dev_read_batch(aln_reader *r, itx_staging *st, size_t cap, aln_side *side
                 const uint8_t *raw = r->dv.d_raw;
                 const uint32_t *ro = r->dv.d_off;
                 const uint8_t *xa = r->dv.d_xa;
+                if (want_r) {                                      /* kept with the slot until its chosen rows are back */
+                    if (side->raw_cap < side->raw_len + (hi - lo)) {
+                        side->raw_cap = (side->raw_len + (hi - lo)) + (hi - lo) / 4;
+                        side->raw = xrealloc(side->raw, side->raw_cap);
+                    }
+                    memcpy(side->raw + side->raw_len, raw, hi - lo);
+                    for (size_t i = 0; i < m; i++) side->raw_off[n + i] = side->raw_len + (ro[i] - lo);
+                    side->raw_len += hi - lo;
+                }
 #pragma omp parallel for schedule(static)
                 for (long i = (long)i0; i < (long)i1; i++)
-                    if (want_q || xa[i]) {
+                    if (want_q || (want_a && xa[i])) {
                         int a1 = 0, x1 = 0;
                         const uint8_t marked = st->flag5[n + (size_t)i] & ITX_F5_NOLOOKUP;       /* set on the device (-R): the record's bytes do not hold it */
                         bam_parse_one(raw + (ro[i] - lo), n + (size_t)i, st, side, &a1, &x1);   /* the same field values again, plus the strings */
                         st->flag5[n + (size_t)i] |= marked;
                     }
             }
-            side->has_strings = 1;                 /* entries outside [i0, i1) were never written: still NULL */
+            if (want_q || want_a) side->has_strings = 1;                 /* entries outside [i0, i1) were never written: still NULL */
         } else {
             DEV_CHK(dev.fetch(dev.ctx, r->dv.drec_next, m, st, n, NULL, NULL), "fetch");
         }

@@ -333,36 +333,58 @@ void add_target(aln_reader *r, const char *name)
     r->cm.tname[r->cm.n_targets++] = xstrdup(name);
 }
 
+/* filter -b: the header's bytes are kept as they are read (aln_keep_header before the reader is opened) */
+static int keep_header;
+void aln_keep_header(int on) { keep_header = on; }
+const uint8_t *aln_header_bytes(const aln_reader *r, size_t *len)
+{
+    *len = r->cm.hdr_raw_len;
+    return r->cm.hdr_raw;
+}
+static size_t hdr_read(aln_reader *r, void *dst, size_t n)
+{
+    const size_t k = bgzf_read(r, dst, n);
+    if (keep_header && k) {
+        if (r->cm.hdr_raw_len + k > r->cm.hdr_raw_cap) {
+            r->cm.hdr_raw_cap = (r->cm.hdr_raw_len + k) * 2 + 4096;
+            r->cm.hdr_raw = xrealloc(r->cm.hdr_raw, r->cm.hdr_raw_cap);
+        }
+        memcpy(r->cm.hdr_raw + r->cm.hdr_raw_len, dst, k);
+        r->cm.hdr_raw_len += k;
+    }
+    return k;
+}
+
 static int bam_read_header(aln_reader *r)
 {
     uint8_t b[8];
-    if (bgzf_read(r, b, 4) != 4 || memcmp(b, "BAM\1", 4) != 0) {
+    if (hdr_read(r, b, 4) != 4 || memcmp(b, "BAM\1", 4) != 0) {
         fprintf(stderr, "[bam_header_read] invalid BAM binary header (this is not a BAM file).\n");
         return -1;
     }
-    if (bgzf_read(r, b, 4) != 4) return -1;
+    if (hdr_read(r, b, 4) != 4) return -1;
     int32_t l_text = rd_i32(b);
     while (l_text > 0) {                     /* the text header is not needed: tids come from the binary list */
         uint8_t skip[4096];
         size_t k = (size_t)l_text < sizeof skip ? (size_t)l_text : sizeof skip;
-        if (bgzf_read(r, skip, k) != k) return -1;
+        if (hdr_read(r, skip, k) != k) return -1;
         l_text -= (int32_t)k;
     }
-    if (bgzf_read(r, b, 4) != 4) return -1;
+    if (hdr_read(r, b, 4) != 4) return -1;
     const int32_t n_ref = rd_i32(b);
     for (int32_t i = 0; i < n_ref; i++) {
-        if (bgzf_read(r, b, 4) != 4) return -1;
+        if (hdr_read(r, b, 4) != 4) return -1;
         const int32_t l_name = rd_i32(b);
         if (l_name <= 0 || l_name > 1 << 20) return -1;
         char *nm = xmalloc((size_t)l_name + 1);
-        if (bgzf_read(r, nm, (size_t)l_name) != (size_t)l_name) {
+        if (hdr_read(r, nm, (size_t)l_name) != (size_t)l_name) {
             free(nm);
             return -1;
         }
         nm[l_name] = 0;
         add_target(r, nm);
         free(nm);
-        if (bgzf_read(r, b, 4) != 4) return -1;     /* l_ref */
+        if (hdr_read(r, b, 4) != 4) return -1;     /* l_ref */
     }
     return 0;
 }
@@ -681,6 +703,7 @@ aln_reader *aln_open_range(const char *path, size_t lo, size_t hi)
         free(r->cm.tname);
         r->cm.tname = NULL;
         r->cm.n_targets = 0;
+        r->cm.hdr_raw_len = 0;
         if (bam_read_header(r) != 0) {
             aln_close(r);
             return NULL;
@@ -749,6 +772,7 @@ void aln_close(aln_reader *r)
     free(r->hb.blk);
     for (int i = 0; i < r->cm.n_targets; i++) free(r->cm.tname[i]);
     free(r->cm.tname);
+    free(r->cm.hdr_raw);
     names_free(&r->cm.tnames);
     buf_free(r->hb.ubuf);
     free(r->hb.rec_off);

@@ -40,6 +40,48 @@ int bgzf_member(const uint8_t *p, size_t n, size_t *csize, size_t *usize)
     return 1;
 }
 
+/* The frame from the writing side (filter -b: the header of the emitted BAM; the records' members are made on the device by
+ * the same frame, csrc/itx_bgzfmember.h): 18 bytes bgzf_header_ok accepts with BSIZE = size - 1, raw DEFLATE, CRC-32, ISIZE.
+ * At most 0xff00 bytes go into a member, as samtools cuts them, so that a member fits 64 KiB whatever zlib makes of it. */
+int bgzf_write_members(FILE *f, const uint8_t *bytes, size_t len)
+{
+    enum { CHUNK = 0xff00 };
+    uint8_t out[18 + CHUNK + 1024 + 8];
+    for (size_t at = 0; at < len; at += CHUNK) {
+        const size_t n = len - at < CHUNK ? len - at : CHUNK;
+        z_stream zs;
+        memset(&zs, 0, sizeof zs);
+        if (deflateInit2(&zs, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return -1;
+        zs.next_in = (Bytef *)(bytes + at);
+        zs.avail_in = (uInt)n;
+        zs.next_out = out + 18;
+        zs.avail_out = CHUNK + 1024;
+        const int rc = deflate(&zs, Z_FINISH);
+        const size_t z = zs.total_out;
+        deflateEnd(&zs);
+        if (rc != Z_STREAM_END) return -1;
+        const size_t size = 18 + z + 8;
+        const uLong crc = crc32(crc32(0L, NULL, 0), bytes + at, (uInt)n);
+        static const uint8_t head[16] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0};
+        memcpy(out, head, 16);
+        out[16] = (uint8_t)(size - 1);
+        out[17] = (uint8_t)((size - 1) >> 8);
+        for (int i = 0; i < 4; i++) {
+            out[18 + z + i] = (uint8_t)(crc >> (8 * i));
+            out[22 + z + i] = (uint8_t)(n >> (8 * i));
+        }
+        if (size - 1 > 0xffff || fwrite(out, 1, size, f) != size) return -1;
+    }
+    return 0;
+}
+
+/* the empty member every BAM ends with (bgzf.c of samtools: 28 bytes) */
+int bgzf_write_eof(FILE *f)
+{
+    static const uint8_t eof[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    return fwrite(eof, 1, sizeof eof, f) == sizeof eof ? 0 : -1;
+}
+
 /* Raw DEFLATE of one block. libdeflate, when the system has it (dlopen, no build-time dependency), inflates two to three
  * times faster than zlib's inflate(); both are lossless decoders of the same stream, so the bytes are the same.
  * ITX_NO_LIBDEFLATE=1 keeps zlib. */

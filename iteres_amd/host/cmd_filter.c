@@ -23,6 +23,7 @@ static int filter_usage(void)
     fprintf(stderr, "         -c       use repClass as filter [null]\n");
     fprintf(stderr, "         -t       only output repeats have more than [1] reads mapped\n");
     fprintf(stderr, "         -r       output the list of reads [off]\n");
+    fprintf(stderr, "         -b       output the counted reads as <prefix>_<filter>.iteres.bam, every one of them whatever -t says; BAM input only (an extension: not in the reference) [off]\n");
     fprintf(stderr, "         -R       remove redundant reads [off]\n");
     fprintf(stderr, "         -T       treat 1 paired-end read as 2 single-end reads [off]\n");
     fprintf(stderr, "         -D       discard if only one end mapped in a paired end reads [off]\n");
@@ -44,10 +45,10 @@ int main_filter(int argc, char **argv)
     o.isize = 500;
     o.extension = 150;
     o.min_cov = 0.0001f;
-    int optthreshold = 1, optreadlist = 0, optNorm = 0, c, filterField = 0;
+    int optthreshold = 1, optreadlist = 0, optbam = 0, optNorm = 0, c, filterField = 0;
     char *optoutput = NULL, *optname = NULL, *optclass = NULL, *optfamily = NULL;
     const time_t start_time = time(NULL);
-    while ((c = getopt(argc, argv, "SQ:g:N:n:c:t:f:rRTDCE:I:o:h?")) >= 0) {
+    while ((c = getopt(argc, argv, "SQ:g:N:n:c:t:f:rbRTDCE:I:o:h?")) >= 0) {
         switch (c) {
         case 'S': o.is_sam = 1; break;
         case 'Q': o.mapq = (unsigned)strtol(optarg, 0, 0); break;
@@ -55,6 +56,7 @@ int main_filter(int argc, char **argv)
         case 'N': optNorm = (int)(unsigned)strtol(optarg, 0, 0); break;
         case 't': optthreshold = (int)(unsigned)strtol(optarg, 0, 0); break;
         case 'r': optreadlist = 1; break;
+        case 'b': optbam = 1; break;
         case 'R': o.dedup = 1; break;
         case 'T': o.treat = 1; break;
         case 'D': o.discard = 1; break;
@@ -71,6 +73,10 @@ int main_filter(int argc, char **argv)
         }
     }
     if (optind + 4 > argc) return filter_usage();
+    /* -b (an extension) copies records out of the BAM windows the device decoded: there are none for SAM text, nor when the host inflates */
+    if (optbam && o.is_sam) die("-b writes BAM records as they lie in the input: it cannot be combined with -S (SAM text has none)");
+    if (optbam && getenv("ITX_HOST_INFLATE"))
+        die("-b gathers the records on the device, where the BAM is decoded: it cannot be combined with ITX_HOST_INFLATE (the host decoder)");
     o.chr_size_file = argv[optind];
     o.rep_size_file = argv[optind + 1];
     o.rmsk_file = argv[optind + 2];
@@ -100,10 +106,17 @@ int main_filter(int argc, char **argv)
         free(copy);
     }
 
-    /* what is order-dependent stays with one rank: -R, the read-name lists (-r), SAM text */
-    const int splittable = !o.is_sam && !o.dedup && !optreadlist;
+    /* what is order-dependent stays with one rank: -R, the read-name lists (-r), the emitted BAM (-b), SAM text */
+    const int splittable = !o.is_sam && !o.dedup && !optreadlist && !optbam;
     multi_begin(splittable, o.aln_arg, 0);
-    stream_prefetch_allow(&o, 1, !o.is_sam && !o.dedup && !optreadlist);
+    /* (-b: the records parsed ahead are kept as 14 bytes each, their bytes are gone) */
+    stream_prefetch_allow(&o, 1, !o.is_sam && !o.dedup && !optreadlist && !optbam);
+    char *outBam = NULL;
+    if (optbam) {
+        if (asprintf(&outBam, "%s_%s.iteres.bam", output, subfam) < 0) die("Preparing output wrong");
+        o.bam_out_path = outBam;
+        aln_keep_header(1);                      /* before the helper thread opens the file */
+    }
     gpu_warmup_start(!o.is_sam, o.aln_arg, 0, splittable);
     sizes_t chr_sizes, rep_sizes;
     sizes_load(o.chr_size_file, &chr_sizes);

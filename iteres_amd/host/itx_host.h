@@ -112,6 +112,7 @@ typedef struct aln_device_ops {
     int (*push_copied)(itx_inflater *, int);       /* itx_bamwin_push_copied: lane s's compressed bytes have left the caller's buffer */
     int (*bed)(itx_inflater *, itx_bed *, size_t, size_t, uint64_t *);                         /* itx_bamwin_bed */
     int (*names)(itx_inflater *, itx_names *, size_t, size_t, const int32_t *, void *, uint64_t *);   /* itx_bamwin_names */
+    int (*bamout)(itx_inflater *, itx_bamout *, size_t, size_t, const int32_t *, void *);             /* itx_bamwin_bamout */
 } aln_device_ops;
 void aln_use_device(const aln_device_ops *ops);
 size_t aln_raw_step(size_t left);           /* bytes per read step of a regular file with `left` bytes to go (after aln_use_device) */
@@ -140,6 +141,8 @@ int aln_device_bed(aln_reader *r, itx_bed *b, size_t n, uint64_t *n_hard);
 /* the names of the batch aln_read_batch_device has just handed out, appended to the read lists on the device: d_hit_row holds the
  * batch's chosen rows, written on `stream` */
 int aln_device_names(aln_reader *r, itx_names *nm, size_t n, const int32_t *d_hit_row, void *stream, uint64_t *n_hard);
+/* the records of that batch that chose a row, appended to the BAM of filter -b on the device (same arguments) */
+int aln_device_bamout(aln_reader *r, itx_bamout *bo, size_t n, const int32_t *d_hit_row, void *stream);
 void aln_device_rewind(aln_reader *r, size_t n);       /* the last n records handed out by aln_read_batch_device are handed out again (by whichever route reads next) */
 size_t aln_device_left(const aln_reader *r);  /* device decoder: records of the current window not yet taken */
 int aln_device_exhausted(aln_reader *r);
@@ -185,6 +188,13 @@ int aln_range_verified(const aln_reader *r);
  * the block takes *csize bytes; 0 none before the end of the file; -1 the file cannot be read) */
 int aln_find_split(const char *path, size_t at, size_t *block, size_t *off, size_t *csize);
 void aln_close(aln_reader *r);
+/* filter -b: readers opened after aln_keep_header(1) keep the bytes of the BAM header as they read them (magic, text, reference
+ * list: what a BAM that carries the same records starts with); aln_header_bytes hands them out (NULL: not kept, or SAM) */
+void aln_keep_header(int on);
+const uint8_t *aln_header_bytes(const aln_reader *r, size_t *len);
+/* bgzf.c: the bytes as BGZF members of at most 0xff00 bytes each, made with zlib; the 28-byte EOF marker. 0, or -1 when writing fails */
+int bgzf_write_members(FILE *f, const uint8_t *bytes, size_t len);
+int bgzf_write_eof(FILE *f);
 int aln_n_targets(const aln_reader *r);
 const char *aln_target_name(const aln_reader *r, int tid);
 /* What the decoder keeps per record beside the SoA, when the caller wants it (arrays of the batch capacity). */
@@ -194,6 +204,12 @@ typedef struct {
     char **qname;              /* malloc'd copies of the read names (filter -r, stat -B/-V)                              */
     char **xa;                 /* malloc'd value of the XA:Z tag, NULL when the record has none (bam_aux2Z, bam_aux.c:193) */
     int32_t *nm;               /* NM:i, 0 when absent (bam_aux2i, bam_aux.c:159-170)                                      */
+    /* filter -b, batches of a device-decoded window that take the host route: the records' bytes as they lie in the window
+     * (record i: raw + raw_off[i], 4 + its block_size bytes), valid until the slot is filled again */
+    int want_raw;
+    uint8_t *raw;
+    size_t raw_len, raw_cap;
+    size_t *raw_off;
 } aln_side;
 /* Fills up to cap records of the staging slot; returns the number read (0 at end of input).
  * side may be NULL. *any_paired is set when a record with the PAIRED flag was seen; *aux_xa when one carries an XA tag. */
@@ -206,6 +222,7 @@ typedef struct {
     float min_cov;
     const char *chr_size_file, *rep_size_file, *rmsk_file, *aln_arg;
     const char *bed_path, *bed_uniq_path;      /* stat -B / -V (generic.c:925-936), NULL = off */
+    const char *bam_out_path;                  /* filter -b (an extension): the counted records as a BAM, NULL = off */
 } run_opts;
 /* counters of the record loop that only the host sees (generic.c:1048-1060) */
 typedef struct {

@@ -88,7 +88,7 @@ static void use_device_reader(void)
     const aln_device_ops ops = {g_inflater,       itx_bamwin_push_begin, itx_bamwin_push_end, itx_bamwin_patch, itx_bamwin_truncate, itx_bamwin_carry, itx_bamwin_avail, itx_bamwin_peek,
                                 itx_bamwin_skip, itx_bamwin_parse, itx_bamwin_fetch, itx_bamwin_bytes,    itx_bamwin_tids,  itx_bamwin_device_batch,
                                 pool_alloc,      pool_release,     itx_last_error,   g_dev_windows,       g_dev_max_blocks, g_dev_max_bytes, itx_bamwin_xa_veto, itx_bamwin_push_copied,
-                                itx_bamwin_bed,  itx_bamwin_names};
+                                itx_bamwin_bed,  itx_bamwin_names, itx_bamwin_bamout};
     aln_use_device(&ops);
 }
 
@@ -394,6 +394,13 @@ typedef struct {
     itx_names *nm;                                /* the read lists gathered on the device (filter -r) */
     struct { hit_name *v; size_t n, cap; } hn;    /* ... and by the host */
     struct { uint32_t *rows; uint64_t *off; char *bytes; size_t cap_n, cap_b; } nbuf;
+    /* filter -b (csrc/itx_bamout.hip): the counted records become BGZF members on the device; a batch's members are written to
+     * the file while the next batch's kernels run. What the host route counted goes to the same stream, in stream order. */
+    itx_bamout *bo;
+    FILE *bam_f;
+    int bam_header_done;
+    struct { uint8_t *bytes; size_t cap; } bbuf;
+    unsigned long long bam_dev_batches, bam_host_batches;
     /* the host route: two pinned slots, taken when a batch first goes that way; s is filled next, pend[] are in flight */
     itx_staging st[2];
     aln_side side[2];                             /* what the host keeps per record beside the SoA */
@@ -526,6 +533,39 @@ static void collect_names(stream_run *r, int k)
     }
 }
 
+/* filter -b: the members of the batches that wait (all but the newest `keep`) are fetched and written, oldest first */
+static void bam_write_out(stream_run *r, int keep)
+{
+    while (itx_bamout_pending(r->bo) > keep) {
+        itx_bamout_members m;
+        chk(itx_bamout_collect(r->bo, &m), "itx_bamout_collect");
+        if (m.len && fwrite(m.bytes, 1, m.len, r->bam_f) != m.len) die("writing %s: %s", r->o->bam_out_path, strerror(errno));
+    }
+}
+
+/* filter -b: the records of slot k that chose a row, as the reader kept their bytes, to the device's stream in record order */
+static void collect_bam(stream_run *r, int k)
+{
+    const itx_staging *st = &r->st[k];
+    const aln_side *side = &r->side[k];
+    size_t b = 0;
+    for (size_t i = 0; i < r->pend[k]; i++) {
+        if (st->hit_row[i] < 0) continue;
+        uint32_t bs;
+        memcpy(&bs, side->raw + side->raw_off[i], 4);
+        const size_t len = 4 + (size_t)bs;
+        if (r->bbuf.cap < b + len) {
+            r->bbuf.cap = (b + len) * 2;
+            r->bbuf.bytes = xrealloc(r->bbuf.bytes, r->bbuf.cap);
+        }
+        memcpy(r->bbuf.bytes + b, side->raw + side->raw_off[i], len);
+        b += len;
+    }
+    r->bam_host_batches++;
+    chk(itx_bamout_append_host(r->bo, r->bbuf.bytes, b), "itx_bamout_append_host");
+    bam_write_out(r, 1);
+}
+
 static void side_release(aln_side *side, size_t n, int keep_qnames)
 {
     if (!side->has_strings) return;                /* nothing was stored: the arrays are all NULL as they were */
@@ -550,6 +590,7 @@ static double drain_slot(stream_run *r, int k)
     const double waited = now_s() - t0;
     if (!r->pend[k]) return waited;
     if (r->want_qnames) collect_names(r, k);
+    if (r->bo) collect_bam(r, k);
     side_release(&r->side[k], r->pend[k], r->want_qnames);
     r->pend[k] = 0;
     return waited;
@@ -617,12 +658,14 @@ static void open_outputs_and_side_buffers(stream_run *r)
         r->side[k].want_qnames = r->want_qnames || r->want_bed;
         r->side[k].want_aux = r->veto_on || o->bed_path != NULL;
         if (r->side[k].want_qnames) r->side[k].qname = xcalloc(BATCH_RECORDS, sizeof(char *));
+        r->side[k].want_raw = o->bam_out_path != NULL;
+        if (r->side[k].want_raw) r->side[k].raw_off = xcalloc(BATCH_RECORDS, sizeof(size_t));
         if (r->side[k].want_aux) {
             r->side[k].xa = xcalloc(BATCH_RECORDS, sizeof(char *));
             r->side[k].nm = xcalloc(BATCH_RECORDS, sizeof(int32_t));
         }
     }
-    r->any_side = r->side[0].want_qnames || r->side[0].want_aux;
+    r->any_side = r->side[0].want_qnames || r->side[0].want_aux || r->side[0].want_raw;
     if (o->dedup || r->want_bed || r->veto_on) {
         r->iv = xcalloc(BATCH_RECORDS, sizeof *r->iv);
         r->live = xcalloc(BATCH_RECORDS, 1);
@@ -633,6 +676,7 @@ static void open_outputs_and_side_buffers(stream_run *r)
     if (o->bed_path && !(r->bed_f = fopen(o->bed_path, "w"))) die("mustOpen: Can't open %s to write: %s", o->bed_path, strerror(errno));
     if (o->bed_uniq_path && !(r->bed_uniq_f = fopen(o->bed_uniq_path, "w")))
         die("mustOpen: Can't open %s to write: %s", o->bed_uniq_path, strerror(errno));
+    if (o->bam_out_path && !(r->bam_f = fopen(o->bam_out_path, "wb"))) die("mustOpen: Can't open %s to write: %s", o->bam_out_path, strerror(errno));
 }
 
 /* the list of files (stat: comma separated, generic.c:725; filter: one file) and this rank's share of every one */
@@ -819,6 +863,15 @@ static void map_targets(stream_run *r, stream_file *f)
         g_names = r->nm;
     }
     if (f->dev_bed && !r->bd) create_bed(r, f);
+    if (r->bam_f && !r->bam_header_done) {
+        /* the emitted BAM starts with the input's header as it was read (magic, text, reference list), in members of the host's */
+        size_t hl = 0;
+        const uint8_t *hb = aln_header_bytes(f->rd, &hl);
+        if (!g_inflater || o->is_sam || !hb) die("filter -b needs BAM input decoded on the device: %s", warm_err[0] ? warm_err : "the decoder is not in use");
+        if (bgzf_write_members(r->bam_f, hb, hl) != 0) die("writing %s: %s", o->bam_out_path, strerror(errno));
+        r->bam_header_done = 1;
+        chk(itx_bamout_create(multi_device(), BATCH_RECORDS, 0, &r->bo), "itx_bamout_create");
+    }
 }
 
 /* the records the helper thread parsed while the table was being built: first, in file order */
@@ -885,6 +938,19 @@ static int device_window(stream_run *r, stream_file *f, int xa_window)
             if (aln_device_names(f->rd, r->nm, n, itx_names_hits(r->nm), itx_names_stream(r->nm), &hard) != 0) die("device read lists: %s", itx_last_error());
             if (hard) return host_takes_over(r, f, n, 0, tq);
         }
+        if (r->bo) {
+            /* filter -b, the same order: classify (once for both gatherers when the lists are built here too), gather, submit.
+             * The members of the batch before this one are written to the file while this one's kernels run. */
+            int32_t *hits = r->nm ? itx_names_hits(r->nm) : itx_bamout_hits(r->bo);
+            void *hst = r->nm ? itx_names_stream(r->nm) : itx_bamout_stream(r->bo);
+            if (!r->nm) {
+                drain_slots(r, 0);
+                chk(itx_engine_classify_device(r->eng, &db, n, hits, hst), "itx_engine_classify_device");
+            }
+            if (aln_device_bamout(f->rd, r->bo, n, hits, hst) != 0) die("device BAM output: %s", itx_last_error());
+            r->bam_dev_batches++;
+            bam_write_out(r, 1);
+        }
         if (xa_window) {
             /* classify, let the device read the tags of the classified records, mark the vetoed ones */
             uint64_t vetoed = 0, hard = 0;
@@ -903,6 +969,7 @@ static int device_window(stream_run *r, stream_file *f, int xa_window)
             chk(itx_engine_wait_own(r->eng), "itx_engine_wait_own");
             if (r->bd) chk(itx_bed_wait_kernels(r->bd), "itx_bed_wait_kernels");
             if (r->nm) chk(itx_names_wait_kernels(r->nm), "itx_names_wait_kernels");
+            if (r->bo) chk(itx_bamout_wait_kernels(r->bo), "itx_bamout_wait_kernels");
         }
         f->t_submit += now_s() - tq;
         tq = now_s();
@@ -1035,7 +1102,7 @@ static size_t host_batch(stream_run *r, stream_file *f)
     if (r->veto_on && batch_xa) veto_pass(r, f, n);
     f->t_host += now_s() - tq;
     tq = now_s();
-    chk(itx_engine_submit_slot(r->eng, s, n, f->any_paired, r->want_qnames), "itx_engine_submit_slot");
+    chk(itx_engine_submit_slot(r->eng, s, n, f->any_paired, r->want_qnames || r->bo != NULL), "itx_engine_submit_slot");
     f->t_submit += now_s() - tq;
     r->pend[s] = n;
     r->s ^= 1;
@@ -1061,6 +1128,7 @@ static void record_loop(stream_run *r, stream_file *f)
         }
         while (r->bd && r->bed_pending) bed_write_out(r, 0);
         if (r->nm) chk(itx_names_wait_kernels(r->nm), "itx_names_wait_kernels");
+        if (r->bo) chk(itx_bamout_wait_kernels(r->bo), "itx_bamout_wait_kernels");
         if (host_batch(r, f) == 0) break;
     }
 }
@@ -1136,6 +1204,29 @@ static void scan_again_alone(stream_run *r)
     for (int i = 0; i < r->n_files; i++) r->share[i].lo = 0, r->share[i].hi = SIZE_MAX;
     r->shared = 0;
     for (int fi = 0; fi < r->n_files; fi++) scan_file(r, fi, 1);
+}
+
+/* filter -b: the last, short member, the EOF marker, and the counters for ITX_TIMING */
+static void finish_bam(stream_run *r)
+{
+    if (!r->bam_f) return;
+    if (r->bo) {
+        chk(itx_bamout_finish(r->bo), "itx_bamout_finish");
+        bam_write_out(r, 0);
+    }
+    if (bgzf_write_eof(r->bam_f) != 0 || fclose(r->bam_f) != 0) die("writing %s: %s", r->o->bam_out_path, strerror(errno));
+    r->bam_f = NULL;
+    if (r->timing) {
+        itx_bamout_stats bs;
+        memset(&bs, 0, sizeof bs);
+        if (r->bo) chk(itx_bamout_get_stats(r->bo, &bs), "itx_bamout_get_stats");
+        fprintf(stderr, "[itx timing] bam out: %llu records, %llu payload bytes, %llu members (%llu bytes), %.3f ms in the gather kernels, %.3f ms in the member kernels, host waited %.3f s, %llu batches gathered on the device, %llu batches by the host route\n",
+                (unsigned long long)bs.records, (unsigned long long)bs.payload_bytes, (unsigned long long)bs.members, (unsigned long long)bs.out_bytes, bs.gather_ms,
+                bs.member_ms, 1e-3 * bs.wait_ms, r->bam_dev_batches, r->bam_host_batches);
+    }
+    itx_bamout_destroy(r->bo);
+    r->bo = NULL;
+    free(r->bbuf.bytes);
 }
 
 static void finish_names(stream_run *r, char ***locus_names)
@@ -1228,6 +1319,8 @@ static void teardown(stream_run *r, int lists_taken)
         free(r->side[k].qname);
         free(r->side[k].xa);
         free(r->side[k].nm);
+        free(r->side[k].raw);
+        free(r->side[k].raw_off);
     }
     /* The decoder's device memory (17 GB for a big input) goes back NOW, not when the process ends: the driver clears released
      * memory in the background, and the next command's reservation of the same 17 GB waits for whatever is still uncleared —
@@ -1263,6 +1356,7 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
         exchange(r);
         if (r->boundary_missed) scan_again_alone(r);
     }
+    finish_bam(r);
     release_side_objects(r);
     finish_names(r, locus_names);
     teardown(r, want_qnames && locus_names);

@@ -3,7 +3,7 @@
 Generates the bench inputs once (bench.py's generator), then runs `iteres stat -w` <reps> times per setting, interleaved.
 LD_LIBRARY_PATH in a setting selects another build of libiteres_amd.so (the program's RUNPATH comes after it).
 ITX_AB_FILTER=1 runs `iteres filter -c <the table's biggest class>` instead (ITX_AB_OPTS="-r": with the read lists) and compares
-the .loci / .reportloci files; ITX_AB_FILTER=all runs `iteres filter` without a name filter (every row of the table is a line)."""
+the .loci / .reportloci files (a setting may carry options of its own: `b:ITX_AB_OPTS=-b` is `filter -b` against plain `filter`); ITX_AB_FILTER=all runs `iteres filter` without a name filter (every row of the table is a line)."""
 import json
 import os
 import subprocess
@@ -42,7 +42,7 @@ def main():
                 env[k] = os.path.join(ROOT, v) if k == "LD_LIBRARY_PATH" else v
             out = os.path.join(wd, "ab_" + name)
             args = bench.base_args(wd)
-            extra = os.environ.get("ITX_AB_OPTS", "").split()              # e.g. ITX_AB_OPTS="-R": options behind `stat -w`
+            extra = env.get("ITX_AB_OPTS", "").split()                     # e.g. ITX_AB_OPTS="-R": options behind `stat -w`; inside a setting (b:ITX_AB_OPTS=-b): for that setting alone
             args = args[:2] + extra + args[2:]
             if os.environ.get("ITX_AB_FILTER"):
                 select = [] if os.environ["ITX_AB_FILTER"] == "all" else ["-c", info["filter_class"]["name"]]
