@@ -502,6 +502,28 @@ int itx_bamout_finish(itx_bamout *bo);
 int itx_bamout_collect(itx_bamout *bo, itx_bamout_members *out);
 int itx_bamout_pending(const itx_bamout *bo);
 int itx_bamout_get_stats(const itx_bamout *bo, itx_bamout_stats *out);
+/* The .bai index (SAM v1 section 5.2) of that BAM, built on the device in the same pass (csrc/itx_bamidx.hip; the rule a record
+ * follows is csrc/itx_bairule.h). Its bytes are a function of the BAM: a run of consecutive records with one (tid, bin) is one chunk,
+ * a bin's chunks stay in file order and a chunk is merged into its predecessor when prev.end >> 16 >= beg >> 16; bins ascend,
+ * pseudo-bin 37450 follows them for every reference that has records; an untouched window of the linear index takes the value of
+ * the nearest touched one below (0 when there is none); n_no_coor = 0 ends the file.
+ *   index_enable  before the first batch (ITX_E_STATE after it, or when called twice). l_ref[0 .. n_ref): the reference lengths
+ *               of the BAM's header; they size the linear index. Without this call nothing of the index exists.
+ *   index_finish  after itx_bamout_finish (ITX_E_STATE before it, without index_enable, or when called twice).
+ *               first_member_offset: where the first record member starts in the file (the bytes of the header's members).
+ *               status ITX_BAI_OK (0): bytes / len are the file, in a page-locked buffer that lives as long as the object.
+ *               Otherwise no index can be made, bytes is NULL, and status says why: 1 the records are not in coordinate order,
+ *               2 a record ends beyond 2^29, 3 a record ends beyond its reference's l_ref (or names no reference),
+ *               4 n_ref >= 2^16. The members are the same whether or not an index is made. */
+typedef struct itx_bamout_index_result {
+    const void *bytes;
+    uint64_t len;
+    int32_t status, pad;
+    uint64_t entries, chunks, grows;         /* records indexed; chunks written (pseudo-bins apart); times the entry pool grew */
+    double batch_ms, finish_ms;              /* device time: the per-batch entry kernels; everything index_finish enqueued */
+} itx_bamout_index_result;
+int itx_bamout_index_enable(itx_bamout *bo, int32_t n_ref, const int32_t *l_ref);
+int itx_bamout_index_finish(itx_bamout *bo, uint64_t first_member_offset, itx_bamout_index_result *out);
 
 /* ---- the .loci file of filter / cpgfilter on the device ----------------------------------------------------------------------
  * Replaces the row walk and the fprintf of writeFilterOut (generic.c:1709-1746) and writeFilterOutMRE (generic.c:1748-1772): the

@@ -1,0 +1,766 @@
+// itx_bamidx.hip — the .bai index (SAM v1 section 5.2) of the BAM that `iteres filter -b -i` writes, built where the records lie and
+// in the same pass (an extension, as -b is). csrc/itx_bairule.h states what a record contributes; this file collects it and
+// makes the file's bytes. csrc/itx_bamout.hip calls it (itx_bamidx.h) on its own stream.
+//
+// per batch, behind the gather:
+//   k_bi_entries   one lane per record. A counted record (len != 0) walks its CIGAR where it lies and appends one entry
+//                  {key = tid << 16 | bin, pos, end, its byte in the record stream, its length} to a pool in HBM; its place in the
+//                  stream comes from the gather's own tile bases and itx_tile_offsets, its place in the pool from the tile's record
+//                  count the same way. A record that cannot be indexed (itx_bai_refuses) sets a bit of the flag word.
+//   the batch's member sizes are copied behind those of the batches before (device to device).
+//   The host route's records (whole records one behind the other) are measured by k_bi_measure + k_tile_scan2 and go through the
+//   SAME entry kernel, so the pool is one list in stream order whatever route a window took.
+// at the end (itx_bamidx_finish), N entries, M members:
+//   k_bi_order     entry i against entry i - 1: (tid, pos) below its predecessor's sets the "unsorted" bit. The flag word is read
+//                  once, here; a set bit ends the work: status, no bytes.
+//   k_bi_coff      exclusive sums of ALL member sizes: coff[0 .. M]
+//   k_bi_heads / k_tile_scan2 / k_bi_chunks   a run of consecutive entries with one key is one chunk: run heads are counted per
+//                  tile, scanned, and every run writes (key, chunk number), its first voff and its last end voff
+//   k_sort_*       (itx_radixsort.h) the chunks sorted by key, stable, so a bin's chunks stay in file order
+//   k_bi_merge_count / k_tile_scan2 / k_bi_merge_apply   a chunk is merged into its predecessor when prev.end >> 16 >= beg >> 16
+//                  (ends rise with the file order, so the predicate needs the neighbour only); the same scan numbers the bins; the
+//                  first and last chunk and bin of every reference are noted where the key's tid changes
+//   k_bi_windows   per entry, 64-bit atomicMin of its voff into every window it touches (windows its predecessor on the same
+//                  reference touches too are skipped: that one's voff is lower); first and last entry of every reference
+//   k_bi_fill      one workgroup per reference: n_intv, then untouched windows take the nearest touched value below (carried scan)
+//   k_bi_refsize   one workgroup: the bytes of every reference's part, exclusive sums
+//   k_bi_write_*   the file's bytes. Every field of a .bai lies on a 4-byte boundary, so 8-byte fields go as two 32-bit stores.
+// The finished bytes come back through a page-locked buffer.
+#include "itx_bamidx.h"
+#include "itx_bairule.h"
+#include "itx_radixsort.h"
+#include "itx_textpack.h"
+
+#include <stdlib.h>
+#include <string.h>
+
+typedef unsigned long long ull;
+
+#define BI_TILE ITX_BAMIDX_TILE
+#define BI_P ITX_BAMIDX_PAYLOAD
+#define BI_NONE 0xffffffffffffffffull
+#define BI_FLAG(reason) (1u << (reason))
+
+struct BiEnt {
+    uint32_t key;                    // tid << 16 | bin
+    int32_t pos, end;
+    uint32_t len;                    // 4 + block_size
+    ull soff;                        // the record's first byte in the record stream of the whole run
+};
+static_assert(sizeof(BiEnt) == 24, "BiEnt");
+
+// ---- per batch
+
+// the host route: every record counts, 4 + block_size bytes (the host has checked that they are whole records)
+__global__ __launch_bounds__(BI_TILE) void k_bi_measure(const uint8_t *__restrict__ u, const uint32_t *__restrict__ rec_off, uint32_t n, uint32_t *__restrict__ len_out,
+                                                         ull *__restrict__ tile_sum)
+{
+    __shared__ uint32_t s_w[BI_TILE / 64u];
+    const uint32_t i = blockIdx.x * BI_TILE + threadIdx.x;
+    uint32_t len = 0, total = 0;
+    if (i < n) {
+        len = 4u + itx_bai_u32(u + rec_off[i]);
+        len_out[i] = len;
+    }
+    (void)itx_tile_offsets<BI_TILE>(len, s_w, &total);
+    if (threadIdx.x == 0) {
+        const uint32_t left = n - blockIdx.x * BI_TILE;
+        tile_sum[2u * blockIdx.x] = total;
+        tile_sum[2u * blockIdx.x + 1u] = left < BI_TILE ? left : BI_TILE;
+    }
+}
+
+__global__ __launch_bounds__(BI_TILE) void k_bi_entries(const uint8_t *__restrict__ u, const uint32_t *__restrict__ rec_off, uint32_t n, const uint32_t *__restrict__ len_in,
+                                                         const ull *__restrict__ tile_base, ull stream_at, ull ent_at, BiEnt *__restrict__ ent, int32_t n_ref,
+                                                         const int32_t *__restrict__ l_ref, uint32_t *__restrict__ flag)
+{
+    __shared__ uint32_t s_w[BI_TILE / 64u], s_c[BI_TILE / 64u];
+    const uint32_t i = blockIdx.x * BI_TILE + threadIdx.x;
+    const uint32_t len = i < n ? len_in[i] : 0u;
+    uint32_t total = 0, count = 0;
+    const uint32_t moff = itx_tile_offsets<BI_TILE>(len, s_w, &total);        // the gather's rule for the record's place
+    const uint32_t rank = itx_tile_offsets<BI_TILE>(len ? 1u : 0u, s_c, &count);
+    if (!len) return;
+    const uint8_t *p = u + rec_off[i];
+    ItxBaiRec r;
+    itx_bai_fields(p, len, &r);
+    const int why = itx_bai_refuses(&r, n_ref, l_ref);
+    BiEnt e;
+    e.pos = r.pos;
+    e.len = len;
+    e.soff = stream_at + tile_base[2u * blockIdx.x] + moff;
+    if (why) {                                                             // no index will be made: the entry only keeps the pool's count right
+        atomicOr(flag, BI_FLAG(why));
+        e.key = itx_bai_key(r.tid, 0u);
+        e.end = r.pos;
+    } else {
+        e.key = itx_bai_key(r.tid, itx_bai_reg2bin(r.pos, r.end));
+        e.end = (int32_t)r.end;
+    }
+    ent[ent_at + tile_base[2u * blockIdx.x + 1u] + rank] = e;
+}
+
+// ---- at the end
+
+__global__ __launch_bounds__(256) void k_bi_order(const BiEnt *__restrict__ ent, uint32_t n, uint32_t *__restrict__ flag)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i == 0 || i >= n) return;
+    const int32_t ta = (int32_t)(ent[i - 1].key >> 16), tb = (int32_t)(ent[i].key >> 16);
+    if (tb < ta || (tb == ta && ent[i].pos < ent[i - 1].pos)) atomicOr(flag, BI_FLAG(ITX_BAI_UNSORTED));
+}
+
+// coff[0 .. n]: exclusive sums of the member sizes (one workgroup)
+__global__ __launch_bounds__(ITX_SCAN_WG) void k_bi_coff(const uint32_t *__restrict__ msize, uint64_t n, uint64_t *__restrict__ coff)
+{
+    __shared__ uint64_t s[ITX_SCAN_WG];
+    uint64_t lo, hi;
+    itx_scan_chunk(n, &lo, &hi);
+    uint64_t a = 0, total;
+    for (uint64_t i = lo; i < hi; i++) a += msize[i];
+    uint64_t e = itx_scan_wg(a, s, &total);
+    for (uint64_t i = lo; i < hi; i++) {
+        coff[i] = e;
+        e += msize[i];
+    }
+    if (threadIdx.x == 0) coff[n] = total;
+}
+
+__device__ __forceinline__ bool bi_run_head(const BiEnt *__restrict__ ent, uint32_t i) { return i == 0 || ent[i].key != ent[i - 1].key; }
+
+__global__ __launch_bounds__(BI_TILE) void k_bi_heads(const BiEnt *__restrict__ ent, uint32_t n, ull *__restrict__ tile_sum)
+{
+    __shared__ uint32_t s_w[BI_TILE / 64u];
+    const uint32_t i = blockIdx.x * BI_TILE + threadIdx.x;
+    uint32_t total = 0;
+    (void)itx_tile_offsets<BI_TILE>(i < n && bi_run_head(ent, i) ? 1u : 0u, s_w, &total);
+    if (threadIdx.x == 0) {
+        tile_sum[2u * blockIdx.x] = total;
+        tile_sum[2u * blockIdx.x + 1u] = 0;
+    }
+}
+
+// chunk c = the c-th run of equal keys: (key, c) for the sort, the voff of its first record, the end voff of its last
+__global__ __launch_bounds__(BI_TILE) void k_bi_chunks(const BiEnt *__restrict__ ent, uint32_t n, const ull *__restrict__ tile_base, const uint64_t *__restrict__ coff,
+                                                        uint64_t first, uint2 *__restrict__ ck, uint64_t *__restrict__ cbeg, uint64_t *__restrict__ cend)
+{
+    __shared__ uint32_t s_w[BI_TILE / 64u];
+    const uint32_t i = blockIdx.x * BI_TILE + threadIdx.x;
+    const bool head = i < n && bi_run_head(ent, i);
+    uint32_t total = 0;
+    const uint32_t before = itx_tile_offsets<BI_TILE>(head ? 1u : 0u, s_w, &total);
+    if (i >= n) return;
+    const uint32_t c = (uint32_t)tile_base[2u * blockIdx.x] + before + (head ? 1u : 0u) - 1u;     // the run this entry belongs to
+    const BiEnt e = ent[i];
+    if (head) {
+        ck[c] = make_uint2(e.key, c);
+        cbeg[c] = itx_bai_voff(first, coff, e.soff, BI_P);
+    }
+    if (i + 1u == n || ent[i + 1u].key != e.key) cend[c] = itx_bai_voff(first, coff, e.soff + e.len, BI_P);
+}
+
+// sorted chunk j opens a chunk of the file (it is not merged into its predecessor)
+__device__ __forceinline__ bool bi_chunk_head(const uint2 *__restrict__ s, const uint64_t *__restrict__ cbeg, const uint64_t *__restrict__ cend, uint32_t j)
+{
+    if (j == 0) return true;
+    const uint2 a = s[j - 1], b = s[j];
+    return a.x != b.x || (cend[a.y] >> 16) < (cbeg[b.y] >> 16);
+}
+
+__global__ __launch_bounds__(BI_TILE) void k_bi_merge_count(const uint2 *__restrict__ s, uint32_t n, const uint64_t *__restrict__ cbeg, const uint64_t *__restrict__ cend,
+                                                             ull *__restrict__ tile_sum)
+{
+    __shared__ uint32_t s_a[BI_TILE / 64u], s_b[BI_TILE / 64u];
+    const uint32_t j = blockIdx.x * BI_TILE + threadIdx.x;
+    const bool ch = j < n && bi_chunk_head(s, cbeg, cend, j), bh = j < n && (j == 0 || s[j].x != s[j - 1].x);
+    uint32_t ta = 0, tb = 0;
+    (void)itx_tile_offsets<BI_TILE>(ch ? 1u : 0u, s_a, &ta);
+    (void)itx_tile_offsets<BI_TILE>(bh ? 1u : 0u, s_b, &tb);
+    if (threadIdx.x == 0) {
+        tile_sum[2u * blockIdx.x] = ta;
+        tile_sum[2u * blockIdx.x + 1u] = tb;
+    }
+}
+
+// per reference: chunks [f0, f1), bins [b0, b1), entries [e0, e1), n_intv; all zero for a reference without records
+struct BiRefs {
+    uint32_t *f0, *f1, *b0, *b1, *e0, *e1, *n_intv;
+};
+
+// file chunk f: fkey, fbin (its bin's number among all bins), fbeg, fend; bin b starts at file chunk bin_first[b]
+__global__ __launch_bounds__(BI_TILE) void k_bi_merge_apply(const uint2 *__restrict__ s, uint32_t n, const uint64_t *__restrict__ cbeg, const uint64_t *__restrict__ cend,
+                                                             const ull *__restrict__ tile_base, uint32_t *__restrict__ fkey, uint32_t *__restrict__ fbin,
+                                                             uint64_t *__restrict__ fbeg, uint64_t *__restrict__ fend, uint32_t *__restrict__ bin_first, BiRefs R)
+{
+    __shared__ uint32_t s_a[BI_TILE / 64u], s_b[BI_TILE / 64u];
+    const uint32_t j = blockIdx.x * BI_TILE + threadIdx.x;
+    const bool ch = j < n && bi_chunk_head(s, cbeg, cend, j), bh = j < n && (j == 0 || s[j].x != s[j - 1].x);
+    uint32_t ta = 0, tb = 0;
+    const uint32_t fa = itx_tile_offsets<BI_TILE>(ch ? 1u : 0u, s_a, &ta);
+    const uint32_t fb = itx_tile_offsets<BI_TILE>(bh ? 1u : 0u, s_b, &tb);
+    if (j >= n) return;
+    const uint32_t f = (uint32_t)tile_base[2u * blockIdx.x] + fa + (ch ? 1u : 0u) - 1u;          // the file chunk and the bin this
+    const uint32_t b = (uint32_t)tile_base[2u * blockIdx.x + 1u] + fb + (bh ? 1u : 0u) - 1u;     // sorted chunk belongs to
+    const uint2 me = s[j];
+    const uint32_t tid = me.x >> 16;
+    const bool last = j + 1u == n;
+    if (ch) {
+        fkey[f] = me.x;
+        fbin[f] = b;
+        fbeg[f] = cbeg[me.y];
+    }
+    if (last || bi_chunk_head(s, cbeg, cend, j + 1u)) fend[f] = cend[me.y];
+    if (bh) bin_first[b] = f;
+    if (last) bin_first[b + 1u] = f + 1u;
+    if (j == 0 || (s[j - 1].x >> 16) != tid) {
+        R.f0[tid] = f;
+        R.b0[tid] = b;
+    }
+    if (last || (s[j + 1u].x >> 16) != tid) {
+        R.f1[tid] = f + 1u;
+        R.b1[tid] = b + 1u;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_bi_windows(const BiEnt *__restrict__ ent, uint32_t n, const uint64_t *__restrict__ coff, uint64_t first,
+                                                    const uint64_t *__restrict__ woff, ull *__restrict__ lin, BiRefs R)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const BiEnt e = ent[i];
+    const uint32_t tid = e.key >> 16;
+    uint32_t w = itx_bai_win_first(e.pos);
+    const uint32_t w1 = itx_bai_win_last(e.end);
+    if (i != 0 && (ent[i - 1].key >> 16) == tid) {
+        // the entry before starts no later and lies earlier in the file: the windows it touches too already hold a lower voff
+        const uint32_t pw = itx_bai_win_last(ent[i - 1].end) + 1u;
+        if (pw > w) w = pw;
+    } else {
+        R.e0[tid] = i;
+    }
+    if (i + 1u == n || (ent[i + 1u].key >> 16) != tid) R.e1[tid] = i + 1u;
+    const ull v = itx_bai_voff(first, coff, e.soff, BI_P);
+    ull *row = lin + woff[tid];
+    for (; w <= w1; w++) atomicMin(&row[w], v);                            // (a spliced record may touch thousands: a loop, one lane)
+}
+
+// one workgroup per reference: n_intv = the highest touched window + 1; below it an untouched window takes the value of the
+// nearest touched one below, 0 when there is none
+__global__ __launch_bounds__(256) void k_bi_fill(const uint64_t *__restrict__ woff, ull *__restrict__ lin, uint32_t *__restrict__ n_intv)
+{
+    __shared__ uint32_t s_n;
+    __shared__ int32_t s_idx[256];
+    __shared__ ull s_val[256];
+    const uint32_t t = threadIdx.x;
+    ull *row = lin + woff[blockIdx.x];
+    const uint32_t nw = (uint32_t)(woff[blockIdx.x + 1u] - woff[blockIdx.x]);
+    if (t == 0) s_n = 0;
+    __syncthreads();
+    uint32_t top = 0;
+    for (uint32_t w = t; w < nw; w += 256u)
+        if (row[w] != BI_NONE) top = w + 1u;
+    if (top) atomicMax(&s_n, top);
+    __syncthreads();
+    const uint32_t n = s_n;
+    if (t == 0) n_intv[blockIdx.x] = n;
+    ull carry = 0;
+    for (uint32_t w0 = 0; w0 < n; w0 += 256u) {
+        const uint32_t w = w0 + t;
+        const ull v = w < n ? row[w] : BI_NONE;
+        s_val[t] = v;
+        s_idx[t] = v != BI_NONE ? (int32_t)t : -1;
+        __syncthreads();
+        for (uint32_t o = 1; o < 256u; o <<= 1) {                          // inclusive max scan: the nearest touched lane at or below
+            const int32_t x = t >= o ? s_idx[t - o] : -1;
+            __syncthreads();
+            if (x > s_idx[t]) s_idx[t] = x;
+            __syncthreads();
+        }
+        const int32_t mine = s_idx[t], end = s_idx[255];
+        const ull out = mine >= 0 ? s_val[mine] : carry;
+        if (w < n) row[w] = out;
+        carry = end >= 0 ? s_val[end] : carry;
+        __syncthreads();
+    }
+}
+
+// roff[r]: where reference r's part starts in the file; roff[n_ref]: where n_no_coor stands (one workgroup)
+__global__ __launch_bounds__(ITX_SCAN_WG) void k_bi_refsize(uint32_t n_ref, BiRefs R, uint64_t *__restrict__ roff)
+{
+    __shared__ uint64_t s[ITX_SCAN_WG];
+    uint64_t lo, hi;
+    itx_scan_chunk(n_ref, &lo, &hi);
+    auto size = [&](uint64_t r) -> uint64_t {
+        return 4ull + 8ull * (R.b1[r] - R.b0[r]) + 16ull * (R.f1[r] - R.f0[r]) + (R.e1[r] > R.e0[r] ? 40ull : 0ull) + 4ull + 8ull * R.n_intv[r];
+    };
+    uint64_t a = 0, total;
+    for (uint64_t r = lo; r < hi; r++) a += size(r);
+    uint64_t e = 8ull + itx_scan_wg(a, s, &total);
+    for (uint64_t r = lo; r < hi; r++) {
+        roff[r] = e;
+        e += size(r);
+    }
+    if (threadIdx.x == 0) roff[n_ref] = 8ull + total;
+}
+
+__device__ __forceinline__ void bi_put32(uint8_t *out, uint64_t at, uint32_t v) { *reinterpret_cast<uint32_t *>(out + at) = v; }
+__device__ __forceinline__ void bi_put64(uint8_t *out, uint64_t at, uint64_t v)
+{
+    bi_put32(out, at, (uint32_t)v);
+    bi_put32(out, at + 4u, (uint32_t)(v >> 32));
+}
+
+// magic, n_ref, per reference n_bin, the pseudo-bin and n_intv, and n_no_coor at the end
+__global__ __launch_bounds__(256) void k_bi_write_refs(uint32_t n_ref, BiRefs R, const uint64_t *__restrict__ roff, const BiEnt *__restrict__ ent,
+                                                       const uint64_t *__restrict__ coff, uint64_t first, uint8_t *__restrict__ out)
+{
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r == 0) {
+        bi_put32(out, 0, 0x01494142u);                                     // "BAI\1"
+        bi_put32(out, 4, n_ref);
+        bi_put64(out, roff[n_ref], 0);
+    }
+    if (r >= n_ref) return;
+    const uint32_t nb = R.b1[r] - R.b0[r], nc = R.f1[r] - R.f0[r];
+    const bool has = R.e1[r] > R.e0[r];
+    uint64_t at = roff[r];
+    bi_put32(out, at, nb + (has ? 1u : 0u));
+    at += 4ull + 8ull * nb + 16ull * nc;
+    if (has) {
+        const BiEnt a = ent[R.e0[r]], b = ent[R.e1[r] - 1u];
+        bi_put32(out, at, ITX_BAI_PSEUDO_BIN);
+        bi_put32(out, at + 4u, 2u);
+        bi_put64(out, at + 8u, itx_bai_voff(first, coff, a.soff, BI_P));
+        bi_put64(out, at + 16u, itx_bai_voff(first, coff, b.soff + b.len, BI_P));
+        bi_put64(out, at + 24u, (uint64_t)(R.e1[r] - R.e0[r]));
+        bi_put64(out, at + 32u, 0);
+        at += 40u;
+    }
+    bi_put32(out, at, R.n_intv[r]);
+}
+
+__global__ __launch_bounds__(256) void k_bi_write_chunks(const ull *__restrict__ tot, const uint32_t *__restrict__ fkey, const uint32_t *__restrict__ fbin,
+                                                         const uint64_t *__restrict__ fbeg, const uint64_t *__restrict__ fend, const uint32_t *__restrict__ bin_first, BiRefs R,
+                                                         const uint64_t *__restrict__ roff, uint8_t *__restrict__ out)
+{
+    const uint32_t f = blockIdx.x * 256u + threadIdx.x;
+    if (f >= tot[0]) return;
+    const uint32_t key = fkey[f], tid = key >> 16, b = fbin[f];
+    const uint64_t at = roff[tid] + 4ull + 8ull * (b - R.b0[tid] + 1u) + 16ull * (f - R.f0[tid]);
+    if (bin_first[b] == f) {
+        bi_put32(out, at - 8u, key & 0xffffu);
+        bi_put32(out, at - 4u, bin_first[b + 1u] - f);
+    }
+    bi_put64(out, at, fbeg[f]);
+    bi_put64(out, at + 8u, fend[f]);
+}
+
+__global__ __launch_bounds__(256) void k_bi_write_linear(BiRefs R, const uint64_t *__restrict__ roff, const uint64_t *__restrict__ woff, const ull *__restrict__ lin,
+                                                         uint8_t *__restrict__ out)
+{
+    const uint32_t r = blockIdx.x, n = R.n_intv[r];
+    const uint64_t at = roff[r] + 4ull + 8ull * (R.b1[r] - R.b0[r]) + 16ull * (R.f1[r] - R.f0[r]) + (R.e1[r] > R.e0[r] ? 40ull : 0ull) + 4ull;
+    const ull *row = lin + woff[r];
+    for (uint32_t w = threadIdx.x; w < n; w += 256u) bi_put64(out, at + 8ull * w, row[w]);
+}
+
+// ---- host side
+struct itx_bamidx {
+    int device;
+    int reason;                      // ITX_BAI_TOO_MANY_REFS: there will be no index, nothing is collected
+    int32_t n_ref;
+    int32_t *d_lref;
+    uint64_t *h_woff, *d_woff;       // [n_ref + 1] where every reference's windows start in the linear array
+    uint32_t *d_flag, *h_flag;
+    BiEnt *d_ent;
+    uint64_t n_ent, ent_cap;
+    uint32_t *d_ms;                  // all member sizes of the run
+    uint64_t n_ms, ms_cap;
+    uint32_t *d_hoff, *d_hlen;       // the host route's offsets and lengths
+    ull *d_hts, *d_htb, *d_htot;
+    uint64_t h_cap;
+    hipEvent_t eb[2], ef[2];
+    int batch_timed, done;
+    double batch_ms, finish_ms;
+    uint64_t grows;
+    uint8_t *d_out, *h_out;          // the finished file
+};
+
+static int bi_hip(hipError_t e, const char *what, int line)
+{
+    if (e == hipSuccess) return ITX_OK;
+    itx_set_error("%s failed: %s (%s:%d)", what, hipGetErrorString(e), __FILE__, line);
+    return ITX_E_NO_DEVICE;
+}
+#define BI_TRY(call)                                       \
+    do {                                                   \
+        if ((rc = bi_hip((call), #call, __LINE__)) != 0) goto out; \
+    } while (0)
+
+void itx_bamidx_destroy(itx_bamidx *ix)
+{
+    if (!ix) return;
+    (void)hipSetDevice(ix->device);
+    for (auto &e : ix->eb)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : ix->ef)
+        if (e) (void)hipEventDestroy(e);
+    (void)hipFree(ix->d_lref);
+    (void)hipFree(ix->d_woff);
+    (void)hipFree(ix->d_flag);
+    (void)hipFree(ix->d_ent);
+    (void)hipFree(ix->d_ms);
+    (void)hipFree(ix->d_hoff);
+    (void)hipFree(ix->d_hlen);
+    (void)hipFree(ix->d_hts);
+    (void)hipFree(ix->d_htb);
+    (void)hipFree(ix->d_htot);
+    (void)hipFree(ix->d_out);
+    if (ix->h_flag) (void)hipHostFree(ix->h_flag);
+    if (ix->h_out) (void)hipHostFree(ix->h_out);
+    free(ix->h_woff);
+    delete ix;
+}
+
+int itx_bamidx_create(int device, int32_t n_ref, const int32_t *l_ref, itx_bamidx **out)
+{
+    int rc = ITX_OK;
+    itx_bamidx *ix = new itx_bamidx();
+    ix->device = device;
+    ix->n_ref = n_ref;
+    if (n_ref >= ITX_BAI_MAX_REFS) {
+        ix->reason = ITX_BAI_TOO_MANY_REFS;
+        *out = ix;
+        return ITX_OK;
+    }
+    ix->h_woff = (uint64_t *)malloc(8 * ((size_t)n_ref + 1));
+    if (!ix->h_woff) {
+        itx_set_error("itx_bamout_index_enable: no memory for %d references", n_ref);
+        rc = ITX_E_NOMEM;
+        goto out;
+    }
+    ix->h_woff[0] = 0;
+    for (int32_t r = 0; r < n_ref; r++) ix->h_woff[r + 1] = ix->h_woff[r] + itx_bai_windows(l_ref[r]);
+    BI_TRY(hipSetDevice(device));
+    if (hipMalloc((void **)&ix->d_lref, 4 * ((size_t)n_ref + 1)) != hipSuccess || hipMalloc((void **)&ix->d_woff, 8 * ((size_t)n_ref + 1)) != hipSuccess ||
+        hipMalloc((void **)&ix->d_flag, 16) != hipSuccess) {
+        (void)hipGetLastError();
+        itx_set_error("itx_bamout_index_enable: no device memory for %d references", n_ref);
+        rc = ITX_E_NOMEM;
+        goto out;
+    }
+    BI_TRY(hipHostMalloc((void **)&ix->h_flag, 16, hipHostMallocDefault));
+    if (n_ref) BI_TRY(hipMemcpy(ix->d_lref, l_ref, 4 * (size_t)n_ref, hipMemcpyHostToDevice));
+    BI_TRY(hipMemcpy(ix->d_woff, ix->h_woff, 8 * ((size_t)n_ref + 1), hipMemcpyHostToDevice));
+    BI_TRY(hipMemset(ix->d_flag, 0, 16));
+    for (auto &e : ix->eb) BI_TRY(hipEventCreate(&e));
+    for (auto &e : ix->ef) BI_TRY(hipEventCreate(&e));
+out:
+    if (rc != ITX_OK) {
+        itx_bamidx_destroy(ix);
+        return rc;
+    }
+    *out = ix;
+    return ITX_OK;
+}
+
+int itx_bamidx_reserve(itx_bamidx *ix, hipStream_t st, uint64_t n_entries, uint64_t n_members)
+{
+    if (ix->reason) return ITX_OK;
+    int rc = ITX_OK;
+    BiEnt *nent = nullptr;
+    uint32_t *nms = nullptr;
+    uint64_t want_ent = 0, want_ms = 0;
+    if (ix->n_ent + n_entries > 0xffffff00ull) {
+        itx_set_error("itx_bamout: %llu records to index", (ull)(ix->n_ent + n_entries));
+        return ITX_E_LIMIT;
+    }
+    if (ix->n_ent + n_entries > ix->ent_cap) want_ent = ix->n_ent + n_entries + (ix->n_ent + n_entries) / 2 + 1024;
+    if (ix->n_ms + n_members > ix->ms_cap) want_ms = ix->n_ms + n_members + (ix->n_ms + n_members) / 2 + 1024;
+    if ((want_ent && hipMalloc((void **)&nent, sizeof(BiEnt) * want_ent) != hipSuccess) || (want_ms && hipMalloc((void **)&nms, 4 * want_ms) != hipSuccess)) {
+        (void)hipGetLastError();
+        itx_set_error("itx_bamout: no device memory for the index entries of %llu records and %llu members", (ull)(ix->n_ent + n_entries), (ull)(ix->n_ms + n_members));
+        rc = ITX_E_NOMEM;
+        goto out;
+    }
+    if (nent && ix->n_ent) BI_TRY(hipMemcpyAsync(nent, ix->d_ent, sizeof(BiEnt) * ix->n_ent, hipMemcpyDeviceToDevice, st));
+    if (nms && ix->n_ms) BI_TRY(hipMemcpyAsync(nms, ix->d_ms, 4 * ix->n_ms, hipMemcpyDeviceToDevice, st));
+    if ((nent && ix->n_ent) || (nms && ix->n_ms)) BI_TRY(hipStreamSynchronize(st));            // before the old pools go
+    if (nent) {
+        BiEnt *old = ix->d_ent;
+        ix->d_ent = nent;
+        ix->ent_cap = want_ent;
+        nent = old;
+        if (old) ix->grows++;
+    }
+    if (nms) {
+        uint32_t *old = ix->d_ms;
+        ix->d_ms = nms;
+        ix->ms_cap = want_ms;
+        nms = old;
+    }
+out:
+    (void)hipFree(nent);                                                   // the old pools, or the new ones that were not taken
+    (void)hipFree(nms);
+    return rc;
+}
+
+int itx_bamidx_entries(itx_bamidx *ix, hipStream_t st, const uint8_t *u, const uint32_t *rec_off, uint32_t n, const uint32_t *len_in, const ull *tile_base,
+                       ull stream_at, uint64_t n_counted)
+{
+    if (ix->reason || !n || !n_counted) return ITX_OK;
+    int rc = ITX_OK;
+    if (ix->n_ent + n_counted > ix->ent_cap) {
+        itx_set_error("itx_bamidx_entries: no room was reserved");
+        return ITX_E_STATE;
+    }
+    BI_TRY(hipEventRecord(ix->eb[0], st));
+    hipLaunchKernelGGL(k_bi_entries, dim3((n + BI_TILE - 1) / BI_TILE), dim3(BI_TILE), 0, st, u, rec_off, n, len_in, tile_base, stream_at, (ull)ix->n_ent, ix->d_ent,
+                       ix->n_ref, ix->d_lref, ix->d_flag);
+    BI_TRY(hipGetLastError());
+    BI_TRY(hipEventRecord(ix->eb[1], st));
+    ix->batch_timed = 1;
+    ix->n_ent += n_counted;
+out:
+    return rc;
+}
+
+int itx_bamidx_host_records(itx_bamidx *ix, hipStream_t st, const uint8_t *d_bytes, const uint32_t *h_off, uint32_t n, ull stream_at)
+{
+    if (ix->reason || !n) return ITX_OK;
+    int rc = ITX_OK;
+    const uint32_t nt = (n + BI_TILE - 1) / BI_TILE;
+    if (n > ix->h_cap) {
+        const uint64_t want = (uint64_t)n + n / 2 + 1024, wt = (want + BI_TILE - 1) / BI_TILE + 1;
+        uint32_t *a = nullptr, *b = nullptr;
+        ull *c = nullptr, *d = nullptr, *e = nullptr;
+        if (hipMalloc((void **)&a, 4 * want) != hipSuccess || hipMalloc((void **)&b, 4 * want) != hipSuccess || hipMalloc((void **)&c, 16 * wt) != hipSuccess ||
+            hipMalloc((void **)&d, 16 * wt) != hipSuccess || hipMalloc((void **)&e, 16) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(a);
+            (void)hipFree(b);
+            (void)hipFree(c);
+            (void)hipFree(d);
+            (void)hipFree(e);
+            itx_set_error("itx_bamout_append_host: no device memory for the offsets of %u records", n);
+            return ITX_E_NOMEM;
+        }
+        (void)hipFree(ix->d_hoff);                                         // (st is idle: nothing reads them)
+        (void)hipFree(ix->d_hlen);
+        (void)hipFree(ix->d_hts);
+        (void)hipFree(ix->d_htb);
+        (void)hipFree(ix->d_htot);
+        ix->d_hoff = a;
+        ix->d_hlen = b;
+        ix->d_hts = c;
+        ix->d_htb = d;
+        ix->d_htot = e;
+        ix->h_cap = want;
+    }
+    BI_TRY(hipMemcpyAsync(ix->d_hoff, h_off, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    BI_TRY(hipStreamSynchronize(st));
+    hipLaunchKernelGGL(k_bi_measure, dim3(nt), dim3(BI_TILE), 0, st, d_bytes, ix->d_hoff, n, ix->d_hlen, ix->d_hts);
+    BI_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, st, ix->d_hts, nt, ix->d_htb, ix->d_htot);
+    BI_TRY(hipGetLastError());
+    rc = itx_bamidx_entries(ix, st, d_bytes, ix->d_hoff, n, ix->d_hlen, ix->d_htb, stream_at, n);
+out:
+    return rc;
+}
+
+int itx_bamidx_members(itx_bamidx *ix, hipStream_t st, const uint32_t *d_msize, uint32_t n)
+{
+    if (ix->reason || !n) return ITX_OK;
+    int rc = ITX_OK;
+    if (ix->n_ms + n > ix->ms_cap) {
+        itx_set_error("itx_bamidx_members: no room was reserved");
+        return ITX_E_STATE;
+    }
+    BI_TRY(hipMemcpyAsync(ix->d_ms + ix->n_ms, d_msize, 4 * (size_t)n, hipMemcpyDeviceToDevice, st));
+    ix->n_ms += n;
+out:
+    return rc;
+}
+
+void itx_bamidx_batch_time(itx_bamidx *ix)
+{
+    if (!ix->batch_timed) return;
+    float ms = 0;
+    if (hipEventSynchronize(ix->eb[1]) == hipSuccess && hipEventElapsedTime(&ms, ix->eb[0], ix->eb[1]) == hipSuccess) ix->batch_ms += (double)ms;
+    ix->batch_timed = 0;
+}
+
+static uint32_t bi_sort_passes(int32_t n_ref)
+{
+    uint32_t bits = 16;
+    for (uint32_t v = n_ref > 0 ? (uint32_t)n_ref - 1u : 0u; v; v >>= 1) bits++;
+    return (bits + 7u) / 8u;
+}
+
+int itx_bamidx_finish(itx_bamidx *ix, hipStream_t st, uint64_t first, itx_bamout_index_result *res)
+{
+    memset(res, 0, sizeof *res);
+    if (ix->done) {
+        itx_set_error("itx_bamout_index_finish: called twice");
+        return ITX_E_STATE;
+    }
+    if (ix->reason) {
+        res->status = ix->reason;
+        ix->done = 1;
+        return ITX_OK;
+    }
+    int rc = ITX_OK;
+    const uint32_t N = (uint32_t)ix->n_ent, ntN = (N + BI_TILE - 1) / BI_TILE, n_ref = (uint32_t)ix->n_ref;
+    const uint64_t M = ix->n_ms, W = ix->h_woff[n_ref];
+    uint32_t C = 0, ntC = 0;
+    float ms = 0;
+    uint64_t total = 0;
+    // work arrays: all freed below, whatever happens
+    uint64_t *d_coff = nullptr, *d_cbeg = nullptr, *d_cend = nullptr, *d_fbeg = nullptr, *d_fend = nullptr, *d_roff = nullptr;
+    ull *d_ts = nullptr, *d_tb = nullptr, *d_tot = nullptr, *d_lin = nullptr, *h_tot = nullptr;
+    uint2 *d_k0 = nullptr, *d_k1 = nullptr, *sorted = nullptr;
+    uint32_t *d_hist = nullptr, *d_fkey = nullptr, *d_fbin = nullptr, *d_binfirst = nullptr, *d_refs = nullptr;
+    BiRefs R = {};
+    BI_TRY(hipSetDevice(ix->device));
+    BI_TRY(hipEventRecord(ix->ef[0], st));
+    if (N) {
+        hipLaunchKernelGGL(k_bi_order, dim3((N + 255u) / 256u), dim3(256), 0, st, ix->d_ent, N, ix->d_flag);
+        BI_TRY(hipGetLastError());
+    }
+    BI_TRY(hipMemcpyAsync(ix->h_flag, ix->d_flag, 4, hipMemcpyDeviceToHost, st));
+    BI_TRY(hipStreamSynchronize(st));
+    itx_bamidx_batch_time(ix);
+    res->entries = N;
+    res->grows = ix->grows;
+    res->batch_ms = ix->batch_ms;
+    if (*ix->h_flag) {
+        const uint32_t f = *ix->h_flag;
+        res->status = f & BI_FLAG(ITX_BAI_UNSORTED) ? ITX_BAI_UNSORTED : f & BI_FLAG(ITX_BAI_BEYOND_MAX) ? ITX_BAI_BEYOND_MAX : ITX_BAI_BEYOND_REF;
+        ix->done = 1;
+        goto out;
+    }
+    if (hipMalloc((void **)&d_coff, 8 * (M + 1)) != hipSuccess || hipMalloc((void **)&d_ts, 16 * ((size_t)ntN + 1)) != hipSuccess ||
+        hipMalloc((void **)&d_tb, 16 * ((size_t)ntN + 1)) != hipSuccess || hipMalloc((void **)&d_tot, 16) != hipSuccess ||
+        hipMalloc((void **)&d_lin, 8 * (W + 1)) != hipSuccess || hipMalloc((void **)&d_refs, 4 * 7 * ((size_t)n_ref + 1)) != hipSuccess ||
+        hipMalloc((void **)&d_roff, 8 * ((size_t)n_ref + 1)) != hipSuccess || hipHostMalloc((void **)&h_tot, 16, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        itx_set_error("itx_bamout_index_finish: no memory for %u entries, %llu members and %llu windows", N, (ull)M, (ull)W);
+        rc = ITX_E_NOMEM;
+        goto out;
+    }
+    R.f0 = d_refs;
+    R.f1 = d_refs + 1 * ((size_t)n_ref + 1);
+    R.b0 = d_refs + 2 * ((size_t)n_ref + 1);
+    R.b1 = d_refs + 3 * ((size_t)n_ref + 1);
+    R.e0 = d_refs + 4 * ((size_t)n_ref + 1);
+    R.e1 = d_refs + 5 * ((size_t)n_ref + 1);
+    R.n_intv = d_refs + 6 * ((size_t)n_ref + 1);
+    BI_TRY(hipMemsetAsync(d_refs, 0, 4 * 7 * ((size_t)n_ref + 1), st));
+    BI_TRY(hipMemsetAsync(d_lin, 0xff, 8 * (W + 1), st));
+    BI_TRY(hipMemsetAsync(d_tot, 0, 16, st));
+    hipLaunchKernelGGL(k_bi_coff, dim3(1), dim3(ITX_SCAN_WG), 0, st, ix->d_ms, M, d_coff);
+    BI_TRY(hipGetLastError());
+    if (N) {
+        hipLaunchKernelGGL(k_bi_heads, dim3(ntN), dim3(BI_TILE), 0, st, ix->d_ent, N, d_ts);
+        BI_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, st, d_ts, ntN, d_tb, d_tot);
+        BI_TRY(hipGetLastError());
+        BI_TRY(hipMemcpyAsync(h_tot, d_tot, 16, hipMemcpyDeviceToHost, st));
+        BI_TRY(hipStreamSynchronize(st));                                  // the number of chunks sizes what follows
+        C = (uint32_t)h_tot[0];
+        ntC = (C + BI_TILE - 1) / BI_TILE;
+        const uint32_t nwg = (C + SORT_CHUNK - 1) / SORT_CHUNK, passes = bi_sort_passes(ix->n_ref);
+        if (hipMalloc((void **)&d_cbeg, 8 * (size_t)C) != hipSuccess || hipMalloc((void **)&d_cend, 8 * (size_t)C) != hipSuccess ||
+            hipMalloc((void **)&d_fbeg, 8 * (size_t)C) != hipSuccess || hipMalloc((void **)&d_fend, 8 * (size_t)C) != hipSuccess ||
+            hipMalloc((void **)&d_k0, 8 * (size_t)C) != hipSuccess || hipMalloc((void **)&d_k1, 8 * (size_t)C) != hipSuccess ||
+            hipMalloc((void **)&d_hist, 4 * 256 * (size_t)nwg) != hipSuccess || hipMalloc((void **)&d_fkey, 4 * (size_t)C) != hipSuccess ||
+            hipMalloc((void **)&d_fbin, 4 * (size_t)C) != hipSuccess || hipMalloc((void **)&d_binfirst, 4 * ((size_t)C + 1)) != hipSuccess) {
+            (void)hipGetLastError();
+            itx_set_error("itx_bamout_index_finish: no device memory for %u chunks", C);
+            rc = ITX_E_NOMEM;
+            goto out;
+        }
+        hipLaunchKernelGGL(k_bi_chunks, dim3(ntN), dim3(BI_TILE), 0, st, ix->d_ent, N, d_tb, d_coff, first, d_k0, d_cbeg, d_cend);
+        BI_TRY(hipGetLastError());
+        sorted = d_k0;
+        for (uint32_t p = 0; p < passes; p++) {
+            uint2 *to = sorted == d_k0 ? d_k1 : d_k0;
+            hipLaunchKernelGGL(k_sort_hist, dim3(nwg), dim3(256), 0, st, sorted, C, 8u * p, d_hist, nwg);
+            BI_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(ITX_SCAN_WG), 0, st, d_hist, 256u * nwg);
+            BI_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_sort_scatter, dim3(nwg), dim3(256), 0, st, sorted, to, C, 8u * p, d_hist, nwg);
+            BI_TRY(hipGetLastError());
+            sorted = to;
+        }
+        hipLaunchKernelGGL(k_bi_merge_count, dim3(ntC), dim3(BI_TILE), 0, st, sorted, C, d_cbeg, d_cend, d_ts);
+        BI_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, st, d_ts, ntC, d_tb, d_tot);
+        BI_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_bi_merge_apply, dim3(ntC), dim3(BI_TILE), 0, st, sorted, C, d_cbeg, d_cend, d_tb, d_fkey, d_fbin, d_fbeg, d_fend, d_binfirst, R);
+        BI_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_bi_windows, dim3((N + 255u) / 256u), dim3(256), 0, st, ix->d_ent, N, d_coff, first, ix->d_woff, d_lin, R);
+        BI_TRY(hipGetLastError());
+    }
+    if (n_ref) {
+        hipLaunchKernelGGL(k_bi_fill, dim3(n_ref), dim3(256), 0, st, ix->d_woff, d_lin, R.n_intv);
+        BI_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_bi_refsize, dim3(1), dim3(ITX_SCAN_WG), 0, st, n_ref, R, d_roff);
+    BI_TRY(hipGetLastError());
+    BI_TRY(hipMemcpyAsync(h_tot, d_tot, 16, hipMemcpyDeviceToHost, st));
+    BI_TRY(hipMemcpyAsync(ix->h_flag + 2, d_roff + n_ref, 8, hipMemcpyDeviceToHost, st));
+    BI_TRY(hipStreamSynchronize(st));                                      // the file's size
+    memcpy(&total, ix->h_flag + 2, 8);
+    total += 8;
+    if (hipMalloc((void **)&ix->d_out, total) != hipSuccess || hipHostMalloc((void **)&ix->h_out, total, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        itx_set_error("itx_bamout_index_finish: no memory for an index of %llu bytes", (ull)total);
+        rc = ITX_E_NOMEM;
+        goto out;
+    }
+    hipLaunchKernelGGL(k_bi_write_refs, dim3(n_ref / 256u + 1u), dim3(256), 0, st, n_ref, R, d_roff, ix->d_ent, d_coff, first, ix->d_out);
+    BI_TRY(hipGetLastError());
+    if (C) {
+        hipLaunchKernelGGL(k_bi_write_chunks, dim3(ntC), dim3(256), 0, st, d_tot, d_fkey, d_fbin, d_fbeg, d_fend, d_binfirst, R, d_roff, ix->d_out);
+        BI_TRY(hipGetLastError());
+    }
+    if (n_ref) {
+        hipLaunchKernelGGL(k_bi_write_linear, dim3(n_ref), dim3(256), 0, st, R, d_roff, ix->d_woff, d_lin, ix->d_out);
+        BI_TRY(hipGetLastError());
+    }
+    BI_TRY(hipMemcpyAsync(ix->h_out, ix->d_out, total, hipMemcpyDeviceToHost, st));
+    BI_TRY(hipEventRecord(ix->ef[1], st));
+    BI_TRY(hipStreamSynchronize(st));
+    if (hipEventElapsedTime(&ms, ix->ef[0], ix->ef[1]) == hipSuccess) ix->finish_ms = (double)ms;
+    res->bytes = ix->h_out;
+    res->len = total;
+    res->chunks = C ? h_tot[0] : 0;
+    res->finish_ms = ix->finish_ms;
+    ix->done = 1;
+out:
+    (void)hipFree(d_coff);
+    (void)hipFree(d_cbeg);
+    (void)hipFree(d_cend);
+    (void)hipFree(d_fbeg);
+    (void)hipFree(d_fend);
+    (void)hipFree(d_roff);
+    (void)hipFree(d_ts);
+    (void)hipFree(d_tb);
+    (void)hipFree(d_tot);
+    (void)hipFree(d_lin);
+    (void)hipFree(d_k0);
+    (void)hipFree(d_k1);
+    (void)hipFree(d_hist);
+    (void)hipFree(d_fkey);
+    (void)hipFree(d_fbin);
+    (void)hipFree(d_binfirst);
+    (void)hipFree(d_refs);
+    if (h_tot) (void)hipHostFree(h_tot);
+    if (rc != ITX_OK) {
+        (void)hipFree(ix->d_out);
+        if (ix->h_out) (void)hipHostFree(ix->h_out);
+        ix->d_out = ix->h_out = nullptr;
+    }
+    return rc;
+}

@@ -19,9 +19,12 @@
 // while the next batch's kernels run — the bed route's arrangement.
 // What the host route counted joins the same stream in stream order (itx_bamout_append_host), so the file is one ordered stream
 // whatever route a window took. itx_bamout_finish makes the last, short payload a member.
+// With itx_bamout_index_enable (filter -b -i) the stream's .bai index is collected beside it and made at the end
+// (csrc/itx_bamidx.hip): an entry per counted record behind every gather, every batch's member sizes behind those before.
 //
 // Byte and integer work. k_bo_member is bound by the encoder's serial parse (one lane per member); ITX_BAMOUT_PAYLOAD is chosen
 // for that (itx_bgzfmember.h). No kernel uses scratch (DESIGN.md has the figures).
+#include "itx_bamidx.h"
 #include "itx_textpack.h"
 
 #include <stdlib.h>
@@ -42,6 +45,7 @@ typedef unsigned long long ull;
 #define BO_MAX_RECORD 0x40000000u    // a record of a gibibyte is nobody's: the decoder's windows hold less
 
 static_assert(BO_P % 16u == 0 && BO_P <= ITXD_MAX_IN, "the payload: at most one DEFLATE window, whole 16-byte vectors");
+static_assert(BO_TILE == ITX_BAMIDX_TILE && BO_P == ITX_BAMIDX_PAYLOAD, "the index (itx_bamidx.hip) places records by the gather's tiles and payloads");
 
 __global__ __launch_bounds__(BO_TILE) void k_bo_measure(const uint8_t *__restrict__ u, const uint32_t *__restrict__ rec_off, const int32_t *__restrict__ hit_row,
                                                          uint32_t n, uint32_t *__restrict__ len_out, ull *__restrict__ tile_sum, ull *__restrict__ tot)
@@ -184,6 +188,8 @@ struct itx_bamout {
     int head, pending;               // the oldest batch not yet collected; batches not yet collected
     int finished;
     itx_bamout_stats stats;
+    itx_bamidx *ix;                  // filter -b -i (itx_bamout_index_enable): the .bai index in the making, else null
+    ull stream_base;                 // bytes of the record stream that are members already: d_pay[0] is this byte of the stream
 };
 
 static int bo_hip(hipError_t e, const char *what, int line)
@@ -224,6 +230,7 @@ extern "C" void itx_bamout_destroy(itx_bamout *bo)
     (void)hipFree(bo->d_msize);
     (void)hipFree(bo->d_moff);
     if (bo->h_tot) (void)hipHostFree(bo->h_tot);
+    itx_bamidx_destroy(bo->ix);
     delete bo;
 }
 
@@ -273,6 +280,7 @@ extern "C" void *itx_bamout_stream(itx_bamout *bo) { return bo ? (void *)bo->st 
 
 static void bo_read_gather_time(itx_bamout *bo)
 {
+    if (bo->ix) itx_bamidx_batch_time(bo->ix);
     if (!bo->gather_timed) return;
     float ms = 0;
     if (hipEventElapsedTime(&ms, bo->ev[2], bo->ev[3]) == hipSuccess) bo->stats.gather_ms += (double)ms;
@@ -362,6 +370,7 @@ static int bo_emit(itx_bamout *bo, ull total, int with_tail)
         BO_TRY(hipEventRecord(s->e0, bo->st));
         hipLaunchKernelGGL(k_bo_member, dim3(n_mem), dim3(64), 0, bo->st, bo->d_pay, with_tail ? total : n_full * BO_P, bo->d_mem, bo->d_msize);
         BO_TRY(hipGetLastError());
+        if (bo->ix && (rc = itx_bamidx_members(bo->ix, bo->st, bo->d_msize, n_mem)) != ITX_OK) goto out;
         hipLaunchKernelGGL(k_bo_scan, dim3(1), dim3(ITX_SCAN_WG), 0, bo->st, bo->d_msize, (uint64_t)n_mem, bo->d_moff);
         BO_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_bo_pack, dim3(n_mem), dim3(256), 0, bo->st, bo->d_mem, bo->d_msize, bo->d_moff, s->d_packed);
@@ -379,6 +388,7 @@ static int bo_emit(itx_bamout *bo, ull total, int with_tail)
         if (n_full && rest) BO_TRY(hipMemcpyAsync(bo->d_pay, bo->d_pay + n_full * BO_P, (size_t)rest, hipMemcpyDeviceToDevice, bo->st));   // (rest < BO_P: no overlap)
         bo->carry = (size_t)rest;
     }
+    bo->stream_base += with_tail ? total : n_full * BO_P;
 out:
     return rc;
 }
@@ -431,6 +441,7 @@ int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, 
     }
     total = (ull)bo->carry + bo->h_tot[0];
     if ((rc = bo_reserve(bo, total, total / BO_P)) != ITX_OK) goto out;
+    if (bo->ix && (rc = itx_bamidx_reserve(bo->ix, bo->st, bo->h_tot[1], total / BO_P)) != ITX_OK) goto out;
     BO_TRY(hipEventRecord(bo->ev[2], bo->st));
     if (bo->h_tot[0]) {
         hipLaunchKernelGGL(k_bo_gather, dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, (uint32_t)n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->d_pay);
@@ -438,6 +449,8 @@ int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, 
     }
     BO_TRY(hipEventRecord(bo->ev[3], bo->st));
     bo->gather_timed = 1;
+    if (bo->ix && (rc = itx_bamidx_entries(bo->ix, bo->st, u, rec_off, (uint32_t)n, bo->d_len, bo->d_tile_base, bo->stream_base + bo->carry, bo->h_tot[1])) != ITX_OK)
+        goto out;
     bo->stats.batches++;
     bo->stats.records += bo->h_tot[1];
     bo->stats.payload_bytes += bo->h_tot[0];
@@ -481,6 +494,11 @@ extern "C" int itx_bamout_append_host(itx_bamout *bo, const void *bytes, size_t 
         return ITX_E_STATE;
     }
     size_t at = 0, n_rec = 0;
+    uint32_t *h_off = nullptr;                                             // with an index: where every record starts
+    if (bo->ix && len >= 0xffffff00ull) {
+        itx_set_error("itx_bamout_append_host: %zu bytes in one call while an index is built", len);
+        return ITX_E_LIMIT;
+    }
     while (at < len) {                                                     // whole records, or nothing is appended
         uint32_t bs = 0;
         if (len - at >= 4) memcpy(&bs, (const uint8_t *)bytes + at, 4);
@@ -494,6 +512,19 @@ extern "C" int itx_bamout_append_host(itx_bamout *bo, const void *bytes, size_t 
     if (!len) return ITX_OK;
     int rc = ITX_OK;
     const ull total = (ull)bo->carry + len;
+    if (bo->ix) {
+        if (!(h_off = (uint32_t *)malloc(4 * n_rec))) {
+            itx_set_error("itx_bamout_append_host: no memory for the offsets of %zu records", n_rec);
+            return ITX_E_NOMEM;
+        }
+        at = 0;
+        for (size_t i = 0; i < n_rec; i++) {
+            uint32_t bs;
+            memcpy(&bs, (const uint8_t *)bytes + at, 4);
+            h_off[i] = (uint32_t)at;
+            at += 4 + (size_t)bs;
+        }
+    }
     BO_TRY(hipSetDevice(bo->device));
     {
         const double t0 = itx_wall_now();
@@ -502,13 +533,16 @@ extern "C" int itx_bamout_append_host(itx_bamout *bo, const void *bytes, size_t 
     }
     bo_read_gather_time(bo);
     if ((rc = bo_reserve(bo, total, total / BO_P)) != ITX_OK) goto out;
+    if (bo->ix && (rc = itx_bamidx_reserve(bo->ix, bo->st, n_rec, total / BO_P)) != ITX_OK) goto out;
     BO_TRY(hipMemcpyAsync(bo->d_pay + bo->carry, bytes, len, hipMemcpyHostToDevice, bo->st));
     BO_TRY(hipStreamSynchronize(bo->st));                                  // the caller's bytes are its own again
+    if (bo->ix && (rc = itx_bamidx_host_records(bo->ix, bo->st, bo->d_pay + bo->carry, h_off, (uint32_t)n_rec, bo->stream_base + bo->carry)) != ITX_OK) goto out;
     bo->stats.host_batches++;
     bo->stats.records += n_rec;
     bo->stats.payload_bytes += len;
     rc = bo_emit(bo, total, 0);
 out:
+    free(h_off);
     return rc;
 }
 
@@ -528,6 +562,7 @@ extern "C" int itx_bamout_finish(itx_bamout *bo)
     bo_read_gather_time(bo);
     if (bo->carry) {
         if ((rc = bo_reserve(bo, bo->carry, 1)) != ITX_OK) goto out;
+        if (bo->ix && (rc = itx_bamidx_reserve(bo->ix, bo->st, 0, 1)) != ITX_OK) goto out;
         if ((rc = bo_emit(bo, bo->carry, 1)) != ITX_OK) goto out;
     }
     bo->finished = 1;
@@ -585,4 +620,35 @@ extern "C" int itx_bamout_get_stats(const itx_bamout *bo, itx_bamout_stats *out)
     *out = bo->stats;
     out->carry = bo->carry;
     return ITX_OK;
+}
+
+// ---- the .bai index of the stream (csrc/itx_bamidx.hip)
+extern "C" int itx_bamout_index_enable(itx_bamout *bo, int32_t n_ref, const int32_t *l_ref)
+{
+    if (!bo || n_ref < 0 || (n_ref && !l_ref)) {
+        itx_set_error("itx_bamout_index_enable: bad argument");
+        return ITX_E_ARG;
+    }
+    if (bo->ix || bo->finished || bo->stats.batches || bo->stats.host_batches) {
+        itx_set_error("itx_bamout_index_enable: %s", bo->ix ? "called twice" : "the stream has begun");
+        return ITX_E_STATE;
+    }
+    return itx_bamidx_create(bo->device, n_ref, l_ref, &bo->ix);
+}
+
+extern "C" int itx_bamout_index_finish(itx_bamout *bo, uint64_t first_member_offset, itx_bamout_index_result *out)
+{
+    if (!bo || !out) {
+        itx_set_error("itx_bamout_index_finish: bad argument");
+        return ITX_E_ARG;
+    }
+    if (!bo->ix || !bo->finished) {
+        itx_set_error("itx_bamout_index_finish: %s", bo->ix ? "the stream is not finished (itx_bamout_finish)" : "no index was asked for (itx_bamout_index_enable)");
+        return ITX_E_STATE;
+    }
+    if (first_member_offset >> 47) {
+        itx_set_error("itx_bamout_index_finish: a first member at byte %llu", (ull)first_member_offset);
+        return ITX_E_LIMIT;
+    }
+    return itx_bamidx_finish(bo->ix, bo->st, first_member_offset, out);
 }

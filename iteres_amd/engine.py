@@ -34,7 +34,8 @@ EXPORTS = [
     "itx_names_create", "itx_names_destroy", "itx_names_hits", "itx_names_stream", "itx_bamwin_names", "itx_names_run", "itx_names_wait_kernels", "itx_names_append_host",
     "itx_names_finish", "itx_names_get_stats",
     "itx_bamout_create", "itx_bamout_destroy", "itx_bamout_hits", "itx_bamout_stream", "itx_bamwin_bamout", "itx_bamout_run", "itx_bamout_wait_kernels",
-    "itx_bamout_append_host", "itx_bamout_finish", "itx_bamout_collect", "itx_bamout_pending", "itx_bamout_get_stats",
+    "itx_bamout_append_host", "itx_bamout_finish", "itx_bamout_collect", "itx_bamout_pending", "itx_bamout_get_stats", "itx_bamout_index_enable",
+    "itx_bamout_index_finish",
     "itx_loci_create", "itx_loci_destroy", "itx_loci_order", "itx_loci_filter_text", "itx_loci_cpg_text",
     "itx_samtext_create", "itx_samtext_destroy", "itx_samtext_parse_begin", "itx_samtext_parse_end", "itx_samtext_fetch",
     "itx_samtext_parse_begin_bgzf", "itx_samtext_bgzf_info", "itx_samtext_text", "itx_samtext_strings",
@@ -126,6 +127,11 @@ class BamoutStats(C.Structure):
     _fields_ = [("batches", C.c_uint64), ("host_batches", C.c_uint64), ("records", C.c_uint64), ("payload_bytes", C.c_uint64), ("members", C.c_uint64),
                 ("out_bytes", C.c_uint64), ("grows", C.c_uint64), ("carry", C.c_uint64), ("gather_ms", C.c_double), ("member_ms", C.c_double),
                 ("wait_ms", C.c_double)]
+
+
+class BamoutIndexResult(C.Structure):
+    _fields_ = [("bytes", C.c_void_p), ("len", C.c_uint64), ("status", C.c_int32), ("pad", C.c_int32), ("entries", C.c_uint64), ("chunks", C.c_uint64),
+                ("grows", C.c_uint64), ("batch_ms", C.c_double), ("finish_ms", C.c_double)]
 
 
 class LociText(C.Structure):
@@ -258,6 +264,8 @@ def load():
     L.itx_bamout_collect.argtypes = [C.c_void_p, C.POINTER(BamoutMembers)]
     L.itx_bamout_pending.argtypes = [C.c_void_p]
     L.itx_bamout_get_stats.argtypes = [C.c_void_p, C.POINTER(BamoutStats)]
+    L.itx_bamout_index_enable.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.itx_bamout_index_finish.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(BamoutIndexResult)]
     L.itx_loci_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                   C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
     L.itx_loci_destroy.argtypes = [C.c_void_p]
@@ -790,6 +798,18 @@ class Bamout:
         _chk(load().itx_bamout_finish(self._h), "itx_bamout_finish")
         self._drain()
         return bytes(self.out)
+
+    def index_enable(self, l_ref):
+        """before the first batch: the .bai index of the stream is built beside it (l_ref: the header's reference lengths)"""
+        a = (C.c_int32 * max(len(l_ref), 1))(*l_ref)
+        _chk(load().itx_bamout_index_enable(self._h, len(l_ref), a), "itx_bamout_index_enable")
+
+    def index_finish(self, first_member_offset):
+        """after finish(): (status, the .bai file's bytes or None, the result's counters)"""
+        r = BamoutIndexResult()
+        _chk(load().itx_bamout_index_finish(self._h, first_member_offset, C.byref(r)), "itx_bamout_index_finish")
+        info = {k: getattr(r, k) for k, _ in BamoutIndexResult._fields_ if k not in ("bytes", "pad")}
+        return r.status, (C.string_at(r.bytes, r.len) if r.status == 0 else None), info
 
     def stats(self):
         s = BamoutStats()

@@ -399,6 +399,7 @@ typedef struct {
     itx_bamout *bo;
     FILE *bam_f;
     int bam_header_done;
+    uint64_t bam_first;                            /* -b -i: where the first record member starts in the file */
     struct { uint8_t *bytes; size_t cap; } bbuf;
     unsigned long long bam_dev_batches, bam_host_batches;
     /* the host route: two pinned slots, taken when a batch first goes that way; s is filled next, pend[] are in flight */
@@ -541,6 +542,51 @@ static void bam_write_out(stream_run *r, int keep)
         chk(itx_bamout_collect(r->bo, &m), "itx_bamout_collect");
         if (m.len && fwrite(m.bytes, 1, m.len, r->bam_f) != m.len) die("writing %s: %s", r->o->bam_out_path, strerror(errno));
     }
+}
+
+/* filter -b -i: the index is built beside the stream (csrc/itx_bamidx.hip). The reference lengths of the kept header size its linear
+ * part; the first record member starts where the header's members end. */
+static void bam_index_begin(stream_run *r, const uint8_t *hb, size_t hl)
+{
+    int32_t l_text = 0, n_ref = 0;
+    size_t at = 8;
+    if (hl >= 8) memcpy(&l_text, hb + 4, 4);
+    if (hl < 12 || l_text < 0 || (size_t)l_text > hl - 12) die("%s: the kept BAM header is cut short", r->o->bam_out_path);
+    at += (size_t)l_text;
+    memcpy(&n_ref, hb + at, 4);
+    at += 4;
+    if (n_ref < 0) die("%s: the kept BAM header names %d references", r->o->bam_out_path, n_ref);
+    int32_t *l_ref = xcalloc((size_t)n_ref + 1, sizeof(int32_t));
+    for (int32_t k = 0; k < n_ref; k++) {
+        int32_t l_name = 0;
+        if (hl - at >= 4) memcpy(&l_name, hb + at, 4);
+        if (hl - at < 4 || l_name < 0 || (size_t)l_name + 8 > hl - at) die("%s: the kept BAM header is cut short", r->o->bam_out_path);
+        memcpy(&l_ref[k], hb + at + 4 + (size_t)l_name, 4);
+        at += 8 + (size_t)l_name;
+    }
+    chk(itx_bamout_index_enable(r->bo, n_ref, l_ref), "itx_bamout_index_enable");
+    free(l_ref);
+    const long first = ftell(r->bam_f);
+    if (first < 0) die("%s: %s", r->o->bam_out_path, strerror(errno));
+    r->bam_first = (uint64_t)first;
+}
+
+/* filter -b -i, after the last members: the finished index is written, or one line says why there is none */
+static void bam_index_end(stream_run *r, itx_bamout_index_result *ir)
+{
+    static const char *const why[] = {"", "the counted records are not in coordinate order", "a record ends beyond 2^29", "a record ends beyond its reference's length in the BAM header",
+                                      "the BAM header names 65536 references or more"};
+    chk(itx_bamout_index_finish(r->bo, r->bam_first, ir), "itx_bamout_index_finish");
+    if (ir->status != 0) {
+        fprintf(stderr, "[iteres] no index is written for %s: %s\n", r->o->bam_out_path, ir->status >= 1 && ir->status <= 4 ? why[ir->status] : "unknown reason");
+        return;
+    }
+    char *path = NULL;
+    if (asprintf(&path, "%s.bai", r->o->bam_out_path) < 0) die("Preparing output wrong");
+    FILE *f = fopen(path, "wb");
+    if (!f) die("mustOpen: Can't open %s to write: %s", path, strerror(errno));
+    if (fwrite(ir->bytes, 1, ir->len, f) != ir->len || fclose(f) != 0) die("writing %s: %s", path, strerror(errno));
+    free(path);
 }
 
 /* filter -b: the records of slot k that chose a row, as the reader kept their bytes, to the device's stream in record order */
@@ -871,6 +917,7 @@ static void map_targets(stream_run *r, stream_file *f)
         if (bgzf_write_members(r->bam_f, hb, hl) != 0) die("writing %s: %s", o->bam_out_path, strerror(errno));
         r->bam_header_done = 1;
         chk(itx_bamout_create(multi_device(), BATCH_RECORDS, 0, &r->bo), "itx_bamout_create");
+        if (o->bam_index) bam_index_begin(r, hb, hl);
     }
 }
 
@@ -1216,13 +1263,19 @@ static void finish_bam(stream_run *r)
     }
     if (bgzf_write_eof(r->bam_f) != 0 || fclose(r->bam_f) != 0) die("writing %s: %s", r->o->bam_out_path, strerror(errno));
     r->bam_f = NULL;
+    itx_bamout_index_result ir;
+    memset(&ir, 0, sizeof ir);
+    if (r->bo && r->o->bam_index) bam_index_end(r, &ir);
     if (r->timing) {
         itx_bamout_stats bs;
         memset(&bs, 0, sizeof bs);
         if (r->bo) chk(itx_bamout_get_stats(r->bo, &bs), "itx_bamout_get_stats");
-        fprintf(stderr, "[itx timing] bam out: %llu records, %llu payload bytes, %llu members (%llu bytes), %.3f ms in the gather kernels, %.3f ms in the member kernels, host waited %.3f s, %llu batches gathered on the device, %llu batches by the host route\n",
+        fprintf(stderr, "[itx timing] bam out: %llu records, %llu payload bytes, %llu members (%llu bytes), %.3f ms in the gather kernels, %.3f ms in the member kernels, host waited %.3f s, %llu batches gathered on the device, %llu batches by the host route%s",
                 (unsigned long long)bs.records, (unsigned long long)bs.payload_bytes, (unsigned long long)bs.members, (unsigned long long)bs.out_bytes, bs.gather_ms,
-                bs.member_ms, 1e-3 * bs.wait_ms, r->bam_dev_batches, r->bam_host_batches);
+                bs.member_ms, 1e-3 * bs.wait_ms, r->bam_dev_batches, r->bam_host_batches, r->o->bam_index ? "" : "\n");
+        if (r->o->bam_index)
+            fprintf(stderr, "; index: %llu entries, %llu chunks, %llu bytes, %.3f ms in the entry kernels, %.3f ms in the final kernels\n", (unsigned long long)ir.entries,
+                    (unsigned long long)ir.chunks, (unsigned long long)ir.len, ir.batch_ms, ir.finish_ms);
     }
     itx_bamout_destroy(r->bo);
     r->bo = NULL;
