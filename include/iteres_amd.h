@@ -524,6 +524,27 @@ typedef struct itx_bamout_index_result {
 } itx_bamout_index_result;
 int itx_bamout_index_enable(itx_bamout *bo, int32_t n_ref, const int32_t *l_ref);
 int itx_bamout_index_finish(itx_bamout *bo, uint64_t first_member_offset, itx_bamout_index_result *out);
+/* The same stream in coordinate order (filter -b -s; the order is csrc/itx_bamsortrule.h: tid, pos, reverse strand, equal keys in
+ * stream order). The counted records are held in device memory until the stream ends, sorted there and replayed through the
+ * member path, so the members are those a plain run over the sorted stream would make.
+ *   sort_enable  before the first batch (ITX_E_STATE after it, or when called twice). From then on run / itx_bamwin_bamout /
+ *               append_host make no member (nothing is pending, the two-batch limit does not apply), stats.carry counts the held
+ *               bytes, and itx_bamout_finish is refused with ITX_E_STATE.
+ *   sort_next   after the last batch, in place of finish, until *more is 0 (ITX_E_STATE without sort_enable, and once *more was
+ *               0). The first call sorts; every call replays one round of at most batch_capacity records, which is one batch
+ *               for collect: collect between the calls as between batches. The last round ends with the short last member. A
+ *               counted record with tid < 0 or pos < 0: ITX_E_LIMIT before any member is made. No record: no member. After the
+ *               first call run / append_host are refused with ITX_E_STATE. With index_enable the index is that of the sorted
+ *               stream; index_finish follows the last round.
+ * 2^32 - 2 records or more: ITX_E_LIMIT. The held stream and the sort need device memory for about twice the counted bytes:
+ * ITX_E_NOMEM says to run without the sort; the object stays as it was. */
+typedef struct itx_bamout_sort_stats {
+    uint64_t records, rounds, pool_grows;    /* records held; rounds replayed so far; times the entry pool grew */
+    double sort_ms, replay_ms;               /* device time: the radix sort; the rounds' lengths, scans and gathers */
+} itx_bamout_sort_stats;
+int itx_bamout_sort_enable(itx_bamout *bo);
+int itx_bamout_sort_next(itx_bamout *bo, int *more);
+int itx_bamout_sort_get_stats(const itx_bamout *bo, itx_bamout_sort_stats *out);
 
 /* ---- the .loci file of filter / cpgfilter on the device ----------------------------------------------------------------------
  * Replaces the row walk and the fprintf of writeFilterOut (generic.c:1709-1746) and writeFilterOutMRE (generic.c:1748-1772): the

@@ -19,6 +19,9 @@ int itx_bamidx_reserve(itx_bamidx *ix, hipStream_t st, uint64_t n_entries, uint6
 // the records of the tiles before. n_counted: how many entries that makes (the measure's total). Enqueued, not waited for.
 int itx_bamidx_entries(itx_bamidx *ix, hipStream_t st, const uint8_t *u, const uint32_t *rec_off, uint32_t n, const uint32_t *len_in,
                        const unsigned long long *tile_base, unsigned long long stream_at, uint64_t n_counted);
+// the same with 64-bit offsets: the records of one round of filter -b -s, where they lie in the held stream (itx_bamout_sort_next)
+int itx_bamidx_entries64(itx_bamidx *ix, hipStream_t st, const uint8_t *u, const unsigned long long *rec_off, uint32_t n, const uint32_t *len_in,
+                         const unsigned long long *tile_base, unsigned long long stream_at, uint64_t n_counted);
 // the host route: d_bytes (device) holds n whole records one behind the other, h_off[i] where record i starts in them; the
 // offsets are uploaded (waited for: h_off is the caller's again), measured, and the same entry kernel runs over them
 int itx_bamidx_host_records(itx_bamidx *ix, hipStream_t st, const uint8_t *d_bytes, const uint32_t *h_off, uint32_t n, unsigned long long stream_at);

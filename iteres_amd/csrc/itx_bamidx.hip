@@ -70,7 +70,9 @@ __global__ __launch_bounds__(BI_TILE) void k_bi_measure(const uint8_t *__restric
     }
 }
 
-__global__ __launch_bounds__(BI_TILE) void k_bi_entries(const uint8_t *__restrict__ u, const uint32_t *__restrict__ rec_off, uint32_t n, const uint32_t *__restrict__ len_in,
+// OFF: uint32_t offsets into a window or a host batch; 64-bit offsets into the held stream of filter -b -s (itx_bamout_sort_next)
+template <class OFF>
+__global__ __launch_bounds__(BI_TILE) void k_bi_entries(const uint8_t *__restrict__ u, const OFF *__restrict__ rec_off, uint32_t n, const uint32_t *__restrict__ len_in,
                                                          const ull *__restrict__ tile_base, ull stream_at, ull ent_at, BiEnt *__restrict__ ent, int32_t n_ref,
                                                          const int32_t *__restrict__ l_ref, uint32_t *__restrict__ flag)
 {
@@ -505,8 +507,9 @@ out:
     return rc;
 }
 
-int itx_bamidx_entries(itx_bamidx *ix, hipStream_t st, const uint8_t *u, const uint32_t *rec_off, uint32_t n, const uint32_t *len_in, const ull *tile_base,
-                       ull stream_at, uint64_t n_counted)
+template <class OFF>
+static int bi_entries(itx_bamidx *ix, hipStream_t st, const uint8_t *u, const OFF *rec_off, uint32_t n, const uint32_t *len_in, const ull *tile_base, ull stream_at,
+                      uint64_t n_counted)
 {
     if (ix->reason || !n || !n_counted) return ITX_OK;
     int rc = ITX_OK;
@@ -515,14 +518,26 @@ int itx_bamidx_entries(itx_bamidx *ix, hipStream_t st, const uint8_t *u, const u
         return ITX_E_STATE;
     }
     BI_TRY(hipEventRecord(ix->eb[0], st));
-    hipLaunchKernelGGL(k_bi_entries, dim3((n + BI_TILE - 1) / BI_TILE), dim3(BI_TILE), 0, st, u, rec_off, n, len_in, tile_base, stream_at, (ull)ix->n_ent, ix->d_ent,
-                       ix->n_ref, ix->d_lref, ix->d_flag);
+    hipLaunchKernelGGL((k_bi_entries<OFF>), dim3((n + BI_TILE - 1) / BI_TILE), dim3(BI_TILE), 0, st, u, rec_off, n, len_in, tile_base, stream_at, (ull)ix->n_ent,
+                       ix->d_ent, ix->n_ref, ix->d_lref, ix->d_flag);
     BI_TRY(hipGetLastError());
     BI_TRY(hipEventRecord(ix->eb[1], st));
     ix->batch_timed = 1;
     ix->n_ent += n_counted;
 out:
     return rc;
+}
+
+int itx_bamidx_entries(itx_bamidx *ix, hipStream_t st, const uint8_t *u, const uint32_t *rec_off, uint32_t n, const uint32_t *len_in, const ull *tile_base,
+                       ull stream_at, uint64_t n_counted)
+{
+    return bi_entries(ix, st, u, rec_off, n, len_in, tile_base, stream_at, n_counted);
+}
+
+int itx_bamidx_entries64(itx_bamidx *ix, hipStream_t st, const uint8_t *u, const ull *rec_off, uint32_t n, const uint32_t *len_in, const ull *tile_base, ull stream_at,
+                         uint64_t n_counted)
+{
+    return bi_entries(ix, st, u, rec_off, n, len_in, tile_base, stream_at, n_counted);
 }
 
 int itx_bamidx_host_records(itx_bamidx *ix, hipStream_t st, const uint8_t *d_bytes, const uint32_t *h_off, uint32_t n, ull stream_at)

@@ -22,9 +22,18 @@
 // With itx_bamout_index_enable (filter -b -i) the stream's .bai index is collected beside it and made at the end
 // (csrc/itx_bamidx.hip): an entry per counted record behind every gather, every batch's member sizes behind those before.
 //
+// With itx_bamout_sort_enable (filter -b -s) the stream is held whole instead of being cut: every gather appends to it, and one lane
+// per record appends {tid, pos << 1 | reverse, where the record lies, its length} to a pool (k_bs_entries; the rule is
+// csrc/itx_bamsortrule.h). After the last batch itx_bamout_sort_next sorts (key, index) pairs with itx_radixsort.h, by the low key
+// and then by tid, stable, and replays the records in sorted order a round of at most batch_capacity at a time through the path
+// above: k_bs_lengths lays the round's lengths and 64-bit offsets out in sorted order, k_tile_scan2, then k_bo_gather reads the held
+// stream (scattered, a record each) and writes the payload stream (coalesced), then members, scan and pack as for any batch.
+//
 // Byte and integer work. k_bo_member is bound by the encoder's serial parse (one lane per member); ITX_BAMOUT_PAYLOAD is chosen
 // for that (itx_bgzfmember.h). No kernel uses scratch (DESIGN.md has the figures).
 #include "itx_bamidx.h"
+#include "itx_bamsortrule.h"
+#include "itx_radixsort.h"
 #include "itx_textpack.h"
 
 #include <stdlib.h>
@@ -75,7 +84,9 @@ __global__ __launch_bounds__(BO_TILE) void k_bo_measure(const uint8_t *__restric
     if (threadIdx.x < 2) tile_sum[2u * blockIdx.x + threadIdx.x] = s_sum[threadIdx.x];
 }
 
-__global__ __launch_bounds__(BO_TILE) void k_bo_gather(const uint8_t *__restrict__ u, const uint32_t *__restrict__ rec_off, uint32_t n,
+// OFF: uint32_t offsets into a window; 64-bit offsets into the held stream (the replay of filter -b -s)
+template <class OFF>
+__global__ __launch_bounds__(BO_TILE) void k_bo_gather(const uint8_t *__restrict__ u, const OFF *__restrict__ rec_off, uint32_t n,
                                                         const uint32_t *__restrict__ len_in, const ull *__restrict__ tile_base, ull base, uint8_t *__restrict__ pay)
 {
     __shared__ uint4 s_buf[BO_LDS / 16u];
@@ -92,6 +103,80 @@ __global__ __launch_bounds__(BO_TILE) void k_bo_gather(const uint8_t *__restrict
 #pragma clang loop vectorize(disable)
         for (uint32_t k = from; k < to; k++) dst[k - from] = src[k];
     });
+}
+
+// ---- filter -b -s: what is collected during the pass and the order of the replay
+struct BoSortEnt {
+    uint32_t tid, low;               // the high and the low sort key (itx_bamsortrule.h)
+    ull off;                         // the record's first byte in the held stream
+    uint32_t len, pad;               // 4 + block_size
+};
+static_assert(sizeof(BoSortEnt) == 24, "BoSortEnt");
+
+// behind a batch's gather: one entry per counted record (len != 0). Its place in the held stream comes from the gather's own tile
+// bases and itx_tile_offsets, its place in the pool from the tile's record count the same way (k_bi_entries' arrangement).
+// flag[0] counts the records that cannot be sorted, flag[1] is the highest tid seen; a workgroup adds to them once.
+__global__ __launch_bounds__(BO_TILE) void k_bs_entries(const uint8_t *__restrict__ u, const uint32_t *__restrict__ rec_off, uint32_t n, const uint32_t *__restrict__ len_in,
+                                                         const ull *__restrict__ tile_base, ull stream_at, ull ent_at, BoSortEnt *__restrict__ ent, uint32_t *__restrict__ flag)
+{
+    __shared__ uint32_t s_w[BO_TILE / 64u], s_c[BO_TILE / 64u], s_f[2];
+    if (threadIdx.x < 2) s_f[threadIdx.x] = 0;                             // (the barriers of itx_tile_offsets order this)
+    const uint32_t i = blockIdx.x * BO_TILE + threadIdx.x;
+    const uint32_t len = i < n ? len_in[i] : 0u;
+    uint32_t total = 0, count = 0;
+    const uint32_t moff = itx_tile_offsets<BO_TILE>(len, s_w, &total);
+    const uint32_t rank = itx_tile_offsets<BO_TILE>(len ? 1u : 0u, s_c, &count);
+    if (len) {
+        ItxBamSortKey k;
+        const int bad = itx_bamsort_key(u + rec_off[i], len, &k);
+        BoSortEnt e;
+        e.tid = itx_bamsort_high(&k);
+        e.low = itx_bamsort_low(&k);
+        e.off = stream_at + tile_base[2u * blockIdx.x] + moff;
+        e.len = len;
+        e.pad = 0;
+        ent[ent_at + tile_base[2u * blockIdx.x + 1u] + rank] = e;
+        if (bad) atomicAdd(&s_f[0], 1u);
+        else atomicMax(&s_f[1], e.tid);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_f[0]) atomicAdd(&flag[0], s_f[0]);
+        if (s_f[1]) atomicMax(&flag[1], s_f[1]);
+    }
+}
+
+// the pairs the radix sort moves: (low key, the entry's number); after the passes over the low key the key becomes the entry's tid
+__global__ __launch_bounds__(256) void k_bs_keys(const BoSortEnt *__restrict__ ent, uint32_t n, uint2 *__restrict__ keys)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) keys[i] = make_uint2(ent[i].low, i);
+}
+
+__global__ __launch_bounds__(256) void k_bs_rekey(const BoSortEnt *__restrict__ ent, uint32_t n, uint2 *__restrict__ keys)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) keys[i].x = ent[keys[i].y].tid;
+}
+
+// one round of the replay, records sorted[0 .. n): their lengths and where they lie in the held stream, laid out in sorted order
+// for the gather; a tile's bytes (64 bit) and records as k_bo_measure leaves them
+__global__ __launch_bounds__(BO_TILE) void k_bs_lengths(const uint2 *__restrict__ sorted, const BoSortEnt *__restrict__ ent, uint32_t n, uint32_t *__restrict__ len_out,
+                                                         ull *__restrict__ off_out, ull *__restrict__ tile_sum)
+{
+    __shared__ ull s_sum[2];
+    if (threadIdx.x < 2) s_sum[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * BO_TILE + threadIdx.x;
+    if (i < n) {
+        const BoSortEnt e = ent[sorted[i].y];
+        len_out[i] = e.len;
+        off_out[i] = e.off;
+        atomicAdd(&s_sum[0], (ull)e.len);
+        atomicAdd(&s_sum[1], 1ull);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) tile_sum[2u * blockIdx.x + threadIdx.x] = s_sum[threadIdx.x];
 }
 
 // LDS of one member's encoder (itxd_ws), for payloads of up to BO_P bytes
@@ -190,6 +275,22 @@ struct itx_bamout {
     itx_bamout_stats stats;
     itx_bamidx *ix;                  // filter -b -i (itx_bamout_index_enable): the .bai index in the making, else null
     ull stream_base;                 // bytes of the record stream that are members already: d_pay[0] is this byte of the stream
+    // filter -b -s (itx_bamout_sort_enable)
+    int sort;                        // 0: off; 1: the stream is held (d_pay is the held stream, carry its bytes); 2: it is replayed
+    int32_t n_ref;                   // from index_enable, else -1: the highest tid seen says how many passes tid takes
+    BoSortEnt *d_sent;               // the pool: an entry per held record, in stream order
+    ull n_sent, sent_cap, sent_grows;
+    uint32_t *d_sflag, *h_sflag;     // [0] records that cannot be sorted, [1] the highest tid (device batches; h_sflag page-locked)
+    ull host_bad;                    // the same of the host route's records
+    uint32_t host_maxtid;
+    uint8_t *d_held;                 // the replay: the held stream, the pairs in both buffers and where the sorted ones are,
+    uint2 *d_k0, *d_k1, *sorted;     // the digit counts, the round's offsets into the held stream
+    uint32_t *d_hist;
+    ull *d_soff;
+    ull sort_done, rounds;           // records replayed; rounds
+    hipEvent_t sev[2];               // around the sort
+    int sort_timed;
+    double sort_ms, replay_ms;
 };
 
 static int bo_hip(hipError_t e, const char *what, int line)
@@ -230,6 +331,16 @@ extern "C" void itx_bamout_destroy(itx_bamout *bo)
     (void)hipFree(bo->d_msize);
     (void)hipFree(bo->d_moff);
     if (bo->h_tot) (void)hipHostFree(bo->h_tot);
+    for (auto &e : bo->sev)
+        if (e) (void)hipEventDestroy(e);
+    (void)hipFree(bo->d_sent);
+    (void)hipFree(bo->d_sflag);
+    if (bo->h_sflag) (void)hipHostFree(bo->h_sflag);
+    (void)hipFree(bo->d_held);
+    (void)hipFree(bo->d_k0);
+    (void)hipFree(bo->d_k1);
+    (void)hipFree(bo->d_hist);
+    (void)hipFree(bo->d_soff);
     itx_bamidx_destroy(bo->ix);
     delete bo;
 }
@@ -245,6 +356,7 @@ extern "C" int itx_bamout_create(int device, size_t batch_capacity, size_t strea
     itx_bamout *bo = new itx_bamout();
     bo->device = device;
     bo->cap = batch_capacity;
+    bo->n_ref = -1;
     const size_t n = batch_capacity + 64, nt = (batch_capacity + BO_TILE - 1) / BO_TILE + 1;
     if (stream_bytes < 4 * (size_t)BO_P) stream_bytes = 4 * (size_t)BO_P;
     bo->pay_cap = stream_bytes;
@@ -283,8 +395,41 @@ static void bo_read_gather_time(itx_bamout *bo)
     if (bo->ix) itx_bamidx_batch_time(bo->ix);
     if (!bo->gather_timed) return;
     float ms = 0;
-    if (hipEventElapsedTime(&ms, bo->ev[2], bo->ev[3]) == hipSuccess) bo->stats.gather_ms += (double)ms;
+    if (hipEventElapsedTime(&ms, bo->ev[2], bo->ev[3]) == hipSuccess) *(bo->sort == 2 ? &bo->replay_ms : &bo->stats.gather_ms) += (double)ms;
     bo->gather_timed = 0;
+}
+
+// filter -b -s: room for n_more more entries in the pool; bo->st is idle. What does not fit leaves the object as it was.
+static int bs_reserve(itx_bamout *bo, ull n_more)
+{
+    int rc = ITX_OK;
+    BoSortEnt *nent = nullptr;
+    const ull want = bo->n_sent + n_more;
+    if (want >= 0xfffffffeull) {
+        itx_set_error("itx_bamout: %llu records to sort (run without -s)", want);
+        return ITX_E_LIMIT;
+    }
+    if (want <= bo->sent_cap) return ITX_OK;
+    const ull cap = want + want / 2 + 1024;
+    if (hipMalloc((void **)&nent, sizeof(BoSortEnt) * cap) != hipSuccess) {
+        (void)hipGetLastError();
+        itx_set_error("itx_bamout: no device memory for the sort entries of %llu records (run without -s)", want);
+        return ITX_E_NOMEM;
+    }
+    if (bo->n_sent) {
+        BO_TRY(hipMemcpyAsync(nent, bo->d_sent, sizeof(BoSortEnt) * bo->n_sent, hipMemcpyDeviceToDevice, bo->st));
+        BO_TRY(hipStreamSynchronize(bo->st));                              // before the old pool goes
+    }
+    {
+        BoSortEnt *old = bo->d_sent;
+        bo->d_sent = nent;
+        bo->sent_cap = cap;
+        nent = old;
+        if (old) bo->sent_grows++;
+    }
+out:
+    (void)hipFree(nent);                                                   // the old pool, or the new one that was not taken
+    return rc;
 }
 
 // Room for a stream of `total` bytes and for the n_mem members made of it next; bo->st is idle when this is called. Every limit is
@@ -313,7 +458,7 @@ static int bo_reserve(itx_bamout *bo, ull total, ull n_mem)
                       hipMalloc((void **)&nmo, 8 * (want_mem + 1)) != hipSuccess)) ||
         (want_pk && (hipMalloc((void **)&npk, want_pk) != hipSuccess || hipHostMalloc((void **)&npin, want_pk, hipHostMallocDefault) != hipSuccess))) {
         (void)hipGetLastError();
-        itx_set_error("itx_bamout: no memory for a stream of %llu bytes in %llu members", total, n_mem);
+        itx_set_error("itx_bamout: no memory for a stream of %llu bytes in %llu members%s", total, n_mem, bo->sort ? " (run without -s)" : "");
         rc = ITX_E_NOMEM;
         goto out;
     }
@@ -404,8 +549,8 @@ int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, 
         itx_set_error("itx_bamout: batch exceeds the capacity");
         return ITX_E_ARG;
     }
-    if (bo->finished) {
-        itx_set_error("itx_bamout: the stream is finished");
+    if (bo->finished || bo->sort == 2) {
+        itx_set_error("itx_bamout: the stream is %s", bo->finished ? "finished" : "being replayed in sorted order");
         return ITX_E_STATE;
     }
     if (!n) return ITX_OK;
@@ -440,21 +585,31 @@ int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, 
         goto out;
     }
     total = (ull)bo->carry + bo->h_tot[0];
-    if ((rc = bo_reserve(bo, total, total / BO_P)) != ITX_OK) goto out;
-    if (bo->ix && (rc = itx_bamidx_reserve(bo->ix, bo->st, bo->h_tot[1], total / BO_P)) != ITX_OK) goto out;
+    // (sort mode: the stream is held whole, no member is made and nothing is indexed before the replay)
+    if ((rc = bo_reserve(bo, total, bo->sort ? 0 : total / BO_P)) != ITX_OK) goto out;
+    if (bo->sort && (rc = bs_reserve(bo, bo->h_tot[1])) != ITX_OK) goto out;
+    if (bo->ix && !bo->sort && (rc = itx_bamidx_reserve(bo->ix, bo->st, bo->h_tot[1], total / BO_P)) != ITX_OK) goto out;
     BO_TRY(hipEventRecord(bo->ev[2], bo->st));
     if (bo->h_tot[0]) {
-        hipLaunchKernelGGL(k_bo_gather, dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, (uint32_t)n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->d_pay);
+        hipLaunchKernelGGL((k_bo_gather<uint32_t>), dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, (uint32_t)n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->d_pay);
         BO_TRY(hipGetLastError());
+    }
+    if (bo->sort && bo->h_tot[1]) {
+        hipLaunchKernelGGL(k_bs_entries, dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, (uint32_t)n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->n_sent, bo->d_sent,
+                           bo->d_sflag);
+        BO_TRY(hipGetLastError());
+        bo->n_sent += bo->h_tot[1];
     }
     BO_TRY(hipEventRecord(bo->ev[3], bo->st));
     bo->gather_timed = 1;
-    if (bo->ix && (rc = itx_bamidx_entries(bo->ix, bo->st, u, rec_off, (uint32_t)n, bo->d_len, bo->d_tile_base, bo->stream_base + bo->carry, bo->h_tot[1])) != ITX_OK)
+    if (bo->ix && !bo->sort &&
+        (rc = itx_bamidx_entries(bo->ix, bo->st, u, rec_off, (uint32_t)n, bo->d_len, bo->d_tile_base, bo->stream_base + bo->carry, bo->h_tot[1])) != ITX_OK)
         goto out;
     bo->stats.batches++;
     bo->stats.records += bo->h_tot[1];
     bo->stats.payload_bytes += bo->h_tot[0];
-    rc = bo_emit(bo, total, 0);
+    if (bo->sort) bo->carry = (size_t)total;
+    else rc = bo_emit(bo, total, 0);
 out:
     return rc;
 }
@@ -489,13 +644,16 @@ extern "C" int itx_bamout_append_host(itx_bamout *bo, const void *bytes, size_t 
         itx_set_error("itx_bamout_append_host: bad argument");
         return ITX_E_ARG;
     }
-    if (bo->finished) {
-        itx_set_error("itx_bamout_append_host: the stream is finished");
+    if (bo->finished || bo->sort == 2) {
+        itx_set_error("itx_bamout_append_host: the stream is %s", bo->finished ? "finished" : "being replayed in sorted order");
         return ITX_E_STATE;
     }
     size_t at = 0, n_rec = 0;
     uint32_t *h_off = nullptr;                                             // with an index: where every record starts
-    if (bo->ix && len >= 0xffffff00ull) {
+    BoSortEnt *h_ent = nullptr;                                            // sort mode: the records' entries, made here
+    ull bad = 0;
+    uint32_t maxtid = 0;
+    if (bo->ix && !bo->sort && len >= 0xffffff00ull) {
         itx_set_error("itx_bamout_append_host: %zu bytes in one call while an index is built", len);
         return ITX_E_LIMIT;
     }
@@ -512,7 +670,26 @@ extern "C" int itx_bamout_append_host(itx_bamout *bo, const void *bytes, size_t 
     if (!len) return ITX_OK;
     int rc = ITX_OK;
     const ull total = (ull)bo->carry + len;
-    if (bo->ix) {
+    if (bo->sort) {
+        if (!(h_ent = (BoSortEnt *)malloc(sizeof(BoSortEnt) * n_rec))) {
+            itx_set_error("itx_bamout_append_host: no memory for the sort entries of %zu records", n_rec);
+            return ITX_E_NOMEM;
+        }
+        at = 0;
+        for (size_t i = 0; i < n_rec; i++) {
+            uint32_t bs;
+            ItxBamSortKey k;
+            memcpy(&bs, (const uint8_t *)bytes + at, 4);
+            if (itx_bamsort_key((const uint8_t *)bytes + at, 4u + bs, &k)) bad++;
+            else if ((uint32_t)k.tid > maxtid) maxtid = (uint32_t)k.tid;
+            h_ent[i].tid = itx_bamsort_high(&k);
+            h_ent[i].low = itx_bamsort_low(&k);
+            h_ent[i].off = (ull)bo->carry + at;
+            h_ent[i].len = 4u + bs;
+            h_ent[i].pad = 0;
+            at += 4 + (size_t)bs;
+        }
+    } else if (bo->ix) {
         if (!(h_off = (uint32_t *)malloc(4 * n_rec))) {
             itx_set_error("itx_bamout_append_host: no memory for the offsets of %zu records", n_rec);
             return ITX_E_NOMEM;
@@ -532,17 +709,29 @@ extern "C" int itx_bamout_append_host(itx_bamout *bo, const void *bytes, size_t 
         bo->stats.wait_ms += 1e3 * (itx_wall_now() - t0);
     }
     bo_read_gather_time(bo);
-    if ((rc = bo_reserve(bo, total, total / BO_P)) != ITX_OK) goto out;
-    if (bo->ix && (rc = itx_bamidx_reserve(bo->ix, bo->st, n_rec, total / BO_P)) != ITX_OK) goto out;
+    if ((rc = bo_reserve(bo, total, bo->sort ? 0 : total / BO_P)) != ITX_OK) goto out;
+    if (bo->sort && (rc = bs_reserve(bo, n_rec)) != ITX_OK) goto out;
+    if (bo->ix && !bo->sort && (rc = itx_bamidx_reserve(bo->ix, bo->st, n_rec, total / BO_P)) != ITX_OK) goto out;
     BO_TRY(hipMemcpyAsync(bo->d_pay + bo->carry, bytes, len, hipMemcpyHostToDevice, bo->st));
+    if (bo->sort) BO_TRY(hipMemcpyAsync(bo->d_sent + bo->n_sent, h_ent, sizeof(BoSortEnt) * n_rec, hipMemcpyHostToDevice, bo->st));
     BO_TRY(hipStreamSynchronize(bo->st));                                  // the caller's bytes are its own again
-    if (bo->ix && (rc = itx_bamidx_host_records(bo->ix, bo->st, bo->d_pay + bo->carry, h_off, (uint32_t)n_rec, bo->stream_base + bo->carry)) != ITX_OK) goto out;
+    if (bo->ix && !bo->sort &&
+        (rc = itx_bamidx_host_records(bo->ix, bo->st, bo->d_pay + bo->carry, h_off, (uint32_t)n_rec, bo->stream_base + bo->carry)) != ITX_OK)
+        goto out;
     bo->stats.host_batches++;
     bo->stats.records += n_rec;
     bo->stats.payload_bytes += len;
-    rc = bo_emit(bo, total, 0);
+    if (bo->sort) {                                                        // held whole: the entries stand in the pool in stream order
+        bo->n_sent += n_rec;
+        bo->host_bad += bad;
+        if (maxtid > bo->host_maxtid) bo->host_maxtid = maxtid;
+        bo->carry = (size_t)total;
+    } else {
+        rc = bo_emit(bo, total, 0);
+    }
 out:
     free(h_off);
+    free(h_ent);
     return rc;
 }
 
@@ -554,6 +743,10 @@ extern "C" int itx_bamout_finish(itx_bamout *bo)
     }
     if (bo->finished) {
         itx_set_error("itx_bamout_finish: called twice");
+        return ITX_E_STATE;
+    }
+    if (bo->sort) {
+        itx_set_error("itx_bamout_finish: the stream is to be sorted (itx_bamout_sort_next)");
         return ITX_E_STATE;
     }
     int rc = ITX_OK;
@@ -587,8 +780,7 @@ extern "C" int itx_bamout_collect(itx_bamout *bo, itx_bamout_members *out)
         BO_TRY(hipEventSynchronize(s->e1));
         bo->stats.wait_ms += 1e3 * (itx_wall_now() - t0);
     }
-    if (hipEventElapsedTime(&ms, s->e0, s->e1) == hipSuccess) bo->stats.member_ms += (double)ms;
-    if (*s->h_total > s->cap) {
+    if (hipEventElapsedTime(&ms, s->e0, s->e1) == hipSuccess) bo->stats.member_ms += (double)ms;    if (*s->h_total > s->cap) {
         itx_set_error("itx_bamout_collect: %llu packed bytes in a buffer of %zu", *s->h_total, s->cap);
         rc = ITX_E_LIMIT;
         goto out;
@@ -622,6 +814,234 @@ extern "C" int itx_bamout_get_stats(const itx_bamout *bo, itx_bamout_stats *out)
     return ITX_OK;
 }
 
+// ---- filter -b -s: the stream held, sorted by coordinate and replayed
+extern "C" int itx_bamout_sort_enable(itx_bamout *bo)
+{
+    if (!bo) {
+        itx_set_error("itx_bamout_sort_enable: bad argument");
+        return ITX_E_ARG;
+    }
+    if (bo->sort || bo->finished || bo->stats.batches || bo->stats.host_batches) {
+        itx_set_error("itx_bamout_sort_enable: %s", bo->sort ? "called twice" : "the stream has begun");
+        return ITX_E_STATE;
+    }
+    int rc = ITX_OK;
+    uint32_t *flag = nullptr, *h_flag = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    BO_TRY(hipSetDevice(bo->device));
+    if (hipMalloc((void **)&flag, 16) != hipSuccess) {
+        (void)hipGetLastError();
+        itx_set_error("itx_bamout_sort_enable: no device memory (run without -s)");
+        rc = ITX_E_NOMEM;
+        goto out;
+    }
+    BO_TRY(hipHostMalloc((void **)&h_flag, 16, hipHostMallocDefault));
+    BO_TRY(hipMemset(flag, 0, 16));
+    BO_TRY(hipEventCreate(&ev[0]));
+    BO_TRY(hipEventCreate(&ev[1]));
+    bo->d_sflag = flag;
+    bo->h_sflag = h_flag;
+    bo->sev[0] = ev[0];
+    bo->sev[1] = ev[1];
+    bo->sort = 1;
+    return ITX_OK;
+out:
+    (void)hipFree(flag);
+    if (h_flag) (void)hipHostFree(h_flag);
+    for (auto &e : ev)
+        if (e) (void)hipEventDestroy(e);
+    return rc;
+}
+
+// the sort's device time is read once its events are through (the round's wait for its totals is behind them)
+static void bs_read_sort_time(itx_bamout *bo)
+{
+    if (!bo->sort_timed) return;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, bo->sev[0], bo->sev[1]) == hipSuccess) bo->sort_ms += (double)ms;
+    bo->sort_timed = 0;
+}
+
+// The first sort_next: the flags are read, the replay's buffers allocated, and the sort of the pool enqueued. bo->st is idle.
+// Nothing of the object changes before every check has passed and every buffer is there.
+static int bs_begin(itx_bamout *bo)
+{
+    int rc = ITX_OK;
+    const uint32_t N = (uint32_t)bo->n_sent, nwg = (N + SORT_CHUNK - 1) / SORT_CHUNK;
+    uint2 *k0 = nullptr, *k1 = nullptr, *sorted = nullptr;
+    uint32_t *hist = nullptr, n_ref = 0, passes = 0;
+    ull *soff = nullptr, bad = 0;
+    uint8_t *npay = nullptr;
+    const size_t pay_cap = 4 * (size_t)BO_P;
+    BO_TRY(hipMemcpyAsync(bo->h_sflag, bo->d_sflag, 8, hipMemcpyDeviceToHost, bo->st));
+    BO_TRY(hipStreamSynchronize(bo->st));
+    bad = bo->host_bad + bo->h_sflag[0];
+    if (bad) {
+        itx_set_error("itx_bamout_sort_next: %llu counted records name no reference or no position (tid or pos below 0): they cannot be sorted by coordinate", bad);
+        rc = ITX_E_LIMIT;
+        goto out;
+    }
+    if (N) {
+        if (hipMalloc((void **)&k0, 8 * (size_t)N) != hipSuccess || hipMalloc((void **)&k1, 8 * (size_t)N) != hipSuccess ||
+            hipMalloc((void **)&hist, 4 * 256 * (size_t)nwg) != hipSuccess || hipMalloc((void **)&soff, 8 * (bo->cap + 64)) != hipSuccess ||
+            hipMalloc((void **)&npay, pay_cap + 16) != hipSuccess) {
+            (void)hipGetLastError();
+            itx_set_error("itx_bamout_sort_next: no device memory to sort %u records beside a held stream of %zu bytes (run without -s)", N, bo->carry);
+            rc = ITX_E_NOMEM;
+            goto out;
+        }
+        n_ref = bo->n_ref > 0 ? (uint32_t)bo->n_ref : 0u;
+        {
+            const uint32_t seen = (bo->h_sflag[1] > bo->host_maxtid ? bo->h_sflag[1] : bo->host_maxtid) + 1u;
+            if (seen > n_ref) n_ref = seen;                                // (a tid beyond the header's list still finds its place)
+        }
+        passes = 4u + itx_bamsort_high_passes(n_ref);
+        BO_TRY(hipEventRecord(bo->sev[0], bo->st));
+        hipLaunchKernelGGL(k_bs_keys, dim3((N + 255u) / 256u), dim3(256), 0, bo->st, bo->d_sent, N, k0);
+        BO_TRY(hipGetLastError());
+        sorted = k0;
+        for (uint32_t p = 0; p < passes; p++) {
+            uint2 *to = sorted == k0 ? k1 : k0;
+            const uint32_t shift = 8u * (p < 4u ? p : p - 4u);
+            if (p == 4u) {
+                hipLaunchKernelGGL(k_bs_rekey, dim3((N + 255u) / 256u), dim3(256), 0, bo->st, bo->d_sent, N, sorted);
+                BO_TRY(hipGetLastError());
+            }
+            hipLaunchKernelGGL(k_sort_hist, dim3(nwg), dim3(256), 0, bo->st, sorted, N, shift, hist, nwg);
+            BO_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(ITX_SCAN_WG), 0, bo->st, hist, 256u * nwg);
+            BO_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_sort_scatter, dim3(nwg), dim3(256), 0, bo->st, sorted, to, N, shift, hist, nwg);
+            BO_TRY(hipGetLastError());
+            sorted = to;
+        }
+        BO_TRY(hipEventRecord(bo->sev[1], bo->st));
+        bo->sort_timed = 1;
+    }
+    // the held stream is what d_pay was; the payload stream starts anew
+    bo->d_held = bo->d_pay;
+    bo->d_pay = npay;
+    bo->pay_cap = npay ? pay_cap : 0;
+    bo->carry = 0;
+    bo->d_k0 = k0;
+    bo->d_k1 = k1;
+    bo->sorted = sorted;
+    bo->d_hist = hist;
+    bo->d_soff = soff;
+    bo->sort = 2;
+    return ITX_OK;
+out:
+    if (k0 || k1) (void)hipStreamSynchronize(bo->st);                      // (kernels that were enqueued before something failed)
+    (void)hipFree(k0);
+    (void)hipFree(k1);
+    (void)hipFree(hist);
+    (void)hipFree(soff);
+    (void)hipFree(npay);
+    return rc;
+}
+
+// the sort's work arrays and the held stream go (the kernels that read them are through)
+static void bs_release(itx_bamout *bo)
+{
+    (void)hipFree(bo->d_held);
+    (void)hipFree(bo->d_k0);
+    (void)hipFree(bo->d_k1);
+    (void)hipFree(bo->d_hist);
+    (void)hipFree(bo->d_soff);
+    (void)hipFree(bo->d_sent);
+    bo->d_held = nullptr;
+    bo->d_k0 = bo->d_k1 = bo->sorted = nullptr;
+    bo->d_hist = nullptr;
+    bo->d_soff = nullptr;
+    bo->d_sent = nullptr;
+    bo->sent_cap = 0;
+}
+
+extern "C" int itx_bamout_sort_next(itx_bamout *bo, int *more)
+{
+    if (!bo || !more) {
+        itx_set_error("itx_bamout_sort_next: bad argument");
+        return ITX_E_ARG;
+    }
+    *more = 0;
+    if (!bo->sort || bo->finished) {
+        itx_set_error("itx_bamout_sort_next: %s", bo->sort ? "the stream is finished" : "no sort was asked for (itx_bamout_sort_enable)");
+        return ITX_E_STATE;
+    }
+    int rc = ITX_OK;
+    float ms = 0;
+    ull total = 0, n_mem = 0;
+    const ull N = bo->n_sent;
+    uint32_t n = 0, nt = 0;
+    int last = 0;
+    BO_TRY(hipSetDevice(bo->device));
+    BO_TRY(hipStreamSynchronize(bo->st));
+    bo_read_gather_time(bo);
+    if (bo->sort == 1 && (rc = bs_begin(bo)) != ITX_OK) goto out;
+    if (!N) {                                                              // nothing was counted: no member
+        bs_release(bo);
+        bo->finished = 1;
+        goto out;
+    }
+    n = (uint32_t)(N - bo->sort_done < bo->cap ? N - bo->sort_done : bo->cap);
+    nt = (n + BO_TILE - 1) / BO_TILE;
+    last = bo->sort_done + n == N;
+    BO_TRY(hipEventRecord(bo->ev[0], bo->st));
+    BO_TRY(hipMemsetAsync(bo->d_tot, 0, 32, bo->st));
+    hipLaunchKernelGGL(k_bs_lengths, dim3(nt), dim3(BO_TILE), 0, bo->st, bo->sorted + bo->sort_done, bo->d_sent, n, bo->d_len, bo->d_soff, bo->d_tile_sum);
+    BO_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, bo->st, bo->d_tile_sum, nt, bo->d_tile_base, bo->d_tot);
+    BO_TRY(hipGetLastError());
+    BO_TRY(hipEventRecord(bo->ev[1], bo->st));
+    BO_TRY(hipMemcpyAsync(bo->h_tot, bo->d_tot, 32, hipMemcpyDeviceToHost, bo->st));
+    {
+        const double t0 = itx_wall_now();
+        BO_TRY(hipStreamSynchronize(bo->st));                              // (the members of the round before are through as well)
+        bo->stats.wait_ms += 1e3 * (itx_wall_now() - t0);
+    }
+    bs_read_sort_time(bo);
+    BO_TRY(hipEventElapsedTime(&ms, bo->ev[0], bo->ev[1]));
+    bo->replay_ms += (double)ms;
+    total = (ull)bo->carry + bo->h_tot[0];
+    n_mem = total / BO_P + (last && total % BO_P ? 1 : 0);
+    if ((rc = bo_reserve(bo, total, n_mem)) != ITX_OK) goto out;
+    if (bo->ix && (rc = itx_bamidx_reserve(bo->ix, bo->st, n, n_mem)) != ITX_OK) goto out;
+    BO_TRY(hipEventRecord(bo->ev[2], bo->st));
+    hipLaunchKernelGGL((k_bo_gather<ull>), dim3(nt), dim3(BO_TILE), 0, bo->st, bo->d_held, bo->d_soff, n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->d_pay);
+    BO_TRY(hipGetLastError());
+    BO_TRY(hipEventRecord(bo->ev[3], bo->st));
+    bo->gather_timed = 1;
+    if (bo->ix && (rc = itx_bamidx_entries64(bo->ix, bo->st, bo->d_held, bo->d_soff, n, bo->d_len, bo->d_tile_base, bo->stream_base + bo->carry, n)) != ITX_OK) goto out;
+    bo->sort_done += n;
+    bo->rounds++;
+    if ((rc = bo_emit(bo, total, last)) != ITX_OK) goto out;
+    if (last) {
+        // the held stream goes as soon as the last gather (and the index's entry kernel behind it) has read it
+        if (bo->ix) itx_bamidx_batch_time(bo->ix);
+        BO_TRY(hipEventSynchronize(bo->ev[3]));
+        bo_read_gather_time(bo);
+        bs_release(bo);
+        bo->finished = 1;
+    }
+    *more = !last;
+out:
+    return rc;
+}
+
+extern "C" int itx_bamout_sort_get_stats(const itx_bamout *bo, itx_bamout_sort_stats *out)
+{
+    if (!bo || !out) {
+        itx_set_error("itx_bamout_sort_get_stats: bad argument");
+        return ITX_E_ARG;
+    }
+    out->records = bo->n_sent;
+    out->rounds = bo->rounds;
+    out->pool_grows = bo->sent_grows;
+    out->sort_ms = bo->sort_ms;
+    out->replay_ms = bo->replay_ms;
+    return ITX_OK;
+}
+
 // ---- the .bai index of the stream (csrc/itx_bamidx.hip)
 extern "C" int itx_bamout_index_enable(itx_bamout *bo, int32_t n_ref, const int32_t *l_ref)
 {
@@ -633,7 +1053,9 @@ extern "C" int itx_bamout_index_enable(itx_bamout *bo, int32_t n_ref, const int3
         itx_set_error("itx_bamout_index_enable: %s", bo->ix ? "called twice" : "the stream has begun");
         return ITX_E_STATE;
     }
-    return itx_bamidx_create(bo->device, n_ref, l_ref, &bo->ix);
+    const int rc = itx_bamidx_create(bo->device, n_ref, l_ref, &bo->ix);
+    if (rc == ITX_OK) bo->n_ref = n_ref;
+    return rc;
 }
 
 extern "C" int itx_bamout_index_finish(itx_bamout *bo, uint64_t first_member_offset, itx_bamout_index_result *out)

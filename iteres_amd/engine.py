@@ -35,7 +35,7 @@ EXPORTS = [
     "itx_names_finish", "itx_names_get_stats",
     "itx_bamout_create", "itx_bamout_destroy", "itx_bamout_hits", "itx_bamout_stream", "itx_bamwin_bamout", "itx_bamout_run", "itx_bamout_wait_kernels",
     "itx_bamout_append_host", "itx_bamout_finish", "itx_bamout_collect", "itx_bamout_pending", "itx_bamout_get_stats", "itx_bamout_index_enable",
-    "itx_bamout_index_finish",
+    "itx_bamout_index_finish", "itx_bamout_sort_enable", "itx_bamout_sort_next", "itx_bamout_sort_get_stats",
     "itx_loci_create", "itx_loci_destroy", "itx_loci_order", "itx_loci_filter_text", "itx_loci_cpg_text",
     "itx_samtext_create", "itx_samtext_destroy", "itx_samtext_parse_begin", "itx_samtext_parse_end", "itx_samtext_fetch",
     "itx_samtext_parse_begin_bgzf", "itx_samtext_bgzf_info", "itx_samtext_text", "itx_samtext_strings",
@@ -132,6 +132,10 @@ class BamoutStats(C.Structure):
 class BamoutIndexResult(C.Structure):
     _fields_ = [("bytes", C.c_void_p), ("len", C.c_uint64), ("status", C.c_int32), ("pad", C.c_int32), ("entries", C.c_uint64), ("chunks", C.c_uint64),
                 ("grows", C.c_uint64), ("batch_ms", C.c_double), ("finish_ms", C.c_double)]
+
+
+class BamoutSortStats(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("rounds", C.c_uint64), ("pool_grows", C.c_uint64), ("sort_ms", C.c_double), ("replay_ms", C.c_double)]
 
 
 class LociText(C.Structure):
@@ -266,6 +270,9 @@ def load():
     L.itx_bamout_get_stats.argtypes = [C.c_void_p, C.POINTER(BamoutStats)]
     L.itx_bamout_index_enable.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     L.itx_bamout_index_finish.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(BamoutIndexResult)]
+    L.itx_bamout_sort_enable.argtypes = [C.c_void_p]
+    L.itx_bamout_sort_next.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    L.itx_bamout_sort_get_stats.argtypes = [C.c_void_p, C.POINTER(BamoutSortStats)]
     L.itx_loci_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                   C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
     L.itx_loci_destroy.argtypes = [C.c_void_p]
@@ -750,7 +757,9 @@ class Bamout:
     stream of bytes and cut into BGZF members there. `append_window` takes records of an Inflater's last parsed window and a torch
     DEVICE int32 tensor of their chosen rows (-1: none), `run` plain torch DEVICE tensors (uint8 record bytes, uint32-as-int32
     offsets, int32 rows), `append_host` whole records as bytes. Every call collects what is pending, so the members made so far are
-    in `self.out` (a bytearray) in stream order; `finish()` adds the last, short member and returns all of them."""
+    in `self.out` (a bytearray) in stream order; `finish()` adds the last, short member and returns all of them. After
+    `sort_enable()` (filter -b -s) nothing leaves during the pass; `sort_all()` in place of `finish()` returns the members of the
+    stream sorted by coordinate."""
 
     def __init__(self, batch_capacity: int = 1 << 20, stream_bytes: int = 0, device: int = 0):
         self._h = C.c_void_p()
@@ -810,6 +819,31 @@ class Bamout:
         _chk(load().itx_bamout_index_finish(self._h, first_member_offset, C.byref(r)), "itx_bamout_index_finish")
         info = {k: getattr(r, k) for k, _ in BamoutIndexResult._fields_ if k not in ("bytes", "pad")}
         return r.status, (C.string_at(r.bytes, r.len) if r.status == 0 else None), info
+
+    def sort_enable(self):
+        """before the first batch: the records are held on the device and leave in coordinate order (sort_next in place of finish)"""
+        _chk(load().itx_bamout_sort_enable(self._h), "itx_bamout_sort_enable")
+
+    def sort_next(self, collect=True):
+        """after the last batch: sorts (the first call) and replays one round of at most batch_capacity records; True while
+        another round follows. `sort_all()` is the whole loop."""
+        if collect:
+            self._drain()
+        more = C.c_int(0)
+        _chk(load().itx_bamout_sort_next(self._h, C.byref(more)), "itx_bamout_sort_next")
+        if collect:
+            self._drain()
+        return bool(more.value)
+
+    def sort_all(self):
+        while self.sort_next():
+            pass
+        return bytes(self.out)
+
+    def sort_stats(self):
+        s = BamoutSortStats()
+        _chk(load().itx_bamout_sort_get_stats(self._h, C.byref(s)), "itx_bamout_sort_get_stats")
+        return {k: getattr(s, k) for k, _ in BamoutSortStats._fields_}
 
     def stats(self):
         s = BamoutStats()

@@ -25,6 +25,7 @@ static int filter_usage(void)
     fprintf(stderr, "         -r       output the list of reads [off]\n");
     fprintf(stderr, "         -b       output the counted reads as <prefix>_<filter>.iteres.bam, every one of them whatever -t says; BAM input only (an extension: not in the reference) [off]\n");
     fprintf(stderr, "         -i       with -b: also write its index <prefix>_<filter>.iteres.bam.bai, for coordinate-sorted input (an extension) [off]\n");
+    fprintf(stderr, "         -s       with -b: write the counted reads sorted by coordinate, so that -i works on input in any order (an extension) [off]\n");
     fprintf(stderr, "         -R       remove redundant reads [off]\n");
     fprintf(stderr, "         -T       treat 1 paired-end read as 2 single-end reads [off]\n");
     fprintf(stderr, "         -D       discard if only one end mapped in a paired end reads [off]\n");
@@ -46,10 +47,10 @@ int main_filter(int argc, char **argv)
     o.isize = 500;
     o.extension = 150;
     o.min_cov = 0.0001f;
-    int optthreshold = 1, optreadlist = 0, optbam = 0, optindex = 0, optNorm = 0, c, filterField = 0;
+    int optthreshold = 1, optreadlist = 0, optbam = 0, optindex = 0, optsort = 0, optNorm = 0, c, filterField = 0;
     char *optoutput = NULL, *optname = NULL, *optclass = NULL, *optfamily = NULL;
     const time_t start_time = time(NULL);
-    while ((c = getopt(argc, argv, "SQ:g:N:n:c:t:f:rbiRTDCE:I:o:h?")) >= 0) {
+    while ((c = getopt(argc, argv, "SQ:g:N:n:c:t:f:rbisRTDCE:I:o:h?")) >= 0) {
         switch (c) {
         case 'S': o.is_sam = 1; break;
         case 'Q': o.mapq = (unsigned)strtol(optarg, 0, 0); break;
@@ -59,6 +60,7 @@ int main_filter(int argc, char **argv)
         case 'r': optreadlist = 1; break;
         case 'b': optbam = 1; break;
         case 'i': optindex = 1; break;
+        case 's': optsort = 1; break;
         case 'R': o.dedup = 1; break;
         case 'T': o.treat = 1; break;
         case 'D': o.discard = 1; break;
@@ -78,6 +80,7 @@ int main_filter(int argc, char **argv)
     /* -b (an extension) copies records out of the BAM windows the device decoded: there are none for SAM text, nor when the host inflates */
     if (optbam && o.is_sam) die("-b writes BAM records as they lie in the input: it cannot be combined with -S (SAM text has none)");
     if (optindex && !optbam) die("-i writes the index of the BAM that -b writes: it cannot be used without -b");
+    if (optsort && !optbam) die("-s sorts the BAM that -b writes: it cannot be used without -b");
     if (optbam && getenv("ITX_HOST_INFLATE"))
         die("-b gathers the records on the device, where the BAM is decoded: it cannot be combined with ITX_HOST_INFLATE (the host decoder)");
     o.chr_size_file = argv[optind];
@@ -119,6 +122,7 @@ int main_filter(int argc, char **argv)
         if (asprintf(&outBam, "%s_%s.iteres.bam", output, subfam) < 0) die("Preparing output wrong");
         o.bam_out_path = outBam;
         o.bam_index = optindex;
+        o.bam_sort = optsort;
         aln_keep_header(1);                      /* before the helper thread opens the file */
     }
     gpu_warmup_start(!o.is_sam, o.aln_arg, 0, splittable);

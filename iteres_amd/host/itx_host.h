@@ -223,6 +223,7 @@ typedef struct {
     const char *chr_size_file, *rep_size_file, *rmsk_file, *aln_arg;
     const char *bed_path, *bed_uniq_path;      /* stat -B / -V (generic.c:925-936), NULL = off */
     const char *bam_out_path;                  /* filter -b (an extension): the counted records as a BAM, NULL = off */
+    int bam_sort;                              /* filter -b -s: the counted records leave sorted by coordinate (held and sorted on the device) */
     int bam_index;                             /* filter -b -i: <bam_out_path>.bai beside it, built on the device in the same pass */
 } run_opts;
 /* counters of the record loop that only the host sees (generic.c:1048-1060) */

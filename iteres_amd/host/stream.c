@@ -6,6 +6,7 @@
  * in file order, the XA veto (side.c), submit. First in the file: the helper thread that starts the runtime and decodes ahead. */
 #define _GNU_SOURCE
 #include "itx_host.h"
+#include "../csrc/itx_bamsortrule.h"
 
 #include <errno.h>
 #include <stdlib.h>
@@ -571,6 +572,24 @@ static void bam_index_begin(stream_run *r, const uint8_t *hb, size_t hl)
     r->bam_first = (uint64_t)first;
 }
 
+/* filter -b -s: the kept header (magic, l_text, text, reference list) with the text the sorted file carries (csrc/itx_bamsortrule.h);
+ * l_text follows the new length, the reference list is untouched. The caller frees the result. */
+static uint8_t *bam_sorted_header(const stream_run *r, const uint8_t *hb, size_t hl, size_t *out_len)
+{
+    int32_t l_text = 0;
+    if (hl >= 8) memcpy(&l_text, hb + 4, 4);
+    if (hl < 12 || l_text < 0 || (size_t)l_text > hl - 12) die("%s: the kept BAM header is cut short", r->o->bam_out_path);
+    uint8_t *nb = xcalloc(hl + ITX_BAMSORT_HEADER_GROWTH, 1);
+    const size_t nl = itx_bamsort_header_text((const char *)hb + 8, (size_t)l_text, (char *)nb + 8);
+    if (nl > INT32_MAX) die("%s: a header text of %zu bytes", r->o->bam_out_path, nl);
+    const int32_t nl32 = (int32_t)nl;
+    memcpy(nb, hb, 4);
+    memcpy(nb + 4, &nl32, 4);
+    memcpy(nb + 8 + nl, hb + 8 + (size_t)l_text, hl - 8 - (size_t)l_text);
+    *out_len = hl - (size_t)l_text + nl;
+    return nb;
+}
+
 /* filter -b -i, after the last members: the finished index is written, or one line says why there is none */
 static void bam_index_end(stream_run *r, itx_bamout_index_result *ir)
 {
@@ -914,10 +933,14 @@ static void map_targets(stream_run *r, stream_file *f)
         size_t hl = 0;
         const uint8_t *hb = aln_header_bytes(f->rd, &hl);
         if (!g_inflater || o->is_sam || !hb) die("filter -b needs BAM input decoded on the device: %s", warm_err[0] ? warm_err : "the decoder is not in use");
+        uint8_t *sorted_hb = o->bam_sort ? bam_sorted_header(r, hb, hl, &hl) : NULL;
+        if (sorted_hb) hb = sorted_hb;
         if (bgzf_write_members(r->bam_f, hb, hl) != 0) die("writing %s: %s", o->bam_out_path, strerror(errno));
         r->bam_header_done = 1;
         chk(itx_bamout_create(multi_device(), BATCH_RECORDS, 0, &r->bo), "itx_bamout_create");
+        if (o->bam_sort) chk(itx_bamout_sort_enable(r->bo), "itx_bamout_sort_enable");
         if (o->bam_index) bam_index_begin(r, hb, hl);
+        free(sorted_hb);
     }
 }
 
@@ -1257,7 +1280,14 @@ static void scan_again_alone(stream_run *r)
 static void finish_bam(stream_run *r)
 {
     if (!r->bam_f) return;
-    if (r->bo) {
+    if (r->bo && r->o->bam_sort) {
+        /* -s: the held records are sorted and replayed a round at a time; a round's members are written while the next round's
+         * kernels run */
+        for (int more = 1; more;) {
+            chk(itx_bamout_sort_next(r->bo, &more), "itx_bamout_sort_next");
+            bam_write_out(r, more ? 1 : 0);
+        }
+    } else if (r->bo) {
         chk(itx_bamout_finish(r->bo), "itx_bamout_finish");
         bam_write_out(r, 0);
     }
@@ -1272,7 +1302,14 @@ static void finish_bam(stream_run *r)
         if (r->bo) chk(itx_bamout_get_stats(r->bo, &bs), "itx_bamout_get_stats");
         fprintf(stderr, "[itx timing] bam out: %llu records, %llu payload bytes, %llu members (%llu bytes), %.3f ms in the gather kernels, %.3f ms in the member kernels, host waited %.3f s, %llu batches gathered on the device, %llu batches by the host route%s",
                 (unsigned long long)bs.records, (unsigned long long)bs.payload_bytes, (unsigned long long)bs.members, (unsigned long long)bs.out_bytes, bs.gather_ms,
-                bs.member_ms, 1e-3 * bs.wait_ms, r->bam_dev_batches, r->bam_host_batches, r->o->bam_index ? "" : "\n");
+                bs.member_ms, 1e-3 * bs.wait_ms, r->bam_dev_batches, r->bam_host_batches, r->o->bam_index || r->o->bam_sort ? "" : "\n");
+        if (r->o->bam_sort) {
+            itx_bamout_sort_stats ss;
+            memset(&ss, 0, sizeof ss);
+            if (r->bo) chk(itx_bamout_sort_get_stats(r->bo, &ss), "itx_bamout_sort_get_stats");
+            fprintf(stderr, "; sort: %llu records sorted, %llu rounds, %.3f ms in the sort kernels, %.3f ms in the replay gathers%s", (unsigned long long)ss.records,
+                    (unsigned long long)ss.rounds, ss.sort_ms, ss.replay_ms, r->o->bam_index ? "" : "\n");
+        }
         if (r->o->bam_index)
             fprintf(stderr, "; index: %llu entries, %llu chunks, %llu bytes, %.3f ms in the entry kernels, %.3f ms in the final kernels\n", (unsigned long long)ir.entries,
                     (unsigned long long)ir.chunks, (unsigned long long)ir.len, ir.batch_ms, ir.finish_ms);

@@ -3,7 +3,8 @@
 Generates the bench inputs once (bench.py's generator), then runs `iteres stat -w` <reps> times per setting, interleaved.
 LD_LIBRARY_PATH in a setting selects another build of libiteres_amd.so (the program's RUNPATH comes after it).
 ITX_AB_FILTER=1 runs `iteres filter -c <the table's biggest class>` instead (ITX_AB_OPTS="-r": with the read lists) and compares
-the .loci / .reportloci files (a setting may carry options of its own: `b:ITX_AB_OPTS=-b` is `filter -b` against plain `filter`); ITX_AB_FILTER=all runs `iteres filter` without a name filter (every row of the table is a line)."""
+the .loci / .reportloci files; ITX_AB_SHUFFLED=1 runs every setting on reads_shuffled.bam, the same reads with mkbam's
+order=shuffled (runs of 65 536 reads in a seeded random order, generated once beside reads.bam) (a setting may carry options of its own: `b:ITX_AB_OPTS=-b` is `filter -b` against plain `filter`); ITX_AB_FILTER=all runs `iteres filter` without a name filter (every row of the table is a line)."""
 import json
 import os
 import subprocess
@@ -28,6 +29,13 @@ def main():
         k, v = kv.split("=", 1)
         setattr(a, k, int(v) if v.isdigit() else v)
     wd, info = bench.ensure_inputs(a, 16)
+    reads = os.path.join(wd, "reads.bam")
+    if os.environ.get("ITX_AB_SHUFFLED"):
+        reads = os.path.join(wd, "reads_shuffled.bam")
+        if not os.path.exists(reads):
+            subprocess.check_call([bench.MKBAM, os.path.join(wd, "chrom.sizes"), str(a.reads), reads + ".tmp", str(a.seq_len), "7"] + bench.mkbam_options(a) + ["order=shuffled"],
+                                  env=dict(os.environ, OMP_NUM_THREADS="16"))
+            os.rename(reads + ".tmp", reads)
     settings = [("base", {})]
     for spec in sys.argv[4:]:
         name, kv = spec.split(":", 1)
@@ -47,7 +55,7 @@ def main():
             if os.environ.get("ITX_AB_FILTER"):
                 select = [] if os.environ["ITX_AB_FILTER"] == "all" else ["-c", info["filter_class"]["name"]]
                 args = ["filter"] + select + extra + args[2:]
-            wall, rc, err, seen = bench.run_timed(bench.OURS, args + [os.path.join(wd, "reads.bam")], out, env, (bench.SCAN_BEGIN, bench.SCAN_END))
+            wall, rc, err, seen = bench.run_timed(bench.OURS, args + [reads], out, env, (bench.SCAN_BEGIN, bench.SCAN_END))
             assert rc == 0, err[-800:]
             walls[name].append(round(wall, 3))
             scans[name].append(round(seen.get(bench.SCAN_END, 0) - seen.get(bench.SCAN_BEGIN, 0), 3))

@@ -19,6 +19,8 @@
  *   paired=1         fragments of two reads (isize ~ N(350, 60), clamped to the read length .. 700; FR orientation, either
  *                    read first; flags 99/147/83/163), 2 % of the fragments with an unmapped mate (flag 0x8 / 0x4 records
  *                    at the mapped read's place) — generic.c:836-860. n_reads counts records.
+ *   order=shuffled   the segments (see below) are written in a seeded random order: an unsorted file whose records are sorted
+ *                    only inside runs of SEG reads (default: order=sorted)
  *   pileup=K         K loci of the genome at ~2000x depth: the reads of 1000 mean gaps either side land within 64 bp
  *
  * The file is a function of the arguments alone: reads are generated in segments of SEG reads, each from a generator seeded
@@ -149,7 +151,7 @@ typedef struct {
 } seg_t;
 
 enum { C_LEGACY, C_HISEQ, C_NOVASEQ };
-static int content = C_LEGACY, cigar_mixed, paired, n_pileup;
+static int content = C_LEGACY, cigar_mixed, paired, n_pileup, shuffled;
 static int nc;
 static char names[256][64];
 static long long sizes[256], nr_of[256];
@@ -385,6 +387,8 @@ int main(int argc, char **argv)
                 paired = atoi(eq + 1) != 0;
             } else if (kl == 6 && !strncmp(argv[i], "pileup", 6)) {
                 n_pileup = atoi(eq + 1);
+            } else if (kl == 5 && !strncmp(argv[i], "order", 5)) {
+                shuffled = !strcmp(eq + 1, "shuffled");
             } else {
                 fprintf(stderr, "mkbam: unknown option '%s'\n", argv[i]);
                 return 1;
@@ -394,7 +398,7 @@ int main(int argc, char **argv)
         }
     }
     if (pn < 4) {
-        fprintf(stderr, "usage: mkbam <chrom.sizes> <n_reads> <out.bam> [seq_len=0] [seed=1] [xa_permille=0] [content=legacy|hiseq|novaseq] [cigar=simple|mixed] [paired=0|1] [pileup=K]\n");
+        fprintf(stderr, "usage: mkbam <chrom.sizes> <n_reads> <out.bam> [seq_len=0] [seed=1] [xa_permille=0] [content=legacy|hiseq|novaseq] [cigar=simple|mixed] [paired=0|1] [pileup=K] [order=sorted|shuffled]\n");
         return 1;
     }
     const long long n_reads = atoll(pv[2]);
@@ -456,6 +460,15 @@ int main(int argc, char **argv)
                 serial += seg[k].count;
                 k++;
             }
+    }
+    if (shuffled) {                                  /* the segments in a seeded random order: each still sorted inside */
+        rng_t S = {seed * 0x9e3779b97f4a7c15ull + 12345};
+        for (long long k = n_seg - 1; k > 0; k--) {
+            const long long j = (long long)(rnd(&S) % (uint64_t)(k + 1));
+            const seg_t t = seg[k];
+            seg[k] = seg[j];
+            seg[j] = t;
+        }
     }
     int io_error = 0;
 #pragma omp parallel
