@@ -545,6 +545,17 @@ typedef struct itx_bamout_sort_stats {
 int itx_bamout_sort_enable(itx_bamout *bo);
 int itx_bamout_sort_next(itx_bamout *bo, int *more);
 int itx_bamout_sort_get_stats(const itx_bamout *bo, itx_bamout_sort_stats *out);
+/* The level of the members (filter -b -l; csrc/itx_bgzflevels.h). Every level frames the same payloads of ITX_BAMOUT_PAYLOAD bytes,
+ * so the records, the index's rule and the sort are untouched; the members' sizes, and with them every virtual offset, differ.
+ *   6  the default: csrc/itx_bgzfmember.h, the only level an object has without this call
+ *   0  a stored DEFLATE block per member: payload + 31 bytes
+ *   1  a dynamic-Huffman block whose parse runs in slices of 128 positions on all lanes of the wave (csrc/itx_deflate_fast.h):
+ *      larger members than level 6, made faster; never more than payload + 31 bytes
+ *   set_level   before the first batch (ITX_E_STATE after it, or when called twice); a level other than 0, 1 or 6: ITX_E_ARG.
+ *               A refused call changes nothing.
+ *   get_level   the level in use (ITX_E_ARG for a null object) */
+int itx_bamout_set_level(itx_bamout *bo, int level);
+int itx_bamout_get_level(const itx_bamout *bo);
 
 /* ---- the .loci file of filter / cpgfilter on the device ----------------------------------------------------------------------
  * Replaces the row walk and the fprintf of writeFilterOut (generic.c:1709-1746) and writeFilterOutMRE (generic.c:1748-1772): the

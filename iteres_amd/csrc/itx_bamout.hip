@@ -10,7 +10,9 @@
 //                  say how many whole payloads the stream now holds, and every buffer is sized before anything is written.
 //   k_bo_gather    one workgroup per tile: the tile's records are ONE contiguous range of the stream, behind what the call before
 //                  left over; staged in LDS a window at a time and stored with 16-byte vectors (itx_textpack.h says why and how).
-//   k_bo_member    one wave per whole payload: the payload into LDS, itx_bgzf_member into the member's slot (a fixed stride)
+//   k_bo_member    one wave per whole payload: the payload into LDS, itx_bgzf_member into the member's slot (a fixed stride).
+//                  After itx_bamout_set_level (filter -b -l) k_bo_member_stored (level 0) or k_bo_member_fast (level 1) stands in
+//                  its place (itx_bgzflevels.h), in the same launch shape; nothing behind it knows the level.
 //   k_bo_scan      exclusive sums of the member sizes, one workgroup     } written as k_bw_scan / k_bw_gather of itx_bigwig.hip
 //   k_bo_pack      the members one behind the other                       }
 //   then the stream's rest, less than one payload, moves to its front (device to device), and the packed total to the host.
@@ -43,7 +45,9 @@
 #define ITXD_SYNC() __syncthreads()
 #define ITXD_AMAX(p, v) atomicMax((p), (v))
 #define ITXD_CTZ(x) ((uint32_t)__builtin_ctz(x))
-#include "itx_bgzfmember.h"
+#define ITXD_AADD(p, v) ((void)atomicAdd((p), (v)))
+#define ITXD_AOR(p, v) ((void)atomicOr((p), (v)))
+#include "itx_bgzflevels.h"
 
 typedef unsigned long long ull;
 
@@ -218,6 +222,70 @@ __global__ __launch_bounds__(64) void k_bo_member(const uint8_t *__restrict__ pa
     if (lane == 0) msize[blockIdx.x] = z;
 }
 
+// ---- filter -b -l: the other levels of the members (itx_bgzflevels.h), in k_bo_member's launch shape
+// payload `m` of the stream into LDS as little-endian words, zero beyond its n bytes; returns n
+__device__ static inline uint32_t bo_load_payload(const uint8_t *__restrict__ pay, ull total, uint32_t *in)
+{
+    const ull at = (ull)blockIdx.x * BO_P;
+    const uint32_t n = total - at < BO_P ? (uint32_t)(total - at) : BO_P;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(pay + at);
+    for (uint32_t i = threadIdx.x; i < BO_P / 4 + 4; i += 64) {
+        uint32_t v = 0;
+        if (4u * i + 4u <= n) {
+            v = src[i];
+        } else {
+            for (uint32_t k = 0; k < 4u && 4u * i + k < n; k++) v |= (uint32_t)pay[at + 4u * i + k] << (8u * k);      // (the last payload's ragged word)
+        }
+        in[i] = v;
+    }
+    __syncthreads();
+    return n;
+}
+
+#define BO_STAGE_WORDS ITXF_STAGE_WORDS(BO_P, ITX_BGZF_LEAD)       // a whole member of a full payload, in words
+static_assert(4u * BO_STAGE_WORDS <= BO_STRIDE, "a member's whole words fit its slot");
+
+// level 0: the payload behind a stored block's 5 bytes. The workspace is the payload, the member and the CRC's terms.
+__global__ __launch_bounds__(64) void k_bo_member_stored(const uint8_t *__restrict__ pay, ull total, uint8_t *__restrict__ mem, uint32_t *__restrict__ msize)
+{
+    __shared__ uint32_t s_in[BO_P / 4 + 4], s_stage[BO_STAGE_WORDS];
+    __shared__ uint64_t s_red[64];
+    const uint32_t n = bo_load_payload(pay, total, s_in);
+    const itxf_ws w = {{s_in, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s_red, nullptr}, s_stage, nullptr};
+    const uint32_t z = itx_bgzf_member_level(w, n, mem + (ull)blockIdx.x * BO_STRIDE, threadIdx.x, 64, 0u);
+    if (threadIdx.x == 0) msize[blockIdx.x] = z;
+}
+
+// LDS of the fast level's encoder: BoLds with the member's staging area over the hash heads (dead when it is first written), which
+// is 32 bytes longer than they are, and the slices' bit counts
+struct BoLdsFast {
+    uint32_t in[BO_P / 4 + 4];
+    uint32_t head[BO_STAGE_WORDS];
+    uint16_t md[BO_P];
+    uint8_t ml[BO_P];
+    uint32_t fq[ITXD_NSYM], key[ITXD_NSYM];
+    uint16_t srt[ITXD_NSYM], code[ITXD_NSYM];
+    uint8_t len[ITXD_NSYM];
+    uint32_t clfq[20];
+    uint16_t clcode[20];
+    uint8_t cllen[20];
+    uint64_t red[128];
+    uint32_t misc[16];
+    uint32_t sbits[ITXF_SLICES(BO_P) + 1];
+};
+static_assert(BO_STAGE_WORDS >= (1u << ITXD_HBITS), "the staging area holds the hash heads");
+static_assert(3u * sizeof(BoLdsFast) <= 160u * 1024u, "three members in flight per CU, as k_bo_member");
+
+// level 1: every stage of the encoder on all 64 lanes (itx_deflate_fast.h)
+__global__ __launch_bounds__(64) void k_bo_member_fast(const uint8_t *__restrict__ pay, ull total, uint8_t *__restrict__ mem, uint32_t *__restrict__ msize)
+{
+    __shared__ BoLdsFast s;
+    const uint32_t n = bo_load_payload(pay, total, s.in);
+    const itxf_ws w = {{s.in, s.head, s.ml, s.md, s.fq, s.key, s.srt, s.len, s.code, s.clfq, s.cllen, s.clcode, s.red, s.misc}, s.head, s.sbits};
+    const uint32_t z = itx_bgzf_member_level(w, n, mem + (ull)blockIdx.x * BO_STRIDE, threadIdx.x, 64, 1u);
+    if (threadIdx.x == 0) msize[blockIdx.x] = z;
+}
+
 // exclusive prefix sum of the member sizes: moff[0 .. n] (one workgroup, itx_device.h)
 __global__ __launch_bounds__(ITX_SCAN_WG) void k_bo_scan(const uint32_t *__restrict__ msize, uint64_t n, uint64_t *__restrict__ moff)
 {
@@ -272,6 +340,7 @@ struct itx_bamout {
     bo_slot slot[2];
     int head, pending;               // the oldest batch not yet collected; batches not yet collected
     int finished;
+    int level, level_set;            // the members' level (itx_bgzflevels.h): 6 unless itx_bamout_set_level chose another
     itx_bamout_stats stats;
     itx_bamidx *ix;                  // filter -b -i (itx_bamout_index_enable): the .bai index in the making, else null
     ull stream_base;                 // bytes of the record stream that are members already: d_pay[0] is this byte of the stream
@@ -357,6 +426,7 @@ extern "C" int itx_bamout_create(int device, size_t batch_capacity, size_t strea
     bo->device = device;
     bo->cap = batch_capacity;
     bo->n_ref = -1;
+    bo->level = 6;
     const size_t n = batch_capacity + 64, nt = (batch_capacity + BO_TILE - 1) / BO_TILE + 1;
     if (stream_bytes < 4 * (size_t)BO_P) stream_bytes = 4 * (size_t)BO_P;
     bo->pay_cap = stream_bytes;
@@ -513,7 +583,10 @@ static int bo_emit(itx_bamout *bo, ull total, int with_tail)
     if (n_mem) {
         bo_slot *s = &bo->slot[(bo->head + bo->pending) & 1];
         BO_TRY(hipEventRecord(s->e0, bo->st));
-        hipLaunchKernelGGL(k_bo_member, dim3(n_mem), dim3(64), 0, bo->st, bo->d_pay, with_tail ? total : n_full * BO_P, bo->d_mem, bo->d_msize);
+        const ull n_bytes = with_tail ? total : n_full * BO_P;
+        if (bo->level == 6) hipLaunchKernelGGL(k_bo_member, dim3(n_mem), dim3(64), 0, bo->st, bo->d_pay, n_bytes, bo->d_mem, bo->d_msize);
+        else if (bo->level == 1) hipLaunchKernelGGL(k_bo_member_fast, dim3(n_mem), dim3(64), 0, bo->st, bo->d_pay, n_bytes, bo->d_mem, bo->d_msize);
+        else hipLaunchKernelGGL(k_bo_member_stored, dim3(n_mem), dim3(64), 0, bo->st, bo->d_pay, n_bytes, bo->d_mem, bo->d_msize);
         BO_TRY(hipGetLastError());
         if (bo->ix && (rc = itx_bamidx_members(bo->ix, bo->st, bo->d_msize, n_mem)) != ITX_OK) goto out;
         hipLaunchKernelGGL(k_bo_scan, dim3(1), dim3(ITX_SCAN_WG), 0, bo->st, bo->d_msize, (uint64_t)n_mem, bo->d_moff);
@@ -813,6 +886,24 @@ extern "C" int itx_bamout_get_stats(const itx_bamout *bo, itx_bamout_stats *out)
     out->carry = bo->carry;
     return ITX_OK;
 }
+
+// ---- filter -b -l: the level of the members
+extern "C" int itx_bamout_set_level(itx_bamout *bo, int level)
+{
+    if (!bo || !ITX_BGZF_LEVEL_OK(level)) {
+        itx_set_error("itx_bamout_set_level: %s", bo ? "the level is 0 (stored), 1 (fast) or 6 (the default)" : "bad argument");
+        return ITX_E_ARG;
+    }
+    if (bo->level_set || bo->finished || bo->stats.batches || bo->stats.host_batches) {
+        itx_set_error("itx_bamout_set_level: %s", bo->level_set ? "called twice" : "the stream has begun");
+        return ITX_E_STATE;
+    }
+    bo->level = level;
+    bo->level_set = 1;
+    return ITX_OK;
+}
+
+extern "C" int itx_bamout_get_level(const itx_bamout *bo) { return bo ? bo->level : ITX_E_ARG; }
 
 // ---- filter -b -s: the stream held, sorted by coordinate and replayed
 extern "C" int itx_bamout_sort_enable(itx_bamout *bo)

@@ -36,6 +36,7 @@ EXPORTS = [
     "itx_bamout_create", "itx_bamout_destroy", "itx_bamout_hits", "itx_bamout_stream", "itx_bamwin_bamout", "itx_bamout_run", "itx_bamout_wait_kernels",
     "itx_bamout_append_host", "itx_bamout_finish", "itx_bamout_collect", "itx_bamout_pending", "itx_bamout_get_stats", "itx_bamout_index_enable",
     "itx_bamout_index_finish", "itx_bamout_sort_enable", "itx_bamout_sort_next", "itx_bamout_sort_get_stats",
+    "itx_bamout_set_level", "itx_bamout_get_level",
     "itx_loci_create", "itx_loci_destroy", "itx_loci_order", "itx_loci_filter_text", "itx_loci_cpg_text",
     "itx_samtext_create", "itx_samtext_destroy", "itx_samtext_parse_begin", "itx_samtext_parse_end", "itx_samtext_fetch",
     "itx_samtext_parse_begin_bgzf", "itx_samtext_bgzf_info", "itx_samtext_text", "itx_samtext_strings",
@@ -273,6 +274,8 @@ def load():
     L.itx_bamout_sort_enable.argtypes = [C.c_void_p]
     L.itx_bamout_sort_next.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     L.itx_bamout_sort_get_stats.argtypes = [C.c_void_p, C.POINTER(BamoutSortStats)]
+    L.itx_bamout_set_level.argtypes = [C.c_void_p, C.c_int]
+    L.itx_bamout_get_level.argtypes = [C.c_void_p]
     L.itx_loci_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                   C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
     L.itx_loci_destroy.argtypes = [C.c_void_p]
@@ -759,7 +762,7 @@ class Bamout:
     offsets, int32 rows), `append_host` whole records as bytes. Every call collects what is pending, so the members made so far are
     in `self.out` (a bytearray) in stream order; `finish()` adds the last, short member and returns all of them. After
     `sort_enable()` (filter -b -s) nothing leaves during the pass; `sort_all()` in place of `finish()` returns the members of the
-    stream sorted by coordinate."""
+    stream sorted by coordinate. `set_level()` (filter -b -l), before the first batch, chooses how the members are encoded."""
 
     def __init__(self, batch_capacity: int = 1 << 20, stream_bytes: int = 0, device: int = 0):
         self._h = C.c_void_p()
@@ -839,6 +842,13 @@ class Bamout:
         while self.sort_next():
             pass
         return bytes(self.out)
+
+    def set_level(self, level: int):
+        """before the first batch: the members' level (filter -b -l): 0 stored, 1 the fast encoder, 6 the default"""
+        _chk(load().itx_bamout_set_level(self._h, level), "itx_bamout_set_level")
+
+    def level(self):
+        return int(load().itx_bamout_get_level(self._h))
 
     def sort_stats(self):
         s = BamoutSortStats()

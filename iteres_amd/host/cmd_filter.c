@@ -26,6 +26,7 @@ static int filter_usage(void)
     fprintf(stderr, "         -b       output the counted reads as <prefix>_<filter>.iteres.bam, every one of them whatever -t says; BAM input only (an extension: not in the reference) [off]\n");
     fprintf(stderr, "         -i       with -b: also write its index <prefix>_<filter>.iteres.bam.bai, for coordinate-sorted input (an extension) [off]\n");
     fprintf(stderr, "         -s       with -b: write the counted reads sorted by coordinate, so that -i works on input in any order (an extension) [off]\n");
+    fprintf(stderr, "         -l       with -b: level of its BGZF members, 0 (stored), 1 (fast) or 6 (smallest) (an extension) [6]\n");
     fprintf(stderr, "         -R       remove redundant reads [off]\n");
     fprintf(stderr, "         -T       treat 1 paired-end read as 2 single-end reads [off]\n");
     fprintf(stderr, "         -D       discard if only one end mapped in a paired end reads [off]\n");
@@ -47,10 +48,10 @@ int main_filter(int argc, char **argv)
     o.isize = 500;
     o.extension = 150;
     o.min_cov = 0.0001f;
-    int optthreshold = 1, optreadlist = 0, optbam = 0, optindex = 0, optsort = 0, optNorm = 0, c, filterField = 0;
+    int optthreshold = 1, optreadlist = 0, optbam = 0, optindex = 0, optsort = 0, optlevel = -1, optNorm = 0, c, filterField = 0;
     char *optoutput = NULL, *optname = NULL, *optclass = NULL, *optfamily = NULL;
     const time_t start_time = time(NULL);
-    while ((c = getopt(argc, argv, "SQ:g:N:n:c:t:f:rbisRTDCE:I:o:h?")) >= 0) {
+    while ((c = getopt(argc, argv, "SQ:g:N:n:c:t:f:rbisl:RTDCE:I:o:h?")) >= 0) {
         switch (c) {
         case 'S': o.is_sam = 1; break;
         case 'Q': o.mapq = (unsigned)strtol(optarg, 0, 0); break;
@@ -61,6 +62,13 @@ int main_filter(int argc, char **argv)
         case 'b': optbam = 1; break;
         case 'i': optindex = 1; break;
         case 's': optsort = 1; break;
+        case 'l': {
+            char *end = NULL;
+            const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || (v != 0 && v != 1 && v != 6)) die("-l takes the level of the BAM's members, 0 (stored), 1 (fast) or 6 (the default): not '%s'", optarg);
+            optlevel = (int)v;
+            break;
+        }
         case 'R': o.dedup = 1; break;
         case 'T': o.treat = 1; break;
         case 'D': o.discard = 1; break;
@@ -81,6 +89,7 @@ int main_filter(int argc, char **argv)
     if (optbam && o.is_sam) die("-b writes BAM records as they lie in the input: it cannot be combined with -S (SAM text has none)");
     if (optindex && !optbam) die("-i writes the index of the BAM that -b writes: it cannot be used without -b");
     if (optsort && !optbam) die("-s sorts the BAM that -b writes: it cannot be used without -b");
+    if (optlevel >= 0 && !optbam) die("-l chooses the level of the BAM that -b writes: it cannot be used without -b");
     if (optbam && getenv("ITX_HOST_INFLATE"))
         die("-b gathers the records on the device, where the BAM is decoded: it cannot be combined with ITX_HOST_INFLATE (the host decoder)");
     o.chr_size_file = argv[optind];
@@ -123,6 +132,8 @@ int main_filter(int argc, char **argv)
         o.bam_out_path = outBam;
         o.bam_index = optindex;
         o.bam_sort = optsort;
+        o.bam_level_given = optlevel >= 0;
+        o.bam_level = optlevel >= 0 ? optlevel : 6;
         aln_keep_header(1);                      /* before the helper thread opens the file */
     }
     gpu_warmup_start(!o.is_sam, o.aln_arg, 0, splittable);

@@ -224,6 +224,8 @@ typedef struct {
     const char *bed_path, *bed_uniq_path;      /* stat -B / -V (generic.c:925-936), NULL = off */
     const char *bam_out_path;                  /* filter -b (an extension): the counted records as a BAM, NULL = off */
     int bam_sort;                              /* filter -b -s: the counted records leave sorted by coordinate (held and sorted on the device) */
+    int bam_level;                             /* filter -b -l: the members' level (0, 1 or 6), read only when bam_level_given: without -l the */
+    int bam_level_given;                       /* writer is not told a level and ITX_TIMING's line is the one it always was */
     int bam_index;                             /* filter -b -i: <bam_out_path>.bai beside it, built on the device in the same pass */
 } run_opts;
 /* counters of the record loop that only the host sees (generic.c:1048-1060) */

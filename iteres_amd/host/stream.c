@@ -938,6 +938,7 @@ static void map_targets(stream_run *r, stream_file *f)
         if (bgzf_write_members(r->bam_f, hb, hl) != 0) die("writing %s: %s", o->bam_out_path, strerror(errno));
         r->bam_header_done = 1;
         chk(itx_bamout_create(multi_device(), BATCH_RECORDS, 0, &r->bo), "itx_bamout_create");
+        if (o->bam_level_given) chk(itx_bamout_set_level(r->bo, o->bam_level), "itx_bamout_set_level");
         if (o->bam_sort) chk(itx_bamout_sort_enable(r->bo), "itx_bamout_sort_enable");
         if (o->bam_index) bam_index_begin(r, hb, hl);
         free(sorted_hb);
@@ -1302,17 +1303,19 @@ static void finish_bam(stream_run *r)
         if (r->bo) chk(itx_bamout_get_stats(r->bo, &bs), "itx_bamout_get_stats");
         fprintf(stderr, "[itx timing] bam out: %llu records, %llu payload bytes, %llu members (%llu bytes), %.3f ms in the gather kernels, %.3f ms in the member kernels, host waited %.3f s, %llu batches gathered on the device, %llu batches by the host route%s",
                 (unsigned long long)bs.records, (unsigned long long)bs.payload_bytes, (unsigned long long)bs.members, (unsigned long long)bs.out_bytes, bs.gather_ms,
-                bs.member_ms, 1e-3 * bs.wait_ms, r->bam_dev_batches, r->bam_host_batches, r->o->bam_index || r->o->bam_sort ? "" : "\n");
+                bs.member_ms, 1e-3 * bs.wait_ms, r->bam_dev_batches, r->bam_host_batches, r->o->bam_index || r->o->bam_sort || r->o->bam_level_given ? "" : "\n");
         if (r->o->bam_sort) {
             itx_bamout_sort_stats ss;
             memset(&ss, 0, sizeof ss);
             if (r->bo) chk(itx_bamout_sort_get_stats(r->bo, &ss), "itx_bamout_sort_get_stats");
             fprintf(stderr, "; sort: %llu records sorted, %llu rounds, %.3f ms in the sort kernels, %.3f ms in the replay gathers%s", (unsigned long long)ss.records,
-                    (unsigned long long)ss.rounds, ss.sort_ms, ss.replay_ms, r->o->bam_index ? "" : "\n");
+                    (unsigned long long)ss.rounds, ss.sort_ms, ss.replay_ms, r->o->bam_index || r->o->bam_level_given ? "" : "\n");
         }
         if (r->o->bam_index)
-            fprintf(stderr, "; index: %llu entries, %llu chunks, %llu bytes, %.3f ms in the entry kernels, %.3f ms in the final kernels\n", (unsigned long long)ir.entries,
-                    (unsigned long long)ir.chunks, (unsigned long long)ir.len, ir.batch_ms, ir.finish_ms);
+            fprintf(stderr, "; index: %llu entries, %llu chunks, %llu bytes, %.3f ms in the entry kernels, %.3f ms in the final kernels%s", (unsigned long long)ir.entries,
+                    (unsigned long long)ir.chunks, (unsigned long long)ir.len, ir.batch_ms, ir.finish_ms, r->o->bam_level_given ? "" : "\n");
+        /* -l: the level the writer used ends the line; without -l the line is the one it was before there were levels */
+        if (r->o->bam_level_given) fprintf(stderr, ", level %d\n", r->bo ? itx_bamout_get_level(r->bo) : r->o->bam_level);
     }
     itx_bamout_destroy(r->bo);
     r->bo = NULL;
