@@ -245,8 +245,11 @@ int itx_engine_get_stats(itx_engine *e, itx_stats *out);
  * i inflated to exactly usize bytes, else a small positive code (the data is damaged or the decoder declined it —
  * the caller's zlib has the last word, as in the reference). Synchronous; one calling thread per inflater. */
 typedef struct itx_inflater itx_inflater;
-#define ITX_BAMWIN_LANES 8        /* pushes that may be in flight at once (push_begin's s); ITX_PUSHES (environment) says how many an inflater sets up */
-#define ITX_BAMWIN_LANES_DEFAULT 8  /* their kernels run in groups of ITX_GROUP (default 4) pushes a launch on ITX_LANES (default 1) compute lanes: the next pushes' bytes cross PCIe while a lane computes */
+#define ITX_BAMWIN_LANES 12       /* pushes that may be in flight at once (push_begin's s); ITX_PUSHES (environment) says how many an inflater sets up */
+#define ITX_BAMWIN_LANES_DEFAULT 12 /* their kernels run in groups of ITX_GROUP (default 4) pushes a launch on ITX_LANES (default 1) compute lanes. A launch
+                                   * covers pass 1 of its group and pass 2 of the group before it on the lane (ITX_FUSE=0: both passes of its own group, two
+                                   * kernels): three groups are alive at once, one whose bytes cross PCIe, one in pass 1, one waiting for pass 2. With
+                                   * itx_inflater_reserve the 12 slots, two scratch buffers and 16 windows of the command's 384 MB chunks are 26 597 153 792 bytes of HBM, 17.3 GB before */
 #define ITX_BAMWIN_WINDOWS 48     /* windows of inflated bytes (w): the decode may run this far ahead of the consumer (a window's
                                    * buffer is allocated when it is first pushed into: 288 GB of HBM is room for a long lead) */
 typedef struct itx_bgzf_block {

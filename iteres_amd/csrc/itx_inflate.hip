@@ -44,6 +44,8 @@ static __device__ inline uint32_t itxi_pksign16(uint32_t a, uint32_t b)
 #include "itx_inflate_core.h"
 #define ITXG_FN static __host__ __device__ inline
 #include "itx_inflate_group.h"
+#define ITXD_FN static __host__ __device__ inline
+#include "itx_decode_roles.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -71,28 +73,31 @@ template <typename T> static __host__ __device__ inline T itxg_pick(T const (&a)
     return v;
 }
 
-// pass 1: lane = block. meta[3g] = status, [3g+1] = literals, [3g+2] = tokens (g: the group-wide index)
-__global__ __launch_bounds__(64) void k_tokens(const GroupArgs G, uint8_t *__restrict__ scr, uint32_t *__restrict__ meta)
-{
+// pass 1 of one wave: lane ln takes the group-wide index g = first + ln (first: a multiple of 64). meta[3g] = status,
+// [3g+1] = literals, [3g+2] = tokens. lds: ITXD_LDS bytes, the wave's own
 #ifndef ITXI_SYM16
-    __shared__ uint32_t s_lhi[9 * 64];                                   // 26 880 bytes in all: six of these workgroups to a CU
-    __shared__ uint16_t s_loffs[16 * 64], s_doffs[16 * 64];
-    __shared__ uint8_t s_lsym8[288 * 64], s_dsym[32 * 64];
+#define ITXD_LDS ((9u * 4u + 16u * 2u + 16u * 2u + 288u + 32u) * 64u)          /* 26 880 bytes in all: six of these workgroups to a CU */
 #else
-    __shared__ uint16_t s_lsym16[288 * 64], s_loffs[16 * 64], s_doffs[16 * 64];      // 43 008 bytes: three to a CU (experiment builds)
-    __shared__ uint8_t s_dsym[32 * 64];
+#define ITXD_LDS ((288u * 2u + 16u * 2u + 16u * 2u + 32u) * 64u)              /* 43 008 bytes: three to a CU (experiment builds) */
 #endif
-    const uint32_t ln = threadIdx.x, g = blockIdx.x * 64u + ln;
+static __device__ inline void pass1_wave(const GroupArgs &G, uint32_t first, uint32_t ln, uint32_t *lds, uint8_t *__restrict__ scr, uint32_t *__restrict__ meta)
+{
+    const uint32_t g = first + ln;
     uint32_t slot, wb;
-    (void)itxg_locate(G.x, blockIdx.x * 64u, &slot, &wb);               // a slot starts at a multiple of 64: the whole wave is in one
+    (void)itxg_locate(G.x, first, &slot, &wb);                          // a slot starts at a multiple of 64: the whole wave is in one
     const uint32_t b = wb + ln;
     if (b >= itxg_pick(G.x.n, slot)) return;
     const itx_bgzf_block *__restrict__ blk = itxg_pick(G.blk, slot);
     const uint32_t *__restrict__ comp = itxg_pick(G.comp, slot);
     const uint32_t coff = blk[b].coff, csize = blk[b].csize, usize = blk[b].usize;
 #ifndef ITXI_SYM16
+    uint32_t *s_lhi = lds;                                              // [9 * 64]
+    uint16_t *s_loffs = reinterpret_cast<uint16_t *>(s_lhi + 9 * 64), *s_doffs = s_loffs + 16 * 64;
+    uint8_t *s_lsym8 = reinterpret_cast<uint8_t *>(s_doffs + 16 * 64), *s_dsym = s_lsym8 + 288 * 64;
     ItxiTab T{s_lsym8, s_lhi, s_dsym, s_loffs, s_doffs};
 #else
+    uint16_t *s_lsym16 = reinterpret_cast<uint16_t *>(lds), *s_loffs = s_lsym16 + 288 * 64, *s_doffs = s_loffs + 16 * 64;
+    uint8_t *s_dsym = reinterpret_cast<uint8_t *>(s_doffs + 16 * 64);
     ItxiTab T{s_lsym16, s_dsym, s_loffs, s_doffs};
 #endif
     uint8_t *region = scr + (size_t)g * SCR_STRIDE;
@@ -105,13 +110,12 @@ __global__ __launch_bounds__(64) void k_tokens(const GroupArgs G, uint8_t *__res
     meta[3 * g + 2] = K.n_tok;
 }
 
-// pass 2: wave = block, the group-wide indices [first, first + n)
-__global__ __launch_bounds__(64) void k_resolve(const GroupArgs G, uint32_t first, uint32_t n, const uint8_t *__restrict__ scr, const uint32_t *__restrict__ meta)
+// pass 2 of one wave: all 64 lanes on the block at the group-wide index g. lds: ITXD_LDS2 bytes, the wave's own: the ring, right
+// behind it the literal stage, then the bitmap of token starts
+#define ITXD_LDS2 (ITXI_RING + ITXI_LSTAGE + ITXI_BMAP / 8u + 8u)
+static __device__ inline void pass2_wave(const GroupArgs &G, uint32_t g, uint32_t lane, uint32_t *lds, const uint8_t *__restrict__ scr, const uint32_t *__restrict__ meta)
 {
-    __shared__ uint32_t s_mem[(ITXI_RING + ITXI_LSTAGE + ITXI_BMAP / 8u + 8u) / 4];       // the ring, right behind it the literal stage, then the bitmap of token starts
-    uint32_t *s_ring = s_mem, *s_stage = s_mem + ITXI_RING / 4, *s_bmap = s_mem + (ITXI_RING + ITXI_LSTAGE) / 4;
-    if (blockIdx.x >= n) return;
-    const uint32_t g = first + blockIdx.x;
+    uint32_t *s_ring = lds, *s_stage = lds + ITXI_RING / 4, *s_bmap = lds + (ITXI_RING + ITXI_LSTAGE) / 4;
     uint32_t slot, b;
     if (!itxg_locate(G.x, g, &slot, &b)) return;                         // padding between two slots
     const itx_bgzf_block *__restrict__ blk = itxg_pick(G.blk, slot);
@@ -119,10 +123,49 @@ __global__ __launch_bounds__(64) void k_resolve(const GroupArgs G, uint32_t firs
     if (rc == ITXI_OK) {
         const uint8_t *region = scr + (size_t)g * SCR_STRIDE;
         rc = itxi_resolve(s_ring, s_stage, s_bmap, region, reinterpret_cast<const uint32_t *>(region + SCR_STRIDE), meta[3 * g + 1], meta[3 * g + 2], itxg_pick(G.out, slot),
-                          blk[b].uoff, blk[b].usize, threadIdx.x);
+                          blk[b].uoff, blk[b].usize, lane);
     }
-    if (threadIdx.x == 0) itxg_pick(G.status, slot)[b] = (uint8_t)rc;
+    if (lane == 0) itxg_pick(G.status, slot)[b] = (uint8_t)rc;
 }
+
+// pass 1 alone: lane = block
+__global__ __launch_bounds__(64) void k_tokens(const GroupArgs G, uint8_t *__restrict__ scr, uint32_t *__restrict__ meta)
+{
+    __shared__ uint32_t s_mem[ITXD_LDS / 4];
+    pass1_wave(G, blockIdx.x * 64u, threadIdx.x, s_mem, scr, meta);
+}
+
+// pass 2 alone: wave = block, the group-wide indices [first, first + n)
+__global__ __launch_bounds__(64) void k_resolve(const GroupArgs G, uint32_t first, uint32_t n, const uint8_t *__restrict__ scr, const uint32_t *__restrict__ meta)
+{
+    __shared__ uint32_t s_mem[ITXD_LDS2 / 4];
+    if (blockIdx.x >= n) return;
+    pass2_wave(G, first + blockIdx.x, threadIdx.x, s_mem, scr, meta);
+}
+
+// Both at once (itx_decode_roles.h): pass 1 of the group C (current) in the first workgroups' wave 0, pass 2 of the group P (the
+// one whose pass 1 the launch before carried) a block per wave in the others. The two share nothing — P's tokens lie in the
+// other scratch buffer — so pass 2's waves fill the CUs that pass 1's few, latency-bound waves leave empty. One static LDS block
+// of pass 1's size: a pass-2 wave uses its own quarter of it.
+#ifndef ITXI_SYM16
+#define ITXD_LDS2_STRIDE ((ITXD_LDS2 + 15u) & ~15u)                /* a wave's quarter starts 16-byte aligned, as k_resolve's block does */
+static_assert(ITXD_WAVES * ITXD_LDS2_STRIDE <= ITXD_LDS, "four pass-2 waves' rings, stages and bitmaps fit pass 1's tables");
+static_assert(ITXD_LDS == 26880u, "six workgroups to a CU");
+// (167 VGPRs, pass 1's 170 less three, no scratch: three waves to a SIMD. Held to 128 — four waves — the compiler spills 20 of them
+// and 34 SGPRs into pass 1's chain, 80 bytes of scratch a lane: the chain is the launch's length, so it keeps its registers.)
+__global__ __launch_bounds__(ITXD_THREADS) void k_decode(const GroupArgs C, const GroupArgs P, const itxd_grid R, uint8_t *__restrict__ scr_c, uint32_t *__restrict__ meta_c,
+                                                         const uint8_t *__restrict__ scr_p, const uint32_t *__restrict__ meta_p)
+{
+    __shared__ uint32_t s_mem[ITXD_LDS / 4];
+    const uint32_t wave = ITXI_UNI(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    uint32_t first;
+    const uint32_t role = itxd_role(R, blockIdx.x, wave, &first);
+    if (role == ITXD_PASS1)
+        pass1_wave(C, first, lane, s_mem, scr_c, meta_c);                // wave 0: lane == threadIdx.x
+    else if (role == ITXD_PASS2)
+        pass2_wave(P, first, lane, s_mem + wave * (ITXD_LDS2_STRIDE / 4), scr_p, meta_p);
+}
+#endif
 
 // =====================================================================================================================
 // The decoded stream stays on the device: a WINDOW of inflated bytes per chunk, the BAM records in it located and
@@ -397,6 +440,26 @@ static int group_size()
     return v;
 }
 
+// ... and whether a launch is FUSED (ITX_FUSE, 0 or 1): one k_decode that carries pass 1 of a group and pass 2 of the group
+// before it on the lane, instead of k_tokens and k_resolve one behind the other. On one lane the pair is strictly serial — pass 2
+// runs alone, 8.3 of every 36.7 ms, on a chip that pass 1's 700 waves left nearly empty a moment before — although pass 2 only
+// needs the tokens of the PREVIOUS launch. With more than one compute lane the launches of different lanes overlap already: those
+// keep the two kernels (ITX_LANES > 1 switches the fusion off).
+#define ITX_FUSE_DEFAULT 1
+static bool fuse_on()
+{
+    static int v = -1;
+    if (v < 0) {
+#ifndef ITXI_SYM16
+        const char *e = getenv("ITX_FUSE");
+        v = ((e && *e) ? atoi(e) != 0 : ITX_FUSE_DEFAULT != 0) && compute_lanes() == 1;
+#else
+        v = 0;
+#endif
+    }
+    return v != 0;
+}
+
 struct itx_inflater {
     int device;
     hipStream_t st[2];
@@ -432,8 +495,10 @@ struct itx_inflater {
     struct {
         int n, slot[ITXG_SLOTS];           // its members, in push order
         int live;                          // members whose push_end is still to come (0: the entry is free)
-        bool launched, timed;
-        hipEvent_t ev[3];                  // ITX_TIMING: before pass 1, between the passes, after pass 2
+        int clane;                         // the compute lane it was launched on
+        bool launched, resolved, timed;    // launched: pass 1 is enqueued; resolved: pass 2 and the status copies too
+        hipEvent_t ev[3];                  // ITX_TIMING: before pass 1, between the passes, after pass 2 (fused: before and after the
+                                           // launch that carries its pass 1)
         hipEvent_t done;                   // both passes and the status copies of every member through
     } grp[ITX_BAMWIN_LANES];
     int open_grp;                          // the group that still takes members (-1: none)
@@ -441,9 +506,14 @@ struct itx_inflater {
     // a compute lane: the stream the two passes of its groups run on, one group after the other, and their scratch
     struct {
         hipStream_t cst;                   // (created when the first group is launched on it)
-        uint8_t *d_lit;
-        uint32_t *d_meta;
-        size_t lit_cap, meta_cap;
+        uint8_t *d_lit[2];                 // fused launches: the lane's q-th group writes buffer q & 1, the launch after it reads it
+        uint32_t *d_meta[2];               // (the two-kernel path uses buffer 0 alone)
+        size_t lit_cap[2], meta_cap[2];
+        unsigned long n_launched;          // groups launched on this lane
+        int pend;                          // fused: the group whose pass 1 the lane's last launch carried and whose pass 2 is still to
+        int pend_buf;                      // come (-1: none), its scratch buffer, span and arguments
+        uint32_t pend_span;
+        GroupArgs pend_args;
     } clane[ITX_BAMWIN_LANES];
     void *d_sum, *h_sum;                   // PieceSum per piece, and its host copy
     uint32_t *d_spec, *d_pb, *h_pb, *d_recoff, *d_flags;
@@ -490,6 +560,7 @@ extern "C" int itx_inflater_create(int device, itx_inflater **out)
         ITX_HIP(hipEventCreateWithFlags(&h->grp[k].done, hipEventDisableTiming));
     }
     h->open_grp = -1;
+    for (int k = 0; k < ITX_BAMWIN_LANES; k++) h->clane[k].pend = -1;
     // ONE stream carries every push's bytes across PCIe, in push order (the link is one: copies side by side only finish later,
     // all of them); a stream per slot also meant more streams than hardware queues, and streams that share a queue run one
     // after the other — two compute lanes on one queue halved pass 1's overlap (1.8 kernels in flight instead of 3)
@@ -541,8 +612,10 @@ extern "C" void itx_inflater_destroy(itx_inflater *h)
         if (!h->arena) {
             (void)hipFree(h->lane[k].d_comp);
             (void)hipFree(h->lane[k].d_status);
-            (void)hipFree(h->clane[k].d_lit);
-            (void)hipFree(h->clane[k].d_meta);
+            for (int q = 0; q < 2; q++) {
+                (void)hipFree(h->clane[k].d_lit[q]);
+                (void)hipFree(h->clane[k].d_meta[q]);
+            }
             (void)hipFree(h->lane[k].d_blk);
         }
         if (h->lane[k].h_blk) (void)hipHostFree(h->lane[k].h_blk);
@@ -745,13 +818,20 @@ extern "C" int itx_backlog_batch(const itx_backlog *b, size_t at, int with_mates
 
 // ITX_TIMING: where the decoder's device-side time goes (printed when the process ends)
 static double g_alloc_s, g_tok_ms, g_res_ms;
-static unsigned long g_allocs, g_pushes, g_launches, g_blocks;
+static unsigned long g_allocs, g_pushes, g_launches, g_blocks, g_flushes;
 static bool g_reported;
 static void report_at_exit()
 {
     if (g_reported || !g_pushes) return;
     g_reported = true;
     const double nl = g_launches ? (double)g_launches : 1.0;
+    if (fuse_on()) {
+        // a fused launch: pass 1 of its group beside pass 2 of the group before; a flush: pass 2 alone, of a group that no later one followed
+        fprintf(stderr, "[itx timing] device decoder: %lu pushes in %lu fused launches of %.0f blocks, %.1f ms per launch (pass 1 beside the previous group's pass 2; "
+                        "HIP events), %lu flush launches, %lu device allocations %.3f s\n", g_pushes, g_launches, (double)g_blocks / nl, g_tok_ms / nl, g_flushes, g_allocs,
+                g_alloc_s);
+        return;
+    }
     fprintf(stderr, "[itx timing] device decoder: %lu pushes in %lu launches of %.0f blocks, pass 1 %.1f ms and pass 2 %.1f ms per launch (HIP events, launches overlap), "
                     "%lu device allocations %.3f s\n", g_pushes, g_launches, (double)g_blocks / nl, g_tok_ms / nl, g_res_ms / nl, g_allocs, g_alloc_s);
 }
@@ -911,16 +991,66 @@ static int check_blocks(const itx_bgzf_block *blk, size_t n_blk, size_t comp_len
 #define BAD_W(w) ((w) < 0 || (w) >= ITX_BAMWIN_WINDOWS)
 #define BAD_S(s) ((s) < 0 || (s) >= lanes_in_use())
 
-/* one launch of each pass over the open group's blocks, on the next compute lane in turn: behind every member's copy, and
- * behind the group that had the lane (and its scratch) before */
+/* pass 2 of group gi is enqueued on st: behind it the status bytes of its members, and the event their push_end waits for */
+static int finish_group(itx_inflater *h, int gi, hipStream_t st)
+{
+    auto &Gr = h->grp[gi];
+    for (int m = 0; m < Gr.n; m++) {
+        auto &Ln = h->lane[Gr.slot[m]];
+        ITX_HIP(hipMemcpyAsync(Ln.h_status, Ln.d_status, Ln.n_blk, hipMemcpyDeviceToHost, st));
+    }
+    ITX_HIP(hipEventRecord(Gr.done, st));
+    Gr.resolved = true;
+    return ITX_OK;
+}
+
+#ifndef ITXI_SYM16
+/* one fused launch on compute lane CL: pass 1 of the group *cur (span blocks, scratch buffer buf; NULL: none, a FLUSH) and pass 2 of
+ * the lane's pending group, if there is one — which is finished with that */
+static int launch_decode(itx_inflater *h, decltype(h->clane[0]) &CL, const GroupArgs *cur, uint32_t span, int buf)
+{
+    static const GroupArgs none = {};
+    itxd_grid R;
+    const uint32_t n_wg = itxd_layout(&R, cur ? span : 0u, CL.pend >= 0 ? CL.pend_span : 0u);
+    if (!n_wg) return ITX_OK;
+    const int pb = CL.pend >= 0 ? CL.pend_buf : buf;
+    hipLaunchKernelGGL(k_decode, dim3(n_wg), dim3(ITXD_THREADS), 0, CL.cst, cur ? *cur : none, CL.pend >= 0 ? CL.pend_args : none, R, CL.d_lit[buf], CL.d_meta[buf],
+                       CL.d_lit[pb], CL.d_meta[pb]);
+    ITX_HIP(hipGetLastError());
+    return ITX_OK;
+}
+#endif
+
+/* the lane's pending group gets its pass 2 in a launch of its own: no later group has come that would carry it */
+static int flush_lane(itx_inflater *h, int cl)
+{
+#ifndef ITXI_SYM16
+    auto &CL = h->clane[cl];
+    if (CL.pend < 0) return ITX_OK;
+    int rc = launch_decode(h, CL, nullptr, 0, 0);
+    if (rc != ITX_OK) return rc;
+    if ((rc = finish_group(h, CL.pend, CL.cst)) != ITX_OK) return rc;
+    CL.pend = -1;
+    g_flushes++;
+#endif
+    return ITX_OK;
+}
+
+/* one launch over the open group's blocks, on the next compute lane in turn: behind every member's copy, and behind the group
+ * that had the lane before. Two kernels, pass 1 then pass 2, on the lane's one scratch buffer — or (fuse_on) one k_decode: pass 1 of
+ * this group into the lane's other scratch buffer, beside pass 2 of the group the lane's last launch left pending; this group is
+ * pending then, until the next launch or a flush (itx_bamwin_push_end) */
 static int launch_group(itx_inflater *h)
 {
     const int gi = h->open_grp;
     if (gi < 0) return ITX_OK;
     auto &Gr = h->grp[gi];
     h->open_grp = -1;
-    auto &CL = h->clane[h->grp_seq % (unsigned long)compute_lanes()];
+    Gr.clane = (int)(h->grp_seq % (unsigned long)compute_lanes());
+    auto &CL = h->clane[Gr.clane];
     h->grp_seq++;
+    const bool fused = fuse_on();
+    const int buf = fused ? (int)(CL.n_launched & 1u) : 0;
     GroupArgs G;
     memset(&G, 0, sizeof G);
     uint32_t counts[ITXG_SLOTS] = {0};
@@ -934,25 +1064,35 @@ static int launch_group(itx_inflater *h)
         G.status[m] = Ln.d_status;
     }
     int rc;
-    if ((rc = grow(&CL.d_lit, &CL.lit_cap, (size_t)span * SCR_STRIDE)) != ITX_OK) return rc;      // (growing frees: that waits for whatever still runs)
-    if ((rc = grow(&CL.d_meta, &CL.meta_cap, 3 * (size_t)span)) != ITX_OK) return rc;
+    if ((rc = grow(&CL.d_lit[buf], &CL.lit_cap[buf], (size_t)span * SCR_STRIDE)) != ITX_OK) return rc;      // (growing frees: that waits for whatever still runs)
+    if ((rc = grow(&CL.d_meta[buf], &CL.meta_cap[buf], 3 * (size_t)span)) != ITX_OK) return rc;
     if (!CL.cst) ITX_HIP(hipStreamCreateWithFlags(&CL.cst, hipStreamNonBlocking));
     hipStream_t st = CL.cst;
     for (int m = 0; m < Gr.n; m++) ITX_HIP(hipStreamWaitEvent(st, h->lane[Gr.slot[m]].copied, 0));
     ITX_HIP(hipEventRecord(Gr.ev[0], st));
-    hipLaunchKernelGGL(k_tokens, dim3((span + 63u) / 64u), dim3(64), 0, st, G, CL.d_lit, CL.d_meta);
-    ITX_HIP(hipGetLastError());
-    // pass 2 on the same stream, one wave per block (every push's pass 2 on one shared stream, or a fixed set of waves
-    // that take blocks in turn, were measured slower: DESIGN.md)
-    ITX_HIP(hipEventRecord(Gr.ev[1], st));
-    hipLaunchKernelGGL(k_resolve, dim3(span), dim3(64), 0, st, G, 0u, span, CL.d_lit, CL.d_meta);
-    ITX_HIP(hipGetLastError());
-    ITX_HIP(hipEventRecord(Gr.ev[2], st));
-    for (int m = 0; m < Gr.n; m++) {
-        auto &Ln = h->lane[Gr.slot[m]];
-        ITX_HIP(hipMemcpyAsync(Ln.h_status, Ln.d_status, Ln.n_blk, hipMemcpyDeviceToHost, st));
+#ifndef ITXI_SYM16
+    if (fused) {
+        if ((rc = launch_decode(h, CL, &G, span, buf)) != ITX_OK) return rc;
+        ITX_HIP(hipEventRecord(Gr.ev[1], st));
+        if (CL.pend >= 0 && (rc = finish_group(h, CL.pend, st)) != ITX_OK) return rc;
+        CL.pend = gi;
+        CL.pend_buf = buf;
+        CL.pend_span = span;
+        CL.pend_args = G;
+    } else
+#endif
+    {
+        hipLaunchKernelGGL(k_tokens, dim3((span + 63u) / 64u), dim3(64), 0, st, G, CL.d_lit[0], CL.d_meta[0]);
+        ITX_HIP(hipGetLastError());
+        // pass 2 on the same stream, one wave per block (every push's pass 2 on one shared stream, or a fixed set of waves
+        // that take blocks in turn, were measured slower: DESIGN.md)
+        ITX_HIP(hipEventRecord(Gr.ev[1], st));
+        hipLaunchKernelGGL(k_resolve, dim3(span), dim3(64), 0, st, G, 0u, span, CL.d_lit[0], CL.d_meta[0]);
+        ITX_HIP(hipGetLastError());
+        ITX_HIP(hipEventRecord(Gr.ev[2], st));
+        if ((rc = finish_group(h, gi, st)) != ITX_OK) return rc;
     }
-    ITX_HIP(hipEventRecord(Gr.done, st));
+    CL.n_launched++;
     Gr.launched = true;
     g_launches++;
     for (int m = 0; m < Gr.n; m++) g_blocks += counts[m];
@@ -1012,7 +1152,7 @@ extern "C" int itx_bamwin_push_begin(itx_inflater *h, int w, int s, const void *
         while (gi < lanes_in_use() && h->grp[gi].live) gi++;       // every live group has a busy slot, and this slot was not: one is free
         if (gi == lanes_in_use()) return ITX_E_STATE;
         h->grp[gi].n = h->grp[gi].live = 0;
-        h->grp[gi].launched = h->grp[gi].timed = false;
+        h->grp[gi].launched = h->grp[gi].resolved = h->grp[gi].timed = false;
         h->open_grp = gi;
     }
     auto &Gr = h->grp[h->open_grp];
@@ -1051,11 +1191,22 @@ extern "C" int itx_bamwin_push_end(itx_inflater *h, int s, uint8_t *status, size
             const int rc = launch_group(h);
             if (rc != ITX_OK) return rc;
         }
+        if (!Gr.resolved) {
+            // fused: its pass 1 went with the lane's last launch, and no later group has been launched that carried its pass 2. The open
+            // group does that, if there is one (it is launched short, as above); else a flush
+            if (h->clane[Gr.clane].pend != Ln.grp) return ITX_E_STATE;
+            int rc = ITX_OK;
+            if (h->open_grp >= 0 && (int)(h->grp_seq % (unsigned long)compute_lanes()) == Gr.clane) rc = launch_group(h);
+            if (rc == ITX_OK && !Gr.resolved) rc = flush_lane(h, Gr.clane);
+            if (rc != ITX_OK) return rc;
+        }
         ITX_HIP(hipEventSynchronize(Gr.done));
         if (!Gr.timed) {
             Gr.timed = true;
             float a = 0, b = 0;
-            if (hipEventElapsedTime(&a, Gr.ev[0], Gr.ev[1]) == hipSuccess && hipEventElapsedTime(&b, Gr.ev[1], Gr.ev[2]) == hipSuccess) {
+            if (fuse_on()) {
+                if (hipEventElapsedTime(&a, Gr.ev[0], Gr.ev[1]) == hipSuccess) g_tok_ms += a;       // (done lies behind the next launch: ev[1] is through)
+            } else if (hipEventElapsedTime(&a, Gr.ev[0], Gr.ev[1]) == hipSuccess && hipEventElapsedTime(&b, Gr.ev[1], Gr.ev[2]) == hipSuccess) {
                 g_tok_ms += a;
                 g_res_ms += b;
             }
@@ -1099,7 +1250,8 @@ extern "C" int itx_inflater_reserve(itx_inflater *h, size_t comp_bytes, size_t m
     const size_t grp_blocks = (size_t)group_size() * ((max_blocks + ITXG_ALIGN - 1) / ITXG_ALIGN * ITXG_ALIGN);
     const size_t sz_lit = al(grp_blocks * (size_t)SCR_STRIDE), sz_meta = al(3 * grp_blocks * 4);
     const int n_comp = compute_lanes();
-    const size_t total = (sz_comp + sz_status + sz_blk) * (size_t)n_lanes + (sz_lit + sz_meta) * (size_t)n_comp + per * n;
+    const int n_scr = fuse_on() ? 2 : 1;                             // fused launches: a lane's two scratch buffers
+    const size_t total = (sz_comp + sz_status + sz_blk) * (size_t)n_lanes + (sz_lit + sz_meta) * (size_t)(n_comp * n_scr) + per * n;
     uint8_t *base = nullptr;
     const double t0 = itx_wall_now();
     hipError_t he = hipMalloc((void **)&base, total);
@@ -1130,8 +1282,10 @@ extern "C" int itx_inflater_reserve(itx_inflater *h, size_t comp_bytes, size_t m
     }
     for (int k = 0; k < n_comp; k++) {
         auto &CL = h->clane[k];
-        CL.d_lit = p; p += sz_lit; CL.lit_cap = grp_blocks * (size_t)SCR_STRIDE;
-        CL.d_meta = (uint32_t *)p; p += sz_meta; CL.meta_cap = 3 * grp_blocks;
+        for (int q = 0; q < n_scr; q++) {
+            CL.d_lit[q] = p; p += sz_lit; CL.lit_cap[q] = grp_blocks * (size_t)SCR_STRIDE;
+            CL.d_meta[q] = (uint32_t *)p; p += sz_meta; CL.meta_cap[q] = 3 * grp_blocks;
+        }
     }
     for (size_t w = 0; w < n; w++) {
         if (h->win[w].buf) (void)hipFree(h->win[w].buf);

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Scratch A/B of the whole command on one box: python tools/ab_cli.py <n_reads> <seq_len> <reps> NAME:VAR=VAL,VAR=VAL ...
 Generates the bench inputs once (bench.py's generator), then runs `iteres stat -w` <reps> times per setting, interleaved.
-LD_LIBRARY_PATH in a setting selects another build of libiteres_amd.so (the program's RUNPATH comes after it).
+LD_LIBRARY_PATH in a setting selects another build of libiteres_amd.so (the program's RUNPATH comes after it); ITX_AB_TREE=<dir below
+the repository> runs the program of another built tree, which finds its own library (parent:ITX_AB_TREE=<an export of the parent commit>).
 ITX_AB_FILTER=1 runs `iteres filter -c <the table's biggest class>` instead (ITX_AB_OPTS="-r": with the read lists) and compares
 the .loci / .reportloci files; ITX_AB_SHUFFLED=1 runs every setting on reads_shuffled.bam, the same reads with mkbam's
 order=shuffled (runs of 65 536 reads in a seeded random order, generated once beside reads.bam) (a setting may carry options of its own: `b:ITX_AB_OPTS=-b` is `filter -b` against plain `filter`); ITX_AB_FILTER=all runs `iteres filter` without a name filter (every row of the table is a line)."""
@@ -55,7 +56,8 @@ def main():
             if os.environ.get("ITX_AB_FILTER"):
                 select = [] if os.environ["ITX_AB_FILTER"] == "all" else ["-c", info["filter_class"]["name"]]
                 args = ["filter"] + select + extra + args[2:]
-            wall, rc, err, seen = bench.run_timed(bench.OURS, args + [reads], out, env, (bench.SCAN_BEGIN, bench.SCAN_END))
+            exe = os.path.join(ROOT, kv["ITX_AB_TREE"], "iteres_amd", "host", "iteres") if "ITX_AB_TREE" in kv else bench.OURS     # parent:ITX_AB_TREE=<dir>: the program (and library) of another built tree
+            wall, rc, err, seen = bench.run_timed(exe, args + [reads], out, env, (bench.SCAN_BEGIN, bench.SCAN_END))
             assert rc == 0, err[-800:]
             walls[name].append(round(wall, 3))
             scans[name].append(round(seen.get(bench.SCAN_END, 0) - seen.get(bench.SCAN_BEGIN, 0), 3))

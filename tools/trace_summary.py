@@ -42,7 +42,7 @@ if iv:
             cur_b = max(cur_b, b)
     busy += cur_b - cur_a
     print(f"kernels span {(t1 - t0) / 1e6:.1f} ms, some kernel running {busy / 1e6:.1f} ms ({100 * busy / (t1 - t0):.0f} %)")
-    for name in ("k_tokens", "k_resolve"):
+    for name in ("k_tokens", "k_resolve", "k_decode"):
         sel = [(a, b) for a, b, n in iv if n.startswith(name)]
         if sel:
             sel.sort()
@@ -90,9 +90,14 @@ if tk and rs:
     d1 = sum(b - a for a, b, n in iv if n.startswith("k_tokens"))
     d2 = sum(b - a for a, b, n in iv if n.startswith("k_resolve"))
     print(f"mean pass-1 kernels in flight while any runs: {d1 / max(length(tk), 1):.2f}; pass-2: {d2 / max(length(rs), 1):.2f}")
+# fused launches (k_decode: pass 1 of a group beside pass 2 of the one before): how long the compute lane ran one, how long it idled
+dk = union([(a, b) for a, b, n in iv if n.startswith("k_decode")])
+if dk:
+    print(f"decoder window {(dk[-1][1] - dk[0][0]) / 1e6:.1f} ms: k_decode running {length(dk) / 1e6:.1f} ms, lane idle {((dk[-1][1] - dk[0][0]) - length(dk)) / 1e6:.1f} ms")
+    tk = tk or dk
 # which hardware queue (and stream) each of the decoder's and the consumer's kernels ran on: streams that share a queue id run
 # their kernels one after the other
-for name in ("k_tokens", "k_resolve", "k_guess", "k_parse", "k_stream"):
+for name in ("k_tokens", "k_resolve", "k_decode", "k_guess", "k_parse", "k_stream"):
     ids = defaultdict(int)
     for r in k:
         if r["Kernel_Name"].replace("void ", "", 1).startswith(name):
