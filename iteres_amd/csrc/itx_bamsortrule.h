@@ -3,9 +3,11 @@
 // and integers, valid as C and as C++.
 //
 //   key      (tid, pos, reverse) read from the record's bytes (rec points at its block_size field), reverse = (flag >> 4) & 1.
-//            Records ascend by tid, then pos, then reverse: `samtools sort`'s comparison. Records with equal keys stay in input
-//            order (the sort is stable). Every counted record is mapped, so tid >= 0 and pos >= 0 hold; a record that breaks this
-//            (or has no fixed part) is reported and no sorted file is written.
+//            Records ascend by tid, then pos, then reverse: the coordinate comparison of `samtools sort` 1.x. The samtools 0.1.18
+//            that the reference vendors compares tid and pos alone (bam_sort.c bam1_lt), so this order is one of those its rule
+//            allows, and its stable sort leaves a file in this order as it is (tests/test_bam_vs_reference.py). Records with equal
+//            keys stay in input order (the sort is stable). Every counted record is mapped, so tid >= 0 and pos >= 0 hold; a record
+//            that breaks this (or has no fixed part) is reported and no sorted file is written.
 //   low key  pos << 1 | reverse, 32 bits; high key: tid. The radix sort runs over the low key's 4 bytes, then over as many bytes
 //            of tid as n_ref - 1 has (itx_bamsort_high_passes).
 //   header   the text of the BAM header under -s: an @HD line at the start keeps its fields in order except SO, GO and SS, and

@@ -6,11 +6,14 @@ project documents); it shares no code with the product.
   parse_bai / reg2bins / fetch                   an independent BAI reader and a region fetch the specification's way: the chunks of
                                                  the region's bins, the linear index's minimum offset, then reading from the virtual
                                                  offset
-  linear_scan                                    the records that overlap a region, found by walking all of them"""
+  linear_scan                                    the records that overlap a region, found by walking all of them
+  with_bin / bam_file                            a record with the bin of its own interval, and a BAM file in the product's layout
+                                                 from a header and a record list, for readers that trust the bin field"""
 import bisect
 import struct
 
 import refio
+from iteres_amd import synth
 
 PAYLOAD = 8192                      # bytes of the record stream per member (csrc/itx_bgzfmember.h ITX_BAMOUT_PAYLOAD)
 MAX_END = 1 << 29
@@ -63,6 +66,26 @@ def records_of(stream):
         at += ln
     assert at == len(stream)
     return out
+
+
+def with_bin(rec):
+    """the record with reg2bin(pos, end) in its bin field (bedcase.record stores 4681 whatever the interval)"""
+    tid, pos, end, ln = record_fields(rec, 0)
+    assert ln == len(rec)
+    out = bytearray(rec)
+    struct.pack_into("<H", out, 14, reg2bin(pos, end))
+    return bytes(out)
+
+
+def bam_file(header, records, payload=PAYLOAD, sorted_=True):
+    """the bytes of a BAM file laid out as `filter -b` lays it out: the header in members of its own, the records' stream cut every
+    `payload` bytes whatever the records' boundaries, the EOF member. header: [(name, length)]; every record gets its own bin"""
+    text = ("@HD\tVN:1.0\tSO:%s\n" % ("coordinate" if sorted_ else "unsorted") + "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in header)).encode()
+    head = b"BAM\1" + struct.pack("<i", len(text)) + text + struct.pack("<i", len(header))
+    for n, l in header:
+        head += struct.pack("<i", len(n) + 1) + n.encode() + b"\0" + struct.pack("<i", l)
+    stream = b"".join(with_bin(r) for r in records)
+    return b"".join(synth.bgzf_block(part[i:i + payload]) for part in (head, stream) for i in range(0, len(part), payload)) + synth.BGZF_EOF
 
 
 def member_walk(data):

@@ -17,28 +17,14 @@ import numpy as np
 import pytest
 
 import baicase as bai
-import bedcase as bc
+import baishapes as shapes
 import goldencase as gc
 import refio
 from iteres_amd import engine as eng, synth
 
 pytestmark = pytest.mark.gpu
 
-P = bai.PAYLOAD
-M, I, D, N, S = 0, 1, 2, 3, 4
-_BASE = len(bc.record(qname=b"q\0", cigar=((M, 50),), aux=bc.tag("ZZ", "Z", b"\0")))
-
-
-def rec(tid, pos, cigar=((M, 50),), L=None):
-    """a record at (tid, pos); L: its exact length in bytes (block_size field included), made up by a Z tag"""
-    extra = 4 * (len(cigar) - 1)
-    if L is None:
-        return bc.record(tid=tid, pos=pos, qname=b"q\0", cigar=cigar)
-    pad = L - _BASE - extra
-    assert pad >= 0, L
-    r = bc.record(tid=tid, pos=pos, qname=b"q\0", cigar=cigar, aux=bc.tag("ZZ", "Z", bytes([65 + pos % 23]) * pad + b"\0"))
-    assert len(r) == L
-    return r
+from baishapes import M, P, all_hit, big_case, rec       # the case inputs: shared with tests/test_gpu_bam_vs_reference.py
 
 
 def tensors(recs):
@@ -84,10 +70,6 @@ def check(l_ref, steps, first=0, cap=None, plain=False):
     return got, stream, idx, info
 
 
-def all_hit(recs):
-    return [0] * len(recs)
-
-
 # ---- 1. shapes
 
 def test_no_records_three_references():
@@ -112,14 +94,11 @@ def test_records_that_are_not_counted_leave_no_trace():
 @pytest.mark.parametrize("n", [255, 256, 257])
 def test_tile_boundaries(n, hit):
     """records on both sides of a 16 KiB window and of a 128 KiB bin boundary, so that chunks start inside a tile and at its edge"""
-    recs = [rec(i * 3 // n, (1 << 17) - 64 * (n // 2) + 64 * i, L=60 + i % 90) for i in range(n)]
-    rows = [0 if hit == "all" or i % 3 == 0 else -1 for i in range(n)]
-    check([1 << 20, 1 << 20, 1 << 20], [("run", recs, rows)], first=4096, plain=True)
+    check(*shapes.tile_boundaries(n, hit), first=4096, plain=True)
 
 
 def test_a_record_starts_on_the_last_byte_of_a_payload():
-    recs = [rec(0, 10, L=P - 1), rec(0, 20, L=100), rec(0, 30, L=P - 100), rec(0, 40_000, L=77)]
-    got, stream, idx, info = check([100_000], [("run", recs, all_hit(recs))], first=500)
+    got, stream, idx, info = check(*shapes.last_byte_of_a_payload(), first=500)
     chunks = bai.parse_bai(idx)[0]["bins"][4681]
     assert chunks[0][0] == 500 << 16 and len(bai.member_walk(got)) == 3
 
@@ -127,8 +106,7 @@ def test_a_record_starts_on_the_last_byte_of_a_payload():
 @pytest.mark.parametrize("tail", [0, 1])
 def test_a_record_ends_exactly_on_a_payload_boundary(tail):
     """without a tail the last chunk ends where whatever follows the members begins; finish with and without a tail member"""
-    recs = [rec(0, 10, L=P // 2), rec(0, 20, L=P // 2), rec(1, 5, L=P)] + ([rec(1, 9, L=50)] if tail else [])
-    got, stream, idx, info = check([1000, 1000], [("run", recs, all_hit(recs))], first=28, plain=True)
+    got, stream, idx, info = check(*shapes.ends_on_a_payload_boundary(tail), first=28, plain=True)
     mem = bai.member_walk(got)
     assert len(mem) == 2 + tail
     r = bai.parse_bai(idx)
@@ -138,16 +116,12 @@ def test_a_record_ends_exactly_on_a_payload_boundary(tail):
 
 
 def test_a_record_of_three_payloads_and_17_bytes():
-    recs = [rec(0, 5, L=300), rec(0, 6, L=3 * P + 17), rec(0, 7, L=300), rec(0, 20_000, L=300)]
-    got, stream, idx, info = check([100_000], [("run", recs, all_hit(recs))], first=3)
+    got, stream, idx, info = check(*shapes.three_payloads_and_17_bytes(), first=3)
     assert len(bai.member_walk(got)) == 4
 
 
 def test_references_without_records_between_references_with_records():
-    l_ref = [50_000, 70_000, 1 << 29, 0, 90_000, 20_000, 16_384]
-    recs = [rec(1, 100), rec(1, 60_000, ((M, 10), (D, 9_000), (M, 10))), rec(2, (1 << 29) - 50), rec(4, 0), rec(4, 16_383, ((S, 5), (M, 1))), rec(4, 16_383, ((M, 2),)),
-            rec(6, 16_334)]
-    got, stream, idx, info = check(l_ref, [("host", recs[:2]), ("run", recs[2:], all_hit(recs[2:]))], first=100)
+    got, stream, idx, info = check(*shapes.references_without_records(), first=100)
     r = bai.parse_bai(idx)
     assert [x["meta"] is not None for x in r] == [False, True, True, False, True, False, True]
     assert len(r[2]["lin"]) == 1 << 15 and r[2]["lin"][-2] == 0 and len(r[6]["lin"]) == 1 and len(r[4]["lin"]) == 2
@@ -157,38 +131,16 @@ def test_references_without_records_between_references_with_records():
 def test_bin_parent_bin_again(L):
     """bin X, its parent, bin X again: inside one member the two runs of X merge into one chunk; when every record fills more
     than a member, the second run begins in a later member than the first ended in, and they stay two chunks"""
-    recs = [rec(0, 100, L=L), rec(0, 110, L=L), rec(0, 200, ((M, 20_000),), L=L), rec(0, 300, L=L), rec(0, 310, L=L)]
-    got, stream, idx, info = check([1 << 20], [("run", recs, all_hit(recs))], first=64)
+    got, stream, idx, info = check(*shapes.bin_parent_bin_again(L), first=64)
     bins = bai.parse_bai(idx)[0]["bins"]
     assert sorted(bins) == [585, 4681] and len(bins[585]) == 1
     assert len(bins[4681]) == (1 if L < P else 2) and info["chunks"] == (2 if L < P else 3)
 
 
 def test_a_spliced_record_over_3000_windows():
-    recs = [rec(0, 900), rec(0, 1000, ((M, 10), (N, 50_000_000), (M, 10))), rec(0, 2000), rec(0, 30_000_000), rec(0, 50_001_015)]
-    got, stream, idx, info = check([60_000_000], [("run", recs, all_hit(recs))], first=11)
+    got, stream, idx, info = check(*shapes.spliced_over_3000_windows(), first=11)
     lin = bai.parse_bai(idx)[0]["lin"]
     assert len(lin) == (50_001_064 >> 14) + 1 > 3000 and len(set(lin[1:30_000_000 >> 14])) == 1
-
-
-def big_case():
-    """70 001 records for three `run` calls (every third is counted) and 404 for three host appends, all in coordinate order over
-    references 0, 2 and 3; now and then a spliced or a long record, so that every bin level has chunks"""
-    l_ref = [40_000_000, 1000, 30_000_000, 5_000_000]
-    n = 70_001 + 404
-    recs = []
-    for k in range(n):
-        tid, pos = (0, k * 500) if k < 30_000 else (2, (k - 30_000) * 500) if k < 60_000 else (3, (k - 60_000) * 400)
-        cig = ((M, 30), (N, 20_000 << (k % 7)), (M, 20)) if k % 101 == 0 and tid != 3 else ((M, 20 + k % 80),) if k % 13 else ((S, 4), (M, 300), (I, 2), (M, 300))
-        recs.append(rec(tid, pos, cig, L=60 + 4 * (len(cig) - 1) + (k * 7) % 90))
-    cuts = [0, 3, 3 + 32768, 3 + 32768 + 400, 3 + 32768 + 400 + 32767, n - 1, n]
-    kinds = ["host", "run", "host", "run", "run", "host"]
-    steps = []
-    for c, kind in enumerate(kinds):
-        part = recs[cuts[c]:cuts[c + 1]]
-        steps.append(("host", part) if kind == "host" else ("run", part, [2 if (cuts[c] + i) % 3 == 0 else -1 for i in range(len(part))]))
-    assert sum(len(s[1]) for s in steps if s[0] == "run") == 70_001
-    return l_ref, steps
 
 
 def regions(l_ref, counted, seed=20, n=300):
