@@ -559,6 +559,23 @@ int itx_bamout_sort_get_stats(const itx_bamout *bo, itx_bamout_sort_stats *out);
  *   get_level   the level in use (ITX_E_ARG for a null object) */
 int itx_bamout_set_level(itx_bamout *bo, int level);
 int itx_bamout_get_level(const itx_bamout *bo);
+/* Every counted record tagged with the row it was counted for (filter -b -a; the rule is csrc/itx_reptag.h). Behind the record's own
+ * bytes go ZN:Z:repName, ZC:Z:repClass, ZF:Z:repFamily, ZS:I:genoStart and ZE:I:genoEnd of the row in d_hit_row, 26 bytes and the
+ * three names, and block_size grows by as much; nothing else of the record changes. Aux bytes the record has are not looked at: a
+ * record that carries one of these tags already gets a second one behind it. The members, the index and the sort take the longer
+ * records as they come; with sort_enable the records are annotated when they are first gathered and the replay copies them.
+ *   annotate_enable  before the first batch (ITX_E_STATE after it, or when called twice). rows[n_rows]: start, end, rep, cla and
+ *               fam are read; the name tables are in the form itx_loci_create takes (name i = bytes[off[i] .. off[i + 1]), off has
+ *               n + 1 elements). Checked before anything is allocated: a null pointer, offsets that do not ascend, a row whose rep,
+ *               cla or fam lies outside its table: ITX_E_ARG; a name of 2^16 bytes or more: ITX_E_LIMIT. No device memory:
+ *               ITX_E_NOMEM. A refused call changes nothing. The rows and names are copied: the caller's arrays are its own again
+ *               on return. From then on a batch whose d_hit_row names a row >= n_rows is refused with ITX_E_ARG, and one whose
+ *               record reaches 1 GiB with its tags with ITX_E_LIMIT, nothing appended.
+ *   append_host stays a taker of whole records: the caller annotates what it counted itself by the same rule (itx_reptag.h builds as C).
+ *   annotate_get_stats  the tag bytes the device batches appended so far (they are part of stats.payload_bytes) */
+int itx_bamout_annotate_enable(itx_bamout *bo, const itx_row *rows, size_t n_rows, const char *rep_bytes, const uint64_t *rep_off, uint32_t n_rep,
+                               const char *cla_bytes, const uint64_t *cla_off, uint32_t n_cla, const char *fam_bytes, const uint64_t *fam_off, uint32_t n_fam);
+int itx_bamout_annotate_get_stats(const itx_bamout *bo, uint64_t *tag_bytes);
 
 /* ---- the .loci file of filter / cpgfilter on the device ----------------------------------------------------------------------
  * Replaces the row walk and the fprintf of writeFilterOut (generic.c:1709-1746) and writeFilterOutMRE (generic.c:1748-1772): the

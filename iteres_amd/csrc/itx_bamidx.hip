@@ -85,7 +85,10 @@ __global__ __launch_bounds__(BI_TILE) void k_bi_entries(const uint8_t *__restric
     if (!len) return;
     const uint8_t *p = u + rec_off[i];
     ItxBaiRec r;
-    itx_bai_fields(p, len, &r);
+    // `len` is the record's length in the stream, which is what its chunk needs. Under filter -b -a that is the annotated length
+    // while the bytes at p are the source record's: the fields are read inside the shorter of the two (equal without -a)
+    const uint32_t src_len = 4u + itx_bai_u32(p);
+    itx_bai_fields(p, src_len < len ? src_len : len, &r);
     const int why = itx_bai_refuses(&r, n_ref, l_ref);
     BiEnt e;
     e.pos = r.pos;

@@ -31,11 +31,17 @@
 // above: k_bs_lengths lays the round's lengths and 64-bit offsets out in sorted order, k_tile_scan2, then k_bo_gather reads the held
 // stream (scattered, a record each) and writes the payload stream (coalesced), then members, scan and pack as for any batch.
 //
+// With itx_bamout_annotate_enable (filter -b -a) a counted record leaves with the tags of its row behind it (csrc/itx_reptag.h):
+// k_bo_measure<true> adds the tags' length, a function of the row alone, k_bo_gather<uint32_t, true> lays the record with
+// itx_reptag_write in place of the byte copy. Everything behind the gather sees a longer record: the members, the index's chunks, the
+// held stream of -s (annotated at the first gather; the replay copies byte for byte). Without the call the <false> instantiations run.
+//
 // Byte and integer work. k_bo_member is bound by the encoder's serial parse (one lane per member); ITX_BAMOUT_PAYLOAD is chosen
 // for that (itx_bgzfmember.h). No kernel uses scratch (DESIGN.md has the figures).
 #include "itx_bamidx.h"
 #include "itx_bamsortrule.h"
 #include "itx_radixsort.h"
+#include "itx_reptag.h"
 #include "itx_textpack.h"
 
 #include <stdlib.h>
@@ -56,42 +62,89 @@ typedef unsigned long long ull;
 #define BO_P ITX_BAMOUT_PAYLOAD
 #define BO_STRIDE ITX_BGZF_MEMBER_CAP(BO_P)      // bytes between two members' slots (a multiple of 4)
 #define BO_MAX_RECORD 0x40000000u    // a record of a gibibyte is nobody's: the decoder's windows hold less
+#define BO_TOT_BYTES 64u             // a batch's totals: bytes, records, records too long; -a: rows outside the table, tag bytes
 
 static_assert(BO_P % 16u == 0 && BO_P <= ITXD_MAX_IN, "the payload: at most one DEFLATE window, whole 16-byte vectors");
 static_assert(BO_TILE == ITX_BAMIDX_TILE && BO_P == ITX_BAMIDX_PAYLOAD, "the index (itx_bamidx.hip) places records by the gather's tiles and payloads");
 
-__global__ __launch_bounds__(BO_TILE) void k_bo_measure(const uint8_t *__restrict__ u, const uint32_t *__restrict__ rec_off, const int32_t *__restrict__ hit_row,
-                                                         uint32_t n, uint32_t *__restrict__ len_out, ull *__restrict__ tile_sum, ull *__restrict__ tot)
+// ---- filter -b -a: the table's rows and names as the kernels read them (one allocation, itx_bamout_annotate_enable)
+struct BoAnn {
+    const uint32_t *rows;            // per row: start, end, rep, cla, fam
+    const ull *rep_off, *cla_off, *fam_off;
+    const uint8_t *rep, *cla, *fam;  // the name pools: name i of a pool is bytes [off[i], off[i + 1])
+    uint32_t n_rows;
+};
+#define BO_ROW_WORDS 5u
+
+__device__ __forceinline__ ItxRepTag bo_row_tag(const BoAnn &a, uint32_t row)
 {
-    __shared__ ull s_sum[2];
-    if (threadIdx.x < 2) s_sum[threadIdx.x] = 0;
+    const uint32_t *r = a.rows + (size_t)BO_ROW_WORDS * row;
+    ItxRepTag t;
+    t.start = r[0];
+    t.end = r[1];
+    const ull r0 = a.rep_off[r[2]], c0 = a.cla_off[r[3]], f0 = a.fam_off[r[4]];
+    t.rep = a.rep + r0;
+    t.rep_len = (uint32_t)(a.rep_off[r[2] + 1u] - r0);
+    t.cla = a.cla + c0;
+    t.cla_len = (uint32_t)(a.cla_off[r[3] + 1u] - c0);
+    t.fam = a.fam + f0;
+    t.fam_len = (uint32_t)(a.fam_off[r[4] + 1u] - f0);
+    return t;
+}
+
+// ANN: the record's length includes the tags of its row (a row outside the table counts as bad, as a record too long does)
+template <bool ANN>
+__global__ __launch_bounds__(BO_TILE) void k_bo_measure(const uint8_t *__restrict__ u, const uint32_t *__restrict__ rec_off, const int32_t *__restrict__ hit_row,
+                                                         uint32_t n, uint32_t *__restrict__ len_out, ull *__restrict__ tile_sum, ull *__restrict__ tot, BoAnn ann)
+{
+    __shared__ ull s_sum[ANN ? 3 : 2];                                     // bytes, records; ANN: and the tag bytes among them
+    if (threadIdx.x < (ANN ? 3 : 2)) s_sum[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t i = blockIdx.x * BO_TILE + threadIdx.x;
-    bool bad = false;
+    bool bad = false, bad_row = false;
     if (i < n) {
         uint32_t len = 0;
         if (hit_row[i] >= 0) {
             const uint8_t *p = u + rec_off[i];
             const uint32_t bs = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
             bad = bs >= BO_MAX_RECORD;
-            if (!bad) {
-                len = 4u + bs;
+            uint32_t tag = 0;
+            if constexpr (ANN) {
+                bad_row = (uint32_t)hit_row[i] >= ann.n_rows;
+                if (!bad && !bad_row) {
+                    const ItxRepTag t = bo_row_tag(ann, (uint32_t)hit_row[i]);
+                    tag = itx_reptag_len(&t);                              // (below 2^18: three names below 2^16 each)
+                    bad = bs + tag >= BO_MAX_RECORD;
+                }
+            }
+            if (!bad && !bad_row) {
+                len = 4u + bs + tag;
                 atomicAdd(&s_sum[0], (ull)len);
                 atomicAdd(&s_sum[1], 1ull);
+                if constexpr (ANN) atomicAdd(&s_sum[2], (ull)tag);
             }
         }
         len_out[i] = len;
     }
     const ull badm = __ballot(bad);
     if ((threadIdx.x & 63u) == 0 && badm) atomicAdd(&tot[2], (ull)__popcll(badm));
+    if constexpr (ANN) {
+        const ull rowm = __ballot(bad_row);
+        if ((threadIdx.x & 63u) == 0 && rowm) atomicAdd(&tot[3], (ull)__popcll(rowm));
+    }
     __syncthreads();
     if (threadIdx.x < 2) tile_sum[2u * blockIdx.x + threadIdx.x] = s_sum[threadIdx.x];
+    if constexpr (ANN) {
+        if (threadIdx.x == 2 && s_sum[2]) atomicAdd(&tot[4], s_sum[2]);
+    }
 }
 
 // OFF: uint32_t offsets into a window; 64-bit offsets into the held stream (the replay of filter -b -s)
-template <class OFF>
+// ANN: len_in are annotated lengths and the record is laid with its row's tags behind it (hit_row and ann are read only then)
+template <class OFF, bool ANN>
 __global__ __launch_bounds__(BO_TILE) void k_bo_gather(const uint8_t *__restrict__ u, const OFF *__restrict__ rec_off, uint32_t n,
-                                                        const uint32_t *__restrict__ len_in, const ull *__restrict__ tile_base, ull base, uint8_t *__restrict__ pay)
+                                                        const uint32_t *__restrict__ len_in, const ull *__restrict__ tile_base, ull base, uint8_t *__restrict__ pay,
+                                                        const int32_t *__restrict__ hit_row, BoAnn ann)
 {
     __shared__ uint4 s_buf[BO_LDS / 16u];
     __shared__ uint32_t s_w[BO_TILE / 64u];
@@ -102,11 +155,19 @@ __global__ __launch_bounds__(BO_TILE) void k_bo_gather(const uint8_t *__restrict
     const ull tb = base + tile_base[2u * blockIdx.x], te = tb + total;
     const ull mb = tb + moff, me = mb + len;
     const uint8_t *src = len ? u + rec_off[i] : u;
-    itx_pack_tile<BO_TILE, BO_LDS>(s_buf, pay, tb, te, mb, me, [=](uint8_t *dst, uint32_t from, uint32_t to) {
-        // a record starts wherever the one before it ended: kept a byte loop (names' gather says why)
+    if constexpr (ANN) {
+        // the measure pass has checked the row; the names are a few cached bytes per lane, read where they are laid
+        ItxRepTag t = {};
+        if (len) t = bo_row_tag(ann, (uint32_t)hit_row[i]);
+        const uint32_t rec_len = len - (len ? itx_reptag_len(&t) : 0u);
+        itx_pack_tile<BO_TILE, BO_LDS>(s_buf, pay, tb, te, mb, me, [=](uint8_t *dst, uint32_t from, uint32_t to) { itx_reptag_write(src, rec_len, &t, from, to, dst); });
+    } else {
+        itx_pack_tile<BO_TILE, BO_LDS>(s_buf, pay, tb, te, mb, me, [=](uint8_t *dst, uint32_t from, uint32_t to) {
+            // a record starts wherever the one before it ended: kept a byte loop (names' gather says why)
 #pragma clang loop vectorize(disable)
-        for (uint32_t k = from; k < to; k++) dst[k - from] = src[k];
-    });
+            for (uint32_t k = from; k < to; k++) dst[k - from] = src[k];
+        });
+    }
 }
 
 // ---- filter -b -s: what is collected during the pass and the order of the replay
@@ -132,7 +193,10 @@ __global__ __launch_bounds__(BO_TILE) void k_bs_entries(const uint8_t *__restric
     const uint32_t rank = itx_tile_offsets<BO_TILE>(len ? 1u : 0u, s_c, &count);
     if (len) {
         ItxBamSortKey k;
-        const int bad = itx_bamsort_key(u + rec_off[i], len, &k);
+        // (under -a `len` is the annotated length while the bytes here are the source record's: the fields lie inside the shorter)
+        const uint8_t *p = u + rec_off[i];
+        const uint32_t src_len = 4u + itx_bamsort_u32(p);
+        const int bad = itx_bamsort_key(p, src_len < len ? src_len : len, &k);
         BoSortEnt e;
         e.tid = itx_bamsort_high(&k);
         e.low = itx_bamsort_low(&k);
@@ -342,6 +406,10 @@ struct itx_bamout {
     int finished;
     int level, level_set;            // the members' level (itx_bgzflevels.h): 6 unless itx_bamout_set_level chose another
     itx_bamout_stats stats;
+    int annotate;                    // filter -b -a (itx_bamout_annotate_enable): d_ann holds the rows and names, ann points into it
+    void *d_ann;
+    BoAnn ann;
+    ull tag_bytes;                   // tag bytes the device batches appended
     itx_bamidx *ix;                  // filter -b -i (itx_bamout_index_enable): the .bai index in the making, else null
     ull stream_base;                 // bytes of the record stream that are members already: d_pay[0] is this byte of the stream
     // filter -b -s (itx_bamout_sort_enable)
@@ -410,6 +478,7 @@ extern "C" void itx_bamout_destroy(itx_bamout *bo)
     (void)hipFree(bo->d_k1);
     (void)hipFree(bo->d_hist);
     (void)hipFree(bo->d_soff);
+    (void)hipFree(bo->d_ann);
     itx_bamidx_destroy(bo->ix);
     delete bo;
 }
@@ -433,13 +502,13 @@ extern "C" int itx_bamout_create(int device, size_t batch_capacity, size_t strea
     BO_TRY(hipSetDevice(device));
     if (hipMalloc((void **)&bo->d_hits, 4 * n) != hipSuccess || hipMalloc((void **)&bo->d_len, 4 * n) != hipSuccess ||
         hipMalloc((void **)&bo->d_tile_sum, 16 * nt) != hipSuccess || hipMalloc((void **)&bo->d_tile_base, 16 * nt) != hipSuccess ||
-        hipMalloc((void **)&bo->d_tot, 32) != hipSuccess || hipMalloc((void **)&bo->d_pay, bo->pay_cap + 16) != hipSuccess) {
+        hipMalloc((void **)&bo->d_tot, BO_TOT_BYTES) != hipSuccess || hipMalloc((void **)&bo->d_pay, bo->pay_cap + 16) != hipSuccess) {
         (void)hipGetLastError();
         itx_set_error("itx_bamout_create: no device memory for batches of %zu records and a stream of %zu bytes", batch_capacity, stream_bytes);
         rc = ITX_E_NOMEM;
         goto out;
     }
-    BO_TRY(hipHostMalloc((void **)&bo->h_tot, 32, hipHostMallocDefault));
+    BO_TRY(hipHostMalloc((void **)&bo->h_tot, BO_TOT_BYTES, hipHostMallocDefault));
     BO_TRY(hipStreamCreateWithFlags(&bo->st, hipStreamNonBlocking));
     BO_TRY(hipStreamCreateWithFlags(&bo->cst, hipStreamNonBlocking));
     for (auto &e : bo->ev) BO_TRY(hipEventCreate(&e));
@@ -637,13 +706,16 @@ int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, 
         BO_TRY(hipStreamWaitEvent(bo->st, bo->ev[4], 0));
     }
     BO_TRY(hipEventRecord(bo->ev[0], bo->st));
-    BO_TRY(hipMemsetAsync(bo->d_tot, 0, 32, bo->st));
-    hipLaunchKernelGGL(k_bo_measure, dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, d_hit_row, (uint32_t)n, bo->d_len, bo->d_tile_sum, bo->d_tot);
+    BO_TRY(hipMemsetAsync(bo->d_tot, 0, BO_TOT_BYTES, bo->st));
+    if (bo->annotate)
+        hipLaunchKernelGGL((k_bo_measure<true>), dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, d_hit_row, (uint32_t)n, bo->d_len, bo->d_tile_sum, bo->d_tot, bo->ann);
+    else
+        hipLaunchKernelGGL((k_bo_measure<false>), dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, d_hit_row, (uint32_t)n, bo->d_len, bo->d_tile_sum, bo->d_tot, bo->ann);
     BO_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, bo->st, bo->d_tile_sum, nt, bo->d_tile_base, bo->d_tot);
     BO_TRY(hipGetLastError());
     BO_TRY(hipEventRecord(bo->ev[1], bo->st));
-    BO_TRY(hipMemcpyAsync(bo->h_tot, bo->d_tot, 32, hipMemcpyDeviceToHost, bo->st));
+    BO_TRY(hipMemcpyAsync(bo->h_tot, bo->d_tot, BO_TOT_BYTES, hipMemcpyDeviceToHost, bo->st));
     {
         const double t0 = itx_wall_now();
         BO_TRY(hipStreamSynchronize(bo->st));
@@ -652,8 +724,13 @@ int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, 
     bo_read_gather_time(bo);                                               // (the batch before this one)
     BO_TRY(hipEventElapsedTime(&ms, bo->ev[0], bo->ev[1]));
     bo->stats.gather_ms += (double)ms;
+    if (bo->h_tot[3]) {
+        itx_set_error("itx_bamout: %llu records chose a row outside the %u rows given to itx_bamout_annotate_enable", bo->h_tot[3], bo->ann.n_rows);
+        rc = ITX_E_ARG;
+        goto out;
+    }
     if (bo->h_tot[2]) {
-        itx_set_error("itx_bamout: %llu records of a gibibyte or more", bo->h_tot[2]);
+        itx_set_error("itx_bamout: %llu records of a gibibyte or more%s", bo->h_tot[2], bo->annotate ? " with their tags" : "");
         rc = ITX_E_LIMIT;
         goto out;
     }
@@ -664,7 +741,12 @@ int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, 
     if (bo->ix && !bo->sort && (rc = itx_bamidx_reserve(bo->ix, bo->st, bo->h_tot[1], total / BO_P)) != ITX_OK) goto out;
     BO_TRY(hipEventRecord(bo->ev[2], bo->st));
     if (bo->h_tot[0]) {
-        hipLaunchKernelGGL((k_bo_gather<uint32_t>), dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, (uint32_t)n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->d_pay);
+        if (bo->annotate)
+            hipLaunchKernelGGL((k_bo_gather<uint32_t, true>), dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, (uint32_t)n, bo->d_len, bo->d_tile_base, (ull)bo->carry,
+                               bo->d_pay, d_hit_row, bo->ann);
+        else
+            hipLaunchKernelGGL((k_bo_gather<uint32_t, false>), dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, (uint32_t)n, bo->d_len, bo->d_tile_base, (ull)bo->carry,
+                               bo->d_pay, d_hit_row, bo->ann);
         BO_TRY(hipGetLastError());
     }
     if (bo->sort && bo->h_tot[1]) {
@@ -681,6 +763,7 @@ int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, 
     bo->stats.batches++;
     bo->stats.records += bo->h_tot[1];
     bo->stats.payload_bytes += bo->h_tot[0];
+    bo->tag_bytes += bo->h_tot[4];
     if (bo->sort) bo->carry = (size_t)total;
     else rc = bo_emit(bo, total, 0);
 out:
@@ -905,6 +988,108 @@ extern "C" int itx_bamout_set_level(itx_bamout *bo, int level)
 
 extern "C" int itx_bamout_get_level(const itx_bamout *bo) { return bo ? bo->level : ITX_E_ARG; }
 
+// ---- filter -b -a: the tags of the chosen row behind every counted record (csrc/itx_reptag.h)
+// one name table's checks: offsets that ascend, no name of 2^16 bytes or more. Returns ITX_OK, ITX_E_ARG or ITX_E_LIMIT.
+static int bo_check_names(const char *what, const uint64_t *off, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; i++) {
+        if (off[i + 1] < off[i]) {
+            itx_set_error("itx_bamout_annotate_enable: the offsets of the %s names do not ascend (name %u)", what, i);
+            return ITX_E_ARG;
+        }
+        if (off[i + 1] - off[i] > ITX_REPTAG_MAX_NAME) {
+            itx_set_error("itx_bamout_annotate_enable: %s name %u has %llu bytes (a tag's name has at most %u)", what, i, (ull)(off[i + 1] - off[i]), ITX_REPTAG_MAX_NAME);
+            return ITX_E_LIMIT;
+        }
+    }
+    return ITX_OK;
+}
+
+extern "C" int itx_bamout_annotate_enable(itx_bamout *bo, const itx_row *rows, size_t n_rows, const char *rep_bytes, const uint64_t *rep_off, uint32_t n_rep,
+                                          const char *cla_bytes, const uint64_t *cla_off, uint32_t n_cla, const char *fam_bytes, const uint64_t *fam_off, uint32_t n_fam)
+{
+    if (!bo || (n_rows && !rows) || !rep_bytes || !rep_off || !cla_bytes || !cla_off || !fam_bytes || !fam_off || n_rows >= 0x7fffffffull) {
+        itx_set_error("itx_bamout_annotate_enable: bad argument");
+        return ITX_E_ARG;
+    }
+    if (bo->annotate || bo->finished || bo->stats.batches || bo->stats.host_batches) {
+        itx_set_error("itx_bamout_annotate_enable: %s", bo->annotate ? "called twice" : "the stream has begun");
+        return ITX_E_STATE;
+    }
+    int rc = ITX_OK;
+    if ((rc = bo_check_names("repName", rep_off, n_rep)) != ITX_OK || (rc = bo_check_names("repClass", cla_off, n_cla)) != ITX_OK ||
+        (rc = bo_check_names("repFamily", fam_off, n_fam)) != ITX_OK)
+        return rc;
+    for (size_t r = 0; r < n_rows; r++)
+        if (rows[r].rep >= n_rep || rows[r].cla >= n_cla || rows[r].fam >= n_fam) {
+            itx_set_error("itx_bamout_annotate_enable: row %zu names repName %u of %u, repClass %u of %u, repFamily %u of %u", r, rows[r].rep, n_rep, rows[r].cla, n_cla,
+                          rows[r].fam, n_fam);
+            return ITX_E_ARG;
+        }
+    // one block, laid out on the host and uploaded once: the three offset arrays (8-byte aligned), the rows, the three pools.
+    // Offsets are rebased to the pool's first used byte, so a caller's off[0] need not be 0.
+    const size_t o_rep = 0, o_cla = o_rep + 8 * ((size_t)n_rep + 1), o_fam = o_cla + 8 * ((size_t)n_cla + 1), o_rows = o_fam + 8 * ((size_t)n_fam + 1);
+    const size_t b_rep = o_rows + 4 * (size_t)BO_ROW_WORDS * n_rows, b_cla = b_rep + (size_t)(rep_off[n_rep] - rep_off[0]);
+    const size_t b_fam = b_cla + (size_t)(cla_off[n_cla] - cla_off[0]), bytes = b_fam + (size_t)(fam_off[n_fam] - fam_off[0]);
+    uint8_t *h = (uint8_t *)malloc(bytes + 16), *d = nullptr;
+    if (!h) {
+        itx_set_error("itx_bamout_annotate_enable: no host memory for a table of %zu bytes", bytes);
+        return ITX_E_NOMEM;
+    }
+    {
+        const uint64_t *const offs[3] = {rep_off, cla_off, fam_off};
+        const char *const pools[3] = {rep_bytes, cla_bytes, fam_bytes};
+        const uint32_t ns[3] = {n_rep, n_cla, n_fam};
+        const size_t at_off[3] = {o_rep, o_cla, o_fam}, at_bytes[3] = {b_rep, b_cla, b_fam};
+        for (int t = 0; t < 3; t++) {
+            ull *o = (ull *)(h + at_off[t]);
+            for (uint32_t i = 0; i <= ns[t]; i++) o[i] = offs[t][i] - offs[t][0];
+            if (o[ns[t]]) memcpy(h + at_bytes[t], pools[t] + offs[t][0], (size_t)o[ns[t]]);
+        }
+        uint32_t *w = (uint32_t *)(h + o_rows);
+        for (size_t r = 0; r < n_rows; r++) {
+            w[BO_ROW_WORDS * r] = rows[r].start;
+            w[BO_ROW_WORDS * r + 1] = rows[r].end;
+            w[BO_ROW_WORDS * r + 2] = rows[r].rep;
+            w[BO_ROW_WORDS * r + 3] = rows[r].cla;
+            w[BO_ROW_WORDS * r + 4] = rows[r].fam;
+        }
+    }
+    BO_TRY(hipSetDevice(bo->device));
+    if (hipMalloc((void **)&d, bytes + 16) != hipSuccess) {
+        (void)hipGetLastError();
+        itx_set_error("itx_bamout_annotate_enable: no device memory for a table of %zu bytes", bytes);
+        rc = ITX_E_NOMEM;
+        goto out;
+    }
+    BO_TRY(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));                 // (synchronous: the caller's arrays and h are free on return)
+    bo->ann.rep_off = (const ull *)(d + o_rep);
+    bo->ann.cla_off = (const ull *)(d + o_cla);
+    bo->ann.fam_off = (const ull *)(d + o_fam);
+    bo->ann.rows = (const uint32_t *)(d + o_rows);
+    bo->ann.rep = d + b_rep;
+    bo->ann.cla = d + b_cla;
+    bo->ann.fam = d + b_fam;
+    bo->ann.n_rows = (uint32_t)n_rows;
+    bo->d_ann = d;
+    bo->annotate = 1;
+    d = nullptr;
+out:
+    (void)hipFree(d);                                                      // (the block that was not taken)
+    free(h);
+    return rc;
+}
+
+extern "C" int itx_bamout_annotate_get_stats(const itx_bamout *bo, uint64_t *tag_bytes)
+{
+    if (!bo || !tag_bytes) {
+        itx_set_error("itx_bamout_annotate_get_stats: bad argument");
+        return ITX_E_ARG;
+    }
+    *tag_bytes = bo->tag_bytes;
+    return ITX_OK;
+}
+
 // ---- filter -b -s: the stream held, sorted by coordinate and replayed
 extern "C" int itx_bamout_sort_enable(itx_bamout *bo)
 {
@@ -1098,7 +1283,9 @@ extern "C" int itx_bamout_sort_next(itx_bamout *bo, int *more)
     if ((rc = bo_reserve(bo, total, n_mem)) != ITX_OK) goto out;
     if (bo->ix && (rc = itx_bamidx_reserve(bo->ix, bo->st, n, n_mem)) != ITX_OK) goto out;
     BO_TRY(hipEventRecord(bo->ev[2], bo->st));
-    hipLaunchKernelGGL((k_bo_gather<ull>), dim3(nt), dim3(BO_TILE), 0, bo->st, bo->d_held, bo->d_soff, n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->d_pay);
+    // (under -a the held records are annotated already: the replay copies them byte for byte)
+    hipLaunchKernelGGL((k_bo_gather<ull, false>), dim3(nt), dim3(BO_TILE), 0, bo->st, bo->d_held, bo->d_soff, n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->d_pay,
+                       (const int32_t *)nullptr, bo->ann);
     BO_TRY(hipGetLastError());
     BO_TRY(hipEventRecord(bo->ev[3], bo->st));
     bo->gather_timed = 1;

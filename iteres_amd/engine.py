@@ -36,7 +36,7 @@ EXPORTS = [
     "itx_bamout_create", "itx_bamout_destroy", "itx_bamout_hits", "itx_bamout_stream", "itx_bamwin_bamout", "itx_bamout_run", "itx_bamout_wait_kernels",
     "itx_bamout_append_host", "itx_bamout_finish", "itx_bamout_collect", "itx_bamout_pending", "itx_bamout_get_stats", "itx_bamout_index_enable",
     "itx_bamout_index_finish", "itx_bamout_sort_enable", "itx_bamout_sort_next", "itx_bamout_sort_get_stats",
-    "itx_bamout_set_level", "itx_bamout_get_level",
+    "itx_bamout_set_level", "itx_bamout_get_level", "itx_bamout_annotate_enable", "itx_bamout_annotate_get_stats",
     "itx_loci_create", "itx_loci_destroy", "itx_loci_order", "itx_loci_filter_text", "itx_loci_cpg_text",
     "itx_samtext_create", "itx_samtext_destroy", "itx_samtext_parse_begin", "itx_samtext_parse_end", "itx_samtext_fetch",
     "itx_samtext_parse_begin_bgzf", "itx_samtext_bgzf_info", "itx_samtext_text", "itx_samtext_strings",
@@ -276,6 +276,8 @@ def load():
     L.itx_bamout_sort_get_stats.argtypes = [C.c_void_p, C.POINTER(BamoutSortStats)]
     L.itx_bamout_set_level.argtypes = [C.c_void_p, C.c_int]
     L.itx_bamout_get_level.argtypes = [C.c_void_p]
+    L.itx_bamout_annotate_enable.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p, C.c_void_p, C.c_uint32] * 3
+    L.itx_bamout_annotate_get_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.itx_loci_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                   C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
     L.itx_loci_destroy.argtypes = [C.c_void_p]
@@ -849,6 +851,23 @@ class Bamout:
 
     def level(self):
         return int(load().itx_bamout_get_level(self._h))
+
+    def annotate_enable(self, rows, reps, clas, fams):
+        """before the first batch (filter -b -a): every counted record leaves with the tags of its row behind it (csrc/itx_reptag.h).
+        rows: a ROW_DTYPE array; reps / clas / fams: the names (bytes) that rows' rep / cla / fam index."""
+        rows = np.ascontiguousarray(rows, ROW_DTYPE)
+        args = []
+        for names in (reps, clas, fams):
+            off = np.cumsum([0] + [len(x) for x in names]).astype(np.uint64)
+            pool = np.frombuffer(b"".join(names) + b"\0", np.uint8).copy()
+            args += [pool, off, len(names)]
+        _chk(load().itx_bamout_annotate_enable(self._h, rows.ctypes.data, len(rows), *[a if isinstance(a, int) else a.ctypes.data for a in args]),
+             "itx_bamout_annotate_enable")
+
+    def tag_bytes(self):
+        n = C.c_uint64(0)
+        _chk(load().itx_bamout_annotate_get_stats(self._h, C.byref(n)), "itx_bamout_annotate_get_stats")
+        return int(n.value)
 
     def sort_stats(self):
         s = BamoutSortStats()

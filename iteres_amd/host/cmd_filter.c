@@ -27,6 +27,7 @@ static int filter_usage(void)
     fprintf(stderr, "         -i       with -b: also write its index <prefix>_<filter>.iteres.bam.bai, for coordinate-sorted input (an extension) [off]\n");
     fprintf(stderr, "         -s       with -b: write the counted reads sorted by coordinate, so that -i works on input in any order (an extension) [off]\n");
     fprintf(stderr, "         -l       with -b: level of its BGZF members, 0 (stored), 1 (fast) or 6 (smallest) (an extension) [6]\n");
+    fprintf(stderr, "         -a       with -b: tag every emitted read with the repeat it was counted for, ZN/ZC/ZF (repName, repClass, repFamily) and ZS/ZE (genoStart, genoEnd) (an extension) [off]\n");
     fprintf(stderr, "         -R       remove redundant reads [off]\n");
     fprintf(stderr, "         -T       treat 1 paired-end read as 2 single-end reads [off]\n");
     fprintf(stderr, "         -D       discard if only one end mapped in a paired end reads [off]\n");
@@ -48,10 +49,10 @@ int main_filter(int argc, char **argv)
     o.isize = 500;
     o.extension = 150;
     o.min_cov = 0.0001f;
-    int optthreshold = 1, optreadlist = 0, optbam = 0, optindex = 0, optsort = 0, optlevel = -1, optNorm = 0, c, filterField = 0;
+    int optthreshold = 1, optreadlist = 0, optbam = 0, optindex = 0, optsort = 0, optlevel = -1, optannotate = 0, optNorm = 0, c, filterField = 0;
     char *optoutput = NULL, *optname = NULL, *optclass = NULL, *optfamily = NULL;
     const time_t start_time = time(NULL);
-    while ((c = getopt(argc, argv, "SQ:g:N:n:c:t:f:rbisl:RTDCE:I:o:h?")) >= 0) {
+    while ((c = getopt(argc, argv, "SQ:g:N:n:c:t:f:rbisl:aRTDCE:I:o:h?")) >= 0) {
         switch (c) {
         case 'S': o.is_sam = 1; break;
         case 'Q': o.mapq = (unsigned)strtol(optarg, 0, 0); break;
@@ -62,6 +63,7 @@ int main_filter(int argc, char **argv)
         case 'b': optbam = 1; break;
         case 'i': optindex = 1; break;
         case 's': optsort = 1; break;
+        case 'a': optannotate = 1; break;
         case 'l': {
             char *end = NULL;
             const long v = strtol(optarg, &end, 10);
@@ -90,6 +92,7 @@ int main_filter(int argc, char **argv)
     if (optindex && !optbam) die("-i writes the index of the BAM that -b writes: it cannot be used without -b");
     if (optsort && !optbam) die("-s sorts the BAM that -b writes: it cannot be used without -b");
     if (optlevel >= 0 && !optbam) die("-l chooses the level of the BAM that -b writes: it cannot be used without -b");
+    if (optannotate && !optbam) die("-a tags the reads of the BAM that -b writes: it cannot be used without -b");
     if (optbam && getenv("ITX_HOST_INFLATE"))
         die("-b gathers the records on the device, where the BAM is decoded: it cannot be combined with ITX_HOST_INFLATE (the host decoder)");
     o.chr_size_file = argv[optind];
@@ -132,6 +135,7 @@ int main_filter(int argc, char **argv)
         o.bam_out_path = outBam;
         o.bam_index = optindex;
         o.bam_sort = optsort;
+        o.bam_annotate = optannotate;
         o.bam_level_given = optlevel >= 0;
         o.bam_level = optlevel >= 0 ? optlevel : 6;
         aln_keep_header(1);                      /* before the helper thread opens the file */

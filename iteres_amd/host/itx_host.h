@@ -227,6 +227,7 @@ typedef struct {
     int bam_level;                             /* filter -b -l: the members' level (0, 1 or 6), read only when bam_level_given: without -l the */
     int bam_level_given;                       /* writer is not told a level and ITX_TIMING's line is the one it always was */
     int bam_index;                             /* filter -b -i: <bam_out_path>.bai beside it, built on the device in the same pass */
+    int bam_annotate;                          /* filter -b -a: every emitted record carries the tags of its row (csrc/itx_reptag.h) */
 } run_opts;
 /* counters of the record loop that only the host sees (generic.c:1048-1060) */
 typedef struct {
@@ -282,6 +283,8 @@ void write_wig_and_stat(const rmsk_t *rm, const itx_result *res, const uint64_t 
 typedef struct loci_dev loci_dev;
 loci_dev *loci_dev_begin(const rmsk_t *rm, int kind, int readlist, int device);
 void loci_dev_free(loci_dev *d);
+/* a name table in the form itx_loci_create and itx_bamout_annotate_enable take: name i = bytes[off[i] .. off[i + 1]); the caller frees both */
+void loci_name_table(const names_t *t, char **bytes, uint64_t **off);
 void write_filter_out(const rmsk_t *rm, const uint32_t *locus_cnt, char **locus_names, const char *path, int readlist, int threshold,
                       const char *subfam, unsigned long long reads_num, loci_dev *dev);
 

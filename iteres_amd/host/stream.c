@@ -7,6 +7,7 @@
 #define _GNU_SOURCE
 #include "itx_host.h"
 #include "../csrc/itx_bamsortrule.h"
+#include "../csrc/itx_reptag.h"
 
 #include <errno.h>
 #include <stdlib.h>
@@ -403,6 +404,7 @@ typedef struct {
     uint64_t bam_first;                            /* -b -i: where the first record member starts in the file */
     struct { uint8_t *bytes; size_t cap; } bbuf;
     unsigned long long bam_dev_batches, bam_host_batches;
+    unsigned long long bam_host_tag_bytes;         /* -b -a: tag bytes the host route appended */
     /* the host route: two pinned slots, taken when a batch first goes that way; s is filled next, pend[] are in flight */
     itx_staging st[2];
     aln_side side[2];                             /* what the host keeps per record beside the SoA */
@@ -572,6 +574,22 @@ static void bam_index_begin(stream_run *r, const uint8_t *hb, size_t hl)
     r->bam_first = (uint64_t)first;
 }
 
+/* filter -b -a: the device's gather gets the rows and the names the tags are made of (csrc/itx_reptag.h); names of 2^16 bytes and
+ * more are refused there */
+static void bam_annotate_begin(stream_run *r)
+{
+    const rmsk_t *rm = r->rm;
+    const names_t *tabs[3] = {&rm->reps, &rm->clas, &rm->fams};
+    char *nb[3];
+    uint64_t *no[3];
+    for (int t = 0; t < 3; t++) loci_name_table(tabs[t], &nb[t], &no[t]);
+    chk(itx_bamout_annotate_enable(r->bo, rm->rows, rm->n_rows, nb[0], no[0], rm->reps.n, nb[1], no[1], rm->clas.n, nb[2], no[2], rm->fams.n), "itx_bamout_annotate_enable");
+    for (int t = 0; t < 3; t++) {
+        free(nb[t]);
+        free(no[t]);
+    }
+}
+
 /* filter -b -s: the kept header (magic, l_text, text, reference list) with the text the sorted file carries (csrc/itx_bamsortrule.h);
  * l_text follows the new length, the reference list is untouched. The caller frees the result. */
 static uint8_t *bam_sorted_header(const stream_run *r, const uint8_t *hb, size_t hl, size_t *out_len)
@@ -608,22 +626,37 @@ static void bam_index_end(stream_run *r, itx_bamout_index_result *ir)
     free(path);
 }
 
-/* filter -b: the records of slot k that chose a row, as the reader kept their bytes, to the device's stream in record order */
+/* filter -b: the records of slot k that chose a row, as the reader kept their bytes, to the device's stream in record order.
+ * -a: each with the tags of its row behind it, by the rule the device's gather follows (csrc/itx_reptag.h), from the host's own table */
 static void collect_bam(stream_run *r, int k)
 {
     const itx_staging *st = &r->st[k];
     const aln_side *side = &r->side[k];
+    const rmsk_t *rm = r->rm;
     size_t b = 0;
     for (size_t i = 0; i < r->pend[k]; i++) {
         if (st->hit_row[i] < 0) continue;
         uint32_t bs;
         memcpy(&bs, side->raw + side->raw_off[i], 4);
-        const size_t len = 4 + (size_t)bs;
+        size_t len = 4 + (size_t)bs;
+        ItxRepTag t;
+        if (r->o->bam_annotate) {
+            if ((size_t)st->hit_row[i] >= rm->n_rows) die("filter -b -a: a record chose row %d of %zu", st->hit_row[i], rm->n_rows);
+            const itx_row *row = &rm->rows[st->hit_row[i]];
+            const char *rep = rm->reps.name[row->rep], *cla = rm->clas.name[row->cla], *fam = rm->fams.name[row->fam];
+            t.rep = (const uint8_t *)rep, t.cla = (const uint8_t *)cla, t.fam = (const uint8_t *)fam;
+            t.rep_len = (uint32_t)strlen(rep), t.cla_len = (uint32_t)strlen(cla), t.fam_len = (uint32_t)strlen(fam);
+            t.start = row->start, t.end = row->end;
+            if (len + itx_reptag_len(&t) >= 0x40000000u) die("filter -b -a: a record of %zu bytes with its tags", len + itx_reptag_len(&t));
+            len += itx_reptag_len(&t);
+            r->bam_host_tag_bytes += itx_reptag_len(&t);
+        }
         if (r->bbuf.cap < b + len) {
             r->bbuf.cap = (b + len) * 2;
             r->bbuf.bytes = xrealloc(r->bbuf.bytes, r->bbuf.cap);
         }
-        memcpy(r->bbuf.bytes + b, side->raw + side->raw_off[i], len);
+        if (r->o->bam_annotate) itx_reptag_write(side->raw + side->raw_off[i], 4u + bs, &t, 0u, (uint32_t)len, r->bbuf.bytes + b);
+        else memcpy(r->bbuf.bytes + b, side->raw + side->raw_off[i], len);
         b += len;
     }
     r->bam_host_batches++;
@@ -940,6 +973,7 @@ static void map_targets(stream_run *r, stream_file *f)
         chk(itx_bamout_create(multi_device(), BATCH_RECORDS, 0, &r->bo), "itx_bamout_create");
         if (o->bam_level_given) chk(itx_bamout_set_level(r->bo, o->bam_level), "itx_bamout_set_level");
         if (o->bam_sort) chk(itx_bamout_sort_enable(r->bo), "itx_bamout_sort_enable");
+        if (o->bam_annotate) bam_annotate_begin(r);
         if (o->bam_index) bam_index_begin(r, hb, hl);
         free(sorted_hb);
     }
@@ -1303,7 +1337,12 @@ static void finish_bam(stream_run *r)
         if (r->bo) chk(itx_bamout_get_stats(r->bo, &bs), "itx_bamout_get_stats");
         fprintf(stderr, "[itx timing] bam out: %llu records, %llu payload bytes, %llu members (%llu bytes), %.3f ms in the gather kernels, %.3f ms in the member kernels, host waited %.3f s, %llu batches gathered on the device, %llu batches by the host route%s",
                 (unsigned long long)bs.records, (unsigned long long)bs.payload_bytes, (unsigned long long)bs.members, (unsigned long long)bs.out_bytes, bs.gather_ms,
-                bs.member_ms, 1e-3 * bs.wait_ms, r->bam_dev_batches, r->bam_host_batches, r->o->bam_index || r->o->bam_sort || r->o->bam_level_given ? "" : "\n");
+                bs.member_ms, 1e-3 * bs.wait_ms, r->bam_dev_batches, r->bam_host_batches, r->o->bam_annotate || r->o->bam_index || r->o->bam_sort || r->o->bam_level_given ? "" : "\n");
+        if (r->o->bam_annotate) {
+            uint64_t tb = 0;
+            if (r->bo) chk(itx_bamout_annotate_get_stats(r->bo, &tb), "itx_bamout_annotate_get_stats");
+            fprintf(stderr, ", %llu tag bytes appended%s", (unsigned long long)tb + r->bam_host_tag_bytes, r->o->bam_index || r->o->bam_sort || r->o->bam_level_given ? "" : "\n");
+        }
         if (r->o->bam_sort) {
             itx_bamout_sort_stats ss;
             memset(&ss, 0, sizeof ss);

@@ -192,7 +192,7 @@ struct loci_dev {
     char why[160];               /* why the host writes the file ("": the device does) */
 };
 
-static void loci_name_table(const names_t *t, char **bytes, uint64_t **off)
+void loci_name_table(const names_t *t, char **bytes, uint64_t **off)
 {
     uint64_t *o = xmalloc(sizeof(uint64_t) * ((size_t)t->n + 1));
     o[0] = 0;
