@@ -577,6 +577,60 @@ int itx_bamout_annotate_enable(itx_bamout *bo, const itx_row *rows, size_t n_row
                                const char *cla_bytes, const uint64_t *cla_off, uint32_t n_cla, const char *fam_bytes, const uint64_t *fam_off, uint32_t n_fam);
 int itx_bamout_annotate_get_stats(const itx_bamout *bo, uint64_t *tag_bytes);
 
+/* ---- the genome coverage of filter -G on the device (an extension: the reference writes no such file) ------------------------------
+ * The depth of the counted reads over the chromosomes of the size file, as two bedGraph texts: all counted reads, and those with
+ * MAPQ >= mapq_min (csrc/itx_gcov.hip). A record counts when it chose a row (d_hit_row >= 0) and does not carry ITX_F5_NOLOOKUP; it
+ * covers the [start, end) of csrc/itx_derive.h, the interval the lookup ran on. 0 <= start < end <= size - 1 is checked: a record
+ * outside adds nothing and is counted in stats.out_of_range. Depth is u32 and wraps. Sums commute: run and add_host in any order.
+ *   create      chrom_size[n_chrom] as for itx_table_create (a size <= 2 has no slots, generic.c:796-797; a size of 2^31 and above:
+ *               ITX_E_LIMIT); p: mapq_min, extension, isize_max, treat_pe_as_se, discard_half_mapped. Two u32 arrays of one slot per
+ *               base are allocated before anything else and zeroed: ITX_E_NOMEM when the device cannot hold them.
+ *   set_tidmap  per input header, as itx_engine_set_tidmap
+ *   hits/stream a device int32[batch_capacity] and a stream of the object's own, for itx_engine_classify_device to leave the chosen
+ *               rows in (any other buffer / stream will do)
+ *   run         n records as DEVICE arrays (mpos / isize NULL: no record is paired) and their chosen rows; enqueued on `stream`, where
+ *               d_hit_row was written, and returns
+ *   wait_kernels  returns when the newest run is through (each run waits for the one before): the arrays may then be overwritten
+ *   add_host    n intervals the caller derived itself (the host route's counted records): chromosome (index into chrom_size), start,
+ *               end, uniq != 0 for MAPQ >= mapq_min. Checked like the records of run. The arrays are the caller's again on return.
+ *   finish      once (ITX_E_STATE the second time, and for run / add_host / set_tidmap after it). order[n_order]: the chromosomes in
+ *               the order the files list them, each at most once (ITX_E_ARG otherwise; one that is left out is not written);
+ *               chromosome c's name = name_bytes[name_off[c] .. name_off[c + 1]) (n_chrom + 1 offsets, a name below 2^16 bytes).
+ *               Finds the change points of both arrays and gives the arrays back. round_bytes (0: 32 MiB, at most 1 GiB): a round
+ *               of text takes max(1, round_bytes / (longest name + 34)) change points, so its text fits round_bytes or is one line.
+ *               ITX_E_NOMEM / ITX_E_ARG leave the object as it was.
+ *   next        the next round of file `which` (0: all counted reads, 1: MAPQ >= mapq_min): waits for it, starts the round after it
+ *               into the other of two page-locked buffers, and hands it out: `bytes` (whole lines "chrom\tstart\tend\tdepth\n", one per
+ *               maximal run of equal depth > 0, 0-based half open, chromosomes in finish's order, starts ascending) stays valid until
+ *               the next call; more == 0: that was the last round (a file without lines: len 0, more 0). One file after the other:
+ *               ITX_E_STATE for the other file while one has rounds left, and for a file that has been handed out.
+ *   get_stats   records added and refused, change points, lines, bytes and rounds per file, device time of the add kernels, of the
+ *               two dense passes and of the text kernels, time the host waited in these calls, and what create's allocation and
+ *               zeroing cost */
+typedef struct itx_gcov itx_gcov;
+typedef struct itx_gcov_text {
+    const char *bytes;
+    uint64_t len;
+    int32_t more, pad;
+} itx_gcov_text;
+typedef struct itx_gcov_stats {
+    uint64_t batches, host_batches, records, out_of_range, records_uniq;
+    uint64_t points[2], lines[2], bytes[2], rounds[2];
+    uint64_t slots, device_bytes;              /* bases with a slot; bytes of the two arrays */
+    double add_ms, points_ms, text_ms, zero_ms, wait_s, alloc_s;
+} itx_gcov_stats;
+int itx_gcov_create(int device, const int64_t *chrom_size, int n_chrom, const itx_params *p, size_t batch_capacity, itx_gcov **out);
+void itx_gcov_destroy(itx_gcov *g);
+int itx_gcov_set_tidmap(itx_gcov *g, const int32_t *tid2chrom, int n_tid);
+int32_t *itx_gcov_hits(itx_gcov *g);
+void *itx_gcov_stream(itx_gcov *g);
+int itx_gcov_run(itx_gcov *g, const itx_batch *d_batch, const int32_t *d_hit_row, size_t n, void *stream);
+int itx_gcov_wait_kernels(itx_gcov *g);
+int itx_gcov_add_host(itx_gcov *g, const int32_t *chrom, const uint32_t *start, const uint32_t *end, const uint8_t *uniq, size_t n);
+int itx_gcov_finish(itx_gcov *g, const uint32_t *order, int n_order, const char *name_bytes, const uint64_t *name_off, size_t round_bytes);
+int itx_gcov_next(itx_gcov *g, int which, itx_gcov_text *out);
+int itx_gcov_get_stats(itx_gcov *g, itx_gcov_stats *out);
+
 /* ---- the .loci file of filter / cpgfilter on the device ----------------------------------------------------------------------
  * Replaces the row walk and the fprintf of writeFilterOut (generic.c:1709-1746) and writeFilterOutMRE (generic.c:1748-1772): the
  * order of the lines is a function of the table alone — hashRmsk's chromosomes in hash order, a chromosome's rows by bin

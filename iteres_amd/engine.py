@@ -33,6 +33,8 @@ EXPORTS = [
     "itx_bed_create", "itx_bed_destroy", "itx_bed_set_tidmap", "itx_bamwin_bed", "itx_bed_run", "itx_bed_wait_kernels", "itx_bed_collect", "itx_bed_get_stats",
     "itx_names_create", "itx_names_destroy", "itx_names_hits", "itx_names_stream", "itx_bamwin_names", "itx_names_run", "itx_names_wait_kernels", "itx_names_append_host",
     "itx_names_finish", "itx_names_get_stats",
+    "itx_gcov_create", "itx_gcov_destroy", "itx_gcov_set_tidmap", "itx_gcov_hits", "itx_gcov_stream", "itx_gcov_run", "itx_gcov_wait_kernels", "itx_gcov_add_host",
+    "itx_gcov_finish", "itx_gcov_next", "itx_gcov_get_stats",
     "itx_bamout_create", "itx_bamout_destroy", "itx_bamout_hits", "itx_bamout_stream", "itx_bamwin_bamout", "itx_bamout_run", "itx_bamout_wait_kernels",
     "itx_bamout_append_host", "itx_bamout_finish", "itx_bamout_collect", "itx_bamout_pending", "itx_bamout_get_stats", "itx_bamout_index_enable",
     "itx_bamout_index_finish", "itx_bamout_sort_enable", "itx_bamout_sort_next", "itx_bamout_sort_get_stats",
@@ -109,6 +111,17 @@ class BedStats(C.Structure):
 
 
 BED_ALL, BED_UNIQ = 1, 2
+
+
+class GcovText(C.Structure):
+    _fields_ = [("bytes", C.c_void_p), ("len", C.c_uint64), ("more", C.c_int32), ("pad", C.c_int32)]
+
+
+class GcovStats(C.Structure):
+    _fields_ = [("batches", C.c_uint64), ("host_batches", C.c_uint64), ("records", C.c_uint64), ("out_of_range", C.c_uint64), ("records_uniq", C.c_uint64),
+                ("points", C.c_uint64 * 2), ("lines", C.c_uint64 * 2), ("bytes", C.c_uint64 * 2), ("rounds", C.c_uint64 * 2), ("slots", C.c_uint64),
+                ("device_bytes", C.c_uint64), ("add_ms", C.c_double), ("points_ms", C.c_double), ("text_ms", C.c_double), ("zero_ms", C.c_double),
+                ("wait_s", C.c_double), ("alloc_s", C.c_double)]
 
 
 class NamesResult(C.Structure):
@@ -254,6 +267,20 @@ def load():
     L.itx_names_append_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.itx_names_finish.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(NamesResult)]
     L.itx_names_get_stats.argtypes = [C.c_void_p, C.POINTER(NamesStats)]
+    L.itx_gcov_create.argtypes = [C.c_int, C.c_void_p, C.c_int, C.POINTER(Params), C.c_size_t, C.POINTER(C.c_void_p)]
+    L.itx_gcov_destroy.argtypes = [C.c_void_p]
+    L.itx_gcov_destroy.restype = None
+    L.itx_gcov_set_tidmap.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.itx_gcov_hits.argtypes = [C.c_void_p]
+    L.itx_gcov_hits.restype = C.c_void_p
+    L.itx_gcov_stream.argtypes = [C.c_void_p]
+    L.itx_gcov_stream.restype = C.c_void_p
+    L.itx_gcov_run.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_size_t, C.c_void_p]
+    L.itx_gcov_wait_kernels.argtypes = [C.c_void_p]
+    L.itx_gcov_add_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.itx_gcov_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.itx_gcov_next.argtypes = [C.c_void_p, C.c_int, C.POINTER(GcovText)]
+    L.itx_gcov_get_stats.argtypes = [C.c_void_p, C.POINTER(GcovStats)]
     L.itx_bamout_create.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]
     L.itx_bamout_destroy.argtypes = [C.c_void_p]
     L.itx_bamout_destroy.restype = None
@@ -682,6 +709,77 @@ class Bed:
     def close(self):
         if self._h:
             load().itx_bed_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Gcov:
+    """The genome coverage of filter -G built on the device (include/iteres_amd.h itx_gcov_*). `run` takes the per-record arrays as
+    torch DEVICE tensors and an int32 tensor of chosen rows (-1: none), `add_host` intervals as host arrays; `finish(order, names)`
+    finds the change points, `text(which)` joins the rounds of a file (0: all counted reads, 1: MAPQ >= -Q) into bytes."""
+
+    def __init__(self, chrom_size, params: dict | None = None, batch_capacity: int = 1 << 20, device: int = 0):
+        q = dict(mapq_min=10, min_cov=1e-4, extension=150, isize_max=500, treat_pe_as_se=False, discard_half_mapped=False)
+        q.update(params or {})
+        p = Params(int(q["mapq_min"]), float(q["min_cov"]), int(q["extension"]), int(q["isize_max"]), int(bool(q["treat_pe_as_se"])),
+                   int(bool(q["discard_half_mapped"])), MODE_FILTER, ACCUM_DEFAULT)
+        cs = np.ascontiguousarray(chrom_size, np.int64)
+        self.n_chrom = len(cs)
+        self._h = C.c_void_p()
+        _chk(load().itx_gcov_create(device, _p(cs), len(cs), C.byref(p), batch_capacity, C.byref(self._h)), "itx_gcov_create")
+
+    def set_tidmap(self, tid2chrom):
+        a = np.ascontiguousarray(tid2chrom, np.int32)
+        _chk(load().itx_gcov_set_tidmap(self._h, _p(a), len(a)), "itx_gcov_set_tidmap")
+
+    def run(self, hit_row, tid, pos, tmpend, mapq, flag5, mpos=None, isize=None):
+        import torch
+        ptr = lambda t: None if t is None else t.data_ptr()
+        b = Batch(ptr(tid), ptr(pos), ptr(tmpend), ptr(mapq), ptr(flag5), ptr(mpos), ptr(isize))
+        _chk(load().itx_gcov_run(self._h, C.byref(b), C.c_void_p(hit_row.data_ptr()), int(hit_row.numel()), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+             "itx_gcov_run")
+
+    def wait_kernels(self):
+        _chk(load().itx_gcov_wait_kernels(self._h), "itx_gcov_wait_kernels")
+
+    def add_host(self, chrom, start, end, uniq):
+        c, s, e, u = (np.ascontiguousarray(chrom, np.int32), np.ascontiguousarray(start, np.uint32), np.ascontiguousarray(end, np.uint32),
+                      np.ascontiguousarray(uniq, np.uint8))
+        _chk(load().itx_gcov_add_host(self._h, _p(c), _p(s), _p(e), _p(u), len(c)), "itx_gcov_add_host")
+
+    def finish(self, order, names, round_bytes: int = 0):
+        o = np.ascontiguousarray(order, np.uint32)
+        names = [n if isinstance(n, bytes) else n.encode() for n in names]
+        off = np.zeros(len(names) + 1, np.uint64)
+        off[1:] = np.cumsum([len(n) for n in names], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(names) + b"\0", np.uint8).copy()
+        _chk(load().itx_gcov_finish(self._h, _p(o), len(o), _p(blob), _p(off), round_bytes), "itx_gcov_finish")
+
+    def next(self, which):
+        t = GcovText()
+        _chk(load().itx_gcov_next(self._h, which, C.byref(t)), "itx_gcov_next")
+        return (C.string_at(t.bytes, t.len) if t.len else b""), bool(t.more)
+
+    def text(self, which):
+        parts, more = [], True
+        while more:
+            b, more = self.next(which)
+            parts.append(b)
+        return b"".join(parts), [len(x) for x in parts]
+
+    def stats(self):
+        s = GcovStats()
+        _chk(load().itx_gcov_get_stats(self._h, C.byref(s)), "itx_gcov_get_stats")
+        return {k: (list(getattr(s, k)) if k in ("points", "lines", "bytes", "rounds") else getattr(s, k)) for k, _ in GcovStats._fields_}
+
+    def close(self):
+        if self._h:
+            load().itx_gcov_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -228,6 +228,7 @@ typedef struct {
     int bam_level_given;                       /* writer is not told a level and ITX_TIMING's line is the one it always was */
     int bam_index;                             /* filter -b -i: <bam_out_path>.bai beside it, built on the device in the same pass */
     int bam_annotate;                          /* filter -b -a: every emitted record carries the tags of its row (csrc/itx_reptag.h) */
+    int gcov;                                  /* filter -G (an extension): the counted reads' genome coverage as bedGraph (csrc/itx_gcov.hip) */
 } run_opts;
 /* counters of the record loop that only the host sees (generic.c:1048-1060) */
 typedef struct {
@@ -338,6 +339,9 @@ int stream_finish(itx_engine *eng, const itx_result *res);
  * lists, every locus_names[row] is a string of its own); stream_names_free releases the lists (locus_names[] point into them) */
 const uint32_t *stream_names_counts(void);
 void stream_names_free(char **locus_names);
+/* filter -G: after run_stream, the two bedGraph files of the coverage the stream accumulated on the device (csrc/itx_gcov.hip):
+ * chromosomes in byte-wise order of their names; round k is written while round k + 1 is formatted. Releases the object. */
+void stream_gcov_write(const sizes_t *chr_sizes, const char *path_all, const char *path_uniq);
 
 int main_cpgstat(int argc, char **argv);
 int main_cpgfilter(int argc, char **argv);

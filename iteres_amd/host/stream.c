@@ -405,6 +405,12 @@ typedef struct {
     struct { uint8_t *bytes; size_t cap; } bbuf;
     unsigned long long bam_dev_batches, bam_host_batches;
     unsigned long long bam_host_tag_bytes;         /* -b -a: tag bytes the host route appended */
+    /* filter -G (csrc/itx_gcov.hip): every counted record adds its interval to the coverage on the device, whatever route it took;
+     * the host route derives the intervals of its own records (collect_gcov). The files are written after the stream
+     * (stream_gcov_write). */
+    itx_gcov *gc;
+    const struct stream_file_s *cur;               /* the file being scanned: its tid map, for the host route's intervals */
+    struct { int32_t *chrom; uint32_t *start, *end; uint8_t *uniq; size_t cap; } gbuf;
     /* the host route: two pinned slots, taken when a batch first goes that way; s is filled next, pend[] are in flight */
     itx_staging st[2];
     aln_side side[2];                             /* what the host keeps per record beside the SoA */
@@ -424,7 +430,7 @@ typedef struct {
 } stream_run;
 
 /* ---- one file of it */
-typedef struct {
+typedef struct stream_file_s {
     aln_reader *rd;
     int nt;                                       /* the header's references: chromosome, -R identity, (renamed) name of each */
     int32_t *t2c;
@@ -664,6 +670,41 @@ static void collect_bam(stream_run *r, int k)
     bam_write_out(r, 1);
 }
 
+/* filter -G: what the stream left on the device for stream_gcov_write, and the batches each route added (ITX_TIMING) */
+static itx_gcov *g_gcov;
+static unsigned long long g_gcov_dev_batches, g_gcov_host_batches;
+
+/* filter -G: the records of slot k that chose a row add the interval the lookup ran on (host_derive: itx_derive of
+ * ../csrc/itx_derive.h). One that has none, which no counted record is, goes up with no chromosome and is counted as out of range. */
+static void collect_gcov(stream_run *r, int k)
+{
+    const itx_staging *st = &r->st[k];
+    const stream_file *f = r->cur;
+    const size_t n = r->pend[k];
+    size_t m = 0;
+    if (r->gbuf.cap < n) {
+        r->gbuf.cap = n + n / 4 + 1;
+        r->gbuf.chrom = xrealloc(r->gbuf.chrom, sizeof(int32_t) * r->gbuf.cap);
+        r->gbuf.start = xrealloc(r->gbuf.start, sizeof(uint32_t) * r->gbuf.cap);
+        r->gbuf.end = xrealloc(r->gbuf.end, sizeof(uint32_t) * r->gbuf.cap);
+        r->gbuf.uniq = xrealloc(r->gbuf.uniq, r->gbuf.cap);
+    }
+    for (size_t i = 0; i < n; i++) {
+        if (st->hit_row[i] < 0) continue;
+        const int32_t t = st->tid[i];
+        const int32_t chrom = (f && t >= 0 && t < f->nt) ? f->t2c[t] : -1;
+        host_iv iv = {0, 0, '+'};
+        const int ok = host_derive(r->o, chrom, chrom >= 0 ? r->chr_sizes->value[chrom] : 0, st->flag5[i], st->pos[i], st->tmpend[i], st->mpos[i], st->isize[i], &iv);
+        r->gbuf.chrom[m] = ok ? chrom : -1;
+        r->gbuf.start[m] = iv.start;
+        r->gbuf.end[m] = iv.end;
+        r->gbuf.uniq[m] = st->mapq[i] >= r->o->mapq;
+        m++;
+    }
+    g_gcov_host_batches++;
+    chk(itx_gcov_add_host(r->gc, r->gbuf.chrom, r->gbuf.start, r->gbuf.end, r->gbuf.uniq, m), "itx_gcov_add_host");
+}
+
 static void side_release(aln_side *side, size_t n, int keep_qnames)
 {
     if (!side->has_strings) return;                /* nothing was stored: the arrays are all NULL as they were */
@@ -689,6 +730,7 @@ static double drain_slot(stream_run *r, int k)
     if (!r->pend[k]) return waited;
     if (r->want_qnames) collect_names(r, k);
     if (r->bo) collect_bam(r, k);
+    if (r->gc) collect_gcov(r, k);
     side_release(&r->side[k], r->pend[k], r->want_qnames);
     r->pend[k] = 0;
     return waited;
@@ -896,6 +938,7 @@ static void attach_tidmaps(stream_run *r, stream_file *f, const void *only)
     const int nt = f->nt > 0 ? f->nt : 0;
     if (!only) chk(itx_engine_set_tidmap(r->eng, f->t2c, nt), "itx_engine_set_tidmap");
     if (r->xv && (!only || only == r->xv)) chk(itx_xaveto_set_tidmap(r->xv, f->t2c, nt), "itx_xaveto_set_tidmap");
+    if (r->gc && !only) chk(itx_gcov_set_tidmap(r->gc, f->t2c, nt), "itx_gcov_set_tidmap");
     if (r->bd && (!only || only == r->bd)) chk(itx_bed_set_tidmap(r->bd, f->t2c, (const char *const *)f->t2name, nt), "itx_bed_set_tidmap");
     if (r->dd && !only) {
         chk(itx_dedup_set_tidmap(r->dd, f->t2c, f->t2id, nt), "itx_dedup_set_tidmap");
@@ -1056,6 +1099,15 @@ static int device_window(stream_run *r, stream_file *f, int xa_window)
             r->bam_dev_batches++;
             bam_write_out(r, 1);
         }
+        if (r->gc) {
+            /* filter -G: the rows the lists or the BAM had classified, else classified into the coverage's own buffer; its kernel
+             * follows on the stream they were written on. Sums commute: no order to keep with the host route's batches. */
+            const int32_t *hits = r->nm ? itx_names_hits(r->nm) : r->bo ? itx_bamout_hits(r->bo) : itx_gcov_hits(r->gc);
+            void *hst = r->nm ? itx_names_stream(r->nm) : r->bo ? itx_bamout_stream(r->bo) : itx_gcov_stream(r->gc);
+            if (!r->nm && !r->bo) chk(itx_engine_classify_device(r->eng, &db, n, itx_gcov_hits(r->gc), hst), "itx_engine_classify_device");
+            chk(itx_gcov_run(r->gc, &db, hits, n, hst), "itx_gcov_run");
+            g_gcov_dev_batches++;
+        }
         if (xa_window) {
             /* classify, let the device read the tags of the classified records, mark the vetoed ones */
             uint64_t vetoed = 0, hard = 0;
@@ -1075,6 +1127,7 @@ static int device_window(stream_run *r, stream_file *f, int xa_window)
             if (r->bd) chk(itx_bed_wait_kernels(r->bd), "itx_bed_wait_kernels");
             if (r->nm) chk(itx_names_wait_kernels(r->nm), "itx_names_wait_kernels");
             if (r->bo) chk(itx_bamout_wait_kernels(r->bo), "itx_bamout_wait_kernels");
+            if (r->gc) chk(itx_gcov_wait_kernels(r->gc), "itx_gcov_wait_kernels");
         }
         f->t_submit += now_s() - tq;
         tq = now_s();
@@ -1207,7 +1260,7 @@ static size_t host_batch(stream_run *r, stream_file *f)
     if (r->veto_on && batch_xa) veto_pass(r, f, n);
     f->t_host += now_s() - tq;
     tq = now_s();
-    chk(itx_engine_submit_slot(r->eng, s, n, f->any_paired, r->want_qnames || r->bo != NULL), "itx_engine_submit_slot");
+    chk(itx_engine_submit_slot(r->eng, s, n, f->any_paired, r->want_qnames || r->bo != NULL || r->gc != NULL), "itx_engine_submit_slot");
     f->t_submit += now_s() - tq;
     r->pend[s] = n;
     r->s ^= 1;
@@ -1234,6 +1287,7 @@ static void record_loop(stream_run *r, stream_file *f)
         while (r->bd && r->bed_pending) bed_write_out(r, 0);
         if (r->nm) chk(itx_names_wait_kernels(r->nm), "itx_names_wait_kernels");
         if (r->bo) chk(itx_bamout_wait_kernels(r->bo), "itx_bamout_wait_kernels");
+        if (r->gc) chk(itx_gcov_wait_kernels(r->gc), "itx_gcov_wait_kernels");
         if (host_batch(r, f) == 0) break;
     }
 }
@@ -1247,6 +1301,7 @@ static void scan_file(stream_run *r, int fi, int pass)
     const int backlog = open_file(r, &f, fi, pass);
     itx_samtext *sam_dev = r->o->is_sam && sam_by_device() ? sam_device_attach(f.rd) : NULL;
     r->s = 0;
+    r->cur = &f;
     map_targets(r, &f);
     if (backlog) submit_backlog(r);
     if (pre_bl && fi == 0 && pass == 0) {                              /* used or not (another share than the plan's): gone */
@@ -1266,6 +1321,7 @@ static void scan_file(stream_run *r, int fi, int pass)
     if (r->timing)
         fprintf(stderr, "[itx timing] stream of %s: decode %.3f s, host passes %.3f s, submit %.3f s, waiting for the device %.3f s\n", r->files[fi], f.t_read,
                 f.t_host, f.t_submit, f.t_wait);
+    r->cur = NULL;                                                     /* (both slots are drained) */
     for (int t = 0; t < f.nt; t++) free(f.t2name[t]);
     free(f.t2name);
     free(f.t2id);
@@ -1447,6 +1503,10 @@ static void teardown(stream_run *r, int lists_taken)
     free(r->nbuf.rows);
     free(r->nbuf.off);
     free(r->nbuf.bytes);
+    free(r->gbuf.chrom);
+    free(r->gbuf.start);
+    free(r->gbuf.end);
+    free(r->gbuf.uniq);
     for (int k = 0; k < 2; k++) {
         free(r->side[k].qname);
         free(r->side[k].xa);
@@ -1468,6 +1528,61 @@ static void teardown(stream_run *r, int lists_taken)
     }
 }
 
+/* filter -G, after the stream: the chromosomes in byte-wise order of their names (LC_ALL=C sort -k1,1), the change points of both
+ * arrays, then each file's text round by round: round k is written while the device formats round k + 1 */
+static const sizes_t *gcov_sort_sizes;
+static int gcov_by_name(const void *a, const void *b)
+{
+    return strcmp(gcov_sort_sizes->names.name[*(const uint32_t *)a], gcov_sort_sizes->names.name[*(const uint32_t *)b]);
+}
+void stream_gcov_write(const sizes_t *chr_sizes, const char *path_all, const char *path_uniq)
+{
+    itx_gcov *g = g_gcov;
+    if (!g) die("filter -G: no coverage was accumulated");
+    const uint32_t n = chr_sizes->names.n;
+    uint32_t *order = xmalloc(sizeof(uint32_t) * ((size_t)n + 1));
+    for (uint32_t c = 0; c < n; c++) order[c] = c;
+    gcov_sort_sizes = chr_sizes;
+    qsort(order, n, sizeof(uint32_t), gcov_by_name);
+    char *nb = NULL;
+    uint64_t *no = NULL;
+    loci_name_table(&chr_sizes->names, &nb, &no);
+    const char *re = getenv("ITX_GCOV_ROUND_BYTES");                       /* tests: many rounds on a small input */
+    const int rc = itx_gcov_finish(g, order, (int)n, nb, no, re && atoll(re) > 0 ? (size_t)atoll(re) : 0);
+    if (rc == ITX_E_NOMEM) die("filter -G: %s", itx_last_error());
+    chk(rc, "itx_gcov_finish");
+    const char *path[2] = {path_all, path_uniq};
+    double t_write = 0;
+    for (int w = 0; w < 2; w++) {
+        FILE *f = fopen(path[w], "w");
+        if (!f) die("mustOpen: Can't open %s to write: %s", path[w], strerror(errno));
+        itx_gcov_text tx;
+        do {
+            chk(itx_gcov_next(g, w, &tx), "itx_gcov_next");
+            const double t0 = now_s();
+            if (tx.len && fwrite(tx.bytes, 1, tx.len, f) != tx.len) die("writing %s: %s", path[w], strerror(errno));
+            t_write += now_s() - t0;
+        } while (tx.more);
+        if (fclose(f) != 0) die("writing %s: %s", path[w], strerror(errno));
+    }
+    if (getenv("ITX_TIMING")) {
+        itx_gcov_stats gs;
+        chk(itx_gcov_get_stats(g, &gs), "itx_gcov_get_stats");
+        fprintf(stderr, "[itx timing] genome coverage: %llu records added (%llu with MAPQ >= -Q, %llu out of range), %llu batches on the device, %llu by the host route; "
+                        "%llu + %llu change points, %llu + %llu lines, %llu + %llu bytes in %llu + %llu rounds; device: add %.3f ms, points %.3f ms, text %.3f ms, zeroing %.3f ms; "
+                        "host waited %.3f s, wrote for %.3f s; two arrays of %llu slots (%llu bytes) allocated in %.3f s\n",
+                (unsigned long long)gs.records, (unsigned long long)gs.records_uniq, (unsigned long long)gs.out_of_range, g_gcov_dev_batches, g_gcov_host_batches,
+                (unsigned long long)gs.points[0], (unsigned long long)gs.points[1], (unsigned long long)gs.lines[0], (unsigned long long)gs.lines[1],
+                (unsigned long long)gs.bytes[0], (unsigned long long)gs.bytes[1], (unsigned long long)gs.rounds[0], (unsigned long long)gs.rounds[1], gs.add_ms, gs.points_ms,
+                gs.text_ms, gs.zero_ms, gs.wait_s, t_write, (unsigned long long)gs.slots, (unsigned long long)gs.device_bytes, gs.alloc_s);
+    }
+    free(nb);
+    free(no);
+    free(order);
+    itx_gcov_destroy(g);
+    g_gcov = NULL;
+}
+
 void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, int filter_mode, int multi_file,
                 unsigned progress_every, int want_qnames, itx_engine **eng_out, itx_table **tab_out, char ***locus_names,
                 host_counts *hc)
@@ -1478,6 +1593,14 @@ void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, i
                       .veto_on = o->xa_veto && !filter_mode, .dev_veto = !getenv("ITX_HOST_VETO")}, *r = &run;
 
     make_table_and_engine(r);
+    if (o->gcov) {
+        /* filter -G: one u32 slot per base of the size file, twice. A device that cannot hold them ends the command here, with one
+         * line, before the stream starts */
+        const int rc = itx_gcov_create(multi_device(), chr_sizes->value, (int)chr_sizes->names.n, &r->p, BATCH_RECORDS, &r->gc);
+        if (rc == ITX_E_NOMEM || rc == ITX_E_LIMIT) die("filter -G: %s", itx_last_error());
+        chk(rc, "itx_gcov_create");
+        g_gcov = r->gc;
+    }
     open_outputs_and_side_buffers(r);
     list_files_and_shares(r);
     join_helper_thread(r);
