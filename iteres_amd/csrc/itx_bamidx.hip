@@ -25,9 +25,10 @@
 //   k_bi_fill      one workgroup per reference: n_intv, then untouched windows take the nearest touched value below (carried scan)
 //   k_bi_refsize   one workgroup: the bytes of every reference's part, exclusive sums
 //   k_bi_write_*   the file's bytes. Every field of a .bai lies on a 4-byte boundary, so 8-byte fields go as two 32-bit stores.
-// The finished bytes come back through a page-locked buffer.
+// The finished bytes come back through a page-locked buffer. The pools grow by the two-phase rule of itx_devbuf.h.
 #include "itx_bamidx.h"
 #include "itx_bairule.h"
+#include "itx_devbuf.h"
 #include "itx_radixsort.h"
 #include "itx_textpack.h"
 
@@ -391,17 +392,6 @@ struct itx_bamidx {
     uint8_t *d_out, *h_out;          // the finished file
 };
 
-static int bi_hip(hipError_t e, const char *what, int line)
-{
-    if (e == hipSuccess) return ITX_OK;
-    itx_set_error("%s failed: %s (%s:%d)", what, hipGetErrorString(e), __FILE__, line);
-    return ITX_E_NO_DEVICE;
-}
-#define BI_TRY(call)                                       \
-    do {                                                   \
-        if ((rc = bi_hip((call), #call, __LINE__)) != 0) goto out; \
-    } while (0)
-
 void itx_bamidx_destroy(itx_bamidx *ix)
 {
     if (!ix) return;
@@ -446,7 +436,7 @@ int itx_bamidx_create(int device, int32_t n_ref, const int32_t *l_ref, itx_bamid
     }
     ix->h_woff[0] = 0;
     for (int32_t r = 0; r < n_ref; r++) ix->h_woff[r + 1] = ix->h_woff[r] + itx_bai_windows(l_ref[r]);
-    BI_TRY(hipSetDevice(device));
+    ITX_TRY(hipSetDevice(device));
     if (hipMalloc((void **)&ix->d_lref, 4 * ((size_t)n_ref + 1)) != hipSuccess || hipMalloc((void **)&ix->d_woff, 8 * ((size_t)n_ref + 1)) != hipSuccess ||
         hipMalloc((void **)&ix->d_flag, 16) != hipSuccess) {
         (void)hipGetLastError();
@@ -454,12 +444,12 @@ int itx_bamidx_create(int device, int32_t n_ref, const int32_t *l_ref, itx_bamid
         rc = ITX_E_NOMEM;
         goto out;
     }
-    BI_TRY(hipHostMalloc((void **)&ix->h_flag, 16, hipHostMallocDefault));
-    if (n_ref) BI_TRY(hipMemcpy(ix->d_lref, l_ref, 4 * (size_t)n_ref, hipMemcpyHostToDevice));
-    BI_TRY(hipMemcpy(ix->d_woff, ix->h_woff, 8 * ((size_t)n_ref + 1), hipMemcpyHostToDevice));
-    BI_TRY(hipMemset(ix->d_flag, 0, 16));
-    for (auto &e : ix->eb) BI_TRY(hipEventCreate(&e));
-    for (auto &e : ix->ef) BI_TRY(hipEventCreate(&e));
+    ITX_TRY(hipHostMalloc((void **)&ix->h_flag, 16, hipHostMallocDefault));
+    if (n_ref) ITX_TRY(hipMemcpy(ix->d_lref, l_ref, 4 * (size_t)n_ref, hipMemcpyHostToDevice));
+    ITX_TRY(hipMemcpy(ix->d_woff, ix->h_woff, 8 * ((size_t)n_ref + 1), hipMemcpyHostToDevice));
+    ITX_TRY(hipMemset(ix->d_flag, 0, 16));
+    for (auto &e : ix->eb) ITX_TRY(hipEventCreate(&e));
+    for (auto &e : ix->ef) ITX_TRY(hipEventCreate(&e));
 out:
     if (rc != ITX_OK) {
         itx_bamidx_destroy(ix);
@@ -472,9 +462,6 @@ out:
 int itx_bamidx_reserve(itx_bamidx *ix, hipStream_t st, uint64_t n_entries, uint64_t n_members)
 {
     if (ix->reason) return ITX_OK;
-    int rc = ITX_OK;
-    BiEnt *nent = nullptr;
-    uint32_t *nms = nullptr;
     uint64_t want_ent = 0, want_ms = 0;
     if (ix->n_ent + n_entries > 0xffffff00ull) {
         itx_set_error("itx_bamout: %llu records to index", (ull)(ix->n_ent + n_entries));
@@ -482,32 +469,21 @@ int itx_bamidx_reserve(itx_bamidx *ix, hipStream_t st, uint64_t n_entries, uint6
     }
     if (ix->n_ent + n_entries > ix->ent_cap) want_ent = ix->n_ent + n_entries + (ix->n_ent + n_entries) / 2 + 1024;
     if (ix->n_ms + n_members > ix->ms_cap) want_ms = ix->n_ms + n_members + (ix->n_ms + n_members) / 2 + 1024;
-    if ((want_ent && hipMalloc((void **)&nent, sizeof(BiEnt) * want_ent) != hipSuccess) || (want_ms && hipMalloc((void **)&nms, 4 * want_ms) != hipSuccess)) {
-        (void)hipGetLastError();
+    const bool first = !ix->d_ent;
+    // the entries and the member sizes are taken together (itx_devbuf.h); what they hold is kept
+    ItxGrow g[2] = {{(void **)&ix->d_ent, sizeof(BiEnt) * ix->n_ent, sizeof(BiEnt) * want_ent}, {(void **)&ix->d_ms, 4 * ix->n_ms, 4 * want_ms}};
+    if (itx_grow_alloc(g, 2) >= 0) {
         itx_set_error("itx_bamout: no device memory for the index entries of %llu records and %llu members", (ull)(ix->n_ent + n_entries), (ull)(ix->n_ms + n_members));
-        rc = ITX_E_NOMEM;
-        goto out;
+        return ITX_E_NOMEM;
     }
-    if (nent && ix->n_ent) BI_TRY(hipMemcpyAsync(nent, ix->d_ent, sizeof(BiEnt) * ix->n_ent, hipMemcpyDeviceToDevice, st));
-    if (nms && ix->n_ms) BI_TRY(hipMemcpyAsync(nms, ix->d_ms, 4 * ix->n_ms, hipMemcpyDeviceToDevice, st));
-    if ((nent && ix->n_ent) || (nms && ix->n_ms)) BI_TRY(hipStreamSynchronize(st));            // before the old pools go
-    if (nent) {
-        BiEnt *old = ix->d_ent;
-        ix->d_ent = nent;
+    const int rc = itx_grow_commit(st, g, 2);
+    if (rc != ITX_OK) return rc;
+    if (want_ent) {
         ix->ent_cap = want_ent;
-        nent = old;
-        if (old) ix->grows++;
+        if (!first) ix->grows++;
     }
-    if (nms) {
-        uint32_t *old = ix->d_ms;
-        ix->d_ms = nms;
-        ix->ms_cap = want_ms;
-        nms = old;
-    }
-out:
-    (void)hipFree(nent);                                                   // the old pools, or the new ones that were not taken
-    (void)hipFree(nms);
-    return rc;
+    if (want_ms) ix->ms_cap = want_ms;
+    return ITX_OK;
 }
 
 template <class OFF>
@@ -520,11 +496,11 @@ static int bi_entries(itx_bamidx *ix, hipStream_t st, const uint8_t *u, const OF
         itx_set_error("itx_bamidx_entries: no room was reserved");
         return ITX_E_STATE;
     }
-    BI_TRY(hipEventRecord(ix->eb[0], st));
+    ITX_TRY(hipEventRecord(ix->eb[0], st));
     hipLaunchKernelGGL((k_bi_entries<OFF>), dim3((n + BI_TILE - 1) / BI_TILE), dim3(BI_TILE), 0, st, u, rec_off, n, len_in, tile_base, stream_at, (ull)ix->n_ent,
                        ix->d_ent, ix->n_ref, ix->d_lref, ix->d_flag);
-    BI_TRY(hipGetLastError());
-    BI_TRY(hipEventRecord(ix->eb[1], st));
+    ITX_TRY(hipGetLastError());
+    ITX_TRY(hipEventRecord(ix->eb[1], st));
     ix->batch_timed = 1;
     ix->n_ent += n_counted;
 out:
@@ -550,37 +526,22 @@ int itx_bamidx_host_records(itx_bamidx *ix, hipStream_t st, const uint8_t *d_byt
     const uint32_t nt = (n + BI_TILE - 1) / BI_TILE;
     if (n > ix->h_cap) {
         const uint64_t want = (uint64_t)n + n / 2 + 1024, wt = (want + BI_TILE - 1) / BI_TILE + 1;
-        uint32_t *a = nullptr, *b = nullptr;
-        ull *c = nullptr, *d = nullptr, *e = nullptr;
-        if (hipMalloc((void **)&a, 4 * want) != hipSuccess || hipMalloc((void **)&b, 4 * want) != hipSuccess || hipMalloc((void **)&c, 16 * wt) != hipSuccess ||
-            hipMalloc((void **)&d, 16 * wt) != hipSuccess || hipMalloc((void **)&e, 16) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(a);
-            (void)hipFree(b);
-            (void)hipFree(c);
-            (void)hipFree(d);
-            (void)hipFree(e);
+        // the offsets, the lengths, the tiles' sums and bases and the totals are taken together; nothing is kept (st is idle: nothing reads them)
+        ItxGrow g[5] = {{(void **)&ix->d_hoff, 0, 4 * want}, {(void **)&ix->d_hlen, 0, 4 * want}, {(void **)&ix->d_hts, 0, 16 * wt}, {(void **)&ix->d_htb, 0, 16 * wt},
+                        {(void **)&ix->d_htot, 0, 16}};
+        if (itx_grow_alloc(g, 5) >= 0) {
             itx_set_error("itx_bamout_append_host: no device memory for the offsets of %u records", n);
             return ITX_E_NOMEM;
         }
-        (void)hipFree(ix->d_hoff);                                         // (st is idle: nothing reads them)
-        (void)hipFree(ix->d_hlen);
-        (void)hipFree(ix->d_hts);
-        (void)hipFree(ix->d_htb);
-        (void)hipFree(ix->d_htot);
-        ix->d_hoff = a;
-        ix->d_hlen = b;
-        ix->d_hts = c;
-        ix->d_htb = d;
-        ix->d_htot = e;
+        if ((rc = itx_grow_commit(st, g, 5)) != ITX_OK) goto out;
         ix->h_cap = want;
     }
-    BI_TRY(hipMemcpyAsync(ix->d_hoff, h_off, 4 * (size_t)n, hipMemcpyHostToDevice, st));
-    BI_TRY(hipStreamSynchronize(st));
+    ITX_TRY(hipMemcpyAsync(ix->d_hoff, h_off, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    ITX_TRY(hipStreamSynchronize(st));
     hipLaunchKernelGGL(k_bi_measure, dim3(nt), dim3(BI_TILE), 0, st, d_bytes, ix->d_hoff, n, ix->d_hlen, ix->d_hts);
-    BI_TRY(hipGetLastError());
+    ITX_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, st, ix->d_hts, nt, ix->d_htb, ix->d_htot);
-    BI_TRY(hipGetLastError());
+    ITX_TRY(hipGetLastError());
     rc = itx_bamidx_entries(ix, st, d_bytes, ix->d_hoff, n, ix->d_hlen, ix->d_htb, stream_at, n);
 out:
     return rc;
@@ -594,7 +555,7 @@ int itx_bamidx_members(itx_bamidx *ix, hipStream_t st, const uint32_t *d_msize, 
         itx_set_error("itx_bamidx_members: no room was reserved");
         return ITX_E_STATE;
     }
-    BI_TRY(hipMemcpyAsync(ix->d_ms + ix->n_ms, d_msize, 4 * (size_t)n, hipMemcpyDeviceToDevice, st));
+    ITX_TRY(hipMemcpyAsync(ix->d_ms + ix->n_ms, d_msize, 4 * (size_t)n, hipMemcpyDeviceToDevice, st));
     ix->n_ms += n;
 out:
     return rc;
@@ -639,14 +600,14 @@ int itx_bamidx_finish(itx_bamidx *ix, hipStream_t st, uint64_t first, itx_bamout
     uint2 *d_k0 = nullptr, *d_k1 = nullptr, *sorted = nullptr;
     uint32_t *d_hist = nullptr, *d_fkey = nullptr, *d_fbin = nullptr, *d_binfirst = nullptr, *d_refs = nullptr;
     BiRefs R = {};
-    BI_TRY(hipSetDevice(ix->device));
-    BI_TRY(hipEventRecord(ix->ef[0], st));
+    ITX_TRY(hipSetDevice(ix->device));
+    ITX_TRY(hipEventRecord(ix->ef[0], st));
     if (N) {
         hipLaunchKernelGGL(k_bi_order, dim3((N + 255u) / 256u), dim3(256), 0, st, ix->d_ent, N, ix->d_flag);
-        BI_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
     }
-    BI_TRY(hipMemcpyAsync(ix->h_flag, ix->d_flag, 4, hipMemcpyDeviceToHost, st));
-    BI_TRY(hipStreamSynchronize(st));
+    ITX_TRY(hipMemcpyAsync(ix->h_flag, ix->d_flag, 4, hipMemcpyDeviceToHost, st));
+    ITX_TRY(hipStreamSynchronize(st));
     itx_bamidx_batch_time(ix);
     res->entries = N;
     res->grows = ix->grows;
@@ -673,25 +634,24 @@ int itx_bamidx_finish(itx_bamidx *ix, hipStream_t st, uint64_t first, itx_bamout
     R.e0 = d_refs + 4 * ((size_t)n_ref + 1);
     R.e1 = d_refs + 5 * ((size_t)n_ref + 1);
     R.n_intv = d_refs + 6 * ((size_t)n_ref + 1);
-    BI_TRY(hipMemsetAsync(d_refs, 0, 4 * 7 * ((size_t)n_ref + 1), st));
-    BI_TRY(hipMemsetAsync(d_lin, 0xff, 8 * (W + 1), st));
-    BI_TRY(hipMemsetAsync(d_tot, 0, 16, st));
+    ITX_TRY(hipMemsetAsync(d_refs, 0, 4 * 7 * ((size_t)n_ref + 1), st));
+    ITX_TRY(hipMemsetAsync(d_lin, 0xff, 8 * (W + 1), st));
+    ITX_TRY(hipMemsetAsync(d_tot, 0, 16, st));
     hipLaunchKernelGGL(k_bi_coff, dim3(1), dim3(ITX_SCAN_WG), 0, st, ix->d_ms, M, d_coff);
-    BI_TRY(hipGetLastError());
+    ITX_TRY(hipGetLastError());
     if (N) {
         hipLaunchKernelGGL(k_bi_heads, dim3(ntN), dim3(BI_TILE), 0, st, ix->d_ent, N, d_ts);
-        BI_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, st, d_ts, ntN, d_tb, d_tot);
-        BI_TRY(hipGetLastError());
-        BI_TRY(hipMemcpyAsync(h_tot, d_tot, 16, hipMemcpyDeviceToHost, st));
-        BI_TRY(hipStreamSynchronize(st));                                  // the number of chunks sizes what follows
+        ITX_TRY(hipGetLastError());
+        ITX_TRY(hipMemcpyAsync(h_tot, d_tot, 16, hipMemcpyDeviceToHost, st));
+        ITX_TRY(hipStreamSynchronize(st));                                  // the number of chunks sizes what follows
         C = (uint32_t)h_tot[0];
         ntC = (C + BI_TILE - 1) / BI_TILE;
-        const uint32_t nwg = (C + SORT_CHUNK - 1) / SORT_CHUNK, passes = bi_sort_passes(ix->n_ref);
         if (hipMalloc((void **)&d_cbeg, 8 * (size_t)C) != hipSuccess || hipMalloc((void **)&d_cend, 8 * (size_t)C) != hipSuccess ||
             hipMalloc((void **)&d_fbeg, 8 * (size_t)C) != hipSuccess || hipMalloc((void **)&d_fend, 8 * (size_t)C) != hipSuccess ||
             hipMalloc((void **)&d_k0, 8 * (size_t)C) != hipSuccess || hipMalloc((void **)&d_k1, 8 * (size_t)C) != hipSuccess ||
-            hipMalloc((void **)&d_hist, 4 * 256 * (size_t)nwg) != hipSuccess || hipMalloc((void **)&d_fkey, 4 * (size_t)C) != hipSuccess ||
+            hipMalloc((void **)&d_hist, itx_sort_hist_bytes(C)) != hipSuccess || hipMalloc((void **)&d_fkey, 4 * (size_t)C) != hipSuccess ||
             hipMalloc((void **)&d_fbin, 4 * (size_t)C) != hipSuccess || hipMalloc((void **)&d_binfirst, 4 * ((size_t)C + 1)) != hipSuccess) {
             (void)hipGetLastError();
             itx_set_error("itx_bamout_index_finish: no device memory for %u chunks", C);
@@ -699,36 +659,26 @@ int itx_bamidx_finish(itx_bamidx *ix, hipStream_t st, uint64_t first, itx_bamout
             goto out;
         }
         hipLaunchKernelGGL(k_bi_chunks, dim3(ntN), dim3(BI_TILE), 0, st, ix->d_ent, N, d_tb, d_coff, first, d_k0, d_cbeg, d_cend);
-        BI_TRY(hipGetLastError());
-        sorted = d_k0;
-        for (uint32_t p = 0; p < passes; p++) {
-            uint2 *to = sorted == d_k0 ? d_k1 : d_k0;
-            hipLaunchKernelGGL(k_sort_hist, dim3(nwg), dim3(256), 0, st, sorted, C, 8u * p, d_hist, nwg);
-            BI_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(ITX_SCAN_WG), 0, st, d_hist, 256u * nwg);
-            BI_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_sort_scatter, dim3(nwg), dim3(256), 0, st, sorted, to, C, 8u * p, d_hist, nwg);
-            BI_TRY(hipGetLastError());
-            sorted = to;
-        }
+        ITX_TRY(hipGetLastError());
+        if ((rc = itx_sort_run(st, d_k0, d_k1, C, 0u, bi_sort_passes(ix->n_ref), d_hist, &sorted)) != ITX_OK) goto out;
         hipLaunchKernelGGL(k_bi_merge_count, dim3(ntC), dim3(BI_TILE), 0, st, sorted, C, d_cbeg, d_cend, d_ts);
-        BI_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, st, d_ts, ntC, d_tb, d_tot);
-        BI_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_bi_merge_apply, dim3(ntC), dim3(BI_TILE), 0, st, sorted, C, d_cbeg, d_cend, d_tb, d_fkey, d_fbin, d_fbeg, d_fend, d_binfirst, R);
-        BI_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_bi_windows, dim3((N + 255u) / 256u), dim3(256), 0, st, ix->d_ent, N, d_coff, first, ix->d_woff, d_lin, R);
-        BI_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
     }
     if (n_ref) {
         hipLaunchKernelGGL(k_bi_fill, dim3(n_ref), dim3(256), 0, st, ix->d_woff, d_lin, R.n_intv);
-        BI_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(k_bi_refsize, dim3(1), dim3(ITX_SCAN_WG), 0, st, n_ref, R, d_roff);
-    BI_TRY(hipGetLastError());
-    BI_TRY(hipMemcpyAsync(h_tot, d_tot, 16, hipMemcpyDeviceToHost, st));
-    BI_TRY(hipMemcpyAsync(ix->h_flag + 2, d_roff + n_ref, 8, hipMemcpyDeviceToHost, st));
-    BI_TRY(hipStreamSynchronize(st));                                      // the file's size
+    ITX_TRY(hipGetLastError());
+    ITX_TRY(hipMemcpyAsync(h_tot, d_tot, 16, hipMemcpyDeviceToHost, st));
+    ITX_TRY(hipMemcpyAsync(ix->h_flag + 2, d_roff + n_ref, 8, hipMemcpyDeviceToHost, st));
+    ITX_TRY(hipStreamSynchronize(st));                                      // the file's size
     memcpy(&total, ix->h_flag + 2, 8);
     total += 8;
     if (hipMalloc((void **)&ix->d_out, total) != hipSuccess || hipHostMalloc((void **)&ix->h_out, total, hipHostMallocDefault) != hipSuccess) {
@@ -738,18 +688,18 @@ int itx_bamidx_finish(itx_bamidx *ix, hipStream_t st, uint64_t first, itx_bamout
         goto out;
     }
     hipLaunchKernelGGL(k_bi_write_refs, dim3(n_ref / 256u + 1u), dim3(256), 0, st, n_ref, R, d_roff, ix->d_ent, d_coff, first, ix->d_out);
-    BI_TRY(hipGetLastError());
+    ITX_TRY(hipGetLastError());
     if (C) {
         hipLaunchKernelGGL(k_bi_write_chunks, dim3(ntC), dim3(256), 0, st, d_tot, d_fkey, d_fbin, d_fbeg, d_fend, d_binfirst, R, d_roff, ix->d_out);
-        BI_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
     }
     if (n_ref) {
         hipLaunchKernelGGL(k_bi_write_linear, dim3(n_ref), dim3(256), 0, st, R, d_roff, ix->d_woff, d_lin, ix->d_out);
-        BI_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
     }
-    BI_TRY(hipMemcpyAsync(ix->h_out, ix->d_out, total, hipMemcpyDeviceToHost, st));
-    BI_TRY(hipEventRecord(ix->ef[1], st));
-    BI_TRY(hipStreamSynchronize(st));
+    ITX_TRY(hipMemcpyAsync(ix->h_out, ix->d_out, total, hipMemcpyDeviceToHost, st));
+    ITX_TRY(hipEventRecord(ix->ef[1], st));
+    ITX_TRY(hipStreamSynchronize(st));
     if (hipEventElapsedTime(&ms, ix->ef[0], ix->ef[1]) == hipSuccess) ix->finish_ms = (double)ms;
     res->bytes = ix->h_out;
     res->len = total;

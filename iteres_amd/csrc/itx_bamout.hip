@@ -36,10 +36,13 @@
 // itx_reptag_write in place of the byte copy. Everything behind the gather sees a longer record: the members, the index's chunks, the
 // held stream of -s (annotated at the first gather; the replay copies byte for byte). Without the call the <false> instantiations run.
 //
+// Every buffer that grows (bo_reserve, bs_reserve) grows by the two-phase rule of itx_devbuf.h; the sort's passes are itx_sort_run's.
+//
 // Byte and integer work. k_bo_member is bound by the encoder's serial parse (one lane per member); ITX_BAMOUT_PAYLOAD is chosen
 // for that (itx_bgzfmember.h). No kernel uses scratch (DESIGN.md has the figures).
 #include "itx_bamidx.h"
 #include "itx_bamsortrule.h"
+#include "itx_devbuf.h"
 #include "itx_radixsort.h"
 #include "itx_reptag.h"
 #include "itx_textpack.h"
@@ -430,17 +433,6 @@ struct itx_bamout {
     double sort_ms, replay_ms;
 };
 
-static int bo_hip(hipError_t e, const char *what, int line)
-{
-    if (e == hipSuccess) return ITX_OK;
-    itx_set_error("%s failed: %s (%s:%d)", what, hipGetErrorString(e), __FILE__, line);
-    return ITX_E_NO_DEVICE;
-}
-#define BO_TRY(call)                                       \
-    do {                                                   \
-        if ((rc = bo_hip((call), #call, __LINE__)) != 0) goto out; \
-    } while (0)
-
 extern "C" void itx_bamout_destroy(itx_bamout *bo)
 {
     if (!bo) return;
@@ -499,7 +491,7 @@ extern "C" int itx_bamout_create(int device, size_t batch_capacity, size_t strea
     const size_t n = batch_capacity + 64, nt = (batch_capacity + BO_TILE - 1) / BO_TILE + 1;
     if (stream_bytes < 4 * (size_t)BO_P) stream_bytes = 4 * (size_t)BO_P;
     bo->pay_cap = stream_bytes;
-    BO_TRY(hipSetDevice(device));
+    ITX_TRY(hipSetDevice(device));
     if (hipMalloc((void **)&bo->d_hits, 4 * n) != hipSuccess || hipMalloc((void **)&bo->d_len, 4 * n) != hipSuccess ||
         hipMalloc((void **)&bo->d_tile_sum, 16 * nt) != hipSuccess || hipMalloc((void **)&bo->d_tile_base, 16 * nt) != hipSuccess ||
         hipMalloc((void **)&bo->d_tot, BO_TOT_BYTES) != hipSuccess || hipMalloc((void **)&bo->d_pay, bo->pay_cap + 16) != hipSuccess) {
@@ -508,14 +500,14 @@ extern "C" int itx_bamout_create(int device, size_t batch_capacity, size_t strea
         rc = ITX_E_NOMEM;
         goto out;
     }
-    BO_TRY(hipHostMalloc((void **)&bo->h_tot, BO_TOT_BYTES, hipHostMallocDefault));
-    BO_TRY(hipStreamCreateWithFlags(&bo->st, hipStreamNonBlocking));
-    BO_TRY(hipStreamCreateWithFlags(&bo->cst, hipStreamNonBlocking));
-    for (auto &e : bo->ev) BO_TRY(hipEventCreate(&e));
+    ITX_TRY(hipHostMalloc((void **)&bo->h_tot, BO_TOT_BYTES, hipHostMallocDefault));
+    ITX_TRY(hipStreamCreateWithFlags(&bo->st, hipStreamNonBlocking));
+    ITX_TRY(hipStreamCreateWithFlags(&bo->cst, hipStreamNonBlocking));
+    for (auto &e : bo->ev) ITX_TRY(hipEventCreate(&e));
     for (auto &s : bo->slot) {
-        BO_TRY(hipEventCreate(&s.e0));
-        BO_TRY(hipEventCreate(&s.e1));
-        BO_TRY(hipHostMalloc((void **)&s.h_total, 16, hipHostMallocDefault));
+        ITX_TRY(hipEventCreate(&s.e0));
+        ITX_TRY(hipEventCreate(&s.e1));
+        ITX_TRY(hipHostMalloc((void **)&s.h_total, 16, hipHostMallocDefault));
     }
 out:
     if (rc != ITX_OK) {
@@ -541,8 +533,6 @@ static void bo_read_gather_time(itx_bamout *bo)
 // filter -b -s: room for n_more more entries in the pool; bo->st is idle. What does not fit leaves the object as it was.
 static int bs_reserve(itx_bamout *bo, ull n_more)
 {
-    int rc = ITX_OK;
-    BoSortEnt *nent = nullptr;
     const ull want = bo->n_sent + n_more;
     if (want >= 0xfffffffeull) {
         itx_set_error("itx_bamout: %llu records to sort (run without -s)", want);
@@ -550,36 +540,24 @@ static int bs_reserve(itx_bamout *bo, ull n_more)
     }
     if (want <= bo->sent_cap) return ITX_OK;
     const ull cap = want + want / 2 + 1024;
-    if (hipMalloc((void **)&nent, sizeof(BoSortEnt) * cap) != hipSuccess) {
-        (void)hipGetLastError();
+    const bool first = !bo->d_sent;
+    ItxGrow g = {(void **)&bo->d_sent, sizeof(BoSortEnt) * bo->n_sent, sizeof(BoSortEnt) * cap};       // the pool alone; its entries are kept
+    if (itx_grow_alloc(&g, 1) >= 0) {
         itx_set_error("itx_bamout: no device memory for the sort entries of %llu records (run without -s)", want);
         return ITX_E_NOMEM;
     }
-    if (bo->n_sent) {
-        BO_TRY(hipMemcpyAsync(nent, bo->d_sent, sizeof(BoSortEnt) * bo->n_sent, hipMemcpyDeviceToDevice, bo->st));
-        BO_TRY(hipStreamSynchronize(bo->st));                              // before the old pool goes
-    }
-    {
-        BoSortEnt *old = bo->d_sent;
-        bo->d_sent = nent;
-        bo->sent_cap = cap;
-        nent = old;
-        if (old) bo->sent_grows++;
-    }
-out:
-    (void)hipFree(nent);                                                   // the old pool, or the new one that was not taken
-    return rc;
+    const int rc = itx_grow_commit(bo->st, &g, 1);
+    if (rc != ITX_OK) return rc;
+    bo->sent_cap = cap;
+    if (!first) bo->sent_grows++;
+    return ITX_OK;
 }
 
 // Room for a stream of `total` bytes and for the n_mem members made of it next; bo->st is idle when this is called. Every limit is
 // checked and every buffer allocated here, before anything is written: what does not fit leaves the object as it was.
 static int bo_reserve(itx_bamout *bo, ull total, ull n_mem)
 {
-    int rc = ITX_OK;
     bo_slot *s = &bo->slot[(bo->head + bo->pending) & 1];
-    uint8_t *npay = nullptr, *nmem = nullptr, *npk = nullptr, *npin = nullptr;
-    uint32_t *nms = nullptr;
-    uint64_t *nmo = nullptr;
     size_t want_pay = 0, want_mem = 0, want_pk = 0;
     if (n_mem > 0x7fffff00ull) {
         itx_set_error("itx_bamout: %llu members in one batch", n_mem);
@@ -592,54 +570,27 @@ static int bo_reserve(itx_bamout *bo, ull total, ull n_mem)
     if (total > bo->pay_cap) want_pay = (size_t)(total + (total > 2 * (ull)bo->pay_cap ? total / 4 : total));
     if (n_mem > bo->mem_cap) want_mem = (size_t)(n_mem + n_mem / 4 + 16);
     if (n_mem && n_mem * BO_STRIDE > s->cap) want_pk = (size_t)((n_mem + n_mem / 4 + 16) * BO_STRIDE);
-    if ((want_pay && hipMalloc((void **)&npay, want_pay + 16) != hipSuccess) ||
-        (want_mem && (hipMalloc((void **)&nmem, want_mem * BO_STRIDE) != hipSuccess || hipMalloc((void **)&nms, 4 * want_mem) != hipSuccess ||
-                      hipMalloc((void **)&nmo, 8 * (want_mem + 1)) != hipSuccess)) ||
-        (want_pk && (hipMalloc((void **)&npk, want_pk) != hipSuccess || hipHostMalloc((void **)&npin, want_pk, hipHostMallocDefault) != hipSuccess))) {
-        (void)hipGetLastError();
+    // taken together: the stream, of which the carry is kept; the members' slots, sizes and offsets; the slot's packed buffer and its
+    // page-locked twin (the slot is not busy: nothing reads its buffers). Of the last five nothing is kept.
+    ItxGrow g[6] = {{(void **)&bo->d_pay, bo->carry, want_pay ? want_pay + 16 : 0},
+                    {(void **)&bo->d_mem, 0, want_mem * BO_STRIDE},
+                    {(void **)&bo->d_msize, 0, 4 * want_mem},
+                    {(void **)&bo->d_moff, 0, want_mem ? 8 * (want_mem + 1) : 0},
+                    {(void **)&s->d_packed, 0, want_pk},
+                    {(void **)&s->h_pin, 0, want_pk, 1}};
+    if (itx_grow_alloc(g, 6) >= 0) {
         itx_set_error("itx_bamout: no memory for a stream of %llu bytes in %llu members%s", total, n_mem, bo->sort ? " (run without -s)" : "");
-        rc = ITX_E_NOMEM;
-        goto out;
+        return ITX_E_NOMEM;
     }
-    if (npay && bo->carry) {
-        BO_TRY(hipMemcpyAsync(npay, bo->d_pay, bo->carry, hipMemcpyDeviceToDevice, bo->st));
-        BO_TRY(hipStreamSynchronize(bo->st));                              // before the old buffer goes
-    }
-    if (npay) {
-        uint8_t *old = bo->d_pay;
-        bo->d_pay = npay;
+    const int rc = itx_grow_commit(bo->st, g, 6);
+    if (rc != ITX_OK) return rc;
+    if (want_pay) {
         bo->pay_cap = want_pay;
-        npay = old;
         bo->stats.grows++;
     }
-    if (nmem) {
-        uint8_t *o1 = bo->d_mem;
-        uint32_t *o2 = bo->d_msize;
-        uint64_t *o3 = bo->d_moff;
-        bo->d_mem = nmem;
-        bo->d_msize = nms;
-        bo->d_moff = nmo;
-        bo->mem_cap = want_mem;
-        nmem = o1;
-        nms = o2;
-        nmo = o3;
-    }
-    if (npk) {                                                             // (the slot is not busy: nothing reads its buffers)
-        uint8_t *o1 = s->d_packed, *o2 = s->h_pin;
-        s->d_packed = npk;
-        s->h_pin = npin;
-        s->cap = want_pk;
-        npk = o1;
-        npin = o2;
-    }
-out:
-    (void)hipFree(npay);                                                   // the old buffers, or the new ones that were not taken
-    (void)hipFree(nmem);
-    (void)hipFree(nms);
-    (void)hipFree(nmo);
-    (void)hipFree(npk);
-    if (npin) (void)hipHostFree(npin);
-    return rc;
+    if (want_mem) bo->mem_cap = want_mem;
+    if (want_pk) s->cap = want_pk;
+    return ITX_OK;
 }
 
 // d_pay holds `total` bytes: its whole payloads (with_tail: and the short rest) become members in the next slot, the rest moves
@@ -651,19 +602,19 @@ static int bo_emit(itx_bamout *bo, ull total, int with_tail)
     const uint32_t n_mem = (uint32_t)(n_full + (with_tail && rest ? 1 : 0));
     if (n_mem) {
         bo_slot *s = &bo->slot[(bo->head + bo->pending) & 1];
-        BO_TRY(hipEventRecord(s->e0, bo->st));
+        ITX_TRY(hipEventRecord(s->e0, bo->st));
         const ull n_bytes = with_tail ? total : n_full * BO_P;
         if (bo->level == 6) hipLaunchKernelGGL(k_bo_member, dim3(n_mem), dim3(64), 0, bo->st, bo->d_pay, n_bytes, bo->d_mem, bo->d_msize);
         else if (bo->level == 1) hipLaunchKernelGGL(k_bo_member_fast, dim3(n_mem), dim3(64), 0, bo->st, bo->d_pay, n_bytes, bo->d_mem, bo->d_msize);
         else hipLaunchKernelGGL(k_bo_member_stored, dim3(n_mem), dim3(64), 0, bo->st, bo->d_pay, n_bytes, bo->d_mem, bo->d_msize);
-        BO_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
         if (bo->ix && (rc = itx_bamidx_members(bo->ix, bo->st, bo->d_msize, n_mem)) != ITX_OK) goto out;
         hipLaunchKernelGGL(k_bo_scan, dim3(1), dim3(ITX_SCAN_WG), 0, bo->st, bo->d_msize, (uint64_t)n_mem, bo->d_moff);
-        BO_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_bo_pack, dim3(n_mem), dim3(256), 0, bo->st, bo->d_mem, bo->d_msize, bo->d_moff, s->d_packed);
-        BO_TRY(hipGetLastError());
-        BO_TRY(hipMemcpyAsync(s->h_total, bo->d_moff + n_mem, 8, hipMemcpyDeviceToHost, bo->st));
-        BO_TRY(hipEventRecord(s->e1, bo->st));
+        ITX_TRY(hipGetLastError());
+        ITX_TRY(hipMemcpyAsync(s->h_total, bo->d_moff + n_mem, 8, hipMemcpyDeviceToHost, bo->st));
+        ITX_TRY(hipEventRecord(s->e1, bo->st));
         s->n_mem = n_mem;
         s->busy = 1;
         bo->pending++;
@@ -672,7 +623,7 @@ static int bo_emit(itx_bamout *bo, ull total, int with_tail)
     if (with_tail) {
         bo->carry = 0;
     } else {
-        if (n_full && rest) BO_TRY(hipMemcpyAsync(bo->d_pay, bo->d_pay + n_full * BO_P, (size_t)rest, hipMemcpyDeviceToDevice, bo->st));   // (rest < BO_P: no overlap)
+        if (n_full && rest) ITX_TRY(hipMemcpyAsync(bo->d_pay, bo->d_pay + n_full * BO_P, (size_t)rest, hipMemcpyDeviceToDevice, bo->st));   // (rest < BO_P: no overlap)
         bo->carry = (size_t)rest;
     }
     bo->stream_base += with_tail ? total : n_full * BO_P;
@@ -700,29 +651,29 @@ int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, 
     float ms = 0;
     ull total = 0;
     const uint32_t nt = (uint32_t)((n + BO_TILE - 1) / BO_TILE);
-    BO_TRY(hipSetDevice(bo->device));
+    ITX_TRY(hipSetDevice(bo->device));
     if ((hipStream_t)stream != bo->st) {                                   // the chosen rows were left on another stream
-        BO_TRY(hipEventRecord(bo->ev[4], (hipStream_t)stream));
-        BO_TRY(hipStreamWaitEvent(bo->st, bo->ev[4], 0));
+        ITX_TRY(hipEventRecord(bo->ev[4], (hipStream_t)stream));
+        ITX_TRY(hipStreamWaitEvent(bo->st, bo->ev[4], 0));
     }
-    BO_TRY(hipEventRecord(bo->ev[0], bo->st));
-    BO_TRY(hipMemsetAsync(bo->d_tot, 0, BO_TOT_BYTES, bo->st));
+    ITX_TRY(hipEventRecord(bo->ev[0], bo->st));
+    ITX_TRY(hipMemsetAsync(bo->d_tot, 0, BO_TOT_BYTES, bo->st));
     if (bo->annotate)
         hipLaunchKernelGGL((k_bo_measure<true>), dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, d_hit_row, (uint32_t)n, bo->d_len, bo->d_tile_sum, bo->d_tot, bo->ann);
     else
         hipLaunchKernelGGL((k_bo_measure<false>), dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, d_hit_row, (uint32_t)n, bo->d_len, bo->d_tile_sum, bo->d_tot, bo->ann);
-    BO_TRY(hipGetLastError());
+    ITX_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, bo->st, bo->d_tile_sum, nt, bo->d_tile_base, bo->d_tot);
-    BO_TRY(hipGetLastError());
-    BO_TRY(hipEventRecord(bo->ev[1], bo->st));
-    BO_TRY(hipMemcpyAsync(bo->h_tot, bo->d_tot, BO_TOT_BYTES, hipMemcpyDeviceToHost, bo->st));
+    ITX_TRY(hipGetLastError());
+    ITX_TRY(hipEventRecord(bo->ev[1], bo->st));
+    ITX_TRY(hipMemcpyAsync(bo->h_tot, bo->d_tot, BO_TOT_BYTES, hipMemcpyDeviceToHost, bo->st));
     {
         const double t0 = itx_wall_now();
-        BO_TRY(hipStreamSynchronize(bo->st));
+        ITX_TRY(hipStreamSynchronize(bo->st));
         bo->stats.wait_ms += 1e3 * (itx_wall_now() - t0);
     }
     bo_read_gather_time(bo);                                               // (the batch before this one)
-    BO_TRY(hipEventElapsedTime(&ms, bo->ev[0], bo->ev[1]));
+    ITX_TRY(hipEventElapsedTime(&ms, bo->ev[0], bo->ev[1]));
     bo->stats.gather_ms += (double)ms;
     if (bo->h_tot[3]) {
         itx_set_error("itx_bamout: %llu records chose a row outside the %u rows given to itx_bamout_annotate_enable", bo->h_tot[3], bo->ann.n_rows);
@@ -739,7 +690,7 @@ int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, 
     if ((rc = bo_reserve(bo, total, bo->sort ? 0 : total / BO_P)) != ITX_OK) goto out;
     if (bo->sort && (rc = bs_reserve(bo, bo->h_tot[1])) != ITX_OK) goto out;
     if (bo->ix && !bo->sort && (rc = itx_bamidx_reserve(bo->ix, bo->st, bo->h_tot[1], total / BO_P)) != ITX_OK) goto out;
-    BO_TRY(hipEventRecord(bo->ev[2], bo->st));
+    ITX_TRY(hipEventRecord(bo->ev[2], bo->st));
     if (bo->h_tot[0]) {
         if (bo->annotate)
             hipLaunchKernelGGL((k_bo_gather<uint32_t, true>), dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, (uint32_t)n, bo->d_len, bo->d_tile_base, (ull)bo->carry,
@@ -747,15 +698,15 @@ int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, 
         else
             hipLaunchKernelGGL((k_bo_gather<uint32_t, false>), dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, (uint32_t)n, bo->d_len, bo->d_tile_base, (ull)bo->carry,
                                bo->d_pay, d_hit_row, bo->ann);
-        BO_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
     }
     if (bo->sort && bo->h_tot[1]) {
         hipLaunchKernelGGL(k_bs_entries, dim3(nt), dim3(BO_TILE), 0, bo->st, u, rec_off, (uint32_t)n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->n_sent, bo->d_sent,
                            bo->d_sflag);
-        BO_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
         bo->n_sent += bo->h_tot[1];
     }
-    BO_TRY(hipEventRecord(bo->ev[3], bo->st));
+    ITX_TRY(hipEventRecord(bo->ev[3], bo->st));
     bo->gather_timed = 1;
     if (bo->ix && !bo->sort &&
         (rc = itx_bamidx_entries(bo->ix, bo->st, u, rec_off, (uint32_t)n, bo->d_len, bo->d_tile_base, bo->stream_base + bo->carry, bo->h_tot[1])) != ITX_OK)
@@ -783,10 +734,10 @@ extern "C" int itx_bamout_wait_kernels(itx_bamout *bo)
         return ITX_E_ARG;
     }
     int rc = ITX_OK;
-    BO_TRY(hipSetDevice(bo->device));
+    ITX_TRY(hipSetDevice(bo->device));
     if (bo->gather_timed) {
         const double t0 = itx_wall_now();
-        BO_TRY(hipEventSynchronize(bo->ev[3]));
+        ITX_TRY(hipEventSynchronize(bo->ev[3]));
         bo->stats.wait_ms += 1e3 * (itx_wall_now() - t0);
         bo_read_gather_time(bo);
     }
@@ -858,19 +809,19 @@ extern "C" int itx_bamout_append_host(itx_bamout *bo, const void *bytes, size_t 
             at += 4 + (size_t)bs;
         }
     }
-    BO_TRY(hipSetDevice(bo->device));
+    ITX_TRY(hipSetDevice(bo->device));
     {
         const double t0 = itx_wall_now();
-        BO_TRY(hipStreamSynchronize(bo->st));                              // device batches before this one have their place
+        ITX_TRY(hipStreamSynchronize(bo->st));                              // device batches before this one have their place
         bo->stats.wait_ms += 1e3 * (itx_wall_now() - t0);
     }
     bo_read_gather_time(bo);
     if ((rc = bo_reserve(bo, total, bo->sort ? 0 : total / BO_P)) != ITX_OK) goto out;
     if (bo->sort && (rc = bs_reserve(bo, n_rec)) != ITX_OK) goto out;
     if (bo->ix && !bo->sort && (rc = itx_bamidx_reserve(bo->ix, bo->st, n_rec, total / BO_P)) != ITX_OK) goto out;
-    BO_TRY(hipMemcpyAsync(bo->d_pay + bo->carry, bytes, len, hipMemcpyHostToDevice, bo->st));
-    if (bo->sort) BO_TRY(hipMemcpyAsync(bo->d_sent + bo->n_sent, h_ent, sizeof(BoSortEnt) * n_rec, hipMemcpyHostToDevice, bo->st));
-    BO_TRY(hipStreamSynchronize(bo->st));                                  // the caller's bytes are its own again
+    ITX_TRY(hipMemcpyAsync(bo->d_pay + bo->carry, bytes, len, hipMemcpyHostToDevice, bo->st));
+    if (bo->sort) ITX_TRY(hipMemcpyAsync(bo->d_sent + bo->n_sent, h_ent, sizeof(BoSortEnt) * n_rec, hipMemcpyHostToDevice, bo->st));
+    ITX_TRY(hipStreamSynchronize(bo->st));                                  // the caller's bytes are its own again
     if (bo->ix && !bo->sort &&
         (rc = itx_bamidx_host_records(bo->ix, bo->st, bo->d_pay + bo->carry, h_off, (uint32_t)n_rec, bo->stream_base + bo->carry)) != ITX_OK)
         goto out;
@@ -906,8 +857,8 @@ extern "C" int itx_bamout_finish(itx_bamout *bo)
         return ITX_E_STATE;
     }
     int rc = ITX_OK;
-    BO_TRY(hipSetDevice(bo->device));
-    BO_TRY(hipStreamSynchronize(bo->st));
+    ITX_TRY(hipSetDevice(bo->device));
+    ITX_TRY(hipStreamSynchronize(bo->st));
     bo_read_gather_time(bo);
     if (bo->carry) {
         if ((rc = bo_reserve(bo, bo->carry, 1)) != ITX_OK) goto out;
@@ -930,10 +881,10 @@ extern "C" int itx_bamout_collect(itx_bamout *bo, itx_bamout_members *out)
     int rc = ITX_OK;
     float ms = 0;
     bo_slot *s = &bo->slot[bo->head];
-    BO_TRY(hipSetDevice(bo->device));
+    ITX_TRY(hipSetDevice(bo->device));
     {
         const double t0 = itx_wall_now();
-        BO_TRY(hipEventSynchronize(s->e1));
+        ITX_TRY(hipEventSynchronize(s->e1));
         bo->stats.wait_ms += 1e3 * (itx_wall_now() - t0);
     }
     if (hipEventElapsedTime(&ms, s->e0, s->e1) == hipSuccess) bo->stats.member_ms += (double)ms;    if (*s->h_total > s->cap) {
@@ -942,8 +893,8 @@ extern "C" int itx_bamout_collect(itx_bamout *bo, itx_bamout_members *out)
         goto out;
     }
     if (*s->h_total) {
-        BO_TRY(hipMemcpyAsync(s->h_pin, s->d_packed, (size_t)*s->h_total, hipMemcpyDeviceToHost, bo->cst));
-        BO_TRY(hipStreamSynchronize(bo->cst));
+        ITX_TRY(hipMemcpyAsync(s->h_pin, s->d_packed, (size_t)*s->h_total, hipMemcpyDeviceToHost, bo->cst));
+        ITX_TRY(hipStreamSynchronize(bo->cst));
     }
     out->bytes = s->h_pin;
     out->len = *s->h_total;
@@ -1055,14 +1006,14 @@ extern "C" int itx_bamout_annotate_enable(itx_bamout *bo, const itx_row *rows, s
             w[BO_ROW_WORDS * r + 4] = rows[r].fam;
         }
     }
-    BO_TRY(hipSetDevice(bo->device));
+    ITX_TRY(hipSetDevice(bo->device));
     if (hipMalloc((void **)&d, bytes + 16) != hipSuccess) {
         (void)hipGetLastError();
         itx_set_error("itx_bamout_annotate_enable: no device memory for a table of %zu bytes", bytes);
         rc = ITX_E_NOMEM;
         goto out;
     }
-    BO_TRY(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));                 // (synchronous: the caller's arrays and h are free on return)
+    ITX_TRY(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));                 // (synchronous: the caller's arrays and h are free on return)
     bo->ann.rep_off = (const ull *)(d + o_rep);
     bo->ann.cla_off = (const ull *)(d + o_cla);
     bo->ann.fam_off = (const ull *)(d + o_fam);
@@ -1104,17 +1055,17 @@ extern "C" int itx_bamout_sort_enable(itx_bamout *bo)
     int rc = ITX_OK;
     uint32_t *flag = nullptr, *h_flag = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
-    BO_TRY(hipSetDevice(bo->device));
+    ITX_TRY(hipSetDevice(bo->device));
     if (hipMalloc((void **)&flag, 16) != hipSuccess) {
         (void)hipGetLastError();
         itx_set_error("itx_bamout_sort_enable: no device memory (run without -s)");
         rc = ITX_E_NOMEM;
         goto out;
     }
-    BO_TRY(hipHostMalloc((void **)&h_flag, 16, hipHostMallocDefault));
-    BO_TRY(hipMemset(flag, 0, 16));
-    BO_TRY(hipEventCreate(&ev[0]));
-    BO_TRY(hipEventCreate(&ev[1]));
+    ITX_TRY(hipHostMalloc((void **)&h_flag, 16, hipHostMallocDefault));
+    ITX_TRY(hipMemset(flag, 0, 16));
+    ITX_TRY(hipEventCreate(&ev[0]));
+    ITX_TRY(hipEventCreate(&ev[1]));
     bo->d_sflag = flag;
     bo->h_sflag = h_flag;
     bo->sev[0] = ev[0];
@@ -1143,14 +1094,14 @@ static void bs_read_sort_time(itx_bamout *bo)
 static int bs_begin(itx_bamout *bo)
 {
     int rc = ITX_OK;
-    const uint32_t N = (uint32_t)bo->n_sent, nwg = (N + SORT_CHUNK - 1) / SORT_CHUNK;
+    const uint32_t N = (uint32_t)bo->n_sent;
     uint2 *k0 = nullptr, *k1 = nullptr, *sorted = nullptr;
-    uint32_t *hist = nullptr, n_ref = 0, passes = 0;
+    uint32_t *hist = nullptr, n_ref = 0, high = 0;
     ull *soff = nullptr, bad = 0;
     uint8_t *npay = nullptr;
     const size_t pay_cap = 4 * (size_t)BO_P;
-    BO_TRY(hipMemcpyAsync(bo->h_sflag, bo->d_sflag, 8, hipMemcpyDeviceToHost, bo->st));
-    BO_TRY(hipStreamSynchronize(bo->st));
+    ITX_TRY(hipMemcpyAsync(bo->h_sflag, bo->d_sflag, 8, hipMemcpyDeviceToHost, bo->st));
+    ITX_TRY(hipStreamSynchronize(bo->st));
     bad = bo->host_bad + bo->h_sflag[0];
     if (bad) {
         itx_set_error("itx_bamout_sort_next: %llu counted records name no reference or no position (tid or pos below 0): they cannot be sorted by coordinate", bad);
@@ -1159,7 +1110,7 @@ static int bs_begin(itx_bamout *bo)
     }
     if (N) {
         if (hipMalloc((void **)&k0, 8 * (size_t)N) != hipSuccess || hipMalloc((void **)&k1, 8 * (size_t)N) != hipSuccess ||
-            hipMalloc((void **)&hist, 4 * 256 * (size_t)nwg) != hipSuccess || hipMalloc((void **)&soff, 8 * (bo->cap + 64)) != hipSuccess ||
+            hipMalloc((void **)&hist, itx_sort_hist_bytes(N)) != hipSuccess || hipMalloc((void **)&soff, 8 * (bo->cap + 64)) != hipSuccess ||
             hipMalloc((void **)&npay, pay_cap + 16) != hipSuccess) {
             (void)hipGetLastError();
             itx_set_error("itx_bamout_sort_next: no device memory to sort %u records beside a held stream of %zu bytes (run without -s)", N, bo->carry);
@@ -1171,27 +1122,18 @@ static int bs_begin(itx_bamout *bo)
             const uint32_t seen = (bo->h_sflag[1] > bo->host_maxtid ? bo->h_sflag[1] : bo->host_maxtid) + 1u;
             if (seen > n_ref) n_ref = seen;                                // (a tid beyond the header's list still finds its place)
         }
-        passes = 4u + itx_bamsort_high_passes(n_ref);
-        BO_TRY(hipEventRecord(bo->sev[0], bo->st));
+        high = itx_bamsort_high_passes(n_ref);
+        ITX_TRY(hipEventRecord(bo->sev[0], bo->st));
         hipLaunchKernelGGL(k_bs_keys, dim3((N + 255u) / 256u), dim3(256), 0, bo->st, bo->d_sent, N, k0);
-        BO_TRY(hipGetLastError());
-        sorted = k0;
-        for (uint32_t p = 0; p < passes; p++) {
-            uint2 *to = sorted == k0 ? k1 : k0;
-            const uint32_t shift = 8u * (p < 4u ? p : p - 4u);
-            if (p == 4u) {
-                hipLaunchKernelGGL(k_bs_rekey, dim3((N + 255u) / 256u), dim3(256), 0, bo->st, bo->d_sent, N, sorted);
-                BO_TRY(hipGetLastError());
-            }
-            hipLaunchKernelGGL(k_sort_hist, dim3(nwg), dim3(256), 0, bo->st, sorted, N, shift, hist, nwg);
-            BO_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(ITX_SCAN_WG), 0, bo->st, hist, 256u * nwg);
-            BO_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_sort_scatter, dim3(nwg), dim3(256), 0, bo->st, sorted, to, N, shift, hist, nwg);
-            BO_TRY(hipGetLastError());
-            sorted = to;
+        ITX_TRY(hipGetLastError());
+        // four passes by the low key; then the keys become the tids, and the shift starts again at 0
+        if ((rc = itx_sort_run(bo->st, k0, k1, N, 0u, 4u, hist, &sorted)) != ITX_OK) goto out;
+        if (high) {
+            hipLaunchKernelGGL(k_bs_rekey, dim3((N + 255u) / 256u), dim3(256), 0, bo->st, bo->d_sent, N, sorted);
+            ITX_TRY(hipGetLastError());
+            if ((rc = itx_sort_run(bo->st, sorted, sorted == k0 ? k1 : k0, N, 0u, high, hist, &sorted)) != ITX_OK) goto out;
         }
-        BO_TRY(hipEventRecord(bo->sev[1], bo->st));
+        ITX_TRY(hipEventRecord(bo->sev[1], bo->st));
         bo->sort_timed = 1;
     }
     // the held stream is what d_pay was; the payload stream starts anew
@@ -1250,8 +1192,8 @@ extern "C" int itx_bamout_sort_next(itx_bamout *bo, int *more)
     const ull N = bo->n_sent;
     uint32_t n = 0, nt = 0;
     int last = 0;
-    BO_TRY(hipSetDevice(bo->device));
-    BO_TRY(hipStreamSynchronize(bo->st));
+    ITX_TRY(hipSetDevice(bo->device));
+    ITX_TRY(hipStreamSynchronize(bo->st));
     bo_read_gather_time(bo);
     if (bo->sort == 1 && (rc = bs_begin(bo)) != ITX_OK) goto out;
     if (!N) {                                                              // nothing was counted: no member
@@ -1262,32 +1204,32 @@ extern "C" int itx_bamout_sort_next(itx_bamout *bo, int *more)
     n = (uint32_t)(N - bo->sort_done < bo->cap ? N - bo->sort_done : bo->cap);
     nt = (n + BO_TILE - 1) / BO_TILE;
     last = bo->sort_done + n == N;
-    BO_TRY(hipEventRecord(bo->ev[0], bo->st));
-    BO_TRY(hipMemsetAsync(bo->d_tot, 0, 32, bo->st));
+    ITX_TRY(hipEventRecord(bo->ev[0], bo->st));
+    ITX_TRY(hipMemsetAsync(bo->d_tot, 0, 32, bo->st));
     hipLaunchKernelGGL(k_bs_lengths, dim3(nt), dim3(BO_TILE), 0, bo->st, bo->sorted + bo->sort_done, bo->d_sent, n, bo->d_len, bo->d_soff, bo->d_tile_sum);
-    BO_TRY(hipGetLastError());
+    ITX_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, bo->st, bo->d_tile_sum, nt, bo->d_tile_base, bo->d_tot);
-    BO_TRY(hipGetLastError());
-    BO_TRY(hipEventRecord(bo->ev[1], bo->st));
-    BO_TRY(hipMemcpyAsync(bo->h_tot, bo->d_tot, 32, hipMemcpyDeviceToHost, bo->st));
+    ITX_TRY(hipGetLastError());
+    ITX_TRY(hipEventRecord(bo->ev[1], bo->st));
+    ITX_TRY(hipMemcpyAsync(bo->h_tot, bo->d_tot, 32, hipMemcpyDeviceToHost, bo->st));
     {
         const double t0 = itx_wall_now();
-        BO_TRY(hipStreamSynchronize(bo->st));                              // (the members of the round before are through as well)
+        ITX_TRY(hipStreamSynchronize(bo->st));                              // (the members of the round before are through as well)
         bo->stats.wait_ms += 1e3 * (itx_wall_now() - t0);
     }
     bs_read_sort_time(bo);
-    BO_TRY(hipEventElapsedTime(&ms, bo->ev[0], bo->ev[1]));
+    ITX_TRY(hipEventElapsedTime(&ms, bo->ev[0], bo->ev[1]));
     bo->replay_ms += (double)ms;
     total = (ull)bo->carry + bo->h_tot[0];
     n_mem = total / BO_P + (last && total % BO_P ? 1 : 0);
     if ((rc = bo_reserve(bo, total, n_mem)) != ITX_OK) goto out;
     if (bo->ix && (rc = itx_bamidx_reserve(bo->ix, bo->st, n, n_mem)) != ITX_OK) goto out;
-    BO_TRY(hipEventRecord(bo->ev[2], bo->st));
+    ITX_TRY(hipEventRecord(bo->ev[2], bo->st));
     // (under -a the held records are annotated already: the replay copies them byte for byte)
     hipLaunchKernelGGL((k_bo_gather<ull, false>), dim3(nt), dim3(BO_TILE), 0, bo->st, bo->d_held, bo->d_soff, n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->d_pay,
                        (const int32_t *)nullptr, bo->ann);
-    BO_TRY(hipGetLastError());
-    BO_TRY(hipEventRecord(bo->ev[3], bo->st));
+    ITX_TRY(hipGetLastError());
+    ITX_TRY(hipEventRecord(bo->ev[3], bo->st));
     bo->gather_timed = 1;
     if (bo->ix && (rc = itx_bamidx_entries64(bo->ix, bo->st, bo->d_held, bo->d_soff, n, bo->d_len, bo->d_tile_base, bo->stream_base + bo->carry, n)) != ITX_OK) goto out;
     bo->sort_done += n;
@@ -1296,7 +1238,7 @@ extern "C" int itx_bamout_sort_next(itx_bamout *bo, int *more)
     if (last) {
         // the held stream goes as soon as the last gather (and the index's entry kernel behind it) has read it
         if (bo->ix) itx_bamidx_batch_time(bo->ix);
-        BO_TRY(hipEventSynchronize(bo->ev[3]));
+        ITX_TRY(hipEventSynchronize(bo->ev[3]));
         bo_read_gather_time(bo);
         bs_release(bo);
         bo->finished = 1;

@@ -112,6 +112,17 @@ int itx_inflate_enqueue(hipStream_t st, const void *d_comp, const itx_bgzf_block
             return ITX_E_NO_DEVICE;                                                           \
         }                                                                                     \
     } while (0)
+// The same for a function that leaves through one cleanup path: `int rc` and the label `out:` are the function's own.
+static inline int itx_hip_rc(hipError_t e, const char *what, const char *file, int line)
+{
+    if (e == hipSuccess) return ITX_OK;
+    itx_set_error("%s failed: %s (%s:%d)", what, hipGetErrorString(e), file, line);
+    return ITX_E_NO_DEVICE;
+}
+#define ITX_TRY(call)                                                                         \
+    do {                                                                                      \
+        if ((rc = itx_hip_rc((call), #call, __FILE__, __LINE__)) != ITX_OK) goto out;         \
+    } while (0)
 // the host's monotonic clock in seconds (time spent waiting for the device, allocation times)
 static inline double itx_wall_now(void)
 {

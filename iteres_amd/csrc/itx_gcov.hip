@@ -328,17 +328,6 @@ struct itx_gcov {
     itx_gcov_stats stats;
 };
 
-static int gc_hip(hipError_t e, const char *what, int line)
-{
-    if (e == hipSuccess) return ITX_OK;
-    itx_set_error("%s failed: %s (%s:%d)", what, hipGetErrorString(e), __FILE__, line);
-    return ITX_E_NO_DEVICE;
-}
-#define GC_TRY(call)                                       \
-    do {                                                   \
-        if ((rc = gc_hip((call), #call, __LINE__)) != 0) goto out; \
-    } while (0)
-
 static void gc_free_arrays(itx_gcov *g)
 {
     for (auto &a : g->d.arr) {
@@ -423,7 +412,7 @@ extern "C" int itx_gcov_create(int device, const int64_t *chrom_size, int n_chro
     }
     g->slots = total;
     const size_t bytes = (size_t)(4ull * (total + 4ull));
-    GC_TRY(hipSetDevice(device));
+    ITX_TRY(hipSetDevice(device));
     {
         // the two arrays first: when the device cannot hold them nothing else has been touched
         const double t0 = itx_wall_now();
@@ -439,27 +428,27 @@ extern "C" int itx_gcov_create(int device, const int64_t *chrom_size, int n_chro
     }
     g->stats.slots = total;
     g->stats.device_bytes = 2ull * bytes;
-    GC_TRY(hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking));
-    for (auto &e : g->ev_add) GC_TRY(hipEventCreate(&e));
+    ITX_TRY(hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking));
+    for (auto &e : g->ev_add) ITX_TRY(hipEventCreate(&e));
     for (auto &s : g->ev_rnd)
-        for (auto &e : s) GC_TRY(hipEventCreate(&e));
-    GC_TRY(hipEventRecord(g->ev_rnd[0][0], g->st));
+        for (auto &e : s) ITX_TRY(hipEventCreate(&e));
+    ITX_TRY(hipEventRecord(g->ev_rnd[0][0], g->st));
     for (auto &a : g->d.arr)
         for (size_t at = 0; at < bytes; at += GC_MEMSET_CHUNK)
-            GC_TRY(hipMemsetAsync((uint8_t *)a + at, 0, bytes - at < GC_MEMSET_CHUNK ? bytes - at : GC_MEMSET_CHUNK, g->st));
-    GC_TRY(hipEventRecord(g->ev_rnd[0][1], g->st));
-    GC_TRY(hipMalloc((void **)&g->d_off, 8 * off.size()));
-    GC_TRY(hipMalloc((void **)&g->d_size, 4 * size.size()));
-    GC_TRY(hipMalloc((void **)&g->d_cnt, 64));
-    GC_TRY(hipMalloc((void **)&g->d_hits, 4 * (batch_capacity + 64)));
-    GC_TRY(hipHostMalloc((void **)&g->h_tot, 64, hipHostMallocDefault));
-    GC_TRY(hipMemcpyAsync(g->d_off, off.data(), 8 * off.size(), hipMemcpyHostToDevice, g->st));
-    GC_TRY(hipMemcpyAsync(g->d_size, size.data(), 4 * size.size(), hipMemcpyHostToDevice, g->st));
-    GC_TRY(hipMemsetAsync(g->d_cnt, 0, 64, g->st));
-    GC_TRY(hipStreamSynchronize(g->st));                                   // off, size are this function's
+            ITX_TRY(hipMemsetAsync((uint8_t *)a + at, 0, bytes - at < GC_MEMSET_CHUNK ? bytes - at : GC_MEMSET_CHUNK, g->st));
+    ITX_TRY(hipEventRecord(g->ev_rnd[0][1], g->st));
+    ITX_TRY(hipMalloc((void **)&g->d_off, 8 * off.size()));
+    ITX_TRY(hipMalloc((void **)&g->d_size, 4 * size.size()));
+    ITX_TRY(hipMalloc((void **)&g->d_cnt, 64));
+    ITX_TRY(hipMalloc((void **)&g->d_hits, 4 * (batch_capacity + 64)));
+    ITX_TRY(hipHostMalloc((void **)&g->h_tot, 64, hipHostMallocDefault));
+    ITX_TRY(hipMemcpyAsync(g->d_off, off.data(), 8 * off.size(), hipMemcpyHostToDevice, g->st));
+    ITX_TRY(hipMemcpyAsync(g->d_size, size.data(), 4 * size.size(), hipMemcpyHostToDevice, g->st));
+    ITX_TRY(hipMemsetAsync(g->d_cnt, 0, 64, g->st));
+    ITX_TRY(hipStreamSynchronize(g->st));                                   // off, size are this function's
     {
         float ms = 0;
-        GC_TRY(hipEventElapsedTime(&ms, g->ev_rnd[0][0], g->ev_rnd[0][1]));
+        ITX_TRY(hipEventElapsedTime(&ms, g->ev_rnd[0][0], g->ev_rnd[0][1]));
         g->stats.zero_ms = (double)ms;
     }
     g->d.off = g->d_off;
@@ -483,8 +472,8 @@ static int gc_settle(itx_gcov *g)
     int rc = ITX_OK;
     if (g->add_timed) {
         float ms = 0;
-        GC_TRY(hipEventSynchronize(g->ev_add[1]));
-        GC_TRY(hipEventElapsedTime(&ms, g->ev_add[0], g->ev_add[1]));
+        ITX_TRY(hipEventSynchronize(g->ev_add[1]));
+        ITX_TRY(hipEventElapsedTime(&ms, g->ev_add[0], g->ev_add[1]));
         g->stats.add_ms += (double)ms;
         g->add_timed = 0;
     }
@@ -509,10 +498,10 @@ extern "C" int itx_gcov_set_tidmap(itx_gcov *g, const int32_t *tid2chrom, int n_
         const int32_t c = tid2chrom[k];
         v[(size_t)k] = make_int2(c, (c >= 0 && (size_t)c < g->chrom_size.size()) ? (int32_t)g->chrom_size[(size_t)c] : 0);
     }
-    GC_TRY(hipSetDevice(g->device));
+    ITX_TRY(hipSetDevice(g->device));
     if ((rc = gc_settle(g)) != ITX_OK) goto out;                           // no kernel reads the old map any more
-    GC_TRY(hipMalloc(&nt, sizeof(int2) * v.size()));
-    GC_TRY(hipMemcpy(nt, v.data(), sizeof(int2) * v.size(), hipMemcpyHostToDevice));
+    ITX_TRY(hipMalloc(&nt, sizeof(int2) * v.size()));
+    ITX_TRY(hipMemcpy(nt, v.data(), sizeof(int2) * v.size(), hipMemcpyHostToDevice));
     {
         void *old = g->d_tid;
         g->d_tid = nt;
@@ -539,12 +528,12 @@ extern "C" int itx_gcov_run(itx_gcov *g, const itx_batch *b, const int32_t *d_hi
     int rc = ITX_OK;
     const GcRecs R = {b->tid, b->pos, b->tmpend, b->mapq, b->flag5, b->mpos, b->isize};
     hipStream_t st = (hipStream_t)stream;
-    GC_TRY(hipSetDevice(g->device));
+    ITX_TRY(hipSetDevice(g->device));
     if ((rc = gc_settle(g)) != ITX_OK) goto out;
-    GC_TRY(hipEventRecord(g->ev_add[0], st));
+    ITX_TRY(hipEventRecord(g->ev_add[0], st));
     hipLaunchKernelGGL(k_gc_add, dim3((uint32_t)((n + GC_WG - 1) / GC_WG)), dim3(GC_WG), 0, st, g->d, R, d_hit_row, (uint32_t)n);
-    GC_TRY(hipGetLastError());
-    GC_TRY(hipEventRecord(g->ev_add[1], st));
+    ITX_TRY(hipGetLastError());
+    ITX_TRY(hipEventRecord(g->ev_add[1], st));
     g->add_timed = 1;
     g->last = st;
     g->stats.batches++;
@@ -559,7 +548,7 @@ extern "C" int itx_gcov_wait_kernels(itx_gcov *g)
         return ITX_E_ARG;
     }
     int rc = ITX_OK;
-    GC_TRY(hipSetDevice(g->device));
+    ITX_TRY(hipSetDevice(g->device));
     {
         const double t0 = itx_wall_now();
         rc = gc_settle(g);
@@ -581,24 +570,24 @@ extern "C" int itx_gcov_add_host(itx_gcov *g, const int32_t *chrom, const uint32
     }
     if (!n) return ITX_OK;
     int rc = ITX_OK;
-    GC_TRY(hipSetDevice(g->device));
+    ITX_TRY(hipSetDevice(g->device));
     if (!g->d_hc) {
-        GC_TRY(hipMalloc((void **)&g->d_hc, 4 * GC_HOST_CHUNK));
-        GC_TRY(hipMalloc((void **)&g->d_hs, 4 * GC_HOST_CHUNK));
-        GC_TRY(hipMalloc((void **)&g->d_he, 4 * GC_HOST_CHUNK));
-        GC_TRY(hipMalloc((void **)&g->d_hu, GC_HOST_CHUNK));
+        ITX_TRY(hipMalloc((void **)&g->d_hc, 4 * GC_HOST_CHUNK));
+        ITX_TRY(hipMalloc((void **)&g->d_hs, 4 * GC_HOST_CHUNK));
+        ITX_TRY(hipMalloc((void **)&g->d_he, 4 * GC_HOST_CHUNK));
+        ITX_TRY(hipMalloc((void **)&g->d_hu, GC_HOST_CHUNK));
     }
     if ((rc = gc_settle(g)) != ITX_OK) goto out;
     for (size_t at = 0; at < n; at += GC_HOST_CHUNK) {
         const size_t m = n - at < GC_HOST_CHUNK ? n - at : GC_HOST_CHUNK;
-        GC_TRY(hipMemcpyAsync(g->d_hc, chrom + at, 4 * m, hipMemcpyHostToDevice, g->st));
-        GC_TRY(hipMemcpyAsync(g->d_hs, start + at, 4 * m, hipMemcpyHostToDevice, g->st));
-        GC_TRY(hipMemcpyAsync(g->d_he, end + at, 4 * m, hipMemcpyHostToDevice, g->st));
-        GC_TRY(hipMemcpyAsync(g->d_hu, uniq + at, m, hipMemcpyHostToDevice, g->st));
-        GC_TRY(hipEventRecord(g->ev_add[0], g->st));
+        ITX_TRY(hipMemcpyAsync(g->d_hc, chrom + at, 4 * m, hipMemcpyHostToDevice, g->st));
+        ITX_TRY(hipMemcpyAsync(g->d_hs, start + at, 4 * m, hipMemcpyHostToDevice, g->st));
+        ITX_TRY(hipMemcpyAsync(g->d_he, end + at, 4 * m, hipMemcpyHostToDevice, g->st));
+        ITX_TRY(hipMemcpyAsync(g->d_hu, uniq + at, m, hipMemcpyHostToDevice, g->st));
+        ITX_TRY(hipEventRecord(g->ev_add[0], g->st));
         hipLaunchKernelGGL(k_gc_add_iv, dim3((uint32_t)((m + GC_WG - 1) / GC_WG)), dim3(GC_WG), 0, g->st, g->d, g->d_hc, g->d_hs, g->d_he, g->d_hu, (uint32_t)m);
-        GC_TRY(hipGetLastError());
-        GC_TRY(hipEventRecord(g->ev_add[1], g->st));
+        ITX_TRY(hipGetLastError());
+        ITX_TRY(hipEventRecord(g->ev_add[1], g->st));
         g->add_timed = 1;
         g->last = g->st;
         if ((rc = gc_settle(g)) != ITX_OK) goto out;                       // the chunk's buffers are free, the caller's arrays its own again
@@ -615,13 +604,13 @@ static int gc_points(itx_gcov *g, int w, uint32_t n_tiles, ull *d_tsum, ull *d_t
     GcFile &F = g->file[w];
     if (!n_tiles) return ITX_OK;
     hipLaunchKernelGGL(k_gc_measure, dim3(n_tiles), dim3(GC_WG), 0, g->st, g->d.arr[w], g->V, d_tsum);
-    GC_TRY(hipGetLastError());
+    ITX_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, g->st, d_tsum, n_tiles, d_tbase, g->d_cnt + 3);
-    GC_TRY(hipGetLastError());
-    GC_TRY(hipMemcpyAsync(g->h_tot, g->d_cnt + 3, 8, hipMemcpyDeviceToHost, g->st));
+    ITX_TRY(hipGetLastError());
+    ITX_TRY(hipMemcpyAsync(g->h_tot, g->d_cnt + 3, 8, hipMemcpyDeviceToHost, g->st));
     {
         const double t0 = itx_wall_now();
-        GC_TRY(hipStreamSynchronize(g->st));
+        ITX_TRY(hipStreamSynchronize(g->st));
         g->stats.wait_s += itx_wall_now() - t0;
     }
     F.n_pts = g->h_tot[0];
@@ -633,7 +622,7 @@ static int gc_points(itx_gcov *g, int w, uint32_t n_tiles, ull *d_tsum, ull *d_t
         return ITX_E_NOMEM;
     }
     hipLaunchKernelGGL(k_gc_points, dim3(n_tiles), dim3(GC_WG), 0, g->st, g->d.arr[w], g->V, d_tsum, d_tbase, F.d_pts);
-    GC_TRY(hipGetLastError());
+    ITX_TRY(hipGetLastError());
 out:
     return rc;
 }
@@ -699,15 +688,15 @@ extern "C" int itx_gcov_finish(itx_gcov *g, const uint32_t *order, int n_order, 
     ull *d_tsum = nullptr, *d_tbase = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     float ms = 0;
-    GC_TRY(hipSetDevice(g->device));
+    ITX_TRY(hipSetDevice(g->device));
     if ((rc = gc_settle(g)) != ITX_OK) goto out;
-    GC_TRY(hipStreamSynchronize(g->st));
-    GC_TRY(hipMemcpy(g->h_tot, g->d_cnt, 24, hipMemcpyDeviceToHost));
+    ITX_TRY(hipStreamSynchronize(g->st));
+    ITX_TRY(hipMemcpy(g->h_tot, g->d_cnt, 24, hipMemcpyDeviceToHost));
     g->stats.records = g->h_tot[0];
     g->stats.out_of_range = g->h_tot[1];
     g->stats.records_uniq = g->h_tot[2];
-    GC_TRY(hipEventCreate(&e0));
-    GC_TRY(hipEventCreate(&e1));
+    ITX_TRY(hipEventCreate(&e0));
+    ITX_TRY(hipEventCreate(&e1));
     // everything the rounds will need, before the first point is made: a refusal leaves the arrays as they were
     if (hipMalloc((void **)&d_tsum, 16 * ((size_t)n_tiles + 1)) != hipSuccess || hipMalloc((void **)&d_tbase, 16 * ((size_t)n_tiles + 1)) != hipSuccess ||
         hipMalloc(&g->d_vfirst, 4 * vfirst.size()) != hipSuccess || hipMalloc(&g->d_voff, 8 * (voff.size() + 1)) != hipSuccess ||
@@ -722,14 +711,14 @@ extern "C" int itx_gcov_finish(itx_gcov *g, const uint32_t *order, int n_order, 
         rc = ITX_E_NOMEM;
         goto out;
     }
-    GC_TRY(hipMemcpyAsync(g->d_vfirst, vfirst.data(), 4 * vfirst.size(), hipMemcpyHostToDevice, g->st));
+    ITX_TRY(hipMemcpyAsync(g->d_vfirst, vfirst.data(), 4 * vfirst.size(), hipMemcpyHostToDevice, g->st));
     if (nv) {
-        GC_TRY(hipMemcpyAsync(g->d_voff, voff.data(), 8 * voff.size(), hipMemcpyHostToDevice, g->st));
-        GC_TRY(hipMemcpyAsync(g->d_vsize, vsize.data(), 4 * vsize.size(), hipMemcpyHostToDevice, g->st));
-        GC_TRY(hipMemcpyAsync(g->d_vname, vname.data(), 8 * vname.size(), hipMemcpyHostToDevice, g->st));
+        ITX_TRY(hipMemcpyAsync(g->d_voff, voff.data(), 8 * voff.size(), hipMemcpyHostToDevice, g->st));
+        ITX_TRY(hipMemcpyAsync(g->d_vsize, vsize.data(), 4 * vsize.size(), hipMemcpyHostToDevice, g->st));
+        ITX_TRY(hipMemcpyAsync(g->d_vname, vname.data(), 8 * vname.size(), hipMemcpyHostToDevice, g->st));
     }
-    GC_TRY(hipMemcpyAsync(g->d_pool, pool.data(), pool.size(), hipMemcpyHostToDevice, g->st));
-    GC_TRY(hipStreamSynchronize(g->st));                                   // the vectors are this function's
+    ITX_TRY(hipMemcpyAsync(g->d_pool, pool.data(), pool.size(), hipMemcpyHostToDevice, g->st));
+    ITX_TRY(hipStreamSynchronize(g->st));                                   // the vectors are this function's
     g->V.first = (const uint32_t *)g->d_vfirst;
     g->V.off = (const ull *)g->d_voff;
     g->V.size = (const uint32_t *)g->d_vsize;
@@ -737,12 +726,12 @@ extern "C" int itx_gcov_finish(itx_gcov *g, const uint32_t *order, int n_order, 
     g->max_name = max_name;
     g->per_round = per_round;
     g->text_cap = text_cap;
-    GC_TRY(hipEventRecord(e0, g->st));
+    ITX_TRY(hipEventRecord(e0, g->st));
     for (int w = 0; w < 2; w++)
         if ((rc = gc_points(g, w, n_tiles, d_tsum, d_tbase)) != ITX_OK) goto out;
-    GC_TRY(hipEventRecord(e1, g->st));
-    GC_TRY(hipStreamSynchronize(g->st));
-    GC_TRY(hipEventElapsedTime(&ms, e0, e1));
+    ITX_TRY(hipEventRecord(e1, g->st));
+    ITX_TRY(hipStreamSynchronize(g->st));
+    ITX_TRY(hipEventElapsedTime(&ms, e0, e1));
     g->stats.points_ms = (double)ms;
     for (int w = 0; w < 2; w++) g->stats.points[w] = g->file[w].n_pts;
     gc_free_arrays(g);                                                     // 4 bytes a base, twice: given back before the text is made
@@ -782,15 +771,15 @@ static int gc_start_round(itx_gcov *g, int w, int s)
     const ull left = F.n_pts - F.cursor;
     const uint32_t n = (uint32_t)(left < g->per_round ? left : g->per_round), nt = (n + GC_TXT_TILE - 1) / GC_TXT_TILE;
     const GcText T = {F.d_pts, F.n_pts, (const uint2 *)g->d_vname, (const uint8_t *)g->d_pool};
-    GC_TRY(hipEventRecord(g->ev_rnd[s][0], g->st));
+    ITX_TRY(hipEventRecord(g->ev_rnd[s][0], g->st));
     hipLaunchKernelGGL(k_gc_text_measure, dim3(nt), dim3(GC_TXT_TILE), 0, g->st, T, F.cursor, n, g->d_tsum);
-    GC_TRY(hipGetLastError());
+    ITX_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, g->st, g->d_tsum, nt, g->d_tbase, g->d_ttot);
-    GC_TRY(hipGetLastError());
-    GC_TRY(hipMemcpyAsync(g->h_tot, g->d_ttot, 16, hipMemcpyDeviceToHost, g->st));
+    ITX_TRY(hipGetLastError());
+    ITX_TRY(hipMemcpyAsync(g->h_tot, g->d_ttot, 16, hipMemcpyDeviceToHost, g->st));
     {
         const double t0 = itx_wall_now();
-        GC_TRY(hipStreamSynchronize(g->st));
+        ITX_TRY(hipStreamSynchronize(g->st));
         g->stats.wait_s += itx_wall_now() - t0;
     }
     F.len[s] = g->h_tot[0];
@@ -804,11 +793,11 @@ static int gc_start_round(itx_gcov *g, int w, int s)
     g->stats.rounds[w]++;
     if (F.len[s]) {
         hipLaunchKernelGGL(k_gc_text_write, dim3(nt), dim3(GC_TXT_TILE), 0, g->st, T, F.cursor, n, g->d_tbase, g->d_text[s]);
-        GC_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
     }
-    GC_TRY(hipEventRecord(g->ev_rnd[s][1], g->st));
-    if (F.len[s]) GC_TRY(hipMemcpyAsync(g->h_text[s], g->d_text[s], (size_t)F.len[s], hipMemcpyDeviceToHost, g->st));
-    GC_TRY(hipEventRecord(g->ev_rnd[s][2], g->st));
+    ITX_TRY(hipEventRecord(g->ev_rnd[s][1], g->st));
+    if (F.len[s]) ITX_TRY(hipMemcpyAsync(g->h_text[s], g->d_text[s], (size_t)F.len[s], hipMemcpyDeviceToHost, g->st));
+    ITX_TRY(hipEventRecord(g->ev_rnd[s][2], g->st));
     F.cursor += n;
     F.slot = s;
     F.flying = 1;
@@ -832,7 +821,7 @@ extern "C" int itx_gcov_next(itx_gcov *g, int which, itx_gcov_text *out)
     out->bytes = nullptr;
     out->len = 0;
     out->more = 0;
-    GC_TRY(hipSetDevice(g->device));
+    ITX_TRY(hipSetDevice(g->device));
     g->cur_file = which;
     if (!F.started) {
         F.started = 1;
@@ -845,9 +834,9 @@ extern "C" int itx_gcov_next(itx_gcov *g, int which, itx_gcov_text *out)
     {
         const int s = F.slot;
         const double t0 = itx_wall_now();
-        GC_TRY(hipEventSynchronize(g->ev_rnd[s][2]));
+        ITX_TRY(hipEventSynchronize(g->ev_rnd[s][2]));
         g->stats.wait_s += itx_wall_now() - t0;
-        GC_TRY(hipEventElapsedTime(&ms, g->ev_rnd[s][0], g->ev_rnd[s][1]));
+        ITX_TRY(hipEventElapsedTime(&ms, g->ev_rnd[s][0], g->ev_rnd[s][1]));
         g->stats.text_ms += (double)ms;
         F.flying = 0;
         out->bytes = F.len[s] ? (const char *)g->h_text[s] : nullptr;
@@ -872,10 +861,10 @@ extern "C" int itx_gcov_get_stats(itx_gcov *g, itx_gcov_stats *out)
     }
     int rc = ITX_OK;
     if (!g->finished) {                                                    // (finish reads the counters for good)
-        GC_TRY(hipSetDevice(g->device));
+        ITX_TRY(hipSetDevice(g->device));
         if ((rc = gc_settle(g)) != ITX_OK) goto out;
-        GC_TRY(hipStreamSynchronize(g->st));
-        GC_TRY(hipMemcpy(g->h_tot, g->d_cnt, 24, hipMemcpyDeviceToHost));
+        ITX_TRY(hipStreamSynchronize(g->st));
+        ITX_TRY(hipMemcpy(g->h_tot, g->d_cnt, 24, hipMemcpyDeviceToHost));
         g->stats.records = g->h_tot[0];
         g->stats.out_of_range = g->h_tot[1];
         g->stats.records_uniq = g->h_tot[2];

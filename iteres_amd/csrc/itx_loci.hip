@@ -14,8 +14,10 @@
 //   k_loci_write    one workgroup per tile: the tile's lines are ONE contiguous range of the text, staged in LDS a window at a
 //                   time and stored with 16-byte vectors (itx_textpack.h says why and how); the bytes come from itx_loci_write
 //   hard > 0: nothing is handed out, the caller writes the file on the host (the bed route's contract).
+// The passes are enqueued by itx_sort_run (itx_radixsort.h); the text leaves through itx_copy_out (itx_devbuf.h).
 //
 // Integer and byte work, two double divisions per line; no kernel uses scratch (DESIGN.md has the figures).
+#include "itx_devbuf.h"
 #include "itx_textpack.h"
 #include "itx_radixsort.h"
 #include "itx_lociline.h"
@@ -31,7 +33,6 @@ typedef unsigned long long ull;
 #define LO_LDS 32768u                // bytes staged at a time: a tile of ordinary lines (256 x 60-90 bytes) in one window
 #define LO_MAX_CHROM (1u << 19)      // rank << 13 stays inside 32 bits
 #define LO_MAX_ROWS 0xfffffffeull
-#define LO_COPY_CHUNK ((size_t)8 << 20)
 #define LO_CANARY 0xA5
 
 // the table as the kernels read it: a row is two vectors {start, end, rep, cla} {fam, chromosome, 0, 0}; names: 0 chromosome, 1 repName,
@@ -166,16 +167,6 @@ struct itx_loci {
     int sort_read;
 };
 
-static int lo_hip(hipError_t e, const char *what, int line)
-{
-    if (e == hipSuccess) return ITX_OK;
-    itx_set_error("%s failed: %s (%s:%d)", what, hipGetErrorString(e), __FILE__, line);
-    return ITX_E_NO_DEVICE;
-}
-#define LO_TRY(call)                                       \
-    do {                                                   \
-        if ((rc = lo_hip((call), #call, __LINE__)) != 0) goto out; \
-    } while (0)
 // a device allocation that may not fit: ITX_E_NOMEM, the caller keeps the host route
 #define LO_ALLOC(ptr, bytes)                                                                           \
     do {                                                                                               \
@@ -282,11 +273,11 @@ extern "C" int itx_loci_create(int device, int kind, const itx_row *rows, const 
     lo->kind = kind;
     lo->n = n_rows;
     lo->n_chrom = n_chrom;
-    const uint32_t n = (uint32_t)n_rows, nt = (uint32_t)((n_rows + LO_TILE - 1) / LO_TILE), nwg = (uint32_t)((n_rows + SORT_CHUNK - 1) / SORT_CHUNK);
+    const uint32_t n = (uint32_t)n_rows, nt = (uint32_t)((n_rows + LO_TILE - 1) / LO_TILE);
     uint32_t bits = 0;
     while ((1u << bits) < n_chrom) bits++;
     lo->passes = (ITX_LOCI_BIN_BITS + bits + 7u) / 8u;
-    LO_TRY(hipSetDevice(device));
+    ITX_TRY(hipSetDevice(device));
     LO_ALLOC(lo->d_rows, 32 * (n_rows + 1));
     LO_ALLOC(lo->d_rank, 4 * ((size_t)n_chrom + 1));
     for (int t = 0; t < 4; t++) {
@@ -295,38 +286,32 @@ extern "C" int itx_loci_create(int device, int kind, const itx_row *rows, const 
     }
     LO_ALLOC(lo->d_key[0], 8 * (n_rows + 1));
     LO_ALLOC(lo->d_key[1], 8 * (n_rows + 1));
-    LO_ALLOC(lo->d_hist, 4 * 256 * ((size_t)nwg + 1));
+    LO_ALLOC(lo->d_hist, itx_sort_hist_bytes(n_rows) + 1024);
     LO_ALLOC(lo->d_len, 4 * (n_rows + 1));
     LO_ALLOC(lo->d_cnt, 4 * (n_rows + 1));
     if (kind == ITX_LOCI_CPG) LO_ALLOC(lo->d_total, 8 * (n_rows + 1));
     LO_ALLOC(lo->d_tsum, 16 * ((size_t)nt + 1));
     LO_ALLOC(lo->d_tbase, 16 * ((size_t)nt + 1));
     LO_ALLOC(lo->d_tot, 32);
-    LO_TRY(hipHostMalloc((void **)&lo->h_tot, 32, hipHostMallocDefault));
-    LO_TRY(hipStreamCreateWithFlags(&lo->st, hipStreamNonBlocking));
-    for (auto &e : lo->ev) LO_TRY(hipEventCreate(&e));
-    if (n_rows) LO_TRY(hipMemcpyAsync(lo->d_rows, packed.data(), 32 * n_rows, hipMemcpyHostToDevice, lo->st));
-    if (n_chrom) LO_TRY(hipMemcpyAsync(lo->d_rank, chrom_rank, 4 * (size_t)n_chrom, hipMemcpyHostToDevice, lo->st));
+    ITX_TRY(hipHostMalloc((void **)&lo->h_tot, 32, hipHostMallocDefault));
+    ITX_TRY(hipStreamCreateWithFlags(&lo->st, hipStreamNonBlocking));
+    for (auto &e : lo->ev) ITX_TRY(hipEventCreate(&e));
+    if (n_rows) ITX_TRY(hipMemcpyAsync(lo->d_rows, packed.data(), 32 * n_rows, hipMemcpyHostToDevice, lo->st));
+    if (n_chrom) ITX_TRY(hipMemcpyAsync(lo->d_rank, chrom_rank, 4 * (size_t)n_chrom, hipMemcpyHostToDevice, lo->st));
     for (int t = 0; t < 4; t++) {
-        if (o32[t][nn[t]]) LO_TRY(hipMemcpyAsync(lo->d_nb[t], nbytes[t] + noff[t][0], o32[t][nn[t]], hipMemcpyHostToDevice, lo->st));
-        LO_TRY(hipMemcpyAsync(lo->d_no[t], o32[t].data(), 4 * ((size_t)nn[t] + 1), hipMemcpyHostToDevice, lo->st));
+        if (o32[t][nn[t]]) ITX_TRY(hipMemcpyAsync(lo->d_nb[t], nbytes[t] + noff[t][0], o32[t][nn[t]], hipMemcpyHostToDevice, lo->st));
+        ITX_TRY(hipMemcpyAsync(lo->d_no[t], o32[t].data(), 4 * ((size_t)nn[t] + 1), hipMemcpyHostToDevice, lo->st));
     }
-    LO_TRY(hipStreamSynchronize(lo->st));                                 // the caller's arrays (and packed, o32) are free again
-    LO_TRY(hipEventRecord(lo->ev[0], lo->st));
+    ITX_TRY(hipStreamSynchronize(lo->st));                                 // the caller's arrays (and packed, o32) are free again
+    ITX_TRY(hipEventRecord(lo->ev[0], lo->st));
     if (n) {
         hipLaunchKernelGGL(k_loci_keys, dim3(nt), dim3(256), 0, lo->st, lo->d_rows, lo->d_rank, n, lo->d_key[0]);
-        LO_TRY(hipGetLastError());
-        for (uint32_t p = 0; p < lo->passes; p++) {
-            hipLaunchKernelGGL(k_sort_hist, dim3(nwg), dim3(256), 0, lo->st, lo->d_key[lo->cur], n, 8u * p, lo->d_hist, nwg);
-            LO_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(ITX_SCAN_WG), 0, lo->st, lo->d_hist, 256u * nwg);
-            LO_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_sort_scatter, dim3(nwg), dim3(256), 0, lo->st, lo->d_key[lo->cur], lo->d_key[lo->cur ^ 1], n, 8u * p, lo->d_hist, nwg);
-            LO_TRY(hipGetLastError());
-            lo->cur ^= 1;
-        }
+        ITX_TRY(hipGetLastError());
+        uint2 *sorted = nullptr;
+        if ((rc = itx_sort_run(lo->st, lo->d_key[0], lo->d_key[1], n, 0u, lo->passes, lo->d_hist, &sorted)) != ITX_OK) goto out;
+        lo->cur = sorted == lo->d_key[1];
     }
-    LO_TRY(hipEventRecord(lo->ev[1], lo->st));                            // not waited for: the sort runs beside the caller's stream
+    ITX_TRY(hipEventRecord(lo->ev[1], lo->st));                            // not waited for: the sort runs beside the caller's stream
 out:
     if (rc != ITX_OK) {
         itx_loci_destroy(lo);
@@ -352,33 +337,12 @@ extern "C" int itx_loci_order(itx_loci *lo, uint32_t *order, double *sort_ms)
     }
     int rc = ITX_OK;
     std::vector<uint2> k(lo->n);
-    LO_TRY(hipSetDevice(lo->device));
-    LO_TRY(hipStreamSynchronize(lo->st));
+    ITX_TRY(hipSetDevice(lo->device));
+    ITX_TRY(hipStreamSynchronize(lo->st));
     lo_read_sort_time(lo);
-    if (lo->n) LO_TRY(hipMemcpy(k.data(), lo->d_key[lo->cur], 8 * lo->n, hipMemcpyDeviceToHost));
+    if (lo->n) ITX_TRY(hipMemcpy(k.data(), lo->d_key[lo->cur], 8 * lo->n, hipMemcpyDeviceToHost));
     for (size_t j = 0; j < lo->n; j++) order[j] = k[j].y;
     if (sort_ms) *sort_ms = lo->sort_ms;
-out:
-    return rc;
-}
-
-// device -> the object's own host memory through the page-locked pair: chunk k + 1 crosses the link while chunk k is copied out
-static int lo_copy_out(itx_loci *lo, void *dst, const void *d_src, size_t bytes)
-{
-    int rc = ITX_OK;
-    size_t done = 0, prev = 0;
-    int k = 0;
-    for (auto &p : lo->h_pin)
-        if (!p) LO_TRY(hipHostMalloc((void **)&p, LO_COPY_CHUNK, hipHostMallocDefault));
-    while (done < bytes || prev) {
-        const size_t m = bytes - done < LO_COPY_CHUNK ? bytes - done : LO_COPY_CHUNK;
-        if (m) LO_TRY(hipMemcpyAsync(lo->h_pin[k], (const uint8_t *)d_src + done, m, hipMemcpyDeviceToHost, lo->st));
-        if (prev) memcpy((uint8_t *)dst + done - prev, lo->h_pin[k ^ 1], prev);
-        LO_TRY(hipStreamSynchronize(lo->st));
-        done += m;
-        prev = m;
-        k ^= 1;
-    }
 out:
     return rc;
 }
@@ -399,25 +363,25 @@ static int lo_text(itx_loci *lo, const void *cnt, const double *total, int thr_i
         T.no[t] = lo->d_no[t];
     }
     memset(res, 0, sizeof *res);
-    LO_TRY(hipSetDevice(lo->device));
+    ITX_TRY(hipSetDevice(lo->device));
     if (n) {
-        LO_TRY(hipMemcpyAsync(lo->d_cnt, cnt, 4 * lo->n, hipMemcpyHostToDevice, lo->st));
-        if (KIND == ITX_LOCI_CPG) LO_TRY(hipMemcpyAsync(lo->d_total, total, 8 * lo->n, hipMemcpyHostToDevice, lo->st));
+        ITX_TRY(hipMemcpyAsync(lo->d_cnt, cnt, 4 * lo->n, hipMemcpyHostToDevice, lo->st));
+        if (KIND == ITX_LOCI_CPG) ITX_TRY(hipMemcpyAsync(lo->d_total, total, 8 * lo->n, hipMemcpyHostToDevice, lo->st));
     }
-    LO_TRY(hipMemsetAsync(lo->d_tot, 0, 32, lo->st));
-    LO_TRY(hipEventRecord(lo->ev[2], lo->st));
+    ITX_TRY(hipMemsetAsync(lo->d_tot, 0, 32, lo->st));
+    ITX_TRY(hipEventRecord(lo->ev[2], lo->st));
     if (n) {
         hipLaunchKernelGGL(k_loci_measure<KIND>, dim3(nt), dim3(LO_TILE), 0, lo->st, T, lo->d_key[lo->cur], n, lo->d_cnt, lo->d_total, reads_num, thr_i, thr_d,
                            lo->d_len, lo->d_tsum, lo->d_tot);
-        LO_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, lo->st, lo->d_tsum, nt, lo->d_tbase, lo->d_tot);
-        LO_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
     }
-    LO_TRY(hipEventRecord(lo->ev[3], lo->st));
-    LO_TRY(hipMemcpyAsync(lo->h_tot, lo->d_tot, 32, hipMemcpyDeviceToHost, lo->st));
-    LO_TRY(hipStreamSynchronize(lo->st));                                 // (the sort of create is through as well)
+    ITX_TRY(hipEventRecord(lo->ev[3], lo->st));
+    ITX_TRY(hipMemcpyAsync(lo->h_tot, lo->d_tot, 32, hipMemcpyDeviceToHost, lo->st));
+    ITX_TRY(hipStreamSynchronize(lo->st));                                 // (the sort of create is through as well)
     lo_read_sort_time(lo);
-    LO_TRY(hipEventElapsedTime(&ms, lo->ev[2], lo->ev[3]));
+    ITX_TRY(hipEventElapsedTime(&ms, lo->ev[2], lo->ev[3]));
     res->sort_ms = lo->sort_ms;
     res->text_ms = (double)ms;
     res->lines = lo->h_tot[1];
@@ -438,16 +402,16 @@ static int lo_text(itx_loci *lo, const void *cnt, const double *total, int thr_i
         rc = ITX_E_NOMEM;
         goto out;
     }
-    LO_TRY(hipMemsetAsync(lo->d_text + bytes, LO_CANARY, cap - (size_t)bytes, lo->st));
-    LO_TRY(hipEventRecord(lo->ev[4], lo->st));
+    ITX_TRY(hipMemsetAsync(lo->d_text + bytes, LO_CANARY, cap - (size_t)bytes, lo->st));
+    ITX_TRY(hipEventRecord(lo->ev[4], lo->st));
     if (bytes) {
         hipLaunchKernelGGL(k_loci_write<KIND>, dim3(nt), dim3(LO_TILE), 0, lo->st, T, lo->d_key[lo->cur], n, lo->d_cnt, lo->d_total, reads_num, thr_i, thr_d,
                            lo->d_len, lo->d_tbase, lo->d_text);
-        LO_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
     }
-    LO_TRY(hipEventRecord(lo->ev[5], lo->st));
-    if ((rc = lo_copy_out(lo, text, lo->d_text, cap)) != ITX_OK) goto out;
-    LO_TRY(hipEventElapsedTime(&ms2, lo->ev[4], lo->ev[5]));
+    ITX_TRY(hipEventRecord(lo->ev[5], lo->st));
+    if ((rc = itx_copy_out(lo->st, lo->h_pin, text, lo->d_text, cap)) != ITX_OK) goto out;
+    ITX_TRY(hipEventElapsedTime(&ms2, lo->ev[4], lo->ev[5]));
     res->text_ms += (double)ms2;
     free(lo->text);
     lo->text = text;

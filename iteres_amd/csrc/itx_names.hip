@@ -20,7 +20,11 @@
 //   append order). Then len + 1 per sorted entry, scanned in 64 bits: each name's place in the text, every name followed by ','
 //   and the last of its row by NUL; the first of a row writes row_off[row]. k_names_write copies pool -> text like the gather.
 //
+// The host half enqueues with the shared plumbing: the passes are itx_sort_run's (itx_radixsort.h), the pool's growth and the way
+// the results leave are itx_devbuf.h's.
+//
 // Byte and integer work; the sort's scatter moves the most bytes. No kernel uses scratch (DESIGN.md has the figures).
+#include "itx_devbuf.h"
 #include "itx_textpack.h"
 #include "itx_radixsort.h"
 #include "itx_bedline.h"
@@ -36,7 +40,6 @@ typedef unsigned long long ull;
 #define NM_LDS 16384u                // bytes staged at a time: a tile of ordinary names (256 x 20-40 bytes) in one window
 #define NM_NOHIT 0xffffffffu
 #define NM_MAX_ENTRIES 0xfffffffeull
-#define NM_COPY_CHUNK ((size_t)8 << 20)
 
 struct NameEnt {                     // 16 bytes, stored as one vector
     uint32_t row, len;
@@ -182,17 +185,6 @@ struct itx_names {
     itx_names_stats stats;
 };
 
-static int nm_hip(hipError_t e, const char *what, int line)
-{
-    if (e == hipSuccess) return ITX_OK;
-    itx_set_error("%s failed: %s (%s:%d)", what, hipGetErrorString(e), __FILE__, line);
-    return ITX_E_NO_DEVICE;
-}
-#define NM_TRY(call)                                       \
-    do {                                                   \
-        if ((rc = nm_hip((call), #call, __LINE__)) != 0) goto out; \
-    } while (0)
-
 extern "C" void itx_names_destroy(itx_names *nm)
 {
     if (!nm) return;
@@ -234,19 +226,19 @@ extern "C" int itx_names_create(int device, size_t batch_capacity, size_t pool_b
         pool_bytes = e && atoll(e) > 0 ? (size_t)atoll(e) : (size_t)64 << 20;
     }
     if (pool_bytes < 256) pool_bytes = 256;
-    NM_TRY(hipSetDevice(device));
-    NM_TRY(hipMalloc((void **)&nm->d_hits, 4 * n));
-    NM_TRY(hipMalloc((void **)&nm->d_len, 4 * n));
-    NM_TRY(hipMalloc((void **)&nm->d_tile_sum, 16 * nt));
-    NM_TRY(hipMalloc((void **)&nm->d_tile_base, 16 * nt));
-    NM_TRY(hipMalloc((void **)&nm->d_tot, 32));
-    NM_TRY(hipHostMalloc((void **)&nm->h_tot, 32, hipHostMallocDefault));
+    ITX_TRY(hipSetDevice(device));
+    ITX_TRY(hipMalloc((void **)&nm->d_hits, 4 * n));
+    ITX_TRY(hipMalloc((void **)&nm->d_len, 4 * n));
+    ITX_TRY(hipMalloc((void **)&nm->d_tile_sum, 16 * nt));
+    ITX_TRY(hipMalloc((void **)&nm->d_tile_base, 16 * nt));
+    ITX_TRY(hipMalloc((void **)&nm->d_tot, 32));
+    ITX_TRY(hipHostMalloc((void **)&nm->h_tot, 32, hipHostMallocDefault));
     nm->pool_cap = pool_bytes;
     nm->ent_cap = pool_bytes / 32 + 16;
-    NM_TRY(hipMalloc((void **)&nm->d_pool, nm->pool_cap + 16));
-    NM_TRY(hipMalloc((void **)&nm->d_ent, sizeof(NameEnt) * nm->ent_cap));
-    NM_TRY(hipStreamCreateWithFlags(&nm->st, hipStreamNonBlocking));
-    for (auto &e : nm->ev) NM_TRY(hipEventCreate(&e));
+    ITX_TRY(hipMalloc((void **)&nm->d_pool, nm->pool_cap + 16));
+    ITX_TRY(hipMalloc((void **)&nm->d_ent, sizeof(NameEnt) * nm->ent_cap));
+    ITX_TRY(hipStreamCreateWithFlags(&nm->st, hipStreamNonBlocking));
+    for (auto &e : nm->ev) ITX_TRY(hipEventCreate(&e));
 out:
     if (rc != ITX_OK) {
         itx_names_destroy(nm);
@@ -263,9 +255,6 @@ extern "C" void *itx_names_stream(itx_names *nm) { return nm ? (void *)nm->st : 
 // before anything is written: what does not fit leaves the object as it was.
 static int names_grow(itx_names *nm, ull add_ent, ull add_bytes)
 {
-    int rc = ITX_OK;
-    uint8_t *np = nullptr;
-    NameEnt *ne = nullptr;
     size_t want_pool = 0, want_ent = 0;
     if ((ull)nm->n_ent + add_ent > NM_MAX_ENTRIES) {
         itx_set_error("itx_names: more than 2^32 - 2 names in one run; ITX_HOST_NAMES=1 builds the lists on the host");
@@ -274,46 +263,26 @@ static int names_grow(itx_names *nm, ull add_ent, ull add_bytes)
     if (nm->pool_used + add_bytes > nm->pool_cap) {
         want_pool = (size_t)(nm->pool_used + add_bytes);
         want_pool = want_pool + (want_pool > 2 * nm->pool_cap ? want_pool / 4 : want_pool);       // at least twice what there was
-        if (hipMalloc((void **)&np, want_pool + 16) != hipSuccess) {
-            (void)hipGetLastError();
-            np = nullptr;
-            itx_set_error("itx_names: no device memory for a pool of %zu bytes; ITX_HOST_NAMES=1 builds the lists on the host", want_pool);
-            rc = ITX_E_NOMEM;
-            goto out;
-        }
     }
     if (nm->n_ent + add_ent > nm->ent_cap) {
         want_ent = (size_t)(nm->n_ent + add_ent);
         want_ent = want_ent + (want_ent > 2 * nm->ent_cap ? want_ent / 4 : want_ent);
         if (want_ent > NM_MAX_ENTRIES) want_ent = (size_t)NM_MAX_ENTRIES;
-        if (hipMalloc((void **)&ne, sizeof(NameEnt) * want_ent) != hipSuccess) {
-            (void)hipGetLastError();
-            ne = nullptr;
-            itx_set_error("itx_names: no device memory for %zu entries; ITX_HOST_NAMES=1 builds the lists on the host", want_ent);
-            rc = ITX_E_NOMEM;
-            goto out;
-        }
     }
-    if (np && nm->pool_used) NM_TRY(hipMemcpyAsync(np, nm->d_pool, nm->pool_used, hipMemcpyDeviceToDevice, nm->st));
-    if (ne && nm->n_ent) NM_TRY(hipMemcpyAsync(ne, nm->d_ent, sizeof(NameEnt) * nm->n_ent, hipMemcpyDeviceToDevice, nm->st));
-    NM_TRY(hipStreamSynchronize(nm->st));                                 // before the old buffers go
-    if (np) {
-        uint8_t *old = nm->d_pool;
-        nm->d_pool = np;
+    // the pool and the entries are taken together (itx_devbuf.h); what they hold is kept
+    ItxGrow g[2] = {{(void **)&nm->d_pool, nm->pool_used, want_pool ? want_pool + 16 : 0}, {(void **)&nm->d_ent, sizeof(NameEnt) * nm->n_ent, sizeof(NameEnt) * want_ent}};
+    const int bad = itx_grow_alloc(g, 2);
+    if (bad == 0) itx_set_error("itx_names: no device memory for a pool of %zu bytes; ITX_HOST_NAMES=1 builds the lists on the host", want_pool);
+    if (bad == 1) itx_set_error("itx_names: no device memory for %zu entries; ITX_HOST_NAMES=1 builds the lists on the host", want_ent);
+    if (bad >= 0) return ITX_E_NOMEM;
+    const int rc = itx_grow_commit(nm->st, g, 2);
+    if (rc != ITX_OK) return rc;
+    if (want_pool) {
         nm->pool_cap = want_pool;
-        np = old;
         nm->stats.grows++;
     }
-    if (ne) {
-        NameEnt *old = nm->d_ent;
-        nm->d_ent = ne;
-        nm->ent_cap = want_ent;
-        ne = old;
-    }
-out:
-    if (np) (void)hipFree(np);                                            // the old buffer, or the new one that was not taken
-    if (ne) (void)hipFree(ne);
-    return rc;
+    if (want_ent) nm->ent_cap = want_ent;
+    return ITX_OK;
 }
 
 static void names_read_gather_time(itx_names *nm)
@@ -344,22 +313,22 @@ int itx_names_start(itx_names *nm, const uint8_t *u, const uint32_t *rec_off, co
     int rc = ITX_OK;
     float ms = 0;
     const uint32_t nt = (uint32_t)((n + NM_TILE - 1) / NM_TILE);
-    NM_TRY(hipSetDevice(nm->device));
+    ITX_TRY(hipSetDevice(nm->device));
     if ((hipStream_t)stream != nm->st) {                                   // the chosen rows were left on another stream
-        NM_TRY(hipEventRecord(nm->ev[4], (hipStream_t)stream));
-        NM_TRY(hipStreamWaitEvent(nm->st, nm->ev[4], 0));
+        ITX_TRY(hipEventRecord(nm->ev[4], (hipStream_t)stream));
+        ITX_TRY(hipStreamWaitEvent(nm->st, nm->ev[4], 0));
     }
-    NM_TRY(hipEventRecord(nm->ev[0], nm->st));
-    NM_TRY(hipMemsetAsync(nm->d_tot, 0, 32, nm->st));
+    ITX_TRY(hipEventRecord(nm->ev[0], nm->st));
+    ITX_TRY(hipMemsetAsync(nm->d_tot, 0, 32, nm->st));
     hipLaunchKernelGGL(k_names_measure, dim3(nt), dim3(NM_TILE), 0, nm->st, u, rec_off, d_hit_row, (uint32_t)n, nm->d_len, nm->d_tile_sum, nm->d_tot);
-    NM_TRY(hipGetLastError());
+    ITX_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, nm->st, nm->d_tile_sum, nt, nm->d_tile_base, nm->d_tot);
-    NM_TRY(hipGetLastError());
-    NM_TRY(hipEventRecord(nm->ev[1], nm->st));
-    NM_TRY(hipMemcpyAsync(nm->h_tot, nm->d_tot, 32, hipMemcpyDeviceToHost, nm->st));
-    NM_TRY(hipStreamSynchronize(nm->st));
+    ITX_TRY(hipGetLastError());
+    ITX_TRY(hipEventRecord(nm->ev[1], nm->st));
+    ITX_TRY(hipMemcpyAsync(nm->h_tot, nm->d_tot, 32, hipMemcpyDeviceToHost, nm->st));
+    ITX_TRY(hipStreamSynchronize(nm->st));
     names_read_gather_time(nm);                                            // (the batch before this one)
-    NM_TRY(hipEventElapsedTime(&ms, nm->ev[0], nm->ev[1]));
+    ITX_TRY(hipEventElapsedTime(&ms, nm->ev[0], nm->ev[1]));
     nm->stats.gather_ms += (double)ms;
     if (nm->h_tot[2]) {                                                    // the host has to look: nothing of this batch is appended
         *n_hard = nm->h_tot[2];
@@ -367,13 +336,13 @@ int itx_names_start(itx_names *nm, const uint8_t *u, const uint32_t *rec_off, co
         goto out;
     }
     if ((rc = names_grow(nm, nm->h_tot[0], nm->h_tot[1])) != ITX_OK) goto out;
-    NM_TRY(hipEventRecord(nm->ev[2], nm->st));
+    ITX_TRY(hipEventRecord(nm->ev[2], nm->st));
     if (nm->h_tot[0]) {
         hipLaunchKernelGGL(k_names_gather, dim3(nt), dim3(NM_TILE), 0, nm->st, u, rec_off, d_hit_row, (uint32_t)n, nm->d_len, nm->d_tile_base, (ull)nm->n_ent,
                            (ull)nm->pool_used, nm->d_ent, nm->d_pool);
-        NM_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
     }
-    NM_TRY(hipEventRecord(nm->ev[3], nm->st));
+    ITX_TRY(hipEventRecord(nm->ev[3], nm->st));
     nm->gather_timed = 1;
     nm->n_ent += (size_t)nm->h_tot[0];
     nm->pool_used += (size_t)nm->h_tot[1];
@@ -396,8 +365,8 @@ extern "C" int itx_names_wait_kernels(itx_names *nm)
         return ITX_E_ARG;
     }
     int rc = ITX_OK;
-    NM_TRY(hipSetDevice(nm->device));
-    NM_TRY(hipStreamSynchronize(nm->st));
+    ITX_TRY(hipSetDevice(nm->device));
+    ITX_TRY(hipStreamSynchronize(nm->st));
     names_read_gather_time(nm);
 out:
     return rc;
@@ -426,8 +395,8 @@ extern "C" int itx_names_append_host(itx_names *nm, const uint32_t *rows, const 
     }
     int rc = ITX_OK;
     std::vector<NameEnt> v(n);
-    NM_TRY(hipSetDevice(nm->device));
-    NM_TRY(hipStreamSynchronize(nm->st));                                  // device batches before this one have their place
+    ITX_TRY(hipSetDevice(nm->device));
+    ITX_TRY(hipStreamSynchronize(nm->st));                                  // device batches before this one have their place
     names_read_gather_time(nm);
     if ((rc = names_grow(nm, n, bytes)) != ITX_OK) goto out;
     for (size_t i = 0; i < n; i++) {
@@ -435,35 +404,14 @@ extern "C" int itx_names_append_host(itx_names *nm, const uint32_t *rows, const 
         v[i].len = (uint32_t)(name_off[i + 1] - name_off[i]);
         v[i].off = (ull)nm->pool_used + (name_off[i] - name_off[0]);
     }
-    NM_TRY(hipMemcpyAsync(nm->d_ent + nm->n_ent, v.data(), sizeof(NameEnt) * n, hipMemcpyHostToDevice, nm->st));
-    if (bytes) NM_TRY(hipMemcpyAsync(nm->d_pool + nm->pool_used, name_bytes + name_off[0], bytes, hipMemcpyHostToDevice, nm->st));
-    NM_TRY(hipStreamSynchronize(nm->st));                                  // the caller's arrays are its own again
+    ITX_TRY(hipMemcpyAsync(nm->d_ent + nm->n_ent, v.data(), sizeof(NameEnt) * n, hipMemcpyHostToDevice, nm->st));
+    if (bytes) ITX_TRY(hipMemcpyAsync(nm->d_pool + nm->pool_used, name_bytes + name_off[0], bytes, hipMemcpyHostToDevice, nm->st));
+    ITX_TRY(hipStreamSynchronize(nm->st));                                  // the caller's arrays are its own again
     nm->n_ent += n;
     nm->pool_used += (size_t)bytes;
     nm->stats.host_batches++;
     nm->stats.entries += n;
     nm->stats.bytes += bytes;
-out:
-    return rc;
-}
-
-// device -> the object's own host memory through the page-locked pair: chunk k + 1 crosses the link while chunk k is copied out
-static int names_copy_out(itx_names *nm, void *dst, const void *d_src, size_t bytes)
-{
-    int rc = ITX_OK;
-    size_t done = 0, prev = 0;
-    int k = 0;
-    for (auto &p : nm->h_pin)
-        if (!p) NM_TRY(hipHostMalloc((void **)&p, NM_COPY_CHUNK, hipHostMallocDefault));
-    while (done < bytes || prev) {
-        const size_t m = bytes - done < NM_COPY_CHUNK ? bytes - done : NM_COPY_CHUNK;
-        if (m) NM_TRY(hipMemcpyAsync(nm->h_pin[k], (const uint8_t *)d_src + done, m, hipMemcpyDeviceToHost, nm->st));
-        if (prev) memcpy((uint8_t *)dst + done - prev, nm->h_pin[k ^ 1], prev);
-        NM_TRY(hipStreamSynchronize(nm->st));
-        done += m;
-        prev = m;
-        k ^= 1;
-    }
 out:
     return rc;
 }
@@ -479,59 +427,50 @@ extern "C" int itx_names_finish(itx_names *nm, size_t n_rows, itx_names_result *
         return ITX_E_STATE;
     }
     int rc = ITX_OK;
-    const uint32_t n = (uint32_t)nm->n_ent, nt = (uint32_t)(((ull)n + NM_TILE - 1) / NM_TILE), nwg = (uint32_t)(((ull)n + SORT_CHUNK - 1) / SORT_CHUNK);
+    const uint32_t n = (uint32_t)nm->n_ent, nt = (uint32_t)(((ull)n + NM_TILE - 1) / NM_TILE);
     uint32_t bits = 0;
     while (((ull)1 << bits) < (ull)n_rows) bits++;
     const uint32_t passes = (bits + 7u) / 8u;
-    uint2 *d_key[2] = {nullptr, nullptr};
+    uint2 *d_key[2] = {nullptr, nullptr}, *sorted = nullptr;
     uint32_t *d_hist = nullptr, *d_cnt = nullptr;
     ull *d_tsum = nullptr, *d_tbase = nullptr, *d_off = nullptr;
     uint8_t *d_text = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    int cur = 0;
     ull total = 0;
     float ms = 0;
     char *text = nullptr;
     uint64_t *row_off = nullptr;
     uint32_t *row_cnt = nullptr;
-    NM_TRY(hipSetDevice(nm->device));
-    NM_TRY(hipStreamSynchronize(nm->st));
+    ITX_TRY(hipSetDevice(nm->device));
+    ITX_TRY(hipStreamSynchronize(nm->st));
     names_read_gather_time(nm);
-    NM_TRY(hipEventCreate(&e0));
-    NM_TRY(hipEventCreate(&e1));
+    ITX_TRY(hipEventCreate(&e0));
+    ITX_TRY(hipEventCreate(&e1));
     row_off = (uint64_t *)malloc(sizeof(uint64_t) * n_rows);
     row_cnt = (uint32_t *)malloc(sizeof(uint32_t) * n_rows);
     if (!row_off || !row_cnt || hipMalloc((void **)&d_off, 8 * n_rows) != hipSuccess || hipMalloc((void **)&d_cnt, 4 * n_rows) != hipSuccess ||
         (n && (hipMalloc((void **)&d_key[0], 8 * (size_t)n) != hipSuccess || hipMalloc((void **)&d_key[1], 8 * (size_t)n) != hipSuccess ||
-               hipMalloc((void **)&d_hist, 4 * 256 * (size_t)nwg) != hipSuccess || hipMalloc((void **)&d_tsum, 16 * (size_t)nt) != hipSuccess ||
+               hipMalloc((void **)&d_hist, itx_sort_hist_bytes(n)) != hipSuccess || hipMalloc((void **)&d_tsum, 16 * (size_t)nt) != hipSuccess ||
                hipMalloc((void **)&d_tbase, 16 * (size_t)nt) != hipSuccess))) {
         (void)hipGetLastError();
         itx_set_error("itx_names_finish: no memory to sort %u names over %zu rows; ITX_HOST_NAMES=1 builds the lists on the host", n, n_rows);
         rc = ITX_E_NOMEM;
         goto out;
     }
-    NM_TRY(hipEventRecord(e0, nm->st));
-    NM_TRY(hipMemsetAsync(d_off, 0xff, 8 * n_rows, nm->st));
-    NM_TRY(hipMemsetAsync(d_cnt, 0, 4 * n_rows, nm->st));
+    ITX_TRY(hipEventRecord(e0, nm->st));
+    ITX_TRY(hipMemsetAsync(d_off, 0xff, 8 * n_rows, nm->st));
+    ITX_TRY(hipMemsetAsync(d_cnt, 0, 4 * n_rows, nm->st));
     if (n) {
-        NM_TRY(hipMemsetAsync(nm->d_tot, 0, 32, nm->st));
+        ITX_TRY(hipMemsetAsync(nm->d_tot, 0, 32, nm->st));
         hipLaunchKernelGGL(k_sort_init, dim3(nt), dim3(256), 0, nm->st, nm->d_ent, n, (uint32_t)n_rows, d_key[0], nm->d_tot + 2);
-        NM_TRY(hipGetLastError());
-        for (uint32_t p = 0; p < passes; p++) {
-            hipLaunchKernelGGL(k_sort_hist, dim3(nwg), dim3(256), 0, nm->st, d_key[cur], n, 8u * p, d_hist, nwg);
-            NM_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(ITX_SCAN_WG), 0, nm->st, d_hist, 256u * nwg);
-            NM_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_sort_scatter, dim3(nwg), dim3(256), 0, nm->st, d_key[cur], d_key[cur ^ 1], n, 8u * p, d_hist, nwg);
-            NM_TRY(hipGetLastError());
-            cur ^= 1;
-        }
-        hipLaunchKernelGGL(k_text_measure, dim3(nt), dim3(NM_TILE), 0, nm->st, d_key[cur], nm->d_ent, n, d_tsum);
-        NM_TRY(hipGetLastError());
+        ITX_TRY(hipGetLastError());
+        if ((rc = itx_sort_run(nm->st, d_key[0], d_key[1], n, 0u, passes, d_hist, &sorted)) != ITX_OK) goto out;
+        hipLaunchKernelGGL(k_text_measure, dim3(nt), dim3(NM_TILE), 0, nm->st, sorted, nm->d_ent, n, d_tsum);
+        ITX_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, nm->st, d_tsum, nt, d_tbase, nm->d_tot);
-        NM_TRY(hipGetLastError());
-        NM_TRY(hipMemcpyAsync(nm->h_tot, nm->d_tot, 32, hipMemcpyDeviceToHost, nm->st));
-        NM_TRY(hipStreamSynchronize(nm->st));
+        ITX_TRY(hipGetLastError());
+        ITX_TRY(hipMemcpyAsync(nm->h_tot, nm->d_tot, 32, hipMemcpyDeviceToHost, nm->st));
+        ITX_TRY(hipStreamSynchronize(nm->st));
         if (nm->h_tot[2]) {
             itx_set_error("itx_names_finish: %llu names sit on rows >= n_rows (%zu)", (unsigned long long)nm->h_tot[2], n_rows);
             rc = ITX_E_ARG;
@@ -545,10 +484,10 @@ extern "C" int itx_names_finish(itx_names *nm, size_t n_rows, itx_names_result *
             rc = ITX_E_NOMEM;
             goto out;
         }
-        hipLaunchKernelGGL(k_names_write, dim3(nt), dim3(NM_TILE), 0, nm->st, d_key[cur], nm->d_ent, n, d_tbase, nm->d_pool, d_text, d_off, d_cnt, (uint32_t)n_rows);
-        NM_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_names_write, dim3(nt), dim3(NM_TILE), 0, nm->st, sorted, nm->d_ent, n, d_tbase, nm->d_pool, d_text, d_off, d_cnt, (uint32_t)n_rows);
+        ITX_TRY(hipGetLastError());
     }
-    NM_TRY(hipEventRecord(e1, nm->st));
+    ITX_TRY(hipEventRecord(e1, nm->st));
     text = (char *)malloc((size_t)total + 1);
     if (!text) {
         itx_set_error("itx_names_finish: no host memory for %llu bytes of text", total);
@@ -556,11 +495,11 @@ extern "C" int itx_names_finish(itx_names *nm, size_t n_rows, itx_names_result *
         goto out;
     }
     text[total] = 0;
-    if (total && (rc = names_copy_out(nm, text, d_text, (size_t)total)) != ITX_OK) goto out;
-    if ((rc = names_copy_out(nm, row_off, d_off, 8 * n_rows)) != ITX_OK) goto out;
-    if ((rc = names_copy_out(nm, row_cnt, d_cnt, 4 * n_rows)) != ITX_OK) goto out;
-    NM_TRY(hipStreamSynchronize(nm->st));
-    NM_TRY(hipEventElapsedTime(&ms, e0, e1));
+    if (total && (rc = itx_copy_out(nm->st, nm->h_pin, text, d_text, (size_t)total)) != ITX_OK) goto out;
+    if ((rc = itx_copy_out(nm->st, nm->h_pin, row_off, d_off, 8 * n_rows)) != ITX_OK) goto out;
+    if ((rc = itx_copy_out(nm->st, nm->h_pin, row_cnt, d_cnt, 4 * n_rows)) != ITX_OK) goto out;
+    ITX_TRY(hipStreamSynchronize(nm->st));
+    ITX_TRY(hipEventElapsedTime(&ms, e0, e1));
     nm->stats.finish_ms = (double)ms;
     nm->text = text;
     nm->row_off = row_off;

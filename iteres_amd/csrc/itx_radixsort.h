@@ -1,10 +1,10 @@
-// itx_radixsort.h — device only: the stable LSD radix sort of (key, payload) pairs, 8 bits a pass between two buffers of 8 bytes per
+// itx_radixsort.h — the stable LSD radix sort of (key, payload) pairs, 8 bits a pass between two buffers of 8 bytes per
 // entry (the read lists of itx_names.hip sort (row, entry) by row; the .loci order of itx_loci.hip sorts (chrom rank | bin, row)).
 // One pass over n pairs, nwg = ceil(n / SORT_CHUNK) workgroups, hist: 256 * nwg words:
 //   k_sort_hist     per-workgroup digit counts, stored digit-major
 //   k_sort_scan     one workgroup, exclusive scan in place: digit-major so that the scan IS the global order
 //   k_sort_scatter  ranks inside a wave by ballot match: equal digits keep their order, so the sort is stable
-// The key is .x, the payload .y; n < 2^32.
+// The key is .x, the payload .y; n < 2^32. The host runs the passes with itx_sort_run (below), the one place that launches the three.
 #pragma once
 #include "itx_device.h"
 
@@ -75,4 +75,29 @@ static __global__ __launch_bounds__(256) void k_sort_scatter(const uint2 *__rest
         s_base[t] += sum;
         __syncthreads();
     }
+}
+
+// ---- host: the three kernels run as one
+// bytes of the digit counts (hist) of a sort of n pairs
+static inline size_t itx_sort_hist_bytes(uint64_t n) { return 4 * 256 * (size_t)((n + SORT_CHUNK - 1) / SORT_CHUNK); }
+
+// `passes` passes over the n pairs of `from`, by the digits at first_shift, first_shift + 8, ..., enqueued on st; the pairs go to and
+// fro between `from` and `other`, *sorted is the one that holds them in the end.
+static inline int itx_sort_run(hipStream_t st, uint2 *from, uint2 *other, uint32_t n, uint32_t first_shift, uint32_t passes, uint32_t *hist, uint2 **sorted)
+{
+    int rc = ITX_OK;
+    const uint32_t nwg = (uint32_t)(((uint64_t)n + SORT_CHUNK - 1) / SORT_CHUNK);
+    *sorted = from;
+    for (uint32_t p = 0; p < passes; p++) {
+        uint2 *to = *sorted == from ? other : from;
+        hipLaunchKernelGGL(k_sort_hist, dim3(nwg), dim3(256), 0, st, *sorted, n, first_shift + 8u * p, hist, nwg);
+        ITX_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(ITX_SCAN_WG), 0, st, hist, 256u * nwg);
+        ITX_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_sort_scatter, dim3(nwg), dim3(256), 0, st, *sorted, to, n, first_shift + 8u * p, hist, nwg);
+        ITX_TRY(hipGetLastError());
+        *sorted = to;
+    }
+out:
+    return rc;
 }
