@@ -284,7 +284,7 @@ int itx_inflater_last_resolve_all_ms(const itx_inflater *h, float *ms);
  *   tids      which references (tid < n_targets) have a mapped record in the last parsed window (one byte each)
  *   device_batch  records [first, ..) of the last parse as DEVICE arrays for itx_engine_submit_device* (first % 16 == 0;
  *             valid until the next parse)
- * Records are located by guess-and-verify (csrc/itx_inflate.hip): exact whatever the bytes look like. A record of
+ * Records are located by guess-and-verify (csrc/itx_bamwin.hip): exact whatever the bytes look like. A record of
  * more than 4 MiB that straddles two chunks makes carry move the fresh bytes back (ITX_E_LIMIT only when the window's buffer
  * cannot hold both). One thread may push while another
  * parses / fetches the OTHER window. */

@@ -47,9 +47,10 @@ size_t aln_raw_step(size_t left)
  * a quarter of the record loop of a BAM the device takes at the rate the page cache delivers it); else one.
  * THE TWO-CHUNK INVARIANT: with n_raw - 3 chunks ahead, chunk f + n_raw is read once raw_next has taken chunk f + 2, so a raw
  * buffer returns to the reader two raw_next calls after the pushes cut from it began — all of them were begun before the
- * chunk after it was taken, and another whole chunk has been indexed since. dev_pushes_copied, on the IO thread, then reads
- * the lanes' busy / n_blk on the device side without a lock while the producer writes them in push_begin / push_end: it is
- * this distance, nothing else, that keeps the two apart. Whoever changes io_ahead or n_raw changes that. */
+ * chunk after it was taken, and another whole chunk has been indexed since. dev_pushes_copied, on the IO thread, reads one
+ * word of a slot on the device side, copy_live (csrc/itx_inflater.h), which the producer stores with release in push_begin /
+ * push_end and itx_bamwin_push_copied loads with acquire; the slot's `copied` event itself has no such guard: it is this
+ * distance, nothing else, that keeps it from being re-recorded under the IO thread. Whoever changes io_ahead or n_raw changes that. */
 static long io_ahead(const aln_reader *r) { return r->raw.n_raw == N_RAW_DEVICE_FILE ? r->raw.n_raw - 3 : 0; }
 
 static void *io_main(void *arg)

@@ -1,4 +1,4 @@
-"""GPU: BAM records located and parsed on the device (itx_bamwin_*, iteres_amd/csrc/itx_inflate.hip) against the
+"""GPU: BAM records located and parsed on the device (itx_bamwin_*, iteres_amd/csrc/itx_bamwin.hip) against the
 independent Python BAM reader of tests/refio.py — whole files in one window, files cut into many chunks (partial blocks
 and partial records carried from window to window), decoy records that mislead the guesses, XA marks and raw bytes for
 the side channels, a malformed length that ends the stream."""
