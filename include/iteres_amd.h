@@ -606,7 +606,7 @@ int itx_bamout_annotate_get_stats(const itx_bamout *bo, uint64_t *tag_bytes);
  *               ITX_E_STATE for the other file while one has rounds left, and for a file that has been handed out.
  *   get_stats   records added and refused, change points, lines, bytes and rounds per file, device time of the add kernels, of the
  *               two dense passes and of the text kernels, time the host waited in these calls, and what create's allocation and
- *               zeroing cost */
+ *               zeroing cost; and what itx_gcov_bigwig_build (below) made of each file: items, sections, levels, summaries, device time */
 typedef struct itx_gcov itx_gcov;
 typedef struct itx_gcov_text {
     const char *bytes;
@@ -618,6 +618,8 @@ typedef struct itx_gcov_stats {
     uint64_t points[2], lines[2], bytes[2], rounds[2];
     uint64_t slots, device_bytes;              /* bases with a slot; bytes of the two arrays */
     double add_ms, points_ms, text_ms, zero_ms, wait_s, alloc_s;
+    uint64_t bw_items[2], bw_sections[2], bw_levels[2], bw_summaries[2];   /* itx_gcov_bigwig_build, per file */
+    double bw_ms;                              /* device time of those builds */
 } itx_gcov_stats;
 int itx_gcov_create(int device, const int64_t *chrom_size, int n_chrom, const itx_params *p, size_t batch_capacity, itx_gcov **out);
 void itx_gcov_destroy(itx_gcov *g);
@@ -775,6 +777,40 @@ int itx_bigwig_start(itx_engine *e, int uniq, const uint64_t *cov_off, const uin
                      uint32_t n_levels, itx_bigwig **out);
 int itx_bigwig_collect(itx_bigwig *b, itx_bw_result *out);
 void itx_bigwig_destroy(itx_bigwig *b);
+
+/* ---- the bigWig content of filter -W: the genome coverage of filter -G as sparse (bedGraph) data, built on the device ---------------
+ * What the reference's converter, bigWigFileCreate(bedGraph, chromSizes, blockSize 256, itemsPerSlot 1024, clip 0, compress 1), makes of
+ * the text that itx_gcov_next hands out for file `which` (csrc/itx_gcovbw.hip; the host lays the file down, host/bigwig.c
+ * write_bigwig_sparse_device). An item is a line of that text: [start, end) with (float)(double)depth. Only chromosomes with an item
+ * get a bigWig id; ids ascend in finish's order (the command gives strcmp order of the names, which the file's B+ tree needs).
+ *   bigwig_build   after itx_gcov_finish (ITX_E_STATE before it, or when the file was built already), before, between or after the
+ *                  text rounds: they do not touch each other. Sections of up to 1024 items (24-byte header, type bedGraph, 12 bytes an
+ *                  item), the first reduction found by the reference's loop (only counts cross the bus), every further level, the
+ *                  zoom blocks of 1024 summaries, all deflated and packed. ITX_E_NOMEM leaves the object as it was: the text can
+ *                  still be taken, and the build tried again.
+ *   bigwig_result  what was built (owned by the object until destroy; ITX_E_STATE when nothing was built): n_items == 0 means the file
+ *                  has no data (the reference's converter refuses such an input) and nothing else is filled in. chrom[id]: index into
+ *                  create's chrom_size; sec_key: (chrom id, first start, last end) per section, sec_count its items; blocks as in
+ *                  itx_bw_result: the sections, then each level's zoom blocks.
+ *   copy_points    the change points of file `which` as they lie on the device, 4 words each: (position, depth from here on, place of
+ *                  the chromosome in finish's order, 0); out holds 4 * stats.points[which] words. For a host-side build. */
+typedef struct itx_gcov_bw_result {
+    uint64_t n_items, n_sec, n_blocks;
+    uint32_t n_chrom, n_levels;
+    const uint32_t *chrom;                    /* n_chrom */
+    const uint32_t *sec_key;                  /* 3 * n_sec */
+    const uint32_t *sec_count;                /* n_sec */
+    uint32_t reduction[10];
+    uint64_t n_sum[10], slot_first[10];
+    const itx_bw_summary *sum[10];
+    const uint64_t *block_off;                /* n_blocks + 1 */
+    const uint8_t *blocks;
+    uint32_t reduce_rounds, pad;              /* times the first reduction was counted */
+    double items_ms, chain_ms, fold_ms, deflate_ms;
+} itx_gcov_bw_result;
+int itx_gcov_bigwig_build(itx_gcov *g, int which);
+int itx_gcov_bigwig_result(itx_gcov *g, int which, itx_gcov_bw_result *out);
+int itx_gcov_copy_points(itx_gcov *g, int which, uint32_t *out);
 
 /* Page-locked host memory for the buffers that cross PCIe on every call (NULL when it cannot be had). */
 void *itx_pinned_alloc(size_t bytes);

@@ -31,6 +31,7 @@
 #include "itx_textpack.h"
 #include "itx_derive.h"
 #include "itx_bedline.h"
+#include "itx_gcovbw.h"
 
 #include <string.h>
 
@@ -296,6 +297,7 @@ struct GcFile {                       // one of the two files, from finish on
     int started, done, flying;        // flying: a round is in slot `slot`
     int slot;
     uint64_t len[2];
+    GcBw *bw;                         // its bigWig content, once built (itx_gcovbw.hip)
 };
 
 struct itx_gcov {
@@ -325,6 +327,7 @@ struct itx_gcov {
     size_t text_cap;
     uint8_t *d_text[2], *h_text[2];
     ull *d_tsum, *d_tbase, *d_ttot;
+    std::vector<uint32_t> h_vsize, h_vchrom;                               // the visited chromosomes: size, index into chrom_size
     itx_gcov_stats stats;
 };
 
@@ -358,7 +361,10 @@ extern "C" void itx_gcov_destroy(itx_gcov *g)
     (void)hipFree(g->d_hs);
     (void)hipFree(g->d_he);
     (void)hipFree(g->d_hu);
-    for (auto &f : g->file) (void)hipFree(f.d_pts);
+    for (auto &f : g->file) {
+        (void)hipFree(f.d_pts);
+        gcbw_free(f.bw);
+    }
     (void)hipFree(g->d_vfirst);
     (void)hipFree(g->d_voff);
     (void)hipFree(g->d_vsize);
@@ -639,7 +645,7 @@ extern "C" int itx_gcov_finish(itx_gcov *g, const uint32_t *order, int n_order, 
     }
     const size_t nc = g->chrom_size.size();
     std::vector<uint8_t> seen(nc + 1, 0);
-    std::vector<uint32_t> vfirst, vsize;
+    std::vector<uint32_t> vfirst, vsize, vchrom;
     std::vector<ull> voff, off(nc + 1, 0ull);
     std::vector<uint2> vname;
     std::string pool;
@@ -665,6 +671,7 @@ extern "C" int itx_gcov_finish(itx_gcov *g, const uint32_t *order, int n_order, 
         const uint32_t len = (uint32_t)(name_off[c + 1] - name_off[c]);
         vfirst.push_back((uint32_t)tiles);
         vsize.push_back((uint32_t)g->chrom_size[c]);
+        vchrom.push_back(c);
         voff.push_back(off[c]);
         vname.push_back(make_uint2((uint32_t)pool.size(), len));
         pool.append(name_bytes + name_off[c], len);
@@ -724,6 +731,8 @@ extern "C" int itx_gcov_finish(itx_gcov *g, const uint32_t *order, int n_order, 
     g->V.size = (const uint32_t *)g->d_vsize;
     g->V.nv = nv;
     g->max_name = max_name;
+    g->h_vsize = vsize;
+    g->h_vchrom = vchrom;
     g->per_round = per_round;
     g->text_cap = text_cap;
     ITX_TRY(hipEventRecord(e0, g->st));
@@ -849,6 +858,66 @@ extern "C" int itx_gcov_next(itx_gcov *g, int which, itx_gcov_text *out)
             F.done = 1;
         }
     }
+out:
+    return rc;
+}
+
+// ---- the bigWig content of a file (itx_gcovbw.hip builds it from the change points; the text rounds read the same points and
+// neither writes them)
+extern "C" int itx_gcov_bigwig_build(itx_gcov *g, int which)
+{
+    if (!g || which < 0 || which > 1) {
+        itx_set_error("itx_gcov_bigwig_build: bad argument");
+        return ITX_E_ARG;
+    }
+    GcFile &F = g->file[which];
+    if (!g->finished || F.bw) {
+        itx_set_error("itx_gcov_bigwig_build: %s", !g->finished ? "itx_gcov_finish comes first" : "this file's bigWig content has been built");
+        return ITX_E_STATE;
+    }
+    GcBw *b = nullptr;
+    const int rc = gcbw_build(g->device, g->st, F.d_pts, F.n_pts, g->h_vsize.data(), g->h_vchrom.data(), (uint32_t)g->h_vsize.size(), &b);
+    if (rc != ITX_OK) return rc;
+    F.bw = b;
+    itx_gcov_bw_result r;
+    gcbw_result(b, &r);
+    g->stats.bw_items[which] = r.n_items;
+    g->stats.bw_sections[which] = r.n_sec;
+    g->stats.bw_levels[which] = r.n_levels;
+    for (uint32_t k = 0; k < r.n_levels; k++) g->stats.bw_summaries[which] += r.n_sum[k];
+    g->stats.bw_ms += gcbw_device_ms(b);
+    return ITX_OK;
+}
+
+extern "C" int itx_gcov_bigwig_result(itx_gcov *g, int which, itx_gcov_bw_result *out)
+{
+    if (!g || !out || which < 0 || which > 1) {
+        itx_set_error("itx_gcov_bigwig_result: bad argument");
+        return ITX_E_ARG;
+    }
+    if (!g->file[which].bw) {
+        itx_set_error("itx_gcov_bigwig_result: itx_gcov_bigwig_build comes first");
+        return ITX_E_STATE;
+    }
+    gcbw_result(g->file[which].bw, out);
+    return ITX_OK;
+}
+
+extern "C" int itx_gcov_copy_points(itx_gcov *g, int which, uint32_t *out)
+{
+    if (!g || which < 0 || which > 1 || (g->finished && g->file[which].n_pts && !out)) {
+        itx_set_error("itx_gcov_copy_points: bad argument");
+        return ITX_E_ARG;
+    }
+    if (!g->finished) {
+        itx_set_error("itx_gcov_copy_points: itx_gcov_finish comes first");
+        return ITX_E_STATE;
+    }
+    int rc = ITX_OK;
+    const GcFile &F = g->file[which];
+    ITX_TRY(hipSetDevice(g->device));
+    ITX_TRY(hipStreamSynchronize(g->st));
+    if (F.n_pts) ITX_TRY(hipMemcpy(out, F.d_pts, sizeof(uint4) * (size_t)F.n_pts, hipMemcpyDeviceToHost));
 out:
     return rc;
 }

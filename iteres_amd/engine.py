@@ -34,7 +34,7 @@ EXPORTS = [
     "itx_names_create", "itx_names_destroy", "itx_names_hits", "itx_names_stream", "itx_bamwin_names", "itx_names_run", "itx_names_wait_kernels", "itx_names_append_host",
     "itx_names_finish", "itx_names_get_stats",
     "itx_gcov_create", "itx_gcov_destroy", "itx_gcov_set_tidmap", "itx_gcov_hits", "itx_gcov_stream", "itx_gcov_run", "itx_gcov_wait_kernels", "itx_gcov_add_host",
-    "itx_gcov_finish", "itx_gcov_next", "itx_gcov_get_stats",
+    "itx_gcov_finish", "itx_gcov_next", "itx_gcov_get_stats", "itx_gcov_bigwig_build", "itx_gcov_bigwig_result", "itx_gcov_copy_points",
     "itx_bamout_create", "itx_bamout_destroy", "itx_bamout_hits", "itx_bamout_stream", "itx_bamwin_bamout", "itx_bamout_run", "itx_bamout_wait_kernels",
     "itx_bamout_append_host", "itx_bamout_finish", "itx_bamout_collect", "itx_bamout_pending", "itx_bamout_get_stats", "itx_bamout_index_enable",
     "itx_bamout_index_finish", "itx_bamout_sort_enable", "itx_bamout_sort_next", "itx_bamout_sort_get_stats",
@@ -121,7 +121,15 @@ class GcovStats(C.Structure):
     _fields_ = [("batches", C.c_uint64), ("host_batches", C.c_uint64), ("records", C.c_uint64), ("out_of_range", C.c_uint64), ("records_uniq", C.c_uint64),
                 ("points", C.c_uint64 * 2), ("lines", C.c_uint64 * 2), ("bytes", C.c_uint64 * 2), ("rounds", C.c_uint64 * 2), ("slots", C.c_uint64),
                 ("device_bytes", C.c_uint64), ("add_ms", C.c_double), ("points_ms", C.c_double), ("text_ms", C.c_double), ("zero_ms", C.c_double),
-                ("wait_s", C.c_double), ("alloc_s", C.c_double)]
+                ("wait_s", C.c_double), ("alloc_s", C.c_double), ("bw_items", C.c_uint64 * 2), ("bw_sections", C.c_uint64 * 2), ("bw_levels", C.c_uint64 * 2),
+                ("bw_summaries", C.c_uint64 * 2), ("bw_ms", C.c_double)]
+
+
+class GcovBwResult(C.Structure):
+    _fields_ = [("n_items", C.c_uint64), ("n_sec", C.c_uint64), ("n_blocks", C.c_uint64), ("n_chrom", C.c_uint32), ("n_levels", C.c_uint32),
+                ("chrom", C.c_void_p), ("sec_key", C.c_void_p), ("sec_count", C.c_void_p), ("reduction", C.c_uint32 * 10), ("n_sum", C.c_uint64 * 10),
+                ("slot_first", C.c_uint64 * 10), ("sum", C.c_void_p * 10), ("block_off", C.c_void_p), ("blocks", C.c_void_p), ("reduce_rounds", C.c_uint32),
+                ("pad", C.c_uint32), ("items_ms", C.c_double), ("chain_ms", C.c_double), ("fold_ms", C.c_double), ("deflate_ms", C.c_double)]
 
 
 class NamesResult(C.Structure):
@@ -281,6 +289,9 @@ def load():
     L.itx_gcov_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     L.itx_gcov_next.argtypes = [C.c_void_p, C.c_int, C.POINTER(GcovText)]
     L.itx_gcov_get_stats.argtypes = [C.c_void_p, C.POINTER(GcovStats)]
+    L.itx_gcov_bigwig_build.argtypes = [C.c_void_p, C.c_int]
+    L.itx_gcov_bigwig_result.argtypes = [C.c_void_p, C.c_int, C.POINTER(GcovBwResult)]
+    L.itx_gcov_copy_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.itx_bamout_create.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]
     L.itx_bamout_destroy.argtypes = [C.c_void_p]
     L.itx_bamout_destroy.restype = None
@@ -775,7 +786,35 @@ class Gcov:
     def stats(self):
         s = GcovStats()
         _chk(load().itx_gcov_get_stats(self._h, C.byref(s)), "itx_gcov_get_stats")
-        return {k: (list(getattr(s, k)) if k in ("points", "lines", "bytes", "rounds") else getattr(s, k)) for k, _ in GcovStats._fields_}
+        return {k: (getattr(s, k) if isinstance(getattr(s, k), (int, float)) else list(getattr(s, k))) for k, _ in GcovStats._fields_}
+
+    def bigwig_build(self, which):
+        """builds the bigWig content of file `which` on the device (after finish; before, between or after the text rounds)"""
+        _chk(load().itx_gcov_bigwig_build(self._h, which), "itx_gcov_bigwig_build")
+
+    def bigwig(self, which):
+        """what bigwig_build made: n_items (0: the file has no data, nothing else is there), chrom (index into chrom_size per bigWig id),
+        sec_key (n_sec x 3: id, start, end), sec_count, reductions, sums (per level, the 32-byte records as bytes), blocks (the zlib
+        streams: sections, then each level's zoom blocks from slot_first[level] on), and the device times of the build's parts"""
+        r = GcovBwResult()
+        _chk(load().itx_gcov_bigwig_result(self._h, which, C.byref(r)), "itx_gcov_bigwig_result")
+        if not r.n_items:
+            return {"n_items": 0}
+        arr = lambda p, n, t: np.frombuffer(C.string_at(p, n * np.dtype(t).itemsize), t).copy()
+        off = arr(r.block_off, r.n_blocks + 1, np.uint64)
+        raw = C.string_at(r.blocks, int(off[-1]))
+        return {"n_items": r.n_items, "chrom": arr(r.chrom, r.n_chrom, np.uint32), "sec_key": arr(r.sec_key, 3 * r.n_sec, np.uint32).reshape(-1, 3),
+                "sec_count": arr(r.sec_count, r.n_sec, np.uint32), "reductions": list(r.reduction[:r.n_levels]),
+                "sums": [C.string_at(r.sum[k], 32 * r.n_sum[k]) for k in range(r.n_levels)], "slot_first": list(r.slot_first[:r.n_levels]),
+                "blocks": [raw[int(off[i]):int(off[i + 1])] for i in range(r.n_blocks)], "reduce_rounds": r.reduce_rounds,
+                "ms": {"items": r.items_ms, "chain": r.chain_ms, "fold": r.fold_ms, "deflate": r.deflate_ms}}
+
+    def points(self, which):
+        """the change points of file `which` as (n, 4) uint32: position, depth from here on, place of the chromosome in finish's order, 0"""
+        n = int(self.stats()["points"][which])
+        out = np.zeros((n, 4), np.uint32)
+        _chk(load().itx_gcov_copy_points(self._h, which, _p(out) if n else None), "itx_gcov_copy_points")
+        return out
 
     def close(self):
         if self._h:

@@ -436,7 +436,12 @@ static void bpt_write(FILE *f, const bw_chrom *chroms, uint64_t n, uint32_t bloc
 }
 
 /* cuskent/bbiWrite.c:478-536: the zoom records, itemsPerSlot to a deflated block, then their R tree */
-static uint64_t write_summary_and_index(FILE *f, bw_sumlist *L, uint32_t block_size, uint32_t items_per_slot, const itx_bw_result *dev,
+typedef struct {                       /* blocks the device deflated, packed: block i at bytes [off[i], off[i + 1]) */
+    const uint8_t *bytes;
+    const uint64_t *off;
+} bw_blocks;
+
+static uint64_t write_summary_and_index(FILE *f, bw_sumlist *L, uint32_t block_size, uint32_t items_per_slot, const bw_blocks *dev,
                                         uint64_t first_block)
 {
     const uint32_t count = (uint32_t)L->n;
@@ -481,7 +486,7 @@ static uint64_t write_summary_and_index(FILE *f, bw_sumlist *L, uint32_t block_s
                 items[i + k].end = s->end;
                 items[i + k].off = pos;
             }
-            if (dev) put(f, dev->blocks + dev->block_off[first_block + sl], (size_t)(dev->block_off[first_block + sl + 1] - dev->block_off[first_block + sl]));
+            if (dev) put(f, dev->bytes + dev->off[first_block + sl], (size_t)(dev->off[first_block + sl + 1] - dev->off[first_block + sl]));
             else put(f, comp + (sl - g0) * comp_cap, csize[sl - g0]);
         }
     }
@@ -656,157 +661,82 @@ void write_bigwig_device(const bw_plan *P, const char *path, const itx_bw_result
     bw_write(P, path, NULL, dev);
 }
 
-/* val: the values of names[i] (zlib source), or dev: the device builder's blocks and summaries */
-static void bw_write(const bw_plan *P, const char *path, const float *const *val, const itx_bw_result *dev)
-{
-    const uint32_t block_size = 256, items_per_slot = 1024;                  /* stat.c:157-158 */
-    BW_T("start");
-    const size_t n_names = P->n_names, n_sec = P->n_sec;
-    const bw_chrom *chroms = P->chroms;
-    const uint32_t max_name = P->max_name;
-    bw_section *sec = xcalloc(n_sec ? n_sec : 1, sizeof *sec);
-    memcpy(sec, P->sec, n_sec * sizeof *sec);
-    const size_t *sec_of = P->sec_of;
-    const int n_sums = P->n_sums;
-    const uint32_t *reductions = P->reductions;
-    bw_sumlist sums[10];
-    if (dev) {
-        for (int i = 0; i < n_sums; i++) {
-            const size_t n = (size_t)dev->n_sum[i];
-            sums[i].v = xmalloc((n ? n : 1) * sizeof *sums[i].v);
-            sums[i].n = sums[i].cap = n;
-            for (size_t j = 0; j < n; j++) {
-                const itx_bw_summary *d = &dev->sum[i][j];
-                bw_summary *s = &sums[i].v[j];
-                s->chrom_id = d->chrom_id;
-                s->start = d->start;
-                s->end = d->end;
-                s->valid_count = d->valid_count;
-                s->min_val = d->min_val;
-                s->max_val = d->max_val;
-                s->sum_data = d->sum_data;
-                s->sum_squares = d->sum_squares;
-                s->file_offset = 0;
-            }
-        }
-    } else {
-        for (size_t i = 0; i < n_sec; i++) sec[i].val = val[P->src[sec[i].chrom_id]] + sec[i].start;
-        BW_T("sections");
-        sums[0] = reduce_sections(sec, sec_of, chroms, n_names, (int)reductions[0]);
-        if ((uint64_t)sums[0].n != P->n_first) die("internal error: bigWig first zoom level has %zu summaries, %llu expected", sums[0].n, (unsigned long long)P->n_first);
-        for (int i = 1; i < n_sums; i++) sums[i] = reduce_summaries(&sums[i - 1], chroms, n_names, (int)reductions[i]);
-    }
+/* ---- the file skeleton (cuskent/bwgCreate.c:887-1019), shared by the dense and the sparse writer: bw_file_begin writes everything
+ * up to the section count, the caller lays its sections down, bw_file_end writes the index, the zoom levels and the numbers that
+ * are known only then */
+typedef struct {
+    FILE *f;
+    const char *path;
+    long chrom_tree_pos, data_pos, index_pos, total_pos, unc_pos, zoom_pos[10];
+    uint64_t total_summary_off;
+} bw_file;
 
-    BW_T("zoom lists");
+static void bw_file_begin(bw_file *F, const char *path, int n_sums, const uint32_t *reductions, const bw_chrom *chroms, size_t n_chroms, uint32_t max_name,
+                          uint64_t section_count)
+{
+    const uint32_t block_size = 256;
     FILE *f = fopen(path, "wb");
     if (!f) die("mustOpen: Can't open %s to write: %s", path, strerror(errno));
-    const uint32_t sig = BW_SIG, res32 = 0;
+    F->f = f;
+    F->path = path;
+    const uint32_t sig = BW_SIG, res32 = 0, unc_buf = 0;
     const uint16_t version = BW_VERSION, summary_count = (uint16_t)n_sums, res16 = 0;
     const uint64_t res64 = 0;
-    uint64_t chrom_tree_off = 0, data_off = 0, index_off = 0, total_summary_off = 0;
-    uint32_t unc_buf = 0;
     PUT(f, sig);
     PUT(f, version);
     PUT(f, summary_count);
-    const long chrom_tree_pos = ftell(f);
-    PUT(f, chrom_tree_off);
-    const long data_pos = ftell(f);
-    PUT(f, data_off);
-    const long index_pos = ftell(f);
-    PUT(f, index_off);
+    F->chrom_tree_pos = ftell(f);
+    PUT(f, res64);
+    F->data_pos = ftell(f);
+    PUT(f, res64);
+    F->index_pos = ftell(f);
+    PUT(f, res64);
     PUT(f, res16);
     PUT(f, res16);
     PUT(f, res64);
-    const long total_pos = ftell(f);
-    PUT(f, total_summary_off);
-    const long unc_pos = ftell(f);
+    F->total_pos = ftell(f);
+    PUT(f, res64);
+    F->unc_pos = ftell(f);
     PUT(f, unc_buf);
     PUT(f, res64);
-    long zoom_pos[10];
     for (int i = 0; i < n_sums; i++) {
         PUT(f, reductions[i]);
         PUT(f, res32);
-        zoom_pos[i] = ftell(f);
+        F->zoom_pos[i] = ftell(f);
         PUT(f, res64);
         PUT(f, res64);
     }
-    total_summary_off = (uint64_t)ftello(f);
+    F->total_summary_off = (uint64_t)ftello(f);
     put_zero(f, 40);
-    chrom_tree_off = (uint64_t)ftello(f);
-    bpt_write(f, chroms, n_names, block_size < n_names ? block_size : (uint32_t)n_names, max_name);
-    data_off = (uint64_t)ftello(f);
-    const uint64_t section_count = n_sec;
+    const uint64_t chrom_tree_off = (uint64_t)ftello(f);
+    bpt_write(f, chroms, n_chroms, block_size < n_chroms ? block_size : (uint32_t)n_chroms, max_name);
+    const uint64_t data_off = (uint64_t)ftello(f);
     PUT(f, section_count);
-    if (dev) {
-        for (size_t i = 0; i < n_sec; i++) {
-            const uint32_t unc = 24 + 4 * sec[i].item_count;
-            if (unc > unc_buf) unc_buf = unc;
-            sec[i].file_offset = (uint64_t)ftello(f);
-            put(f, dev->blocks + dev->block_off[i], (size_t)(dev->block_off[i + 1] - dev->block_off[i]));
-        }
-    } else {
-        /* sections are deflated in parallel into memory, then laid down in order (their offsets feed the index) */
-        const size_t cap = 24 + 4 * (size_t)items_per_slot, ccap = z_buf_size(cap);
-        const size_t group = 4096;
-        char *comp = xmalloc(ccap * group);
-        size_t *csize = xcalloc(group, sizeof *csize);
-        for (size_t g0 = 0; g0 < n_sec; g0 += group) {
-            const size_t g1 = g0 + group < n_sec ? g0 + group : n_sec;
-            uint32_t unc_max = 0;
-#pragma omp parallel for schedule(dynamic, 16) reduction(max : unc_max)
-            for (long i = (long)g0; i < (long)g1; i++) {
-                const bw_section *s = &sec[i];
-                const uint32_t step = 1, span = 1;
-                const uint8_t type = 3, r8 = 0;                                /* bwgTypeFixedStep */
-                const uint16_t cnt = (uint16_t)s->item_count;
-                char buf[24 + 4 * 1024];
-                char *w = buf;
-                memcpy(w, &s->chrom_id, 4); w += 4;
-                memcpy(w, &s->start, 4); w += 4;
-                memcpy(w, &s->end, 4); w += 4;
-                memcpy(w, &step, 4); w += 4;
-                memcpy(w, &span, 4); w += 4;
-                memcpy(w, &type, 1); w += 1;
-                memcpy(w, &r8, 1); w += 1;
-                memcpy(w, &cnt, 2); w += 2;
-                for (uint32_t j = 0; j < s->item_count; j++) {
-                    memcpy(w, &s->val[j], 4);
-                    w += 4;
-                }
-                const uint32_t unc = (uint32_t)(w - buf);
-                if (unc > unc_max) unc_max = unc;
-                csize[i - (long)g0] = z_compress(buf, unc, comp + (size_t)(i - (long)g0) * ccap, ccap);
-            }
-            if (unc_max > unc_buf) unc_buf = unc_max;
-            for (size_t i = g0; i < g1; i++) {
-                sec[i].file_offset = (uint64_t)ftello(f);
-                put(f, comp + (i - g0) * ccap, csize[i - g0]);
-            }
-        }
-        free(comp);
-        free(csize);
-    }
+    fseek(f, F->data_pos, SEEK_SET);
+    PUT(f, data_off);
+    fseek(f, F->chrom_tree_pos, SEEK_SET);
+    PUT(f, chrom_tree_off);
+    fseeko(f, (off_t)data_off + 8, SEEK_SET);
+}
+
+/* sec[i]: key and file offset of section i; unc_buf: the largest section's payload; dev: where the zoom blocks come from (or NULL:
+ * zlib), level i's first at block slot_first[i] */
+static void bw_file_end(bw_file *F, const ritem *sec, size_t n_sec, bw_sumlist *sums, int n_sums, uint32_t unc_buf, const bw_blocks *dev, const uint64_t *slot_first)
+{
+    const uint32_t block_size = 256, items_per_slot = 1024;
+    FILE *f = F->f;
     BW_T("data");
-    index_off = (uint64_t)ftello(f);
-    {
-        ritem *items = xcalloc(n_sec ? n_sec : 1, sizeof *items);
-        for (size_t i = 0; i < n_sec; i++) {
-            items[i].chrom = sec[i].chrom_id;
-            items[i].start = sec[i].start;
-            items[i].end = sec[i].end;
-            items[i].off = sec[i].file_offset;
-        }
-        cir_tree_write(f, items, n_sec, block_size, 1, index_off);
-        free(items);
-    }
+    const uint64_t index_off = (uint64_t)ftello(f);
+    cir_tree_write(f, sec, n_sec, block_size, 1, index_off);
     BW_T("index");
     uint64_t zoom_data[10], zoom_index[10];
     for (int i = 0; i < n_sums; i++) {
         zoom_data[i] = (uint64_t)ftello(f);
-        zoom_index[i] = write_summary_and_index(f, &sums[i], block_size, items_per_slot, dev, dev ? dev->slot_first[i] : 0);
+        zoom_index[i] = write_summary_and_index(f, &sums[i], block_size, items_per_slot, dev, dev ? slot_first[i] : 0);
     }
     BW_T("zooms");
     /* the file-wide summary from the first zoom level (bwgCreate.c:966-988) */
+    uint64_t total_summary_off = F->total_summary_off;
     if (sums[0].n) {
         const bw_summary *s = &sums[0].v[0];
         uint64_t valid = s->valid_count;
@@ -827,25 +757,313 @@ static void bw_write(const bw_plan *P, const char *path, const float *const *val
         PUT(f, sq);
     } else
         total_summary_off = 0;
-    fseek(f, data_pos, SEEK_SET);
-    PUT(f, data_off);
-    fseek(f, index_pos, SEEK_SET);
+    fseek(f, F->index_pos, SEEK_SET);
     PUT(f, index_off);
-    fseek(f, chrom_tree_pos, SEEK_SET);
-    PUT(f, chrom_tree_off);
-    fseek(f, total_pos, SEEK_SET);
+    fseek(f, F->total_pos, SEEK_SET);
     PUT(f, total_summary_off);
     if (32 * items_per_slot > unc_buf) unc_buf = 32 * items_per_slot;
-    fseek(f, unc_pos, SEEK_SET);
+    fseek(f, F->unc_pos, SEEK_SET);
     PUT(f, unc_buf);
     for (int i = 0; i < n_sums; i++) {
-        fseek(f, zoom_pos[i], SEEK_SET);
+        fseek(f, F->zoom_pos[i], SEEK_SET);
         PUT(f, zoom_data[i]);
         PUT(f, zoom_index[i]);
     }
     fseek(f, 0L, SEEK_END);
+    const uint32_t sig = BW_SIG;
     PUT(f, sig);
-    if (fclose(f) != 0) die("carefulClose: error closing %s", path);
+    if (fclose(f) != 0) die("carefulClose: error closing %s", F->path);
+}
+
+/* the device's summaries of one level as the writer keeps them */
+static bw_sumlist sumlist_from_device(const itx_bw_summary *d, size_t n)
+{
+    bw_sumlist L;
+    L.v = xmalloc((n ? n : 1) * sizeof *L.v);
+    L.n = L.cap = n;
+    for (size_t j = 0; j < n; j++) {
+        bw_summary *s = &L.v[j];
+        s->chrom_id = d[j].chrom_id;
+        s->start = d[j].start;
+        s->end = d[j].end;
+        s->valid_count = d[j].valid_count;
+        s->min_val = d[j].min_val;
+        s->max_val = d[j].max_val;
+        s->sum_data = d[j].sum_data;
+        s->sum_squares = d[j].sum_squares;
+        s->file_offset = 0;
+    }
+    return L;
+}
+
+/* sections deflated in parallel into memory, a group at a time, then laid down in order (their offsets feed the index):
+ * fill(i, buf) writes section i's payload and returns its length (at most cap) */
+typedef uint32_t (*bw_fill_fn)(const void *ctx, size_t i, char *buf);
+static uint32_t put_sections_zlib(FILE *f, ritem *sec, size_t n_sec, size_t cap, bw_fill_fn fill, const void *ctx)
+{
+    const size_t ccap = z_buf_size(cap), group = 4096;
+    char *comp = xmalloc(ccap * group);
+    size_t *csize = xcalloc(group, sizeof *csize);
+    uint32_t unc_buf = 0;
+    for (size_t g0 = 0; g0 < n_sec; g0 += group) {
+        const size_t g1 = g0 + group < n_sec ? g0 + group : n_sec;
+        uint32_t unc_max = 0;
+#pragma omp parallel for schedule(dynamic, 16) reduction(max : unc_max)
+        for (long i = (long)g0; i < (long)g1; i++) {
+            char *buf = xmalloc(cap);
+            const uint32_t unc = fill(ctx, (size_t)i, buf);
+            if (unc > unc_max) unc_max = unc;
+            csize[i - (long)g0] = z_compress(buf, unc, comp + (size_t)(i - (long)g0) * ccap, ccap);
+            free(buf);
+        }
+        if (unc_max > unc_buf) unc_buf = unc_max;
+        for (size_t i = g0; i < g1; i++) {
+            sec[i].off = (uint64_t)ftello(f);
+            put(f, comp + (i - g0) * ccap, csize[i - g0]);
+        }
+    }
+    free(comp);
+    free(csize);
+    return unc_buf;
+}
+
+static char *put_section_header(char *w, uint32_t chrom_id, uint32_t start, uint32_t end, uint32_t step, uint32_t span, uint8_t type, uint16_t cnt)
+{
+    const uint8_t r8 = 0;
+    memcpy(w, &chrom_id, 4); w += 4;
+    memcpy(w, &start, 4); w += 4;
+    memcpy(w, &end, 4); w += 4;
+    memcpy(w, &step, 4); w += 4;
+    memcpy(w, &span, 4); w += 4;
+    memcpy(w, &type, 1); w += 1;
+    memcpy(w, &r8, 1); w += 1;
+    memcpy(w, &cnt, 2); w += 2;
+    return w;
+}
+
+static uint32_t fill_fixed_step(const void *ctx, size_t i, char *buf)
+{
+    const bw_section *s = (const bw_section *)ctx + i;
+    char *w = put_section_header(buf, s->chrom_id, s->start, s->end, 1, 1, 3, (uint16_t)s->item_count);      /* bwgTypeFixedStep */
+    memcpy(w, s->val, 4 * (size_t)s->item_count);
+    return 24 + 4 * s->item_count;
+}
+
+/* val: the values of names[i] (zlib source), or dev: the device builder's blocks and summaries */
+static void bw_write(const bw_plan *P, const char *path, const float *const *val, const itx_bw_result *dev)
+{
+    const uint32_t items_per_slot = 1024;                                    /* stat.c:157-158 */
+    BW_T("start");
+    const size_t n_names = P->n_names, n_sec = P->n_sec;
+    const bw_chrom *chroms = P->chroms;
+    bw_section *sec = xcalloc(n_sec ? n_sec : 1, sizeof *sec);
+    memcpy(sec, P->sec, n_sec * sizeof *sec);
+    const int n_sums = P->n_sums;
+    const uint32_t *reductions = P->reductions;
+    bw_sumlist sums[10];
+    if (dev) {
+        for (int i = 0; i < n_sums; i++) sums[i] = sumlist_from_device(dev->sum[i], (size_t)dev->n_sum[i]);
+    } else {
+        for (size_t i = 0; i < n_sec; i++) sec[i].val = val[P->src[sec[i].chrom_id]] + sec[i].start;
+        BW_T("sections");
+        sums[0] = reduce_sections(sec, P->sec_of, chroms, n_names, (int)reductions[0]);
+        if ((uint64_t)sums[0].n != P->n_first) die("internal error: bigWig first zoom level has %zu summaries, %llu expected", sums[0].n, (unsigned long long)P->n_first);
+        for (int i = 1; i < n_sums; i++) sums[i] = reduce_summaries(&sums[i - 1], chroms, n_names, (int)reductions[i]);
+    }
+    BW_T("zoom lists");
+    bw_file F;
+    bw_file_begin(&F, path, n_sums, reductions, chroms, n_names, P->max_name, n_sec);
+    ritem *items = xcalloc(n_sec ? n_sec : 1, sizeof *items);
+    for (size_t i = 0; i < n_sec; i++) {
+        items[i].chrom = sec[i].chrom_id;
+        items[i].start = sec[i].start;
+        items[i].end = sec[i].end;
+    }
+    uint32_t unc_buf = 0;
+    const bw_blocks blocks = {dev ? dev->blocks : NULL, dev ? dev->block_off : NULL};
+    if (dev) {
+        for (size_t i = 0; i < n_sec; i++) {
+            const uint32_t unc = 24 + 4 * sec[i].item_count;
+            if (unc > unc_buf) unc_buf = unc;
+            items[i].off = (uint64_t)ftello(F.f);
+            put(F.f, dev->blocks + dev->block_off[i], (size_t)(dev->block_off[i + 1] - dev->block_off[i]));
+        }
+    } else {
+        unc_buf = put_sections_zlib(F.f, items, n_sec, 24 + 4 * (size_t)items_per_slot, fill_fixed_step, sec);
+    }
+    bw_file_end(&F, items, n_sec, sums, n_sums, unc_buf, dev ? &blocks : NULL, dev ? dev->slot_first : NULL);
+    free(items);
     for (int i = 0; i < n_sums; i++) free(sums[i].v);
     free(sec);
+}
+
+/* ---- sparse data: the bigWig of a bedGraph (filter -W) ---------------------------------------------------------------------------
+ * What bigWigFileCreate makes of bedGraph lines (cuskent/bwgCreate.c:470-575 parses them into sections of <= itemsPerSlot items,
+ * type bwgTypeBedGraph): only chromosomes with an item get an id (:584-627), the first reduction is found by reducing again and again
+ * (:826-865, with the average resolution of :629-686), every further level is reduced from the last level kept (:867-885), and the
+ * summaries follow the data: they start where it starts and re-anchor after a gap (add_to_summary above states the rule). */
+typedef struct {
+    const bw_item *it;
+    const ritem *sec;
+    const size_t *first;              /* section i holds items first[i] .. first[i + 1] */
+} bw_sparse_ctx;
+
+static uint32_t fill_bedgraph(const void *ctx, size_t i, char *buf)
+{
+    const bw_sparse_ctx *C = ctx;
+    const size_t a = C->first[i], b = C->first[i + 1];
+    char *w = put_section_header(buf, C->sec[i].chrom, C->sec[i].start, C->sec[i].end, 0, 0, 1, (uint16_t)(b - a));     /* bwgTypeBedGraph */
+    for (size_t k = a; k < b; k++) {
+        memcpy(w, &C->it[k].start, 4); w += 4;
+        memcpy(w, &C->it[k].end, 4); w += 4;
+        memcpy(w, &C->it[k].val, 4); w += 4;
+    }
+    return (uint32_t)(w - buf);
+}
+
+/* the chromosomes that get an id: used[k] != 0, in the order given (strcmp order of the names) */
+static bw_chrom *sparse_chroms(const char *const *names, const uint32_t *sizes, const uint32_t *pick, size_t n, uint32_t *max_name)
+{
+    bw_chrom *ch = xcalloc(n ? n : 1, sizeof *ch);
+    *max_name = 0;
+    for (size_t i = 0; i < n; i++) {
+        ch[i].name = names[pick[i]];
+        ch[i].id = (uint32_t)i;
+        ch[i].size = sizes[pick[i]];
+        const uint32_t l = (uint32_t)strlen(ch[i].name);
+        if (l > *max_name) *max_name = l;
+        if (i && strcmp(ch[i - 1].name, ch[i].name) >= 0) die("internal error: bigWig chromosomes %s, %s are not in strcmp order", ch[i - 1].name, ch[i].name);
+    }
+    return ch;
+}
+
+int write_bigwig_sparse(const char *path, const char *const *names, const uint32_t *sizes, const bw_item *items, size_t n_items)
+{
+    const uint32_t items_per_slot = 1024;
+    if (!n_items) return 0;
+    BW_T("start");
+    /* ids, and the items with them */
+    uint32_t *pick = xcalloc(n_items, sizeof *pick);
+    bw_item *it = xmalloc(n_items * sizeof *it);
+    size_t n_ids = 0;
+    for (size_t k = 0; k < n_items; k++) {
+        if (!k || items[k].chrom != items[k - 1].chrom) pick[n_ids++] = items[k].chrom;
+        else if (items[k].start < items[k - 1].end) die("Overlap between %s %u %u and %u %u", names[items[k].chrom], items[k - 1].start, items[k - 1].end, items[k].start, items[k].end);
+        if (items[k].start >= items[k].end || items[k].end > sizes[items[k].chrom]) die("bedGraph item %s %u %u is empty or ends behind the chromosome's %u bases", names[items[k].chrom], items[k].start, items[k].end, sizes[items[k].chrom]);
+        it[k] = items[k];
+        it[k].chrom = (uint32_t)(n_ids - 1);
+    }
+    uint32_t max_name = 0;
+    bw_chrom *chroms = sparse_chroms(names, sizes, pick, n_ids, &max_name);
+    /* sections */
+    size_t n_sec = 0;
+    for (size_t k = 0, run = 0; k < n_items; k++) {
+        if (k && it[k].chrom != it[k - 1].chrom) run = 0;
+        if (run++ % items_per_slot == 0) n_sec++;
+    }
+    ritem *sec = xcalloc(n_sec, sizeof *sec);
+    size_t *first = xcalloc(n_sec + 1, sizeof *first);
+    uint64_t total_res = 0, full_size = 0;
+    {
+        size_t s = 0;
+        for (size_t k = 0, run = 0; k < n_items; k++) {
+            if (k && it[k].chrom != it[k - 1].chrom) run = 0;
+            if (run++ % items_per_slot == 0) first[s++] = k;
+        }
+        first[n_sec] = n_items;
+        for (s = 0; s < n_sec; s++) {
+            int res = 0x3fffffff;                                           /* BIGNUM */
+            for (size_t k = first[s]; k < first[s + 1]; k++)
+                if (res > (int)(it[k].end - it[k].start)) res = (int)(it[k].end - it[k].start);
+            total_res += (uint64_t)res;
+            sec[s].chrom = it[first[s]].chrom;
+            sec[s].start = it[first[s]].start;
+            sec[s].end = it[first[s + 1] - 1].end;
+            full_size += 24 + 12 * (uint64_t)(first[s + 1] - first[s]);
+        }
+    }
+    const int min_res = (int)((total_res + (uint32_t)n_sec / 2) / (uint32_t)n_sec);
+    /* the first reduction: reduce, look at the size, reduce again */
+    int reduction0 = min_res * 10;
+    const uint64_t max_reduced = full_size / 2;
+    uint64_t last_summary_size = 0;
+    bw_sumlist sums[10];
+    uint32_t reductions[10];
+    for (;;) {
+        bw_sumlist L = {NULL, 0, 0};
+        for (size_t k = 0; k < n_items; k++) {
+            const int size = (int)(it[k].end - it[k].start);
+            const double v = (double)it[k].val, sum = size * v;
+            add_to_summary(&L, it[k].chrom, chroms[it[k].chrom].size, it[k].start, it[k].end, (uint32_t)size, v, v, sum, sum * v, reduction0);
+        }
+        const uint64_t size = 2 * 32 * (uint64_t)L.n;
+        if (size >= max_reduced && size != last_summary_size) {
+            int next = (int)(1.1 * reduction0 * (double)size / (double)max_reduced);
+            if (next < reduction0 * 2) next = reduction0 * 2;
+            reduction0 = next;
+            last_summary_size = size;
+            free(L.v);
+        } else {
+            sums[0] = L;
+            break;
+        }
+    }
+    int n_sums = 1;
+    reductions[0] = (uint32_t)reduction0;
+    uint64_t reduction = (uint64_t)reduction0;
+    for (int i = 0; i < 9; i++) {
+        reduction *= 4;
+        if (reduction > 1000000000) break;
+        bw_sumlist L = reduce_summaries(&sums[n_sums - 1], chroms, n_ids, (int)reduction);
+        const size_t n = L.n;
+        if (32 * (uint64_t)n != last_summary_size) {
+            sums[n_sums] = L;
+            reductions[n_sums++] = (uint32_t)reduction;
+        } else
+            free(L.v);
+        if (n <= n_ids) break;
+    }
+    BW_T("zoom lists");
+    bw_file F;
+    bw_file_begin(&F, path, n_sums, reductions, chroms, n_ids, max_name, n_sec);
+    const bw_sparse_ctx ctx = {it, sec, first};
+    const uint32_t unc_buf = put_sections_zlib(F.f, sec, n_sec, 24 + 12 * (size_t)items_per_slot, fill_bedgraph, &ctx);
+    bw_file_end(&F, sec, n_sec, sums, n_sums, unc_buf, NULL, NULL);
+    for (int i = 0; i < n_sums; i++) free(sums[i].v);
+    free(first);
+    free(sec);
+    free(chroms);
+    free(it);
+    free(pick);
+    return 1;
+}
+
+int write_bigwig_sparse_device(const char *path, const char *const *names, const uint32_t *sizes, const itx_gcov_bw_result *dev)
+{
+    if (!dev->n_items) return 0;
+    uint32_t max_name = 0;
+    bw_chrom *chroms = sparse_chroms(names, sizes, dev->chrom, dev->n_chrom, &max_name);
+    const size_t n_sec = (size_t)dev->n_sec;
+    const int n_sums = (int)dev->n_levels;
+    bw_sumlist sums[10];
+    for (int i = 0; i < n_sums; i++) sums[i] = sumlist_from_device(dev->sum[i], (size_t)dev->n_sum[i]);
+    bw_file F;
+    bw_file_begin(&F, path, n_sums, dev->reduction, chroms, dev->n_chrom, max_name, n_sec);
+    ritem *sec = xcalloc(n_sec ? n_sec : 1, sizeof *sec);
+    uint32_t unc_buf = 0;
+    for (size_t i = 0; i < n_sec; i++) {
+        sec[i].chrom = dev->sec_key[3 * i];
+        sec[i].start = dev->sec_key[3 * i + 1];
+        sec[i].end = dev->sec_key[3 * i + 2];
+        sec[i].off = (uint64_t)ftello(F.f);
+        const uint32_t unc = 24 + 12 * dev->sec_count[i];
+        if (unc > unc_buf) unc_buf = unc;
+        put(F.f, dev->blocks + dev->block_off[i], (size_t)(dev->block_off[i + 1] - dev->block_off[i]));
+    }
+    const bw_blocks blocks = {dev->blocks, dev->block_off};
+    bw_file_end(&F, sec, n_sec, sums, n_sums, unc_buf, &blocks, dev->slot_first);
+    for (int i = 0; i < n_sums; i++) free(sums[i].v);
+    free(sec);
+    free(chroms);
+    return 1;
 }

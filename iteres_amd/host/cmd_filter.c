@@ -29,6 +29,7 @@ static int filter_usage(void)
     fprintf(stderr, "         -l       with -b: level of its BGZF members, 0 (stored), 1 (fast) or 6 (smallest) (an extension) [6]\n");
     fprintf(stderr, "         -a       with -b: tag every emitted read with the repeat it was counted for, ZN/ZC/ZF (repName, repClass, repFamily) and ZS/ZE (genoStart, genoEnd) (an extension) [off]\n");
     fprintf(stderr, "         -G       output the genome coverage of the counted reads as <prefix>_<filter>.iteres.bedGraph and, for MAPQ >= -Q, .iteres.unique.bedGraph (an extension) [off]\n");
+    fprintf(stderr, "         -W       output that genome coverage as bigWig, <prefix>_<filter>.iteres.bigWig and .iteres.unique.bigWig, with or without -G (an extension) [off]\n");
     fprintf(stderr, "         -R       remove redundant reads [off]\n");
     fprintf(stderr, "         -T       treat 1 paired-end read as 2 single-end reads [off]\n");
     fprintf(stderr, "         -D       discard if only one end mapped in a paired end reads [off]\n");
@@ -50,10 +51,10 @@ int main_filter(int argc, char **argv)
     o.isize = 500;
     o.extension = 150;
     o.min_cov = 0.0001f;
-    int optthreshold = 1, optreadlist = 0, optbam = 0, optindex = 0, optsort = 0, optlevel = -1, optannotate = 0, optgcov = 0, optNorm = 0, c, filterField = 0;
+    int optthreshold = 1, optreadlist = 0, optbam = 0, optindex = 0, optsort = 0, optlevel = -1, optannotate = 0, optgcov = 0, optbigwig = 0, optNorm = 0, c, filterField = 0;
     char *optoutput = NULL, *optname = NULL, *optclass = NULL, *optfamily = NULL;
     const time_t start_time = time(NULL);
-    while ((c = getopt(argc, argv, "SQ:g:N:n:c:t:f:rbisl:aGRTDCE:I:o:h?")) >= 0) {
+    while ((c = getopt(argc, argv, "SQ:g:N:n:c:t:f:rbisl:aGWRTDCE:I:o:h?")) >= 0) {
         switch (c) {
         case 'S': o.is_sam = 1; break;
         case 'Q': o.mapq = (unsigned)strtol(optarg, 0, 0); break;
@@ -66,6 +67,7 @@ int main_filter(int argc, char **argv)
         case 's': optsort = 1; break;
         case 'a': optannotate = 1; break;
         case 'G': optgcov = 1; break;
+        case 'W': optbigwig = 1; break;
         case 'l': {
             char *end = NULL;
             const long v = strtol(optarg, &end, 10);
@@ -127,12 +129,12 @@ int main_filter(int argc, char **argv)
     }
 
     /* what is order-dependent stays with one rank: -R, the read-name lists (-r), the emitted BAM (-b), SAM text; so
-     * does the genome coverage (-G), whose dense arrays are not reduced across ranks */
-    const int splittable = !o.is_sam && !o.dedup && !optreadlist && !optbam && !optgcov;
-    o.gcov = optgcov;
+     * does the genome coverage (-G, -W), whose dense arrays are not reduced across ranks */
+    const int splittable = !o.is_sam && !o.dedup && !optreadlist && !optbam && !optgcov && !optbigwig;
+    o.gcov = optgcov || optbigwig;                /* -W accumulates the coverage -G accumulates, whether or not its text is wanted */
     multi_begin(splittable, o.aln_arg, 0);
     /* (-b: the records parsed ahead are kept as 14 bytes each, their bytes are gone) */
-    stream_prefetch_allow(&o, 1, !o.is_sam && !o.dedup && !optreadlist && !optbam && !optgcov);
+    stream_prefetch_allow(&o, 1, splittable);
     char *outBam = NULL;
     if (optbam) {
         if (asprintf(&outBam, "%s_%s.iteres.bam", output, subfam) < 0) die("Preparing output wrong");
@@ -184,13 +186,17 @@ int main_filter(int argc, char **argv)
             if (names_cnt[r] != res.locus_cnt[r])
                 die("read lists: row %zu has %u names but %u counted reads (ITX_HOST_NAMES=1 builds the lists on the host)", r, names_cnt[r], res.locus_cnt[r]);
     write_filter_out(&rm, res.locus_cnt, locus_names, out, optreadlist, optthreshold, subfam, cnt[nindex], ldev);
-    if (optgcov) {
-        char *outG = NULL, *outGU = NULL;
-        if (asprintf(&outG, "%s_%s.iteres.bedGraph", output, subfam) < 0) die("Preparing output wrong");
-        if (asprintf(&outGU, "%s_%s.iteres.unique.bedGraph", output, subfam) < 0) die("Preparing output wrong");
-        stream_gcov_write(&chr_sizes, outG, outGU);
-        free(outG);
-        free(outGU);
+    if (optgcov || optbigwig) {
+        char *text[2] = {NULL, NULL}, *bw[2] = {NULL, NULL};
+        if (asprintf(&text[0], "%s_%s.iteres.bedGraph", output, subfam) < 0) die("Preparing output wrong");
+        if (asprintf(&text[1], "%s_%s.iteres.unique.bedGraph", output, subfam) < 0) die("Preparing output wrong");
+        if (asprintf(&bw[0], "%s_%s.iteres.bigWig", output, subfam) < 0) die("Preparing output wrong");
+        if (asprintf(&bw[1], "%s_%s.iteres.unique.bigWig", output, subfam) < 0) die("Preparing output wrong");
+        stream_gcov_write(&chr_sizes, optgcov ? (const char *const *)text : NULL, optbigwig ? (const char *const *)bw : NULL);
+        for (int w = 0; w < 2; w++) {
+            free(text[w]);
+            free(bw[w]);
+        }
     }
     loci_dev_free(ldev);
     if (names_cnt) {

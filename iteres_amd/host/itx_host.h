@@ -301,6 +301,17 @@ size_t bw_plan_chroms(const bw_plan *p, const size_t **src, uint32_t *size);
 int bw_plan_levels(const bw_plan *p, const uint32_t **reductions);
 void write_bigwig_device(const bw_plan *p, const char *path, const itx_bw_result *dev);
 void bw_plan_free(bw_plan *p);
+/* Sparse data, the bigWig of a bedGraph (filter -W): what the reference's converter makes of the lines "name start end value".
+ * names / sizes: the chromosomes; items: grouped by chromosome (chrom: index into names), the chromosomes that occur in strcmp order
+ * of their names, starts ascending, no overlap. write_bigwig_sparse builds everything here with zlib (the reference's bytes),
+ * write_bigwig_sparse_device lays the file down around what itx_gcov_bigwig_build left. Both return 0 and write nothing when there
+ * is no item (the converter refuses such an input), 1 otherwise. */
+typedef struct {
+    uint32_t chrom, start, end;
+    float val;
+} bw_item;
+int write_bigwig_sparse(const char *path, const char *const *names, const uint32_t *sizes, const bw_item *items, size_t n_items);
+int write_bigwig_sparse_device(const char *path, const char *const *names, const uint32_t *sizes, const itx_gcov_bw_result *dev);
 /* tables.c: a whole text file in memory, through the same openers as the rmsk file (plain, .gz/.Z, .bz2, .zip) */
 char *slurp_text(const char *path, size_t *len);
 
@@ -339,9 +350,11 @@ int stream_finish(itx_engine *eng, const itx_result *res);
  * lists, every locus_names[row] is a string of its own); stream_names_free releases the lists (locus_names[] point into them) */
 const uint32_t *stream_names_counts(void);
 void stream_names_free(char **locus_names);
-/* filter -G: after run_stream, the two bedGraph files of the coverage the stream accumulated on the device (csrc/itx_gcov.hip):
- * chromosomes in byte-wise order of their names; round k is written while round k + 1 is formatted. Releases the object. */
-void stream_gcov_write(const sizes_t *chr_sizes, const char *path_all, const char *path_uniq);
+/* filter -G / -W: after run_stream, the files of the coverage the stream accumulated on the device (csrc/itx_gcov.hip). text[2]: the
+ * two bedGraph files (NULL: -G was not given, no text round runs), chromosomes in byte-wise order of their names; round k is written
+ * while round k + 1 is formatted. bigwig[2]: the two bigWig files of the same lines (NULL: no -W; csrc/itx_gcovbw.hip, or with
+ * ITX_BW_HOST=1 zlib on the host); a file without a line is not written, one of that name is removed. Releases the object. */
+void stream_gcov_write(const sizes_t *chr_sizes, const char *const *text, const char *const *bigwig);
 
 int main_cpgstat(int argc, char **argv);
 int main_cpgfilter(int argc, char **argv);

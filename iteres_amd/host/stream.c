@@ -1528,17 +1528,41 @@ static void teardown(stream_run *r, int lists_taken)
     }
 }
 
-/* filter -G, after the stream: the chromosomes in byte-wise order of their names (LC_ALL=C sort -k1,1), the change points of both
- * arrays, then each file's text round by round: round k is written while the device formats round k + 1 */
+/* filter -G / -W, after the stream: the chromosomes in byte-wise order of their names (LC_ALL=C sort -k1,1), the change points of
+ * both arrays; then (-W) each file's bigWig content, built on the device from those points and laid down by bigwig.c, and (-G) each
+ * file's text round by round: round k is written while the device formats round k + 1 */
 static const sizes_t *gcov_sort_sizes;
 static int gcov_by_name(const void *a, const void *b)
 {
     return strcmp(gcov_sort_sizes->names.name[*(const uint32_t *)a], gcov_sort_sizes->names.name[*(const uint32_t *)b]);
 }
-void stream_gcov_write(const sizes_t *chr_sizes, const char *path_all, const char *path_uniq)
+
+/* ITX_BW_HOST=1: the items from the change points copied back, everything else by bigwig.c with zlib (the reference's bytes) */
+static int gcov_bigwig_host(itx_gcov *g, int w, const sizes_t *chr_sizes, const uint32_t *order, const uint32_t *size32, const char *path)
+{
+    itx_gcov_stats gs;
+    chk(itx_gcov_get_stats(g, &gs), "itx_gcov_get_stats");
+    const size_t n = (size_t)gs.points[w];
+    uint32_t *pts = xmalloc(16 * (n + 1));
+    chk(itx_gcov_copy_points(g, w, pts), "itx_gcov_copy_points");
+    bw_item *it = xmalloc(sizeof *it * (n + 1));
+    size_t k = 0;
+    for (size_t j = 0; j + 1 < n; j++) {
+        const uint32_t *p = pts + 4 * j, *q = p + 4;
+        if (p[1] == 0 || q[2] != p[2]) continue;
+        it[k++] = (bw_item){order[p[2]], p[0], q[0], (float)(double)p[1]};
+    }
+    /* (the points follow `order`, which is strcmp order: the items are grouped and sorted as the writer wants them) */
+    const int wrote = write_bigwig_sparse(path, (const char *const *)chr_sizes->names.name, size32, it, k);
+    free(it);
+    free(pts);
+    return wrote;
+}
+
+void stream_gcov_write(const sizes_t *chr_sizes, const char *const *text, const char *const *bigwig)
 {
     itx_gcov *g = g_gcov;
-    if (!g) die("filter -G: no coverage was accumulated");
+    if (!g) die("filter -G / -W: no coverage was accumulated");
     const uint32_t n = chr_sizes->names.n;
     uint32_t *order = xmalloc(sizeof(uint32_t) * ((size_t)n + 1));
     for (uint32_t c = 0; c < n; c++) order[c] = c;
@@ -1551,19 +1575,53 @@ void stream_gcov_write(const sizes_t *chr_sizes, const char *path_all, const cha
     const int rc = itx_gcov_finish(g, order, (int)n, nb, no, re && atoll(re) > 0 ? (size_t)atoll(re) : 0);
     if (rc == ITX_E_NOMEM) die("filter -G: %s", itx_last_error());
     chk(rc, "itx_gcov_finish");
-    const char *path[2] = {path_all, path_uniq};
-    double t_write = 0;
-    for (int w = 0; w < 2; w++) {
-        FILE *f = fopen(path[w], "w");
-        if (!f) die("mustOpen: Can't open %s to write: %s", path[w], strerror(errno));
+    double t_write = 0, t_bw = 0;
+    if (bigwig) {
+        /* the visited chromosomes of finish (a size <= 2 has no slots and is not visited) in its order: place -> index */
+        uint32_t *visited = xmalloc(sizeof(uint32_t) * ((size_t)n + 1)), *size32 = xmalloc(sizeof(uint32_t) * ((size_t)n + 1)), nv = 0;
+        for (uint32_t k = 0; k < n; k++)
+            if (chr_sizes->value[order[k]] > 2) visited[nv++] = order[k];
+        for (uint32_t c = 0; c < n; c++) size32[c] = (uint32_t)chr_sizes->value[c];
+        const int host = getenv("ITX_BW_HOST") != NULL;
+        for (int w = 0; w < 2; w++) {
+            const double t0 = now_s();
+            int wrote;
+            if (host) {
+                wrote = gcov_bigwig_host(g, w, chr_sizes, visited, size32, bigwig[w]);
+            } else {
+                const int brc = itx_gcov_bigwig_build(g, w);
+                if (brc == ITX_E_NOMEM || brc == ITX_E_LIMIT) die("filter -W: %s", itx_last_error());
+                chk(brc, "itx_gcov_bigwig_build");
+                itx_gcov_bw_result r;
+                chk(itx_gcov_bigwig_result(g, w, &r), "itx_gcov_bigwig_result");
+                wrote = write_bigwig_sparse_device(bigwig[w], (const char *const *)chr_sizes->names.name, size32, &r);
+                if (wrote && getenv("ITX_TIMING"))
+                    fprintf(stderr, "[itx timing] genome coverage bigWig %d: %llu items, %llu sections, %u levels (first reduction %u after %u tries), %llu blocks; "
+                                    "device: items %.3f ms, chain %.3f ms, fold %.3f ms, deflate %.3f ms\n",
+                            w, (unsigned long long)r.n_items, (unsigned long long)r.n_sec, r.n_levels, r.reduction[0], r.reduce_rounds, (unsigned long long)r.n_blocks,
+                            r.items_ms, r.chain_ms, r.fold_ms, r.deflate_ms);
+            }
+            if (!wrote) {
+                /* the reference's converter refuses an input without a line; a file an earlier run left would be taken for this run's */
+                if (remove(bigwig[w]) != 0 && errno != ENOENT) die("removing %s: %s", bigwig[w], strerror(errno));
+                fprintf(stderr, "* %s is not written: the coverage has no data\n", bigwig[w]);
+            }
+            t_bw += now_s() - t0;
+        }
+        free(visited);
+        free(size32);
+    }
+    for (int w = 0; text && w < 2; w++) {
+        FILE *f = fopen(text[w], "w");
+        if (!f) die("mustOpen: Can't open %s to write: %s", text[w], strerror(errno));
         itx_gcov_text tx;
         do {
             chk(itx_gcov_next(g, w, &tx), "itx_gcov_next");
             const double t0 = now_s();
-            if (tx.len && fwrite(tx.bytes, 1, tx.len, f) != tx.len) die("writing %s: %s", path[w], strerror(errno));
+            if (tx.len && fwrite(tx.bytes, 1, tx.len, f) != tx.len) die("writing %s: %s", text[w], strerror(errno));
             t_write += now_s() - t0;
         } while (tx.more);
-        if (fclose(f) != 0) die("writing %s: %s", path[w], strerror(errno));
+        if (fclose(f) != 0) die("writing %s: %s", text[w], strerror(errno));
     }
     if (getenv("ITX_TIMING")) {
         itx_gcov_stats gs;
@@ -1575,6 +1633,12 @@ void stream_gcov_write(const sizes_t *chr_sizes, const char *path_all, const cha
                 (unsigned long long)gs.points[0], (unsigned long long)gs.points[1], (unsigned long long)gs.lines[0], (unsigned long long)gs.lines[1],
                 (unsigned long long)gs.bytes[0], (unsigned long long)gs.bytes[1], (unsigned long long)gs.rounds[0], (unsigned long long)gs.rounds[1], gs.add_ms, gs.points_ms,
                 gs.text_ms, gs.zero_ms, gs.wait_s, t_write, (unsigned long long)gs.slots, (unsigned long long)gs.device_bytes, gs.alloc_s);
+        if (bigwig)
+            fprintf(stderr, "[itx timing] genome coverage bigWigs: %llu + %llu items, %llu + %llu sections, %llu + %llu levels, %llu + %llu summaries; device %.3f ms; "
+                            "built and written in %.3f s\n",
+                    (unsigned long long)gs.bw_items[0], (unsigned long long)gs.bw_items[1], (unsigned long long)gs.bw_sections[0], (unsigned long long)gs.bw_sections[1],
+                    (unsigned long long)gs.bw_levels[0], (unsigned long long)gs.bw_levels[1], (unsigned long long)gs.bw_summaries[0], (unsigned long long)gs.bw_summaries[1],
+                    gs.bw_ms, t_bw);
     }
     free(nb);
     free(no);
