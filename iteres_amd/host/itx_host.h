@@ -130,7 +130,7 @@ size_t aln_raw_step(size_t left);           /* bytes per read step of a regular 
  * aln_read_batch_device: the next <= cap records of that window as device arrays, valid until the next reader call. */
 int aln_device_window(aln_reader *r, int *flags, const uint8_t **tid_seen);
 /* Device decoder only: fn(ctx, n_rec) is called once for every window right after its records have been located and parsed, in
- * file order, before any of them is handed out (-R on the device marks its duplicates there: stream.c) */
+ * file order, before any of them is handed out (-R on the device marks its duplicates there: stream.c dedup_window) */
 void aln_set_window_hook(aln_reader *r, void (*fn)(void *ctx, size_t n_rec), void *ctx);
 size_t aln_read_batch_device(aln_reader *r, size_t cap, itx_batch *b);
 /* the XA veto over the batch aln_read_batch_device has just handed out (its chosen rows are in the veto object's buffer);
@@ -259,12 +259,12 @@ char *filename_without_ext(const char *path);
 /* Runs the record loop (generic.c:700-1062 / 343-697) over one or more files through the engine.
  * progress_every: 100000 (stat, generic.c:760) or 10000 (filter, generic.c:397). want_qnames: per-locus read
  * names (filter -r): *locus_names[row] receives a comma-joined list in BAM order (NULL: no read chose the row). */
-/* records parsed ahead of the table by the helper thread (stream.c): allowed when nothing per record is the host's business;
+/* records parsed ahead of the table by the helper thread (warmup.c): allowed when nothing per record is the host's business;
  * the size file's table has to be announced once it is loaded */
 void stream_prefetch_allow(const run_opts *o, int filter_mode, int allowed);
 void stream_sizes_ready(const sizes_t *chr_sizes);
-void gpu_warmup_start(int bam_input, const char *aln_arg, int multi_file, int splittable);  /* starts the HIP runtime on a helper thread (and, for BAM input, the device inflater with its
-                                        * page-locked buffers); run_stream joins it */
+void gpu_warmup_start(int bam_input, const char *aln_arg, int multi_file, int splittable);  /* warmup.c: starts the HIP runtime on a helper thread (and, for BAM input, the device inflater
+                                        * with its page-locked buffers); run_stream joins it */
 void run_stream(const run_opts *o, const rmsk_t *rm, const sizes_t *chr_sizes, int filter_mode, int multi_file,
                 unsigned progress_every, int want_qnames, itx_engine **eng_out, itx_table **tab_out, char ***locus_names,
                 host_counts *hc);
@@ -320,7 +320,7 @@ char *slurp_text(const char *path, size_t *len);
  * other devices) before anything touches a GPU; a launcher that starts the ranks
  * itself (bench.py under torch.distributed.run) sets ITX_RANK / ITX_WORLD / ITX_DEVICE / ITX_COMM_ID / ITX_EXCHANGE instead.
  * Every rank parses the same inputs, holds a replica of the table and takes its share of the alignment files' compressed
- * bytes (stream.c); ONE sum-reduce of the engines' partials onto rank 0 ends the stream (include/iteres_amd.h: itx_comm_*),
+ * bytes (stream.c list_files_and_shares; the first file's by the helper thread, warmup.c); ONE sum-reduce of the engines' partials onto rank 0 ends the stream (include/iteres_amd.h: itx_comm_*),
  * rank 0 writes the files, the others leave. */
 void multi_early(int argc, char **argv);            /* from main(): picks up a launcher's rank, quiets ranks > 0 */
 void multi_begin(int splittable, const char *aln_arg, int multi_file);   /* after the options are known, before the first GPU call: starts the other ranks */
@@ -346,11 +346,11 @@ void exchange_comm_early(void);
 void exchange_partials(itx_engine *eng, uint64_t *meta, size_t n_meta, int timing, void **d_u64, void **d_u32);
 /* stream.c: what the writers read — itx_engine_finish, or, after a multi-GPU stream, the same from the reduced partial */
 int stream_finish(itx_engine *eng, const itx_result *res);
-/* filter -r with the lists built on the device: after run_stream, the number of names per table row (NULL: the host built the
+/* out_names.c: filter -r with the lists built on the device: after run_stream, the number of names per table row (NULL: the host built the
  * lists, every locus_names[row] is a string of its own); stream_names_free releases the lists (locus_names[] point into them) */
 const uint32_t *stream_names_counts(void);
 void stream_names_free(char **locus_names);
-/* filter -G / -W: after run_stream, the files of the coverage the stream accumulated on the device (csrc/itx_gcov.hip). text[2]: the
+/* out_gcov.c: filter -G / -W: after run_stream, the files of the coverage the stream accumulated on the device (csrc/itx_gcov.hip). text[2]: the
  * two bedGraph files (NULL: -G was not given, no text round runs), chromosomes in byte-wise order of their names; round k is written
  * while round k + 1 is formatted. bigwig[2]: the two bigWig files of the same lines (NULL: no -W; csrc/itx_gcovbw.hip, or with
  * ITX_BW_HOST=1 zlib on the host); a file without a line is not written, one of that name is removed. Releases the object. */

@@ -199,7 +199,7 @@ def test_rccl_bring_up_with_one_rank(tmp_path):
 @pytest.mark.parametrize("head", [["stat", "-w"], ["filter", "-n", "Rep3"]])
 def test_command_walks_the_rccl_exchange_with_one_rank(head, exe, big_case, tmp_path):
     """ITX_COMM_SELFTEST + ITX_WORLD=1: the command as a job of ONE rank that still makes its RCCL communicator beside the
-    scan (the early thread of host/stream.c), exports its partial, reduces it through ncclReduce and finishes from the reduced
+    scan (the early thread of host/warmup.c), exports its partial, reduces it through ncclReduce and finishes from the reduced
     buffers — the N > 1 path end to end as far as a one-GPU box can take it. Same files as the plain run."""
     d = big_case
     aln = str(d / "a.bam")
@@ -343,7 +343,7 @@ def test_two_launcher_ranks_meet_in_rccl(exe, big_case, tmp_path):
     assert os.listdir(str(tmp_path / "rank1")) == []
 
 
-# ---- records parsed ahead of the table by the helper thread (host/stream.c prefetch_records) ---------------------------------
+# ---- records parsed ahead of the table by the helper thread (host/warmup.c prefetch_records) ---------------------------------
 @pytest.mark.parametrize("head", [["stat", "-w"], ["filter", "-n", "Rep3"], ["stat", "-w", "-x", "-E", "0"]])
 def test_records_parsed_ahead_of_the_table(head, exe, big_case, tmp_path):
     """While the rmsk file is parsed and the table built the helper thread parses the decoded windows and keeps their records in a

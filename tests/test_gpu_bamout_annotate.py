@@ -235,7 +235,7 @@ def test_three_calls_with_host_appends_between(rule, host_rule):
             hrecs = mixed_records(50 + c, 37)
             hhit = pattern("all", 37)
             mine = host_rule(TAB7, hrecs, hhit)
-            assert mine == rt.annotate_rows(hrecs, hhit, *TAB7)             # the C build of the rule, as host/stream.c uses it
+            assert mine == rt.annotate_rows(hrecs, hhit, *TAB7)             # the C build of the rule, as host/out_bam.c uses it
             bo.append_host(b"".join(mine))
             want += mine
     got = bo.finish()
@@ -488,7 +488,7 @@ def test_command(which, pile, exe, tmp_path):
 
 @pytest.mark.parametrize("extra", [(), ("-s", "-i")], ids=["plain", "sorted_indexed"])
 def test_command_both_routes_in_one_file(extra, pile, exe, tmp_path):
-    """mixed.bam: the windows with chrU records take the host route, whose records the host annotates (host/stream.c)"""
+    """mixed.bam: the windows with chrU records take the host route, whose records the host annotates (host/out_bam.c)"""
     root, d, big, name = pile
     with_a = check_command(exe, root, "bamout", d, d / "mixed.bam", tmp_path, ("-c", big), extra)
     r = routes(with_a.stderr)

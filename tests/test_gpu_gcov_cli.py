@@ -123,6 +123,17 @@ def test_with_the_read_lists_and_the_bam(extra, case, exe, bam_run, tmp_path):
         run_filter(exe, d, str(tmp_path / "gh"), ("-G",) + extra, "reads.bam")
         assert graphs(tmp_path / "gh") == bam_run[1]
         same_other_outputs(tmp_path / "gh", tmp_path / "plain")
+    if extra == ("-r", "-b"):
+        # the lists own the batch's rows and the BAM reads them: the BAM is the one -b alone writes from rows of its own, and the lists'
+        # files are the ones -r alone writes
+        run_filter(exe, d, str(tmp_path / "r"), ("-r",), "reads.bam", env)
+        run_filter(exe, d, str(tmp_path / "b"), ("-b",), "reads.bam", env)
+        bams = [fn for fn in os.listdir(tmp_path / "b") if fn.endswith(".bam")]
+        assert len(bams) == 1 and os.path.getsize(tmp_path / "b" / bams[0]) > 28
+        assert filecmp.cmp(tmp_path / "plain" / bams[0], tmp_path / "b" / bams[0], shallow=False)
+        assert os.listdir(tmp_path / "r") and set(os.listdir(tmp_path / "r")) <= set(os.listdir(tmp_path / "plain"))
+        for fn in os.listdir(tmp_path / "r"):
+            assert filecmp.cmp(tmp_path / "plain" / fn, tmp_path / "r" / fn, shallow=False), fn
 
 
 def test_threshold_does_not_change_the_coverage(case, exe, bam_run, tmp_path):

@@ -1,5 +1,5 @@
 """The tags of `filter -b -a` (iteres_amd/csrc/itx_reptag.h, what k_bo_gather<.., true> of csrc/itx_bamout.hip and the host route of
-host/stream.c lay behind a counted record) built for the host (tests/reptag_host.cpp) and held against the Python restatement
+host/out_bam.c lay behind a counted record) built for the host (tests/reptag_host.cpp) and held against the Python restatement
 (tests/reptagcase.py):
 1. whole records: every name length in every position, the coordinates' edge values, records from 36 to 70 000 bytes, seeded pairs;
 2. the piecewise writer: every (from, to) of a short record, every pair of cuts near a field boundary of a long one, guard bytes;
