@@ -465,7 +465,8 @@ int itx_names_get_stats(const itx_names *nm, itx_names_stats *out);
 /* ---- the BAM of filter -b on the device (an extension: the reference writes no such file) -------------------------------------
  * Every record that chose a row, block_size and bytes unchanged and in file order, becomes part of one stream of bytes in device
  * memory; every ITX_BAMOUT_PAYLOAD bytes of it (csrc/itx_bgzfmember.h: 8192) are made one BGZF member there, and the members
- * are handed out packed one behind the other (csrc/itx_bamout.hip). The header's members and the EOF marker are the caller's.
+ * are handed out packed one behind the other (csrc/itx_bamout.hip; the members: csrc/itx_bamout_members.hip). The header's members
+ * and the EOF marker are the caller's.
  *   create      batch_capacity: the most records a batch may carry; stream_bytes: a first size for the stream's buffer
  *               (at least four payloads are taken). Every buffer grows on demand.
  *   hits/stream as for itx_names_*
@@ -527,8 +528,8 @@ typedef struct itx_bamout_index_result {
 } itx_bamout_index_result;
 int itx_bamout_index_enable(itx_bamout *bo, int32_t n_ref, const int32_t *l_ref);
 int itx_bamout_index_finish(itx_bamout *bo, uint64_t first_member_offset, itx_bamout_index_result *out);
-/* The same stream in coordinate order (filter -b -s; the order is csrc/itx_bamsortrule.h: tid, pos, reverse strand, equal keys in
- * stream order). The counted records are held in device memory until the stream ends, sorted there and replayed through the
+/* The same stream in coordinate order (filter -b -s, csrc/itx_bamout_sort.hip; the order is csrc/itx_bamsortrule.h: tid, pos, reverse
+ * strand, equal keys in stream order). The counted records are held in device memory until the stream ends, sorted there and replayed through the
  * member path, so the members are those a plain run over the sorted stream would make.
  *   sort_enable  before the first batch (ITX_E_STATE after it, or when called twice). From then on run / itx_bamwin_bamout /
  *               append_host make no member (nothing is pending, the two-batch limit does not apply), stats.carry counts the held
@@ -548,7 +549,7 @@ typedef struct itx_bamout_sort_stats {
 int itx_bamout_sort_enable(itx_bamout *bo);
 int itx_bamout_sort_next(itx_bamout *bo, int *more);
 int itx_bamout_sort_get_stats(const itx_bamout *bo, itx_bamout_sort_stats *out);
-/* The level of the members (filter -b -l; csrc/itx_bgzflevels.h). Every level frames the same payloads of ITX_BAMOUT_PAYLOAD bytes,
+/* The level of the members (filter -b -l; csrc/itx_bamout_members.hip over csrc/itx_bgzflevels.h). Every level frames the same payloads of ITX_BAMOUT_PAYLOAD bytes,
  * so the records, the index's rule and the sort are untouched; the members' sizes, and with them every virtual offset, differ.
  *   6  the default: csrc/itx_bgzfmember.h, the only level an object has without this call
  *   0  a stored DEFLATE block per member: payload + 31 bytes
@@ -559,7 +560,7 @@ int itx_bamout_sort_get_stats(const itx_bamout *bo, itx_bamout_sort_stats *out);
  *   get_level   the level in use (ITX_E_ARG for a null object) */
 int itx_bamout_set_level(itx_bamout *bo, int level);
 int itx_bamout_get_level(const itx_bamout *bo);
-/* Every counted record tagged with the row it was counted for (filter -b -a; the rule is csrc/itx_reptag.h). Behind the record's own
+/* Every counted record tagged with the row it was counted for (filter -b -a, csrc/itx_bamout_annotate.hip; the rule is csrc/itx_reptag.h). Behind the record's own
  * bytes go ZN:Z:repName, ZC:Z:repClass, ZF:Z:repFamily, ZS:I:genoStart and ZE:I:genoEnd of the row in d_hit_row, 26 bytes and the
  * three names, and block_size grows by as much; nothing else of the record changes. Aux bytes the record has are not looked at: a
  * record that carries one of these tags already gets a second one behind it. The members, the index and the sort take the longer

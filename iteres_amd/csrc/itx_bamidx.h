@@ -1,11 +1,12 @@
-// itx_bamidx.h — internal: what csrc/itx_bamout.hip calls in csrc/itx_bamidx.hip when `filter -b -i` asked for the .bai index.
+// itx_bamidx.h — internal: what the BAM writer (csrc/itx_bamout.hip and, for the members' sizes and the replay of -s,
+// itx_bamout_members.hip and itx_bamout_sort.hip) calls in csrc/itx_bamidx.hip when `filter -b -i` asked for the .bai index.
 // The index object lives inside the itx_bamout object; every call works on the bamout object's stream `st`.
 #pragma once
 #include "itx_common.h"
 
 #define ITX_BAMIDX_TILE 256u         // records per workgroup of the entry kernel: the gather's tile (BO_TILE), whose tile bases it uses
 
-#define ITX_BAMIDX_PAYLOAD 8192u      // bytes of the record stream per member: ITX_BAMOUT_PAYLOAD (itx_bamout.hip asserts it)
+#define ITX_BAMIDX_PAYLOAD 8192u      // bytes of the record stream per member: ITX_BAMOUT_PAYLOAD (itx_bamout_priv.h asserts it)
 
 struct itx_bamidx;
 

@@ -1,6 +1,6 @@
 // itx_bamidx.hip — the .bai index (SAM v1 section 5.2) of the BAM that `iteres filter -b -i` writes, built where the records lie and
 // in the same pass (an extension, as -b is). csrc/itx_bairule.h states what a record contributes; this file collects it and
-// makes the file's bytes. csrc/itx_bamout.hip calls it (itx_bamidx.h) on its own stream.
+// makes the file's bytes. The BAM writer (csrc/itx_bamout*.hip) calls it (itx_bamidx.h) on its own stream.
 //
 // per batch, behind the gather:
 //   k_bi_entries   one lane per record. A counted record (len != 0) walks its CIGAR where it lies and appends one entry
@@ -13,7 +13,7 @@
 // at the end (itx_bamidx_finish), N entries, M members:
 //   k_bi_order     entry i against entry i - 1: (tid, pos) below its predecessor's sets the "unsorted" bit. The flag word is read
 //                  once, here; a set bit ends the work: status, no bytes.
-//   k_bi_coff      exclusive sums of ALL member sizes: coff[0 .. M]
+//   k_size_scan    (itx_textpack.h) exclusive sums of ALL member sizes: coff[0 .. M]
 //   k_bi_heads / k_tile_scan2 / k_bi_chunks   a run of consecutive entries with one key is one chunk: run heads are counted per
 //                  tile, scanned, and every run writes (key, chunk number), its first voff and its last end voff
 //   k_sort_*       (itx_radixsort.h) the chunks sorted by key, stable, so a bin's chunks stay in file order
@@ -114,22 +114,6 @@ __global__ __launch_bounds__(256) void k_bi_order(const BiEnt *__restrict__ ent,
     if (i == 0 || i >= n) return;
     const int32_t ta = (int32_t)(ent[i - 1].key >> 16), tb = (int32_t)(ent[i].key >> 16);
     if (tb < ta || (tb == ta && ent[i].pos < ent[i - 1].pos)) atomicOr(flag, BI_FLAG(ITX_BAI_UNSORTED));
-}
-
-// coff[0 .. n]: exclusive sums of the member sizes (one workgroup)
-__global__ __launch_bounds__(ITX_SCAN_WG) void k_bi_coff(const uint32_t *__restrict__ msize, uint64_t n, uint64_t *__restrict__ coff)
-{
-    __shared__ uint64_t s[ITX_SCAN_WG];
-    uint64_t lo, hi;
-    itx_scan_chunk(n, &lo, &hi);
-    uint64_t a = 0, total;
-    for (uint64_t i = lo; i < hi; i++) a += msize[i];
-    uint64_t e = itx_scan_wg(a, s, &total);
-    for (uint64_t i = lo; i < hi; i++) {
-        coff[i] = e;
-        e += msize[i];
-    }
-    if (threadIdx.x == 0) coff[n] = total;
 }
 
 __device__ __forceinline__ bool bi_run_head(const BiEnt *__restrict__ ent, uint32_t i) { return i == 0 || ent[i].key != ent[i - 1].key; }
@@ -637,7 +621,7 @@ int itx_bamidx_finish(itx_bamidx *ix, hipStream_t st, uint64_t first, itx_bamout
     ITX_TRY(hipMemsetAsync(d_refs, 0, 4 * 7 * ((size_t)n_ref + 1), st));
     ITX_TRY(hipMemsetAsync(d_lin, 0xff, 8 * (W + 1), st));
     ITX_TRY(hipMemsetAsync(d_tot, 0, 16, st));
-    hipLaunchKernelGGL(k_bi_coff, dim3(1), dim3(ITX_SCAN_WG), 0, st, ix->d_ms, M, d_coff);
+    hipLaunchKernelGGL(k_size_scan, dim3(1), dim3(ITX_SCAN_WG), 0, st, ix->d_ms, M, d_coff);
     ITX_TRY(hipGetLastError());
     if (N) {
         hipLaunchKernelGGL(k_bi_heads, dim3(ntN), dim3(BI_TILE), 0, st, ix->d_ent, N, d_ts);

@@ -1,4 +1,4 @@
-// itx_bamsortrule.h — the coordinate order of `iteres filter -b -s`, stated once for the device (csrc/itx_bamout.hip), for the host
+// itx_bamsortrule.h — the coordinate order of `iteres filter -b -s`, stated once for the device (csrc/itx_bamout_sort.hip), for the host
 // (host/stream.c) and for the host build the tests hold against a Python restatement (tests/bamsortrule_host.cpp). Plain C over bytes
 // and integers, valid as C and as C++.
 //

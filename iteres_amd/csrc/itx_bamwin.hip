@@ -8,6 +8,7 @@
 // there; the host then checks the pieces in stream order — a piece counts only if its guess is exactly where the chain
 // of the pieces before it arrives, otherwise it is walked again from there (k_rewalk) — which makes the result exact
 // whatever the guesses were (same scheme as the host reader's locate_records, iteres_amd/host/bamio.c).
+#include "itx_bamout_priv.h"         /* itx_bamout_start */
 #include "itx_device.h"
 #include "itx_inflater.h"
 
@@ -510,8 +511,6 @@ extern "C" int itx_bamwin_names(itx_inflater *h, itx_names *nm, size_t first, si
     const int w = h->parse.parsed_w;
     return itx_names_start(nm, h->wins.win[w].buf, h->parse.d_recoff + first, d_hit_row, n, stream, n_hard);
 }
-
-int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, const int32_t *d_hit_row, size_t n, void *stream);   // itx_bamout.hip
 
 /* records [first, first + n) of the last parsed window that chose a row, appended to the BAM of filter -b (csrc/itx_bamout.hip) */
 extern "C" int itx_bamwin_bamout(itx_inflater *h, itx_bamout *bo, size_t first, size_t n, const int32_t *d_hit_row, void *stream)

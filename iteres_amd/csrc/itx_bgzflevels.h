@@ -1,4 +1,4 @@
-// itx_bgzflevels.h — the levels of a BGZF member of `filter -b -l` (itx_bamout.hip calls it per payload; tests/bgzflevels_host.cpp
+// itx_bgzflevels.h — the levels of a BGZF member of `filter -b -l` (itx_bamout_members.hip calls it per payload; tests/bgzflevels_host.cpp
 // is the host build the device's bytes are held to). The frame, the CRC-32 and ISIZE are itx_bgzfmember.h's at every level; what
 // differs is the DEFLATE block between them:
 //   level 6   itx_bgzf_member, unchanged: the default, and the only level without -l

@@ -1,6 +1,6 @@
 // itx_bgzfmember.h — one BGZF member (the gzip member of SAM/BAM files: RFC 1952 with the 6-byte "BC" extra field) made of a
 // payload of at most ITX_BAMOUT_PAYLOAD bytes, by one wave on a GPU or by one "lane" on the host. The writer of `filter -b`
-// (itx_bamout.hip) calls it per payload; tests/bgzfmember_host.cpp is the host build the device's bytes are held to.
+// (itx_bamout_members.hip) calls it per payload; tests/bgzfmember_host.cpp is the host build the device's bytes are held to.
 //
 // The member:
 //   [0, 18)          1f 8b 08 04, mtime 0, XFL 0, OS 255, XLEN 6, 'B' 'C', SLEN 2, BSIZE = size - 1

@@ -268,8 +268,8 @@ static int bw_start(itx_bigwig *b, itx_engine *e, int uniq, const uint64_t *cov_
     }
     if (b->n_blocks > b->n_sec) k_bw_zoom<<<dim3((uint32_t)(b->n_blocks - b->n_sec)), dim3(64), 0, b->st>>>(d);
     if (b->n_blocks) {
-        k_bw_scan<<<dim3(1), dim3(ITX_SCAN_WG), 0, b->st>>>(b->d_csize, b->n_blocks, b->d_poff);
-        k_bw_gather<<<dim3((uint32_t)b->n_blocks), dim3(256), 0, b->st>>>(b->d_out, b->d_out_off, b->d_csize, b->d_poff, b->d_packed);
+        k_size_scan<<<dim3(1), dim3(ITX_SCAN_WG), 0, b->st>>>(b->d_csize, b->n_blocks, b->d_poff);
+        k_pack_blocks<<<dim3((uint32_t)b->n_blocks), dim3(256), 0, b->st>>>(b->d_out, b->d_out_off, 0u, b->d_csize, b->d_poff, b->d_packed);
     }
     ITX_HIP(hipGetLastError());
     ITX_HIP(hipEventRecord(b->ev1, b->st));

@@ -22,6 +22,7 @@
 //
 // Hooks the including file defines: ITXD_FN (function attributes), ITXD_SYNC() (a barrier of the block's lanes: the
 // wave's workgroup on the device, nothing on the host), ITXD_AMAX(p, v) (atomic max of a uint32 in LDS), ITXD_CTZ(x).
+// Device code includes itx_deflate_device.h, which defines them and has the workspace as an LDS struct.
 #pragma once
 #include <stdint.h>
 

@@ -23,7 +23,8 @@
 // The block's bytes are a pure function of the input bytes, for any number of lanes, on host and device.
 //
 // Hooks, beside the core's: ITXD_AADD(p, v) and ITXD_AOR(p, v), an atomic add and an atomic OR on a uint32_t in LDS (plain
-// operations for one lane on the host). Only files that include this header define them.
+// operations for one lane on the host). The device's are in itx_deflate_device.h with the core's; a host build defines them
+// only when it includes this header.
 #pragma once
 #include "itx_deflate_core.h"
 

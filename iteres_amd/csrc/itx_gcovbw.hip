@@ -27,7 +27,7 @@
 //                step (two 16-byte loads each).
 //   the fold     k_ch_fold: one lane per output summary finds its run and its first item by search and folds in the
 //                reference's order with its widths: double operations, a float (or u32) store after each, no contraction.
-//   zoom blocks  k_gbw_zoom, a wave per 1024 summaries (itx_bwblock.h bw_zoom_block), then k_bw_scan / k_bw_gather pack.
+//   zoom blocks  k_gbw_zoom, a wave per 1024 summaries (itx_bwblock.h bw_zoom_block), then k_size_scan / k_pack_blocks pack.
 // Only the packed blocks, the section keys and the summaries go back to the host. The chain and fold kernels use no scratch; the two
 // deflating kernels have the 144 bytes a lane that itx_deflate_core.h costs the dense builder's kernels too.
 #include "itx_bwblock.h"
@@ -745,9 +745,9 @@ int gcbw_build(int device, hipStream_t st, const uint4 *pts, ull n_pts, const ui
         for (uint32_t k = 0; k < B->n_levels; k++)
             hipLaunchKernelGGL(k_gbw_zoom, dim3((uint32_t)((B->n_sum[k] + kItems - 1) / kItems)), dim3(64), 0, st, level[k].as<itx_bw_summary>(), (uint32_t)B->n_sum[k],
                                B->slot_first[k], d_out_off.as<ull>(), d_out.as<uint8_t>(), d_csize.as<uint32_t>());
-        hipLaunchKernelGGL(k_bw_scan, dim3(1), dim3(ITX_SCAN_WG), 0, st, d_csize.as<uint32_t>(), (uint64_t)nb, d_poff.as<uint64_t>());
-        hipLaunchKernelGGL(k_bw_gather, dim3((uint32_t)nb), dim3(256), 0, st, d_out.as<uint8_t>(), d_out_off.as<uint64_t>(), d_csize.as<uint32_t>(), d_poff.as<uint64_t>(),
-                           d_packed.as<uint8_t>());
+        hipLaunchKernelGGL(k_size_scan, dim3(1), dim3(ITX_SCAN_WG), 0, st, d_csize.as<uint32_t>(), (uint64_t)nb, d_poff.as<uint64_t>());
+        hipLaunchKernelGGL(k_pack_blocks, dim3((uint32_t)nb), dim3(256), 0, st, d_out.as<uint8_t>(), d_out_off.as<uint64_t>(), 0u, d_csize.as<uint32_t>(),
+                           d_poff.as<uint64_t>(), d_packed.as<uint8_t>());
         ITX_TRY(hipGetLastError());
         if ((rc = gbw_lap(st, T, &B->ms[3])) != ITX_OK) goto out;         // (waits: out_off is this function's)
         B->poff.assign((size_t)nb + 1, 0);

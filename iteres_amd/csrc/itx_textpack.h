@@ -15,6 +15,8 @@
 //
 // TILE and LDS are template parameters: bed packs 256 lines through 32 KiB, names 256 names through 16 KiB. The scan routines
 // (wave_incl_scan_u32, itx_scan_chunk, itx_scan_wg) are in itx_device.h.
+// Also here, for blocks that are made apart and packed afterwards (the bigWig blocks, the BAM's members): k_size_scan and
+// k_pack_blocks.
 #pragma once
 #include "itx_device.h"
 
@@ -43,6 +45,35 @@ static __global__ __launch_bounds__(ITX_SCAN_WG) void k_tile_scan2(const unsigne
         tot[0] = ta;
         tot[1] = tb;
     }
+}
+
+// exclusive sums of n sizes: off[0 .. n], 64 bit (the compressed blocks of a bigWig, the members of a BAM batch, all members of
+// a BAM for its index); one workgroup of ITX_SCAN_WG threads, a thread sums a chunk of the sizes when there are more than that
+static __global__ __launch_bounds__(ITX_SCAN_WG) void k_size_scan(const uint32_t *__restrict__ size, uint64_t n, uint64_t *__restrict__ off)
+{
+    __shared__ uint64_t s[ITX_SCAN_WG];
+    uint64_t lo, hi;
+    itx_scan_chunk(n, &lo, &hi);
+    uint64_t a = 0, total;
+    for (uint64_t i = lo; i < hi; i++) a += size[i];
+    uint64_t e = itx_scan_wg(a, s, &total);
+    for (uint64_t i = lo; i < hi; i++) {
+        off[i] = e;
+        e += size[i];
+    }
+    if (threadIdx.x == 0) off[n] = total;
+}
+
+// the blocks one behind the other: block b's size[b] bytes go to packed + dst_off[b] (k_size_scan's offsets), a workgroup per
+// block. src_off: where block b lies in src; null: it lies at b * stride, and a size beyond the stride is cut to it.
+static __global__ __launch_bounds__(256) void k_pack_blocks(const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off, uint32_t stride,
+                                                            const uint32_t *__restrict__ size, const uint64_t *__restrict__ dst_off, uint8_t *__restrict__ packed)
+{
+    const uint64_t b = blockIdx.x;
+    const uint8_t *from = src + (src_off ? src_off[b] : b * stride);
+    uint8_t *dst = packed + dst_off[b];
+    const uint32_t z = src_off || size[b] < stride ? size[b] : stride;
+    for (uint32_t i = threadIdx.x; i < z; i += 256) dst[i] = from[i];
 }
 
 // where the lane's `len` bytes start inside the tile, and the tile's total: wave scan, then the waves' sums through LDS

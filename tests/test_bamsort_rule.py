@@ -1,4 +1,4 @@
-"""The coordinate order of `filter -b -s` (iteres_amd/csrc/itx_bamsortrule.h, what csrc/itx_bamout.hip and host/out_bam.c run) built
+"""The coordinate order of `filter -b -s` (iteres_amd/csrc/itx_bamsortrule.h, what csrc/itx_bamout_sort.hip, csrc/itx_bamout.hip and host/out_bam.c run) built
 for the host (tests/bamsortrule_host.cpp) and held against a Python parse of the record and a Python restatement of the header rule:
 1. the key: both strands at one position, pos 0 and 2^31 - 1, tid 0 and 65 535, tid = -1 and pos = -1 reported, the passes over tid;
 2. the header text: with and without @HD, SO / GO / SS dropped wherever they stand, trailing NULs and every later line untouched;

@@ -120,6 +120,14 @@ def test_a_record_of_three_payloads_and_17_bytes():
     assert len(bai.member_walk(got)) == 4
 
 
+def test_one_batch_of_more_than_1024_members():
+    """more members than the one-workgroup scan of ALL member sizes has threads (k_size_scan, csrc/itx_textpack.h, 1024), so a thread
+    sums several sizes: every chunk's virtual offset rests on those sums. 24 000 counted records in one batch, one reference"""
+    recs = [rec(0, 1000 + 40 * i, L=300 + i % 101) for i in range(24_000)]
+    got, stream, idx, info = check([2_000_000], [("run", recs, all_hit(recs))], first=200, plain=True)
+    assert len(bai.member_walk(got)) > 1024
+
+
 def test_references_without_records_between_references_with_records():
     got, stream, idx, info = check(*shapes.references_without_records(), first=100)
     r = bai.parse_bai(idx)

@@ -143,6 +143,19 @@ def test_a_record_longer_than_three_payloads(rule):
     assert st["members"] >= 4
 
 
+def test_one_batch_of_1026_members(rule):
+    """more members in one batch than the one-workgroup scan of their sizes has threads (k_size_scan, csrc/itx_textpack.h, 1024): a
+    thread sums two sizes and the threads behind the ragged end none. 23 995 records, 1025 whole payloads and a tail"""
+    P = rule.payload
+    recs, total = [], 0
+    while total <= 1025 * P + 100:
+        recs.append(rec_of_len(300 + len(recs) % 101, len(recs)))
+        total += len(recs[-1])
+    assert 1025 * P < total < 1026 * P
+    got, st = run_once(rule, recs, np.full(len(recs), 5, np.int32))
+    assert st["members"] == 1026 and st["batches"] == 1
+
+
 @pytest.mark.parametrize("delta", [-1, 0, 1])
 @pytest.mark.parametrize("k", [1, 3])
 def test_totals_around_whole_payloads(rule, k, delta):

@@ -1,4 +1,4 @@
-"""GPU: the levels of the BAM's members (`filter -b -l`; include/iteres_amd.h itx_bamout_set_level, csrc/itx_bamout.hip
+"""GPU: the levels of the BAM's members (`filter -b -l`; include/iteres_amd.h itx_bamout_set_level, csrc/itx_bamout_members.hip
 k_bo_member_stored / k_bo_member_fast over csrc/itx_bgzflevels.h).
 1. through engine.Bamout, for levels 0 and 1: the device's member sequence equals the host build of the same headers
    (tests/bgzflevels_host.cpp) over payload-sized slices of the expected stream, in the shapes test_gpu_bamout.py uses for the

@@ -1,5 +1,5 @@
 """GPU: `filter -b -s`, the counted records held on the device, sorted by coordinate and replayed through the member path
-(include/iteres_amd.h itx_bamout_sort_*, csrc/itx_bamout.hip; the order is csrc/itx_bamsortrule.h).
+(include/iteres_amd.h itx_bamout_sort_*, csrc/itx_bamout_sort.hip; the order is csrc/itx_bamsortrule.h).
 The oracle is Python and shares no code with the product: sorted(records, key=(tid, pos, reverse)) over the records of the stream as
 -b alone would write it (Python's sort is stable). Every ABI case compares three things with it: the collected members' bytes (the
 host build of the member rule, tests/bgzfmemberhost.py, over payload-sized slices of the sorted stream), the decoded record sequence,

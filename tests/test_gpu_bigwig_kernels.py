@@ -12,7 +12,7 @@ difference arrays, so D = diff(wanted coverage) mod 2^32 makes k_finish_unit's c
             2^24 and its neighbours, uniform uint32, values next to 2^32 - 1, a pile-up with peaks of millions
   geometry  GEOMETRY below: lengths around 1, the section size and the reductions; r0 of 1, 2, 10, 34, 1000; ratios 4, 16
             and 64; 0, 1 and 10 levels; no sequence at all; one sequence of 1.2 M bases (35 zoom blocks at level 0, more
-            than 1024 blocks: k_bw_scan gives a thread several); 2500 short sequences; offsets unordered, with gaps and
+            than 1024 blocks: k_size_scan gives a thread several); 2500 short sequences; offsets unordered, with gaps and
             overlaps
 
 Every (content, geometry) pair is a case; each is checked for uniq 0 and 1: the counts, every block inflating to the
