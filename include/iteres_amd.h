@@ -752,14 +752,16 @@ int itx_samtext_strings(itx_samtext *x, int slot, size_t first, size_t n, int wa
 void itx_timing_report(void);
 
 /* bigWig files of `iteres stat` built on the device from the engine's coverage (csrc/itx_bigwig.hip): every section's
- * payload and every zoom level's summaries (the arithmetic of host/bigwig.c), each block deflated into a zlib stream by
- * csrc/itx_deflate_core.h. The host lays the files down around what comes back (host/bigwig.c write_bigwig_from).
+ * payload and every zoom level's summaries (the arithmetic of host/bw_sum.c, one step of it in csrc/itx_bwfold.h), each block deflated into a zlib stream by
+ * csrc/itx_deflate_core.h. The host lays the files down around what comes back (host/bw_dense.c write_bigwig_device).
  *   start    after itx_engine_finish / itx_engine_finish_partial; uniq: the unique-read coverage instead of all reads;
  *            the chromosomes in bigWig id order as (offset into the coverage, length > 0), the zoom reductions (each a
  *            power-of-4 multiple of the one before). Launches on a stream of its own and returns.
  *   collect  waits, then hands out the results (owned by the build until destroy): the compressed blocks packed one after
  *            the other (sections in file order, then each level's zoom blocks of 1024 summaries), block i at
- *            bytes [block_off[i], block_off[i+1]), and each level's summaries. */
+ *            bytes [block_off[i], block_off[i+1]), and each level's summaries.
+ * Device memory that does not fit is ITX_E_NOMEM ("itx_bigwig_start: no device memory for N bytes"); collect answers ITX_E_LIMIT
+ * if the packed blocks were to exceed the room laid out for them. */
 typedef struct itx_bigwig itx_bigwig;
 typedef struct {
     uint32_t chrom_id, start, end, valid_count;
@@ -781,7 +783,7 @@ void itx_bigwig_destroy(itx_bigwig *b);
 
 /* ---- the bigWig content of filter -W: the genome coverage of filter -G as sparse (bedGraph) data, built on the device ---------------
  * What the reference's converter, bigWigFileCreate(bedGraph, chromSizes, blockSize 256, itemsPerSlot 1024, clip 0, compress 1), makes of
- * the text that itx_gcov_next hands out for file `which` (csrc/itx_gcovbw.hip; the host lays the file down, host/bigwig.c
+ * the text that itx_gcov_next hands out for file `which` (csrc/itx_gcovbw.hip; the host lays the file down, host/bw_sparse.c
  * write_bigwig_sparse_device). An item is a line of that text: [start, end) with (float)(double)depth. Only chromosomes with an item
  * get a bigWig id; ids ascend in finish's order (the command gives strcmp order of the names, which the file's B+ tree needs).
  *   bigwig_build   after itx_gcov_finish (ITX_E_STATE before it, or when the file was built already), before, between or after the

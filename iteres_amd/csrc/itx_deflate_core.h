@@ -1,7 +1,7 @@
 // itx_deflate_core.h — a zlib stream (RFC 1950 around one RFC 1951 block) of at most 32 KiB of input, made by one
 // wave on a GPU, or by one "lane" on the host.
 //
-// What it replaces: zlib's compress() of the bigWig data sections and zoom blocks (bigwig.c z_compress). A bigWig is tens
+// What it replaces: zlib's compress() of the bigWig data sections and zoom blocks (host/bigwig.c z_compress). A bigWig is tens
 // of thousands of independent blocks of <= 32 KiB, each inside one DEFLATE window, so one wave takes one block and the
 // blocks need nothing from each other.
 //

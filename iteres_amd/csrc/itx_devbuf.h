@@ -1,10 +1,39 @@
 // itx_devbuf.h — host only: the plumbing the device objects' host halves share ("Host-side plumbing of the device objects").
 //   itx_grow_alloc, itx_grow_commit   buffers grow and keep what they hold; several are taken together or not at all
 //   itx_copy_out                      device memory to host memory, in chunks through a page-locked pair
+//   ItxBuf, itx_buf_need              a device buffer that lives as long as its scope (a build's working memory, an object's
+//                                     members): made or enlarged on demand WITHOUT keeping what it held, freed by its destructor
 #pragma once
 #include "itx_common.h"
 
 #include <string.h>
+
+struct ItxBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    ItxBuf() = default;
+    ItxBuf(const ItxBuf &) = delete;
+    ItxBuf &operator=(const ItxBuf &) = delete;
+    ~ItxBuf() { drop(); }                    // (the owner has waited for the work that uses it)
+    void drop() { (void)hipFree(p), p = nullptr, cap = 0; }
+    template <class T>
+    T *as() const { return (T *)p; }
+};
+
+// ITX_OK, or ITX_E_NOMEM with "who: no device memory for N bytes" (HIP's error is cleared, the buffer is empty)
+static inline int itx_buf_need(const char *who, ItxBuf &b, size_t bytes)
+{
+    if (bytes <= b.cap && b.p) return ITX_OK;
+    b.drop();
+    if (hipMalloc(&b.p, bytes ? bytes : 16) != hipSuccess) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        itx_set_error("%s: no device memory for %zu bytes", who, bytes);
+        return ITX_E_NOMEM;
+    }
+    b.cap = bytes;
+    return ITX_OK;
+}
 
 // One buffer of a growth: *ptr becomes a buffer of `want` bytes (0: it stays as it is) that holds the first `keep` bytes of the old one.
 struct ItxGrow {

@@ -2,7 +2,7 @@
 // reference's converter would write it from the bedGraph text, built from the change points where they lie.
 //
 // Sparse data is what itx_bigwig.hip never met: `stat` covers every chromosome base by base from 0, so its summaries tile in fixed
-// steps. Here the summaries follow the data (host/bigwig.c add_to_summary is the rule): the first one of a chromosome starts at
+// steps. Here the summaries follow the data (host/bw_sum.c add_to_summary is the rule): the first one of a chromosome starts at
 // the first item's start; the open summary [S, E) takes what reaches into it; an item base at or behind E opens the next one,
 // at E when that base lies before E + R (R: the reduction), at the base itself otherwise (a new ANCHOR); and an item that a
 // boundary cuts gives the fraction overlap / (what is LEFT of the item) to each summary, not overlap / its length.
@@ -27,11 +27,12 @@
 //                step (two 16-byte loads each).
 //   the fold     k_ch_fold: one lane per output summary finds its run and its first item by search and folds in the
 //                reference's order with its widths: double operations, a float (or u32) store after each, no contraction.
-//   zoom blocks  k_gbw_zoom, a wave per 1024 summaries (itx_bwblock.h bw_zoom_block), then k_size_scan / k_pack_blocks pack.
+//   zoom blocks  itx_bwblock.h (layout, k_bw_zoom, packing, copies back); which levels there are is itx_bwzoomrule.h.
 // Only the packed blocks, the section keys and the summaries go back to the host. The chain and fold kernels use no scratch; the two
 // deflating kernels have the 144 bytes a lane that itx_deflate_core.h costs the dense builder's kernels too.
 #include "itx_bwblock.h"
-#include "itx_textpack.h"
+#include "itx_bwfold.h"
+#include "itx_bwzoomrule.h"
 #include "itx_gcovbw.h"
 
 #include <string.h>
@@ -172,17 +173,6 @@ __global__ __launch_bounds__(64) void k_gbw_sections(GbwSec S, const ull *__rest
     __syncthreads();
     const uint32_t z = itxd_deflate(ws_of(s), n, out + out_off[blockIdx.x], lane, 64);
     if (lane == 0) csize[blockIdx.x] = z;
-}
-
-// one wave per zoom block of one level: block b0 + blockIdx.x holds the summaries from 1024 blockIdx.x on
-__global__ __launch_bounds__(64) void k_gbw_zoom(const itx_bw_summary *__restrict__ sum, uint32_t n_sum, ull b0, const ull *__restrict__ out_off,
-                                                 uint8_t *__restrict__ out, uint32_t *__restrict__ csize)
-{
-    __shared__ BwLds<kZoomMax> s;
-    const uint32_t first = blockIdx.x * kItems;
-    const uint32_t cnt = n_sum - first < kItems ? n_sum - first : kItems;
-    const ull b = b0 + blockIdx.x;
-    bw_zoom_block(s, sum + first, cnt, out + out_off[b], &csize[b]);
 }
 
 // ---- the chain
@@ -330,7 +320,7 @@ __global__ __launch_bounds__(kWg) void k_ch_runbase(ChIn I, const uint32_t *__re
     if (i == 0u) run_base[n_runs] = n_cells;
 }
 
-// ---- the fold: host/bigwig.c add_to_summary, one lane per summary. L0: the items are level-0 items (bbiAddRangeToSummary's
+// ---- the fold: host/bw_sum.c add_to_summary with itx_bwfold.h's step, one lane per summary. L0: the items are level-0 items (bbiAddRangeToSummary's
 // numbers: valid count = size, sum = size * val, sum of squares = sum * val), otherwise the summaries of the level below
 template <bool L0>
 __global__ __launch_bounds__(kWg) void k_ch_fold(ChIn I, const uint32_t *__restrict__ anc_list, const uint32_t *__restrict__ run_base, uint32_t n_runs, uint32_t n_out,
@@ -356,8 +346,7 @@ __global__ __launch_bounds__(kWg) void k_ch_fold(ChIn I, const uint32_t *__restr
         if ((e < size ? e : size) > cs) b = mid;
         else a = mid + 1u;
     }
-    uint32_t vc = 0;
-    float mn = 0.0f, mx = 0.0f, sd = 0.0f, sq = 0.0f;
+    itx_bw_summary acc = {c, cs, ce, 0, 0, 0, 0, 0};
     bool fresh = true;
     for (uint32_t i = a; i < ie; i++) {
         uint32_t s, e, ivc;
@@ -387,46 +376,17 @@ __global__ __launch_bounds__(kWg) void k_ch_fold(ChIn I, const uint32_t *__restr
         const int overlap = (int)((ec < ce ? ec : ce) - st), left = (int)(ec - st);
         const double f = (double)overlap / left;
         if (fresh) {
-            mn = (float)imn;
-            mx = (float)imx;
+            itx_bwfold_open(&acc, imn, imx);
             fresh = false;
         }
-        vc = (uint32_t)(vc + f * ivc);
-        if (mn > imn) mn = (float)imn;
-        if (mx < imx) mx = (float)imx;
-        sd = (float)(sd + f * isd);
-        sq = (float)(sq + f * isq);
+        itx_bwfold_add(&acc, f, (double)ivc, imn, imx, isd, isq);
     }
-    out[j] = itx_bw_summary{c, cs, ce, vc, mn, mx, sd, sq};
+    out[j] = acc;
 }
 
 // ---- host side
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-    ~Buf() { (void)hipFree(p); }
-    template <class T>
-    T *as() const { return (T *)p; }
-};
-
-// false: the device cannot hold it (HIP's error is cleared)
-bool need(Buf &b, size_t bytes)
-{
-    if (bytes <= b.cap && b.p) return true;
-    (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    if (hipMalloc(&b.p, bytes ? bytes : 16) != hipSuccess) {
-        (void)hipGetLastError();
-        b.p = nullptr;
-        return false;
-    }
-    b.cap = bytes;
-    return true;
-}
-
 struct Chain {                        // what a chain over n items works in
-    Buf anc, def_list, def_amb, amb_list, anc_list, run_of, run_base, tsum, tbase, tot;
+    ItxBuf anc, def_list, def_amb, amb_list, anc_list, run_of, run_base, tsum, tbase, tot;
     ull *h_tot = nullptr;             // page-locked, 4 words
     ~Chain()
     {
@@ -434,13 +394,9 @@ struct Chain {                        // what a chain over n items works in
     }
 };
 
-#define GBW_NEED(buf, bytes)                                                                          \
-    do {                                                                                              \
-        if (!need((buf), (bytes))) {                                                                  \
-            itx_set_error("itx_gcov_bigwig_build: no device memory for %zu bytes", (size_t)(bytes)); \
-            rc = ITX_E_NOMEM;                                                                         \
-            goto out;                                                                                 \
-        }                                                                                             \
+#define GBW_NEED(buf, bytes)                                                                  \
+    do {                                                                                      \
+        if ((rc = itx_buf_need("itx_gcov_bigwig_build", (buf), (bytes))) != ITX_OK) goto out; \
     } while (0)
 
 struct Timer {
@@ -514,14 +470,11 @@ out:
 }  // namespace
 
 struct GcBw {                         // what a build leaves: host memory only
-    ull n_items = 0, n_sec = 0, n_blocks = 0;
-    uint32_t n_levels = 0, rounds = 0;
+    ull n_items = 0;
+    uint32_t rounds = 0;
     std::vector<uint32_t> chrom, sec_key, sec_count;
-    uint32_t reduction[10] = {0};
-    ull n_sum[10] = {0}, slot_first[10] = {0};
-    std::vector<itx_bw_summary> sum[10];
-    std::vector<uint64_t> poff;
-    std::vector<uint8_t> packed;
+    uint32_t reduction[kBwMaxLevels] = {0};
+    BwPack pack;                      // (its device buffers go when the blocks are back)
     double ms[4] = {0, 0, 0, 0};      // items and sections' numbers, chains, folds, deflate and packing
 };
 
@@ -534,21 +487,12 @@ void gcbw_result(const GcBw *b, itx_gcov_bw_result *out)
     memset(out, 0, sizeof *out);
     out->n_items = b->n_items;
     if (!b->n_items) return;
-    out->n_sec = b->n_sec;
-    out->n_blocks = b->n_blocks;
+    bw_pack_result(b->pack, out);
     out->n_chrom = (uint32_t)b->chrom.size();
-    out->n_levels = b->n_levels;
     out->chrom = b->chrom.data();
     out->sec_key = b->sec_key.data();
     out->sec_count = b->sec_count.data();
-    for (uint32_t k = 0; k < b->n_levels; k++) {
-        out->reduction[k] = b->reduction[k];
-        out->n_sum[k] = b->n_sum[k];
-        out->slot_first[k] = b->slot_first[k];
-        out->sum[k] = b->sum[k].data();
-    }
-    out->block_off = b->poff.data();
-    out->blocks = b->packed.data();
+    for (uint32_t k = 0; k < b->pack.L.n; k++) out->reduction[k] = b->reduction[k];
     out->reduce_rounds = b->rounds;
     out->items_ms = b->ms[0];
     out->chain_ms = b->ms[1];
@@ -577,9 +521,9 @@ int gcbw_build(int device, hipStream_t st, const uint4 *pts, ull n_pts, const ui
     GcBw *B = new GcBw();
     Chain C;
     Timer T;
-    Buf items, first, idmap, sizes, sec_first, item_first, secstat, tsum, tbase, tot, d_out, d_packed, d_out_off, d_poff, d_csize, level[10];
-    std::vector<uint32_t> h_first((size_t)nv + 1, 0u), id_of(nv ? nv : 1, 0u), id_size, id_item_first, h_stat;
-    std::vector<ull> id_sec_first, out_off;
+    ItxBuf items, first, idmap, sizes, sec_first, item_first, secstat, tsum, tbase, tot, level[kBwMaxLevels];
+    std::vector<uint32_t> h_first((size_t)nv + 1, 0u), id_of(nv ? nv : 1, 0u), id_size, id_item_first, h_stat, payload;
+    std::vector<ull> id_sec_first;
     uint32_t n_items = 0, n_chrom = 0, n_sec = 0;
     ull h_tot[2] = {0, 0};
     ITX_TRY(hipSetDevice(device));
@@ -654,7 +598,6 @@ int gcbw_build(int device, hipStream_t st, const uint4 *pts, ull n_pts, const ui
         ITX_TRY(hipMemcpyAsync(h_stat.data(), secstat.p, 20 * (size_t)n_sec, hipMemcpyDeviceToHost, st));
         if ((rc = gbw_lap(st, T, &B->ms[0])) != ITX_OK) goto out;         // (waits: the host vectors above are this function's)
         ull total_res = 0, full_size = 0;
-        B->n_sec = n_sec;
         B->sec_key.resize(3 * (size_t)n_sec);
         B->sec_count.resize(n_sec);
         for (uint32_t s = 0; s < n_sec; s++) {
@@ -666,103 +609,52 @@ int gcbw_build(int device, hipStream_t st, const uint4 *pts, ull n_pts, const ui
             total_res += (ull)(int)q[4];
             full_size += 24 + 12 * (ull)q[3];
         }
-        // ---- the first reduction (bwgCreate.c:833-865): count, look at the size, count again
-        const int min_res = (int)((total_res + n_sec / 2u) / n_sec);
-        long long red = (long long)min_res * 10;
-        const ull max_reduced = full_size / 2;
-        ull last_size = 0, n_cells = 0;
+        // ---- the levels (itx_bwzoomrule.h): the first reduction is counted until it fits, every further one from the last level kept
+        itx_bwzoom Z;
+        uint64_t n_sum[kBwMaxLevels] = {0};
+        ull n_cells = 0;
         uint32_t n_runs = 0;
         ChIn I = {items.as<uint32_t>(), 4u, n_items, (uint32_t)0, sizes.as<uint32_t>()};
-        for (;;) {
-            if (red < 1 || red > 0x3fffffffll) {
-                itx_set_error("itx_gcov_bigwig_build: a first reduction of %lld", red);
-                rc = ITX_E_LIMIT;
-                goto out;
-            }
-            I.red = (uint32_t)red;
+        int w = itx_bwzoom_init(&Z, full_size, (int)((total_res + n_sec / 2u) / n_sec), n_chrom);
+        while (w == ITX_BWZ_COUNT) {
+            I.red = (uint32_t)Z.red;
             if ((rc = chain_count(st, C, I, &n_runs, &n_cells)) != ITX_OK) goto out;
-            B->rounds++;
-            const ull size = 2ull * 32ull * n_cells;
-            if (size >= max_reduced && size != last_size) {
-                long long next = (long long)(int)(1.1 * (int)red * (double)size / (double)max_reduced);
-                if (next < red * 2) next = red * 2;
-                red = next;
-                last_size = size;
-            } else
-                break;
+            w = itx_bwzoom_first(&Z, n_cells);
+        }
+        if (w == ITX_BWZ_RANGE) {
+            itx_set_error("itx_gcov_bigwig_build: a first reduction of %lld", Z.red);
+            rc = ITX_E_LIMIT;
+            goto out;
         }
         if ((rc = gbw_lap(st, T, &B->ms[1])) != ITX_OK) goto out;
         GBW_NEED(level[0], 32 * ((size_t)n_cells + 1));
         if ((rc = chain_fold(st, C, I, true, n_runs, (uint32_t)n_cells, level[0].as<itx_bw_summary>())) != ITX_OK) goto out;
         if ((rc = gbw_lap(st, T, &B->ms[2])) != ITX_OK) goto out;
-        B->n_levels = 1;
-        B->reduction[0] = (uint32_t)red;
-        B->n_sum[0] = n_cells;
-        // ---- further levels (bwgCreate.c:867-885), each from the last level kept
-        ull reduction = (ull)red;
-        for (int i = 0; i < 9; i++) {
-            reduction *= 4;
-            if (reduction > 1000000000ull) break;
-            const uint32_t k = B->n_levels;
-            const ChIn J = {level[k - 1].as<uint32_t>(), 8u, (uint32_t)B->n_sum[k - 1], (uint32_t)reduction, sizes.as<uint32_t>()};
+        n_sum[0] = n_cells;
+        while (itx_bwzoom_next(&Z)) {
+            const int k = Z.n_levels;
+            const ChIn J = {level[k - 1].as<uint32_t>(), 8u, (uint32_t)n_sum[k - 1], (uint32_t)Z.red, sizes.as<uint32_t>()};
             if ((rc = chain_count(st, C, J, &n_runs, &n_cells)) != ITX_OK) goto out;
             if ((rc = gbw_lap(st, T, &B->ms[1])) != ITX_OK) goto out;
-            if (32ull * n_cells != last_size) {
-                GBW_NEED(level[k], 32 * ((size_t)n_cells + 1));
-                if ((rc = chain_fold(st, C, J, false, n_runs, (uint32_t)n_cells, level[k].as<itx_bw_summary>())) != ITX_OK) goto out;
-                if ((rc = gbw_lap(st, T, &B->ms[2])) != ITX_OK) goto out;
-                B->reduction[k] = (uint32_t)reduction;
-                B->n_sum[k] = n_cells;
-                B->n_levels = k + 1;
-            }
-            if (n_cells <= n_chrom) break;
+            if (!itx_bwzoom_keep(&Z, n_cells)) continue;
+            GBW_NEED(level[k], 32 * ((size_t)n_cells + 1));
+            if ((rc = chain_fold(st, C, J, false, n_runs, (uint32_t)n_cells, level[k].as<itx_bw_summary>())) != ITX_OK) goto out;
+            if ((rc = gbw_lap(st, T, &B->ms[2])) != ITX_OK) goto out;
+            n_sum[k] = n_cells;
         }
-        // ---- the blocks: sections, then each level's zoom blocks; deflated, packed, copied back with the summaries
-        ull at = 0, nb = n_sec;
-        for (uint32_t k = 0; k < B->n_levels; k++) {
-            B->slot_first[k] = nb;
-            nb += (B->n_sum[k] + kItems - 1) / kItems;
-        }
-        B->n_blocks = nb;
-        out_off.resize((size_t)nb + 1);
-        for (uint32_t s = 0; s < n_sec; s++) {
-            out_off[s] = at;
-            at += ITXD_OUT_CAP(24u + 12u * B->sec_count[s]);
-        }
-        for (uint32_t k = 0; k < B->n_levels; k++)
-            for (ull j = 0; j < B->n_sum[k]; j += kItems) {
-                out_off[(size_t)(B->slot_first[k] + j / kItems)] = at;
-                at += ITXD_OUT_CAP(32u * (uint32_t)(B->n_sum[k] - j < kItems ? B->n_sum[k] - j : kItems));
-            }
-        out_off[(size_t)nb] = at;
-        GBW_NEED(d_out, (size_t)at + 16);
-        GBW_NEED(d_packed, (size_t)at + 16);
-        GBW_NEED(d_out_off, 8 * ((size_t)nb + 1));
-        GBW_NEED(d_poff, 8 * ((size_t)nb + 1));
-        GBW_NEED(d_csize, 4 * ((size_t)nb + 1));
-        ITX_TRY(hipMemcpyAsync(d_out_off.p, out_off.data(), 8 * ((size_t)nb + 1), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_gbw_sections, dim3(n_sec), dim3(64), 0, st, S, d_out_off.as<ull>(), d_out.as<uint8_t>(), d_csize.as<uint32_t>());
-        for (uint32_t k = 0; k < B->n_levels; k++)
-            hipLaunchKernelGGL(k_gbw_zoom, dim3((uint32_t)((B->n_sum[k] + kItems - 1) / kItems)), dim3(64), 0, st, level[k].as<itx_bw_summary>(), (uint32_t)B->n_sum[k],
-                               B->slot_first[k], d_out_off.as<ull>(), d_out.as<uint8_t>(), d_csize.as<uint32_t>());
-        hipLaunchKernelGGL(k_size_scan, dim3(1), dim3(ITX_SCAN_WG), 0, st, d_csize.as<uint32_t>(), (uint64_t)nb, d_poff.as<uint64_t>());
-        hipLaunchKernelGGL(k_pack_blocks, dim3((uint32_t)nb), dim3(256), 0, st, d_out.as<uint8_t>(), d_out_off.as<uint64_t>(), 0u, d_csize.as<uint32_t>(),
-                           d_poff.as<uint64_t>(), d_packed.as<uint8_t>());
-        ITX_TRY(hipGetLastError());
-        if ((rc = gbw_lap(st, T, &B->ms[3])) != ITX_OK) goto out;         // (waits: out_off is this function's)
-        B->poff.assign((size_t)nb + 1, 0);
-        ITX_TRY(hipMemcpy(B->poff.data(), d_poff.p, 8 * ((size_t)nb + 1), hipMemcpyDeviceToHost));
-        if (B->poff[(size_t)nb] > at) {
-            itx_set_error("itx_gcov_bigwig_build: %llu packed bytes in room for %llu", (ull)B->poff[(size_t)nb], at);
-            rc = ITX_E_LIMIT;
-            goto out;
-        }
-        B->packed.resize((size_t)B->poff[(size_t)nb] + 1);
-        if (B->poff[(size_t)nb]) ITX_TRY(hipMemcpy(B->packed.data(), d_packed.p, (size_t)B->poff[(size_t)nb], hipMemcpyDeviceToHost));
-        for (uint32_t k = 0; k < B->n_levels; k++) {
-            B->sum[k].resize((size_t)B->n_sum[k] + 1);
-            if (B->n_sum[k]) ITX_TRY(hipMemcpy(B->sum[k].data(), level[k].p, 32 * (size_t)B->n_sum[k], hipMemcpyDeviceToHost));
-        }
+        B->rounds = Z.reduce_rounds;
+        memcpy(B->reduction, Z.reduction, sizeof B->reduction);
+        // ---- the blocks (itx_bwblock.h): sections, then each level's zoom blocks; deflated, packed, copied back with the summaries
+        BwPack &P = B->pack;
+        payload.resize(n_sec);
+        for (uint32_t s = 0; s < n_sec; s++) payload[s] = 24u + 12u * B->sec_count[s];
+        if ((rc = bw_pack_layout(P, "itx_gcov_bigwig_build", st, payload.data(), n_sec, (uint32_t)Z.n_levels, n_sum)) != ITX_OK) goto out;
+        for (int k = 0; k < Z.n_levels; k++) P.L.sum[k] = level[k].as<itx_bw_summary>();
+        hipLaunchKernelGGL(k_gbw_sections, dim3(n_sec), dim3(64), 0, st, S, P.out_off.as<ull>(), P.out.as<uint8_t>(), P.csize.as<uint32_t>());
+        if ((rc = bw_pack_run(P, st)) != ITX_OK) goto out;
+        if ((rc = gbw_lap(st, T, &B->ms[3])) != ITX_OK) goto out;
+        if ((rc = bw_pack_collect(P, "itx_gcov_bigwig_build", st)) != ITX_OK) goto out;
+        for (ItxBuf *d : {&P.out, &P.packed, &P.out_off, &P.poff, &P.csize}) d->drop();   // (what is kept is host memory)
     }
 out:
     if (rc != ITX_OK) {

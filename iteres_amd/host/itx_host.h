@@ -289,7 +289,8 @@ void loci_name_table(const names_t *t, char **bytes, uint64_t **off);
 void write_filter_out(const rmsk_t *rm, const uint32_t *locus_cnt, char **locus_names, const char *path, int readlist, int threshold,
                       const char *subfam, unsigned long long reads_num, loci_dev *dev);
 
-/* bigwig.c: the bigWig of one set of wig blocks (stat.c:156-158); only names with a consensus length belong here */
+/* bw_dense.c (with bigwig.c, bw_sum.c; bw_priv.h): the bigWig of one set of wig blocks (stat.c:156-158); only names with a consensus
+ * length belong here */
 void write_bigwig(const char *path, const char *wig_name, const char *const *names, const uint32_t *len, const float *const *val,
                   size_t n_names);
 /* The same file in two steps, with the blocks from the device (include/iteres_amd.h: itx_bigwig_*): the plan is the layout,
@@ -301,7 +302,7 @@ size_t bw_plan_chroms(const bw_plan *p, const size_t **src, uint32_t *size);
 int bw_plan_levels(const bw_plan *p, const uint32_t **reductions);
 void write_bigwig_device(const bw_plan *p, const char *path, const itx_bw_result *dev);
 void bw_plan_free(bw_plan *p);
-/* Sparse data, the bigWig of a bedGraph (filter -W): what the reference's converter makes of the lines "name start end value".
+/* bw_sparse.c: sparse data, the bigWig of a bedGraph (filter -W): what the reference's converter makes of the lines "name start end value".
  * names / sizes: the chromosomes; items: grouped by chromosome (chrom: index into names), the chromosomes that occur in strcmp order
  * of their names, starts ascending, no overlap. write_bigwig_sparse builds everything here with zlib (the reference's bytes),
  * write_bigwig_sparse_device lays the file down around what itx_gcov_bigwig_build left. Both return 0 and write nothing when there

@@ -89,7 +89,7 @@ void gcov_free(stream_run *r)
 }
 
 /* filter -G / -W, after the stream: the chromosomes in byte-wise order of their names (LC_ALL=C sort -k1,1), the change points of
- * both arrays; then (-W) each file's bigWig content, built on the device from those points and laid down by bigwig.c, and (-G) each
+ * both arrays; then (-W) each file's bigWig content, built on the device from those points and laid down by bw_sparse.c, and (-G) each
  * file's text round by round: round k is written while the device formats round k + 1 */
 static const sizes_t *gcov_sort_sizes;
 static int gcov_by_name(const void *a, const void *b)
@@ -97,7 +97,7 @@ static int gcov_by_name(const void *a, const void *b)
     return strcmp(gcov_sort_sizes->names.name[*(const uint32_t *)a], gcov_sort_sizes->names.name[*(const uint32_t *)b]);
 }
 
-/* ITX_BW_HOST=1: the items from the change points copied back, everything else by bigwig.c with zlib (the reference's bytes) */
+/* ITX_BW_HOST=1: the items from the change points copied back, everything else by bw_sparse.c with zlib (the reference's bytes) */
 static int gcov_bigwig_host(itx_gcov *g, int w, const sizes_t *chr_sizes, const uint32_t *order, const uint32_t *size32, const char *path)
 {
     itx_gcov_stats gs;

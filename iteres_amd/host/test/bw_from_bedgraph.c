@@ -1,5 +1,5 @@
 /* bw_from_bedgraph.c — test tool: feeds a bedGraph ("chrom start end value" lines) and a chromosome size file to the product's
- * sparse bigWig writer (bigwig.c write_bigwig_sparse), so the writer can be checked on a machine without a GPU.
+ * sparse bigWig writer (bw_sparse.c write_bigwig_sparse), so the writer can be checked on a machine without a GPU.
  *   bw_from_bedgraph <in.bedGraph> <chrom.sizes> <out.bigWig>
  * Status 255 and no file when the bedGraph has no line, as the reference's converter ends. */
 #define _GNU_SOURCE

@@ -1,5 +1,5 @@
 /* bw_from_wig.c — test tool: feeds a text wig of "fixedStep chrom=<name> start=1 step=1 span=1" blocks to the
- * product's bigWig writer (bigwig.c), so the writer can be checked on a machine without a GPU.
+ * product's bigWig writer (bw_dense.c write_bigwig), so the writer can be checked on a machine without a GPU.
  *   bw_from_wig <in.wig> <out.bigWig> */
 #define _GNU_SOURCE
 #include "../itx_host.h"

@@ -1,4 +1,4 @@
-"""A plain restatement (numpy, no device, no code shared with csrc/itx_bigwig.hip or host/bigwig.c) of what a bigWig
+"""A plain restatement (numpy, no device, no code shared with csrc/itx_bigwig.hip, csrc/itx_bwfold.h or host/bw_sum.c) of what a bigWig
 of `iteres stat` holds for a coverage vector: the data sections, every zoom level's summaries and the zoom blocks.
 
 The summaries follow bbiAddToSummary (cuskent/bbiWrite.c:370-421) for items that tile a sequence from 0: a summary of

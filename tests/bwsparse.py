@@ -171,6 +171,43 @@ def chain(items, sizes, red):
     return out
 
 
+MAX_RED = 0x3fffffff                                      # the reference's BIGNUM: no reduction above it (or below 1) is counted
+
+
+def zoom_levels(full, min_res, n_chrom, count):
+    """which zoom levels a file gets, from counts alone. full: the bytes of all sections' payloads; min_res: the mean of the sections'
+    smallest item lengths; count(red, src): the summaries reduction `red` gives over the data (src None) or over the level of
+    reduction `src`. -> tries (the first reductions counted), refused (the first reduction that was outside 1 .. MAX_RED, or None),
+    levels (the reductions kept), dropped (refused by the size comparison), steps [(reduction, the level it was counted from, kept)]"""
+    red, last, tries = min_res * 10, 0, []
+    out = {"tries": tries, "refused": None, "levels": [], "dropped": [], "steps": []}
+    while True:
+        if not 1 <= red <= MAX_RED:
+            out["refused"] = red
+            return out
+        n = count(red, None)
+        tries.append(red)
+        size = 2 * 32 * n
+        if size >= full // 2 and size != last:
+            red = max(int(1.1 * red * size / (full // 2)), 2 * red)
+            last = size
+        else:
+            break
+    out["levels"].append(red)
+    for _ in range(9):
+        red *= 4
+        if red > 1000000000:
+            break
+        src = out["levels"][-1]
+        n = count(red, src)
+        keep = 32 * n != last
+        out["levels" if keep else "dropped"].append(red)
+        out["steps"].append((red, src, keep))
+        if n <= n_chrom:
+            break
+    return out
+
+
 def pack_summaries(v):
     return b"".join(struct.pack("<IIIIffff", *r) for r in v)
 
@@ -197,29 +234,14 @@ def model(items, sizes):
             size = e - s
             level0.append((cid[n], s, e, size, x, x, size * x, (size * x) * x))
     n_sec = len(sections)
-    red = ((res_sum + n_sec // 2) // n_sec) * 10
-    last, rounds = 0, 0
-    while True:
-        sums = chain(level0, size_of, red)
-        rounds += 1
-        size = 2 * 32 * len(sums)
-        if size >= full // 2 and size != last:
-            red = max(int(1.1 * red * size / (full // 2)), 2 * red)
-            last = size
-        else:
-            break
-    zooms, dropped = [(red, sums)], []
-    for _ in range(9):
-        red *= 4
-        if red > 1000000000:
-            break
-        nxt = chain(zooms[-1][1], size_of, red)
-        if 32 * len(nxt) != last:
-            zooms.append((red, nxt))
-        else:
-            dropped.append(red)
-        if len(nxt) <= len(names):
-            break
+    made = {}
+
+    def count(red, src):
+        made[red] = chain(level0 if src is None else made[src], size_of, red)
+        return len(made[red])
+    z = zoom_levels(full, (res_sum + n_sec // 2) // n_sec, len(names), count)
+    assert z["refused"] is None, z
+    zooms, rounds, dropped = [(r, made[r]) for r in z["levels"]], len(z["tries"]), z["dropped"]
     first = zooms[0][1]
     total = (sum(r[3] for r in first), min(r[4] for r in first), max(r[5] for r in first), _sum_in_order(first, 6), _sum_in_order(first, 7))
     return {"chroms": chroms, "sections": sections, "zooms": [(r, pack_summaries(v)) for r, v in zooms], "total": total,

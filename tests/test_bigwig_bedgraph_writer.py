@@ -1,4 +1,4 @@
-"""The sparse bigWig writer of the host program (iteres_amd/host/bigwig.c write_bigwig_sparse, through the test tool
+"""The sparse bigWig writer of the host program (iteres_amd/host/bw_sparse.c write_bigwig_sparse, through the test tool
 bw_from_bedgraph) against the reference's converter, on CPU: a driver of a few lines (bwsparse.DRIVER) calls bigWigFileCreate from
 oracle/_ref/libcuskent.a on the same bedGraph and size file. The two files are the same bytes (same rule, same zlib), and the model
 of the rule (bwsparse.model) gives the sections and zoom records that the file decodes to.

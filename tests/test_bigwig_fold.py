@@ -1,4 +1,4 @@
-"""The host bigWig writer (iteres_amd/host/bigwig.c, through the test tool bw_from_wig) against tests/bwfold.py, the
+"""The host bigWig writer (iteres_amd/host/bw_dense.c and bw_sum.c, through the test tool bw_from_wig) against tests/bwfold.py, the
 plain numpy restatement of the sections and of bbiAddToSummary's sequential float fold, on wigs that leave the exact
 regime of the golden runs: counts above 2^24 (up to 4294967295), plateaus that make sum_data round at level 0, and
 sequence lengths around the section size and around every reduction the plan picks. And, where the reference binary

@@ -1,4 +1,4 @@
-"""The bigWig writer of the host program (iteres_amd/host/bigwig.c) against the reference's own bigWig files, on CPU:
+"""The bigWig writer of the host program (iteres_amd/host/bw_dense.c write_bigwig, with bigwig.c and bw_sum.c) against the reference's own bigWig files, on CPU:
 the golden wig of a run goes through the writer (test tool bw_from_wig) and must decode to what the reference's
 converter made of the same wig (manifest digests; for one run the reference's bytes are kept and compared in full)."""
 import os
