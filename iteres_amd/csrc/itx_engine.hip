@@ -41,7 +41,39 @@ struct itx_engine {
     double stage_ms[5];
     uint64_t records, submits, keys;
     ItxPartWork *pw;      // scratch of the partition path
+    // u64, u32, the finish-time buffers and the first tid map's records are ONE device allocation: the tail of the partition
+    // path's workspace, or (atomic path) own_base. A hipMalloc holds up the other threads' HIP calls, the decoder's among them.
+    void *own_base;
+    ItxTidRec *tidrec_own;    // a map with more tids than the block has room for: its own allocation
+    hipEvent_t zeroed;        // the accumulators' first zeroing, enqueued on `compute` by itx_engine_create
+    bool zero_pending;        // ... not yet known to be through
+    bool any_batch;           // a batch has been submitted since the last wait for all of them
+    bool finished;            // d_counts, d_cov, ... hold a finish's results
 };
+#define ENGINE_TIDS 4096      // tid records inside the engine's block
+
+// Batches on `compute` follow the zeroing by stream order; any other stream, and the host, wait for its event.
+static int after_zeroing(itx_engine *e, hipStream_t st, bool host)
+{
+    if (!e->zero_pending) return ITX_OK;
+    if (host) {
+        ITX_HIP(hipEventSynchronize(e->zeroed));
+        e->zero_pending = false;
+    } else if (st != e->compute) {
+        ITX_HIP(hipStreamWaitEvent(st, e->zeroed, 0));
+    }
+    return ITX_OK;
+}
+
+// Every batch submitted so far is through, on whichever stream it ran: each left an event behind (run_batch). Not a wait for the
+// device: the decoder's streams are none of the engine's business.
+static int wait_batches(itx_engine *e)
+{
+    if (e->any_batch)
+        for (auto &pr : e->ev) ITX_HIP(hipEventSynchronize(pr.second));
+    e->any_batch = false;
+    return ITX_OK;
+}
 
 static int use_device(const itx_engine *e)
 {
@@ -98,17 +130,34 @@ extern "C" int itx_engine_create(const itx_table *t, const itx_params *p, size_t
     e->records = e->submits = e->keys = 0;
     memset(e->stage_ms, 0, sizeof e->stage_ms);
     e->pw = nullptr;
-    hipError_t he = hipMalloc((void **)&e->u64, (partial_u64(e) + 2) * sizeof(uint64_t));
-    if (he == hipSuccess) he = hipMemset(e->u64, 0, (partial_u64(e) + 2) * sizeof(uint64_t));
-    if (he == hipSuccess) he = hipMalloc((void **)&e->u32, (e->L.n_u32 + 4) * sizeof(uint32_t));
-    if (he == hipSuccess) he = hipMemset(e->u32, 0, (e->L.n_u32 + 4) * sizeof(uint32_t));
+    e->own_base = nullptr;
+    e->tidrec_own = nullptr;
+    e->zeroed = nullptr;
+    e->zero_pending = e->any_batch = e->finished = false;
+    hipError_t he = hipStreamCreateWithFlags(&e->compute, hipStreamNonBlocking);
+    if (he == hipSuccess) he = hipEventCreateWithFlags(&e->zeroed, hipEventDisableTiming);
     if (he != hipSuccess) {
-        itx_set_error("itx_engine_create: device allocation failed: %s", hipGetErrorString(he));
+        itx_set_error("itx_engine_create: stream: %s", hipGetErrorString(he));
         itx_engine_destroy(e);
-        return ITX_E_NOMEM;
+        return ITX_E_NO_DEVICE;
     }
+    // the block: accumulators | own partial | finished results | tid records, each 256-byte aligned
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = off;
+        off = (off + bytes + 255) & ~size_t(255);
+        return o;
+    };
+    const size_t b_u64 = (partial_u64(e) + 2) * sizeof(uint64_t), b_u32 = (e->L.n_u32 + 4) * sizeof(uint32_t);
+    const size_t o_u64 = take(b_u64), o_u32 = take(b_u32);
+    const size_t o_p64 = take(b_u64), o_p32 = take((partial_u32(e) + 4) * sizeof(uint32_t));
+    const size_t o_counts = take(sizeof(uint64_t) * (2 * ((size_t)t->n_rep + t->n_fam + t->n_cla) + 2));
+    const size_t o_cov = take(sizeof(uint32_t) * (t->cov_len + 2)), o_covu = take(sizeof(uint32_t) * (t->cov_len + 2));
+    const size_t o_locus = take(sizeof(uint32_t) * ((size_t)t->n_rows + 2));
+    const size_t o_tid = take(sizeof(ItxTidRec) * (ENGINE_TIDS + 1));
+    char *base = nullptr;
     if (e->p.accum == ITX_ACCUM_PARTITION) {
-        int rc = itx_part_create(t, batch_capacity, &e->pw);
+        int rc = itx_part_create(t, batch_capacity, off, (void **)&base, e->compute, &e->pw);
         if (rc == ITX_E_LIMIT && accum_default) {
             // a slot space beyond the partition path's widest partitions (> 4096 x 65536 consensus slots): the device atomics
             // path gives the same sums, slower; only an explicit ITX_ACCUM_PARTITION request fails
@@ -119,6 +168,34 @@ extern "C" int itx_engine_create(const itx_table *t, const itx_params *p, size_t
             return rc;
         }
     }
+    if (!e->pw) {
+        he = hipMalloc((void **)&base, off);
+        if (he != hipSuccess) {
+            itx_set_error("itx_engine_create: device allocation of %zu bytes failed: %s", off, hipGetErrorString(he));
+            itx_engine_destroy(e);
+            return ITX_E_NOMEM;
+        }
+        e->own_base = base;
+    }
+    e->u64 = (uint64_t *)(base + o_u64);
+    e->u32 = (uint32_t *)(base + o_u32);
+    e->p64 = (uint64_t *)(base + o_p64);
+    e->p32 = (uint32_t *)(base + o_p32);
+    e->d_counts = (uint64_t *)(base + o_counts);
+    e->d_cov = (uint32_t *)(base + o_cov);
+    e->d_cov_uniq = (uint32_t *)(base + o_covu);
+    e->d_locus_out = (uint32_t *)(base + o_locus);
+    e->d_tidrec = (ItxTidRec *)(base + o_tid);
+    e->cap_tid = ENGINE_TIDS;
+    // zeroed on the engine's stream, beside whatever else the device is doing (u64 and u32 lie next to each other)
+    he = hipMemsetAsync(e->u64, 0, o_u32 + b_u32 - o_u64, e->compute);
+    if (he == hipSuccess) he = hipEventRecord(e->zeroed, e->compute);
+    if (he != hipSuccess) {
+        itx_set_error("itx_engine_create: zeroing the accumulators: %s", hipGetErrorString(he));
+        itx_engine_destroy(e);
+        return ITX_E_NO_DEVICE;
+    }
+    e->zero_pending = true;
     *out = e;
     return ITX_OK;
 }
@@ -150,9 +227,9 @@ extern "C" void itx_engine_destroy(itx_engine *e)
             if (e->slot[s].done) (void)hipEventDestroy(e->slot[s].done);
         }
     if (e->compute) (void)hipStreamDestroy(e->compute);
-    void *bufs[] = {e->u64, e->u32, e->d_tidrec, e->p64, e->p32, e->d_counts, e->d_cov, e->d_cov_uniq, e->d_locus_out};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    if (e->zeroed) (void)hipEventDestroy(e->zeroed);
+    if (e->tidrec_own) (void)hipFree(e->tidrec_own);
+    if (e->own_base) (void)hipFree(e->own_base);
     if (e->pw) itx_part_destroy(e->pw);
     delete e;
 }
@@ -170,11 +247,15 @@ extern "C" int itx_engine_set_tidmap(itx_engine *e, const int32_t *tid2chrom, in
         }
     int rc = use_device(e);
     if (rc) return rc;
-    ITX_HIP(hipDeviceSynchronize());   // earlier batches may still read the previous map
+    // earlier batches may still read the previous map: the engine's own batches are waited for, not the device (the first map
+    // of a run has none, and the decoder's queued pushes are not its business)
+    rc = wait_batches(e);
+    if (rc) return rc;
     if (n_tid > e->cap_tid) {
-        if (e->d_tidrec) ITX_HIP(hipFree(e->d_tidrec));
-        e->d_tidrec = nullptr;
-        ITX_HIP(hipMalloc((void **)&e->d_tidrec, sizeof(ItxTidRec) * (size_t)(n_tid + 1)));
+        if (e->tidrec_own) ITX_HIP(hipFree(e->tidrec_own));
+        e->tidrec_own = nullptr;
+        ITX_HIP(hipMalloc((void **)&e->tidrec_own, sizeof(ItxTidRec) * (size_t)(n_tid + 1)));
+        e->d_tidrec = e->tidrec_own;
         e->cap_tid = n_tid;
     }
     // one 32-byte record per BAM reference id: chromosome, its size, its slice of the table and of the binned index
@@ -198,18 +279,10 @@ extern "C" int itx_engine_set_tidmap(itx_engine *e, const int32_t *tid2chrom, in
     return ITX_OK;
 }
 
-static int ensure_compute(itx_engine *e)
-{
-    if (!e->compute) ITX_HIP(hipStreamCreateWithFlags(&e->compute, hipStreamNonBlocking));
-    return ITX_OK;
-}
-
 static int ensure_slots(itx_engine *e)
 {
     if (e->slots_ready) return ITX_OK;
     const size_t n = e->cap + ITX_STREAM_TILE;
-    int rc0 = ensure_compute(e);
-    if (rc0) return rc0;
     for (int s = 0; s < 2; s++) {
         ItxSlot &S = e->slot[s];
         ITX_HIP(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
@@ -271,11 +344,13 @@ static int run_batch(itx_engine *e, const ItxDevBatch &B, size_t n, int32_t *d_h
     P.mode = e->p.mode;
     P.n_tid = e->n_tid;
     P.tidrec = e->d_tidrec;
+    int rc = after_zeroing(e, st, false);
+    if (rc) return rc;
+    e->any_batch = true;
     hipEvent_t a, b;
     ITX_HIP(hipEventCreate(&a));
     ITX_HIP(hipEventCreate(&b));
     ITX_HIP(hipEventRecord(a, st));
-    int rc;
     const bool accumulate = kind == RUN_ACCUMULATE;
     if (accumulate && e->p.accum == ITX_ACCUM_PARTITION) {
         rc = itx_part_run(e->pw, e->t->dev, P, B, n, d_hit_row, e->u64, e->u32, e->L, st);
@@ -396,9 +471,7 @@ extern "C" int itx_engine_submit_device_own(itx_engine *e, const itx_batch *b, s
     }
     int rc = use_device(e);
     if (rc) return rc;
-    rc = ensure_compute(e);                  /* the stream alone: a run that never takes the host route needs no pinned slots */
-    if (rc) return rc;
-    if (n > e->cap) {
+    if (n > e->cap) {                        /* (a run that never takes the host route needs no pinned slots) */
         itx_set_error("itx_engine_submit_device_own: %zu records exceed the batch capacity %zu", n, e->cap);
         return ITX_E_ARG;
     }
@@ -442,6 +515,7 @@ extern "C" int itx_engine_sync(itx_engine *e)
     int rc = use_device(e);
     if (rc) return rc;
     ITX_HIP(hipDeviceSynchronize());
+    e->zero_pending = e->any_batch = false;
     if (e->slots_ready) e->slot[0].busy = e->slot[1].busy = false;
     return ITX_OK;
 }
@@ -496,6 +570,8 @@ extern "C" int itx_engine_export_partial(itx_engine *e, void *d_u64, void *d_u32
     }
     int rc = use_device(e);
     if (rc) return rc;
+    rc = after_zeroing(e, (hipStream_t)stream, false);
+    if (rc) return rc;
     return itx_launch_export(e->t, e->p.mode, e->u64, e->u32, e->L, (uint64_t *)d_u64, (uint32_t *)d_u32, (hipStream_t)stream);
 }
 
@@ -509,23 +585,8 @@ extern "C" int itx_engine_partial_buffers(itx_engine *e, void **d_u64, void **d_
     }
     int rc = use_device(e);
     if (rc) return rc;
-    if (!e->p64) {
-        ITX_HIP(hipMalloc((void **)&e->p64, sizeof(uint64_t) * (partial_u64(e) + 2)));
-        ITX_HIP(hipMalloc((void **)&e->p32, sizeof(uint32_t) * (partial_u32(e) + 4)));
-    }
     *d_u64 = e->p64;
     *d_u32 = e->p32;
-    return ITX_OK;
-}
-
-static int ensure_finish_buffers(itx_engine *e)
-{
-    const itx_table *t = e->t;
-    if (e->d_counts) return ITX_OK;
-    ITX_HIP(hipMalloc((void **)&e->d_counts, sizeof(uint64_t) * (2 * ((size_t)t->n_rep + t->n_fam + t->n_cla) + 2)));
-    ITX_HIP(hipMalloc((void **)&e->d_cov, sizeof(uint32_t) * (t->cov_len + 2)));
-    ITX_HIP(hipMalloc((void **)&e->d_cov_uniq, sizeof(uint32_t) * (t->cov_len + 2)));
-    ITX_HIP(hipMalloc((void **)&e->d_locus_out, sizeof(uint32_t) * ((size_t)t->n_rows + 2)));
     return ITX_OK;
 }
 
@@ -538,13 +599,12 @@ extern "C" int itx_engine_finish_partial(itx_engine *e, const void *d_u64, const
     int rc = use_device(e);
     if (rc) return rc;
     ITX_HIP(hipDeviceSynchronize());
-    rc = ensure_finish_buffers(e);
-    if (rc) return rc;
     const itx_table *t = e->t;
     rc = itx_launch_finish(t, e->p.mode, (const uint64_t *)d_u64, (const uint32_t *)d_u32, e->d_counts, e->d_cov, e->d_cov_uniq,
                            e->d_locus_out, 0);
     if (rc) return rc;
     ITX_HIP(hipDeviceSynchronize());
+    e->finished = true;
     if (out->cnt) {
         uint64_t c[16];
         ITX_HIP(hipMemcpy(c, d_u64, sizeof c, hipMemcpyDeviceToHost));
@@ -577,10 +637,6 @@ extern "C" int itx_engine_finish(itx_engine *e, const itx_result *out)
     }
     int rc = itx_engine_sync(e);
     if (rc) return rc;
-    if (!e->p64) {
-        ITX_HIP(hipMalloc((void **)&e->p64, sizeof(uint64_t) * (partial_u64(e) + 2)));
-        ITX_HIP(hipMalloc((void **)&e->p32, sizeof(uint32_t) * (partial_u32(e) + 4)));
-    }
     rc = itx_launch_export(e->t, e->p.mode, e->u64, e->u32, e->L, e->p64, e->p32, 0);
     if (rc) return rc;
     return itx_engine_finish_partial(e, e->p64, e->p32, out);
@@ -588,7 +644,7 @@ extern "C" int itx_engine_finish(itx_engine *e, const itx_result *out)
 
 int itxe_cov_device(itx_engine *e, int uniq, const uint32_t **cov, uint64_t *cov_len, int *device)
 {
-    if (!e || !e->d_cov || e->p.mode != ITX_MODE_STAT) {
+    if (!e || !e->finished || e->p.mode != ITX_MODE_STAT) {
         itx_set_error("the engine holds no finished coverage (itx_engine_finish first)");
         return ITX_E_STATE;
     }
@@ -610,6 +666,8 @@ extern "C" int itx_engine_get_stats(itx_engine *e, itx_stats *out)
     out->submits = e->submits;
     out->keys = e->keys;
     memcpy(out->stage_ms, e->stage_ms, sizeof e->stage_ms);
+    rc = after_zeroing(e, nullptr, true);
+    if (rc) return rc;
     uint64_t c[16];
     ITX_HIP(hipMemcpy(c, e->u64, sizeof c, hipMemcpyDeviceToHost));
     out->hits = c[9];

@@ -4,7 +4,9 @@
 #include "itx_common.h"
 
 struct ItxPartWork;
-int itx_part_create(const itx_table *t, size_t batch_capacity, ItxPartWork **out);
+// The workspace and, behind it in the SAME device allocation, tail_bytes for the caller (*tail, 256-byte aligned, freed with the
+// workspace). What has to start as zero is zeroed on st, without waiting.
+int itx_part_create(const itx_table *t, size_t batch_capacity, size_t tail_bytes, void **tail, hipStream_t st, ItxPartWork **out);
 void itx_part_destroy(ItxPartWork *w);
 // Folds the per-stage HIP events recorded by itx_part_run since the last call into ms[5]
 // (stream, count, plan, scatter, hist) and returns the keys emitted by the most recent batch.

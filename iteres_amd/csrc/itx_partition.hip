@@ -60,7 +60,7 @@ struct ItxPartWork {
 
 static inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
 
-int itx_part_create(const itx_table *t, size_t cap, ItxPartWork **out)
+int itx_part_create(const itx_table *t, size_t cap, size_t tail_bytes, void **tail, hipStream_t st, ItxPartWork **out)
 {
     // A partition is one or more LDS windows of k_hist (2^ITX_LOGW slots each): as many as keep the partitions within what
     // the per-region LDS tables of k_stream / k_scatter hold. Up to 2^16 slots per partition the 4-byte keys of k_scatter
@@ -100,6 +100,7 @@ int itx_part_create(const itx_table *t, size_t cap, ItxPartWork **out)
     const size_t o_om = off; off = al256(off + (size_t)w->max_blocks * w->n_part * 4);
     const size_t o_it = off; off = al256(off + (size_t)w->max_items * 16);
     const size_t o_ni = off; off = al256(off + 16);
+    const size_t o_tail = off; off = al256(off + tail_bytes);          // the engine's own arrays: one allocation for both
     char *base = nullptr;
     hipError_t he = hipMalloc((void **)&base, off);
     if (he != hipSuccess) {
@@ -108,8 +109,9 @@ int itx_part_create(const itx_table *t, size_t cap, ItxPartWork **out)
         return ITX_E_NOMEM;
     }
     w->base = base;
-    if (hipMemset(base + o_sc, 0, ((size_t)w->n_part * ITX_SUB + 1) * 4) != hipSuccess) {      // k_hist keeps it zero between batches
-        itx_set_error("partition path: hipMemset failed");
+    // k_hist keeps it zero between batches; zeroed on the engine's stream, which every batch of the partition path follows
+    if (hipMemsetAsync(base + o_sc, 0, ((size_t)w->n_part * ITX_SUB + 1) * 4, st) != hipSuccess) {
+        itx_set_error("partition path: hipMemsetAsync failed");
         (void)hipFree(base);
         delete w;
         return ITX_E_NO_DEVICE;
@@ -121,6 +123,7 @@ int itx_part_create(const itx_table *t, size_t cap, ItxPartWork **out)
     w->offm = (uint32_t *)(base + o_om);
     w->items = (uint4 *)(base + o_it);
     w->n_items = (uint32_t *)(base + o_ni);
+    if (tail) *tail = base + o_tail;
     *out = w;
     return ITX_OK;
 }

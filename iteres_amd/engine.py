@@ -19,7 +19,7 @@ ACCUM_DEFAULT, ACCUM_ATOMIC, ACCUM_PARTITION = 0, 1, 2
 
 EXPORTS = [
     "itx_last_error", "itx_abi_version", "itx_device_count", "itx_table_create", "itx_table_destroy",
-    "itx_table_get_info", "itx_table_cov_offsets", "itx_engine_create", "itx_engine_destroy", "itx_engine_set_tidmap",
+    "itx_table_get_info", "itx_table_cov_offsets", "itx_table_debug_copy", "itx_engine_create", "itx_engine_destroy", "itx_engine_set_tidmap",
     "itx_engine_staging", "itx_engine_submit_slot", "itx_engine_classify_slot", "itx_engine_wait_slot", "itx_engine_submit_device",
     "itx_engine_classify_device", "itx_engine_first_hit_slot", "itx_engine_first_hit_device", "itx_engine_sync", "itx_engine_reset", "itx_engine_finish", "itx_engine_get_stats",
     "itx_engine_partial_size", "itx_engine_export_partial", "itx_engine_finish_partial",
@@ -203,6 +203,7 @@ def load():
     L.itx_table_destroy.restype = None
     L.itx_table_get_info.argtypes = [C.c_void_p, C.POINTER(TableInfo)]
     L.itx_table_cov_offsets.argtypes = [C.c_void_p, C.c_void_p]
+    L.itx_table_debug_copy.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.itx_engine_create.argtypes = [C.c_void_p, C.POINTER(Params), C.c_size_t, C.POINTER(C.c_void_p)]
     L.itx_engine_partial_size.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.itx_engine_export_partial.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -384,6 +385,21 @@ class Table:
         _chk(L.itx_table_cov_offsets(self._h, _p(self.cov_off)), "itx_table_cov_offsets")
         self.n_rep, self.n_fam, self.n_cla, self.n_rows = len(rl), int(n_fam), int(n_cla), len(self.rows)
         self.device = device
+
+    # include/iteres_amd.h ITX_TABLE_*: the arrays of the built table, in that order
+    SNAPSHOT = ("iv", "orig", "bl", "row_unit", "part_unit", "unit_slot", "unit_ids", "unit_covoff", "chrom_off", "bin_off")
+
+    def snapshot(self):
+        """Tests only: every array of the built table as raw bytes (itx_table_debug_copy), by name."""
+        L = load()
+        out = {}
+        for which, name in enumerate(self.SNAPSHOT):
+            nb = C.c_size_t(0)
+            _chk(L.itx_table_debug_copy(self._h, which, None, 0, C.byref(nb)), "itx_table_debug_copy")
+            a = np.zeros(nb.value, np.uint8)
+            _chk(L.itx_table_debug_copy(self._h, which, _p(a), a.nbytes, C.byref(nb)), "itx_table_debug_copy")
+            out[name] = a
+        return out
 
     def close(self):
         if getattr(self, "_h", None):

@@ -72,11 +72,14 @@ static void *early_comm_main(void *arg)
     return NULL;
 }
 
+int exchange_comm_early_wanted(void)
+{
+    return (multi_world() > 1 || multi_selftest()) && multi_comm_mode() == ITX_COMM_RCCL && !getenv("ITX_NO_EARLY_COMM");
+}
+
 void exchange_comm_early(void)
 {
-    if ((multi_world() > 1 || multi_selftest()) && multi_comm_mode() == ITX_COMM_RCCL && !getenv("ITX_NO_EARLY_COMM") &&
-        pthread_create(&early_comm.th, NULL, early_comm_main, NULL) == 0)
-        early_comm.on = 1;
+    if (exchange_comm_early_wanted() && pthread_create(&early_comm.th, NULL, early_comm_main, NULL) == 0) early_comm.on = 1;
 }
 
 /* the RCCL communicator the early thread made, when every rank has one; else the files, agreed on through the markers */

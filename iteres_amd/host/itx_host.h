@@ -344,6 +344,7 @@ const char *multi_comm_id(void);
  * communicator beside the scan; exchange_partials exports the engine's partial into its own buffers (*d_u64 / *d_u32), agrees
  * with the other ranks on RCCL or files, sums partials and meta[] onto rank 0 and ends the ranks above 0 */
 void exchange_comm_early(void);
+int exchange_comm_early_wanted(void);   /* this run will make its communicator beside the scan (asked before any thread is started) */
 void exchange_partials(itx_engine *eng, uint64_t *meta, size_t n_meta, int timing, void **d_u64, void **d_u32);
 /* stream.c: what the writers read — itx_engine_finish, or, after a multi-GPU stream, the same from the reduced partial */
 int stream_finish(itx_engine *eng, const itx_result *res);

@@ -244,6 +244,10 @@ static void *warm_main(void *arg)
         }
     }
     const double c = now_s();
+    /* ITX_DECODE_AFTER_TABLE=1 (measuring): the decoder's first push waits until table and engine exist, so that it runs beside
+     * nothing of theirs — the rate it reaches then is the ceiling of a run. Nothing is parsed ahead in such a run. */
+    if (out.inflater && out.first && getenv("ITX_DECODE_AFTER_TABLE") && atoi(getenv("ITX_DECODE_AFTER_TABLE")) != 0)
+        while (!__atomic_load_n(&pre_stop, __ATOMIC_ACQUIRE)) usleep(200);
     if (out.inflater && out.first) {
         /* the first file's header, and its first windows decoded while the main thread is still parsing the rmsk file; a
          * file that does not open is left to run_stream, which reports it where the reference does */
@@ -293,6 +297,13 @@ void gpu_warmup_start(int bam_input, const char *aln_arg, int multi_file, int sp
         }
         free(all);
     }
+    /* A rank that makes its RCCL communicator beside the scan builds its table on the host, as every run did before the device
+     * build: the early thread loads librccl — which registers its kernels with the HIP runtime — and runs ncclCommInitRank at the
+     * very moment the device build would launch its first kernels on the main thread, and such a run (tests/test_cli_multi.py,
+     * one rank walking the RCCL exchange) died with a segmentation fault in one of two tries, before either thread had printed a
+     * timing line. With the host build the main thread launches nothing in that window, as before. Set here, before any other
+     * thread of the process reads the environment; a value the user gave stays. */
+    if (exchange_comm_early_wanted()) setenv("ITX_TABLE_HOST", "1", 0);
     if (!warm_on && pthread_create(&warm_thread, NULL, warm_main, NULL) == 0) warm_on = 1;
 }
 helper_out *gpu_warmup_join(void)
