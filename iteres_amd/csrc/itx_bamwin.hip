@@ -8,6 +8,7 @@
 // there; the host then checks the pieces in stream order — a piece counts only if its guess is exactly where the chain
 // of the pieces before it arrives, otherwise it is walked again from there (k_rewalk) — which makes the result exact
 // whatever the guesses were (same scheme as the host reader's locate_records, iteres_amd/host/bamio.c).
+#include "itx_auxwalk.h"
 #include "itx_bamout_priv.h"         /* itx_bamout_start */
 #include "itx_device.h"
 #include "itx_inflater.h"
@@ -114,35 +115,6 @@ __global__ __launch_bounds__(64) void k_compact(const uint32_t *__restrict__ spe
     for (uint32_t j = threadIdx.x; j < n; j += 64u) rec_off[b + j] = spec[(size_t)t * PIECE_SLOTS + j];
 }
 
-// cussamtools/bam_aux.c:36-48 walk, as the host reader's aux_find: is there an XA tag?
-static __device__ inline bool has_xa(const uint8_t *s, const uint8_t *end)
-{
-    while (s + 3 <= end) {
-        if (s[0] == 'X' && s[1] == 'A') return true;
-        uint32_t type = s[2];
-        if (type >= 'a' && type <= 'z') type -= 32u;
-        s += 3;
-        if (type == 'A' || type == 'C') s += 1;
-        else if (type == 'S') s += 2;
-        else if (type == 'I' || type == 'F') s += 4;
-        else if (type == 'D') s += 8;
-        else if (type == 'Z' || type == 'H') {
-            while (s < end && *s) ++s;
-            ++s;
-        } else if (type == 'B') {
-            if (s + 5 > end) return false;
-            uint32_t sub = s[0];
-            if (sub >= 'a' && sub <= 'z') sub -= 32u;
-            const uint32_t cnt = ld32(s + 1);
-            const uint32_t esz = (sub == 'C' || sub == 'A') ? 1u : (sub == 'S') ? 2u : 4u;
-            if ((uint64_t)cnt * esz > (uint64_t)(end - s)) return false;
-            s += 5u + cnt * esz;
-        } else
-            return false;
-    }
-    return false;
-}
-
 // one thread per record: the fields generic.c:745-905 reads, bam_calend (bam.c:17-27: M, D, N advance) or pos + l_qseq
 __global__ __launch_bounds__(256) void k_parse(const uint8_t *__restrict__ u, const uint32_t *__restrict__ rec_off, uint32_t n, int32_t *__restrict__ tid_o,
                                                int32_t *__restrict__ pos_o, int32_t *__restrict__ end_o, uint8_t *__restrict__ mapq_o, uint8_t *__restrict__ f5_o,
@@ -181,9 +153,11 @@ __global__ __launch_bounds__(256) void k_parse(const uint8_t *__restrict__ u, co
         isize_o[i] = isize;
         paired = flag & 1u;
         if (!(flag & 4u) && tid >= 0 && tid < n_targets) seen[tid] = 1;          /* a mapped record on this reference (generic.c:764,781) */
-        const uint64_t ql = l_qseq > 0 ? (uint64_t)l_qseq : 0;
-        const uint64_t off = (uint64_t)l_qname + 4ull * n_cigar + (ql + 1) / 2 + ql;
-        xa = off < dlen && has_xa(data + off, data + dlen);
+        const uint8_t *as, *ae, *xt;                                             /* is there an XA tag? (itx_auxwalk.h) */
+        if (itx_aux_bounds(p, &as, &ae)) {
+            itx_aux_find(as, ae, ITX_AUX_TAG('X', 'A'), &xt, 0, nullptr);
+            xa = xt != nullptr;
+        }
         xa_o[i] = xa ? 1 : 0;
     }
     const unsigned long long bp = __ballot(paired), bx = __ballot(xa);

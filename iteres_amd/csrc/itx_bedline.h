@@ -5,8 +5,8 @@
 //
 // stated once for the device (csrc/itx_bed.hip) and for the host build the tests hold against an independent parse
 // (tests/bedline_host.cpp). Three steps, all plain C++ over bytes:
-//   itx_bed_scan    what the line takes from the record's own bytes: the read name, the first XA tag (the walk of bam_aux_get,
-//                   bam_aux.c:36-48) and the first NM tag read as bam_aux2i reads it (bam_aux.c:159-170)
+//   itx_bed_scan    what the line takes from the record's own bytes: the read name, the first XA tag and the first NM tag as
+//                   bam_aux_get finds them and bam_aux2Z / bam_aux2i read them (itx_auxwalk.h)
 //   itx_bed_len     the byte length of the line
 //   itx_bed_write   the bytes [lo, hi) of the line, so that a line may be laid down piece by piece (a tile of lines is staged
 //                   in LDS a window at a time, and a long XA string spans windows)
@@ -14,6 +14,8 @@
 // each, independent of one another): no chain of dependent divisions, and any digit can be had without the ones before it.
 #pragma once
 #include <stdint.h>
+
+#include "itx_auxwalk.h"
 
 #ifndef ITX_BED_FN
 #ifdef __HIPCC__
@@ -37,7 +39,7 @@ struct ItxBedLine {
 // What itx_bed_scan finds in a record: offsets are relative to the record's first byte (its block_len field).
 struct ItxBedScan {
     uint32_t qname_len;                    // bytes up to the first NUL; 0 when l_qname == 0 or l_qname > the data length
-    uint32_t xa_off, xa_len;               // xa_off == ITX_BED_NO_XA: no XA tag; a tag of a type other than Z / H: length 0
+    uint32_t xa_off, xa_len;               // xa_off == ITX_BED_NO_XA: no XA tag; a tag that has no string (itx_aux_str): length 0
     int32_t nm;
     bool hard;                             // the name has no NUL before the record ends: not modelled, the host has to look
 };
@@ -56,8 +58,7 @@ ITX_BED_FN ItxBedScan itx_bed_scan(const uint8_t *p, bool want_xa)
     const uint8_t *data = p + 36;
     const uint32_t dlen = block_len - 32u;
     const uint8_t *end = data + dlen;
-    const uint32_t x1 = itx_bed_ld32(p + 12), x2 = itx_bed_ld32(p + 16);
-    const uint32_t l_qname = x1 & 0xffu, n_cigar = x2 & 0xffffu;
+    const uint32_t l_qname = p[12];
     if (l_qname && l_qname <= dlen) {
         const uint8_t *z = data;
         while (z < end && *z) ++z;
@@ -65,51 +66,12 @@ ITX_BED_FN ItxBedScan itx_bed_scan(const uint8_t *p, bool want_xa)
         r.qname_len = (uint32_t)(z - data);
     }
     if (!want_xa) return r;
-    const int32_t l_qseq = (int32_t)itx_bed_ld32(p + 20);
-    const uint64_t ql = l_qseq > 0 ? (uint64_t)l_qseq : 0;
-    const uint64_t off = (uint64_t)l_qname + 4ull * n_cigar + (ql + 1) / 2 + ql;
-    if (off >= dlen) return r;
-    const uint8_t *xa = nullptr, *nmv = nullptr;                    // the TYPE byte of the tag
-    const uint8_t *s = data + off;
-    while (s + 3 <= end && (!xa || !nmv)) {
-        if (!xa && s[0] == 'X' && s[1] == 'A') xa = s + 2;
-        if (!nmv && s[0] == 'N' && s[1] == 'M') nmv = s + 2;
-        uint32_t type = s[2];
-        if (type >= 'a' && type <= 'z') type -= 32u;
-        s += 3;
-        if (type == 'A' || type == 'C') s += 1;
-        else if (type == 'S') s += 2;
-        else if (type == 'I' || type == 'F') s += 4;
-        else if (type == 'D') s += 8;
-        else if (type == 'Z' || type == 'H') {
-            while (s < end && *s) ++s;
-            ++s;
-        } else if (type == 'B') {
-            if (s + 5 > end) break;
-            uint32_t sub = s[0];
-            if (sub >= 'a' && sub <= 'z') sub -= 32u;
-            const uint32_t cnt = itx_bed_ld32(s + 1);
-            const uint32_t esz = (sub == 'C' || sub == 'A') ? 1u : (sub == 'S') ? 2u : 4u;
-            if ((uint64_t)cnt * esz > (uint64_t)(end - s)) break;
-            s += 5u + cnt * esz;
-        } else
-            break;
-    }
+    const uint8_t *as, *ae, *xa, *nmv;                              // the TYPE byte of the tag
+    if (!itx_aux_bounds(p, &as, &ae)) return r;
+    itx_aux_find(as, ae, ITX_AUX_TAG('X', 'A'), &xa, ITX_AUX_TAG('N', 'M'), &nmv);
     if (!xa) return r;                                              // NM is printed only next to XA
-    if (nmv) {
-        const uint8_t ty = *nmv, *q = nmv + 1;
-        if (ty == 'c' && q + 1 <= end) r.nm = (int32_t)(int8_t)q[0];
-        else if (ty == 'C' && q + 1 <= end) r.nm = (int32_t)q[0];
-        else if (ty == 's' && q + 2 <= end) r.nm = (int32_t)(int16_t)(q[0] | q[1] << 8);
-        else if (ty == 'S' && q + 2 <= end) r.nm = (int32_t)(uint16_t)(q[0] | q[1] << 8);
-        else if ((ty == 'i' || ty == 'I') && q + 4 <= end) r.nm = (int32_t)itx_bed_ld32(q);
-    }
-    r.xa_off = (uint32_t)(xa + 1 - p);
-    if (*xa == 'Z' || *xa == 'H') {
-        const uint8_t *z = xa + 1;
-        while (z < end && *z) ++z;                                  // up to its NUL, or the end of the record
-        r.xa_len = (uint32_t)(z - (xa + 1));
-    }
+    r.nm = itx_aux_int(nmv, ae);
+    r.xa_off = (uint32_t)(itx_aux_str(xa, ae, &r.xa_len) - p);
     return r;
 }
 

@@ -21,6 +21,7 @@
 // not by anything a roofline prices — it has to beat a PCIe round trip of the window, and does by an order of magnitude.
 #include "itx_device.h"
 #include "itx_derive.h"
+#include "itx_auxwalk.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -61,8 +62,6 @@ struct itx_xaveto {
     size_t cap;
     hipStream_t st;
 };
-
-static __device__ inline uint32_t xld32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 
 // strtol(s, 0, 0) on [s, e) as far as plain decimal goes: optional sign, digits; stops at the first other byte. *hard is set for
 // what base 0 would read differently (leading blanks, a leading 0 followed by more, more than nine digits).
@@ -121,57 +120,14 @@ __global__ __launch_bounds__(256) void k_xa_verdict(ItxDevTable T, XaDev D, cons
         (void)itx_derive(&D.o, tr.x, tr.y, f5_a[i], pos_a[i], end_a[i], mpos_a ? mpos_a[i] : 0, isize_a ? isize_a[i] : 0, &st, &en, &strand);
         const int32_t qlen = (int32_t)(en - st);
         const uint32_t word = D.rep_word[D.row_rep[h]];
-        // ---- the tags: first XA (any type) and first NM, each by the walk of bam_aux_get
+        // ---- the tags: first XA (any type) and first NM, each by the walk of bam_aux_get (itx_auxwalk.h)
         const uint8_t *p = u + rec_off[i];
-        const uint32_t block_len = xld32(p);
-        const uint8_t *data = p + 36;
-        const uint32_t dlen = block_len - 32u;
-        const uint32_t x1 = xld32(p + 12), x2 = xld32(p + 16);
-        const uint32_t l_qname = x1 & 0xffu, n_cigar = x2 & 0xffffu;
-        const int32_t l_qseq = (int32_t)xld32(p + 20);
-        const uint64_t ql = l_qseq > 0 ? (uint64_t)l_qseq : 0;
-        const uint64_t off = (uint64_t)l_qname + 4ull * n_cigar + (ql + 1) / 2 + ql;
-        const uint8_t *end = data + dlen;
-        const uint8_t *xa = nullptr, *nmv = nullptr;                // the TYPE byte of the tag
-        if (off < dlen) {
-            const uint8_t *s = data + off;
-            while (s + 3 <= end && (!xa || !nmv)) {
-                if (!xa && s[0] == 'X' && s[1] == 'A') xa = s + 2;
-                if (!nmv && s[0] == 'N' && s[1] == 'M') nmv = s + 2;
-                uint32_t type = s[2];
-                if (type >= 'a' && type <= 'z') type -= 32u;
-                s += 3;
-                if (type == 'A' || type == 'C') s += 1;
-                else if (type == 'S') s += 2;
-                else if (type == 'I' || type == 'F') s += 4;
-                else if (type == 'D') s += 8;
-                else if (type == 'Z' || type == 'H') {
-                    while (s < end && *s) ++s;
-                    ++s;
-                } else if (type == 'B') {
-                    if (s + 5 > end) break;
-                    uint32_t sub = s[0];
-                    if (sub >= 'a' && sub <= 'z') sub -= 32u;
-                    const uint32_t cnt = xld32(s + 1);
-                    const uint32_t esz = (sub == 'C' || sub == 'A') ? 1u : (sub == 'S') ? 2u : 4u;
-                    if ((uint64_t)cnt * esz > (uint64_t)(end - s)) break;
-                    s += 5u + cnt * esz;
-                } else
-                    break;
-            }
-        }
-        int32_t nm = 0;                                              // bam_aux2i, bam_aux.c:159-170
-        if (nmv) {
-            const uint8_t ty = *nmv, *q = nmv + 1;
-            if (ty == 'c' && q + 1 <= end) nm = (int32_t)(int8_t)q[0];
-            else if (ty == 'C' && q + 1 <= end) nm = (int32_t)q[0];
-            else if (ty == 's' && q + 2 <= end) nm = (int32_t)(int16_t)(q[0] | q[1] << 8);
-            else if (ty == 'S' && q + 2 <= end) nm = (int32_t)(uint16_t)(q[0] | q[1] << 8);
-            else if ((ty == 'i' || ty == 'I') && q + 4 <= end) nm = (int32_t)xld32(q);
-        }
-        if (xa && (*xa == 'Z' || *xa == 'H')) {
-            const uint8_t *s = xa + 1, *z = s;
-            while (z < end && *z) ++z;                               // the string: up to its NUL, or the end of the record
+        const uint8_t *as, *end, *xa = nullptr, *nmv = nullptr;     // the TYPE byte of the tag
+        if (itx_aux_bounds(p, &as, &end)) itx_aux_find(as, end, ITX_AUX_TAG('X', 'A'), &xa, ITX_AUX_TAG('N', 'M'), &nmv);
+        const int32_t nm = itx_aux_int(nmv, end);                   // bam_aux2i, bam_aux.c:159-170
+        uint32_t xlen;
+        const uint8_t *s = itx_aux_str(xa, end, &xlen), *const z = s + xlen;
+        if (xa) {                                                    // a tag that is no string, or runs out of the record: the empty string
             bool hard = false, veto = false;
             uint32_t fields = 0;
             // chopByChar(ahstring, ';', row, 100): 100 fields at most, what follows the 100th ';' is not looked at

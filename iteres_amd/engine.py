@@ -261,6 +261,16 @@ def load():
     L.itx_bamwin_bed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
     L.itx_bed_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Batch), C.c_size_t, C.POINTER(C.c_uint64)]
     L.itx_bed_wait_kernels.argtypes = [C.c_void_p]
+    L.itx_bamwin_device_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(Batch)]
+    L.itx_xaveto_create.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
+    L.itx_xaveto_destroy.argtypes = [C.c_void_p]
+    L.itx_xaveto_destroy.restype = None
+    L.itx_xaveto_set_tidmap.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.itx_xaveto_hits.argtypes = [C.c_void_p]
+    L.itx_xaveto_hits.restype = C.c_void_p
+    L.itx_xaveto_stream.argtypes = [C.c_void_p]
+    L.itx_xaveto_stream.restype = C.c_void_p
+    L.itx_bamwin_xa_veto.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.itx_bed_collect.argtypes = [C.c_void_p, C.POINTER(BedText)]
     L.itx_bed_get_stats.argtypes = [C.c_void_p, C.POINTER(BedStats)]
     L.itx_names_create.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]
@@ -682,6 +692,45 @@ class Dedup:
     def close(self):
         if self._h:
             load().itx_dedup_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class XaVeto:
+    """The XA / NM veto on the device (include/iteres_amd.h itx_xaveto_*, replacing generic.c:303-341 and 972-982) over the records of
+    an Inflater's last parsed window. `judge` classifies records [first, first + n) with the engine into the object's own buffer of
+    chosen rows, the way the command does, lets the device read their tags and returns (n_vetoed, n_hard): with n_hard > 0
+    nothing was marked, else the vetoed records carry ITX_F5_NOLOOKUP in the window's flag5."""
+
+    def __init__(self, engine: "Engine", row_rep, rep_word, chrom_names, batch_capacity: int = 1 << 20):
+        rr = np.ascontiguousarray(row_rep, np.uint32)
+        rw = np.ascontiguousarray(rep_word, np.uint32)
+        names = (C.c_char_p * len(chrom_names))(*[s if isinstance(s, bytes) else s.encode() for s in chrom_names])
+        self.engine = engine
+        self._h = C.c_void_p()
+        _chk(load().itx_xaveto_create(engine.table._h, C.byref(engine.params), _p(rr), _p(rw), names, len(chrom_names), batch_capacity, C.byref(self._h)), "itx_xaveto_create")
+
+    def set_tidmap(self, tid2chrom):
+        a = np.ascontiguousarray(tid2chrom, np.int32)
+        _chk(load().itx_xaveto_set_tidmap(self._h, _p(a), len(a)), "itx_xaveto_set_tidmap")
+
+    def judge(self, inflater, first, n, with_mates=False):
+        L = load()
+        db = Batch()
+        _chk(L.itx_bamwin_device_batch(inflater._h, first, int(with_mates), C.byref(db)), "itx_bamwin_device_batch")
+        _chk(L.itx_engine_classify_device(self.engine._h, C.byref(db), n, L.itx_xaveto_hits(self._h), L.itx_xaveto_stream(self._h)), "itx_engine_classify_device")
+        vetoed, hard = C.c_uint64(), C.c_uint64()
+        _chk(L.itx_bamwin_xa_veto(inflater._h, self._h, first, n, C.byref(vetoed), C.byref(hard)), "itx_bamwin_xa_veto")
+        return vetoed.value, hard.value
+
+    def close(self):
+        if self._h:
+            load().itx_xaveto_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -4,6 +4,7 @@
 #ifndef ALN_PRIV_H
 #define ALN_PRIV_H
 #include "itx_host.h"
+#include "../csrc/itx_auxwalk.h"
 
 #include <ctype.h>
 #include <pthread.h>
@@ -285,46 +286,6 @@ static inline char *xstrndup_bound(const char *s, size_t max)
     return d;
 }
 
-/* bam_aux.c:36-48 (the aux walk of bam_aux_get): pointer to the type byte of the first tag `t0 t1`, or NULL */
-static inline const uint8_t *aux_find(const uint8_t *s, const uint8_t *end, char t0, char t1)
-{
-    while (s + 3 <= end) {
-        const int hit = s[0] == (uint8_t)t0 && s[1] == (uint8_t)t1;
-        const int type = toupper(s[2]);
-        if (hit) return s + 2;
-        s += 3;
-        if (type == 'A' || type == 'C') s += 1;
-        else if (type == 'S') s += 2;
-        else if (type == 'I' || type == 'F') s += 4;
-        else if (type == 'D') s += 8;
-        else if (type == 'Z' || type == 'H') {
-            while (s < end && *s) ++s;
-            ++s;
-        } else if (type == 'B') {
-            if (s + 5 > end) return NULL;
-            const int sub = toupper(s[0]);
-            const uint32_t cnt = rd_u32(s + 1);
-            const size_t esz = (sub == 'C' || sub == 'A') ? 1 : (sub == 'S') ? 2 : 4;
-            s += 5 + (size_t)cnt * esz;
-        } else
-            return NULL;
-    }
-    return NULL;
-}
-
-/* bam_aux2i, bam_aux.c:159-170 */
-static inline int32_t aux_to_int(const uint8_t *s, const uint8_t *end)
-{
-    if (!s) return 0;
-    const int type = *s++;
-    if (type == 'c' && s + 1 <= end) return (int32_t)(int8_t)s[0];
-    if (type == 'C' && s + 1 <= end) return (int32_t)s[0];
-    if (type == 's' && s + 2 <= end) return (int32_t)(int16_t)(s[0] | s[1] << 8);
-    if (type == 'S' && s + 2 <= end) return (int32_t)(uint16_t)(s[0] | s[1] << 8);
-    if ((type == 'i' || type == 'I') && s + 4 <= end) return rd_i32(s);
-    return 0;
-}
-
 /* bam.c:179-210 for one record that is completely in memory */
 static inline void bam_parse_one(const uint8_t *p, size_t n, itx_staging *st, aln_side *side, int *any_paired, int *aux_xa)
 {
@@ -356,9 +317,9 @@ static inline void bam_parse_one(const uint8_t *p, size_t n, itx_staging *st, al
     st->isize[n] = isize;
     if (flag & 1) *any_paired = 1;
     if (side && side->want_qnames) side->qname[n] = xstrdup(l_qname && l_qname <= dlen ? (const char *)data : "");
-    const size_t ql = l_qseq > 0 ? (size_t)l_qseq : 0;
-    const size_t off = (size_t)l_qname + 4 * (size_t)n_cigar + (ql + 1) / 2 + ql;
-    const uint8_t *xa = off < dlen ? aux_find(data + off, data + dlen, 'X', 'A') : NULL;
+    /* the optional fields as the reference walks and reads them: ../csrc/itx_auxwalk.h */
+    const uint8_t *as, *ae, *xa = NULL, *nmv = NULL;
+    if (itx_aux_bounds(p, &as, &ae)) itx_aux_find(as, ae, ITX_AUX_TAG('X', 'A'), &xa, ITX_AUX_TAG('N', 'M'), side && side->want_aux ? &nmv : NULL);
     if (xa) *aux_xa = 1;
     if (side && side->want_aux) {
         side->xa[n] = NULL;
@@ -366,10 +327,10 @@ static inline void bam_parse_one(const uint8_t *p, size_t n, itx_staging *st, al
         if (xa) {
             /* bam_aux2Z (bam_aux.c:193-199): the string of a Z/H tag; an XA tag of another type has no string the
              * reference could copy (it would crash there) and reads as empty here */
-            const uint8_t *e = data + dlen;
-            const char *z = (*xa == 'Z' || *xa == 'H') ? (const char *)(xa + 1) : "";
-            side->xa[n] = xstrndup_bound(z, (*xa == 'Z' || *xa == 'H') ? (size_t)(e - (xa + 1)) : 0);
-            side->nm[n] = aux_to_int(aux_find(data + off, e, 'N', 'M'), e);
+            uint32_t xl;
+            const uint8_t *z = itx_aux_str(xa, ae, &xl);
+            side->xa[n] = xstrndup_bound((const char *)z, xl);
+            side->nm[n] = itx_aux_int(nmv, ae);
         }
     }
 }

@@ -188,7 +188,7 @@ class Reads:
     isize: np.ndarray            # int32
     cigars: list                 # list[list[(op_char, len)]] ([] = '*')
     qname: list
-    aux: list | None = None      # optional list[bytes-like str] of SAM aux text fields e.g. ["NM:i:1", "XA:Z:..."]
+    aux: list | None = None      # optional, per read: list[str] of SAM aux text fields e.g. ["NM:i:1", "XA:Z:..."], or the raw BAM bytes (write_bam only)
 
     def __len__(self):
         return len(self.tid)
@@ -315,6 +315,8 @@ def _reg2bin(beg, end):
 
 
 def _aux_bin(fields):
+    if isinstance(fields, (bytes, bytearray)):           # the optional fields as they lie in the record
+        return bytes(fields)
     out = bytearray()
     for fld in fields or ():
         tag, ty, val = fld.split(":", 2)

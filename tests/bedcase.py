@@ -1,4 +1,4 @@
-"""Records with awkward names and tags as raw BAM bytes, an independent reading of them, and the bed lines of `stat -B / -V`
+"""Records with awkward names and tags as raw BAM bytes, an independent reading of them (the tags: tests/auxmodel.py), and the bed lines of `stat -B / -V`
 formatted from that reading with Python's own `%` — what tests/test_bedline.py and tests/test_gpu_bed.py hold the shared line
 rule (iteres_amd/csrc/itx_bedline.h) and the device build (csrc/itx_bed.hip) against. The derivation of (start, end, strand)
 is goldencase.derive_py, the suite's own statement of generic.c:764-905."""
@@ -6,6 +6,7 @@ import struct
 
 import numpy as np
 
+import auxmodel
 import goldencase as gc
 import refio
 from iteres_amd import synth
@@ -36,49 +37,9 @@ def bam_bytes(header, records, block=0xff00):
 
 # ---- the independent reading
 
-_FIXED = {"A": 1, "c": 1, "C": 1, "s": 2, "S": 2, "i": 4, "I": 4, "f": 4, "d": 8}
-
-
-def _tags(aux):
-    """(name, type, value bytes) of every tag, as far as the walk of bam_aux_get gets (bam_aux.c:36-48: the size of a tag goes by
-    its type letter without case; an unknown type ends the walk)"""
-    out, p = [], 0
-    while p + 3 <= len(aux):
-        name, ty = aux[p:p + 2], chr(aux[p + 2])
-        p += 3
-        up = ty.upper()
-        if up in ("A", "C"):
-            q = p + 1
-        elif up == "S":
-            q = p + 2
-        elif up in ("I", "F"):
-            q = p + 4
-        elif up == "D":
-            q = p + 8
-        elif up in ("Z", "H"):
-            z = aux.find(b"\0", p)
-            out.append((name, ty, aux[p:] if z < 0 else aux[p:z]))
-            p = len(aux) + 1 if z < 0 else z + 1
-            continue
-        elif up == "B":
-            out.append((name, ty, b""))
-            if p + 5 > len(aux):
-                break
-            sub = chr(aux[p]).upper()
-            cnt, = struct.unpack_from("<I", aux, p + 1)
-            p += 5 + cnt * (1 if sub in ("C", "A") else 2 if sub == "S" else 4)
-            continue
-        else:
-            out.append((name, ty, b""))
-            break
-        out.append((name, ty, aux[p:q]))
-        p = q
-    return out
-
-
 def read_record(rec):
-    """qname / XA / NM of one record the way the reference takes them: bam1_qname up to its NUL, bam_aux_get's first XA (string
-    only for Z / H), bam_aux2i of the first NM"""
+    """qname / XA / NM of one record the way the reference takes them: bam1_qname up to its NUL; XA and NM by the literal model of
+    bam_aux_get, bam_aux2Z and bam_aux2i (tests/auxmodel.py), with the project's rule where the reference leaves the record"""
     bl, = struct.unpack_from("<i", rec, 0)
     tid, pos, x1, x2, l_qseq, mtid, mpos, isize = struct.unpack_from("<iiIIiiii", rec, 4)
     lq, mapq, flag, ncig = x1 & 0xff, (x1 >> 8) & 0xff, x2 >> 16, x2 & 0xffff
@@ -94,15 +55,9 @@ def read_record(rec):
         if c & 0xf in (0, 2, 3):
             e += c >> 4
     tmpend = e if ncig else pos + l_qseq
-    off = lq + 4 * ncig + (max(l_qseq, 0) + 1) // 2 + max(l_qseq, 0)
-    tags = _tags(data[off:]) if off < len(data) else []
-    xa = next((t for t in tags if t[0] == b"XA"), None)
-    nmt = next((t for t in tags if t[0] == b"NM"), None)
-    nm = 0
-    if nmt is not None and len(nmt[2]) == _FIXED.get(nmt[1], -1) and nmt[1] in "cCsSiI":
-        nm = struct.unpack("<" + {"c": "b", "C": "B", "s": "h", "S": "H", "i": "i", "I": "i"}[nmt[1]], nmt[2])[0]
+    a = auxmodel.answer(rec)
     return dict(tid=tid, pos=pos, tmpend=tmpend, mapq=mapq, flag=flag,
-                mpos=mpos, isize=isize, qname=qname, has_xa=xa is not None, xa=(xa[2] if xa is not None and xa[1] in "ZH" else b""), nm=nm)
+                mpos=mpos, isize=isize, qname=qname, has_xa=a.has_xa, xa=a.p_xa, nm=a.p_nm)
 
 
 def soa(recs):

@@ -15,6 +15,8 @@ import zlib
 
 import numpy as np
 
+import auxmodel
+
 
 def open_maybe_gz(path, mode="rt"):
     if os.path.exists(path):
@@ -197,35 +199,12 @@ def read_bam(path):
         recs["mpos"].append(mpos)
         recs["isize"].append(isize)
         recs["qname"].append(qname)
-        aux = _bam_aux(raw[p + 4 * n_cig + (l_seq + 1) // 2 + l_seq: off + 4 + bs])
-        recs["xa"].append(aux.get("XA"))
-        recs["nm"].append(int(aux.get("NM", 0)) if "XA" in aux else 0)
+        # the first XA and NM as the reference's walk finds and reads them (tests/auxmodel.py)
+        a = auxmodel.Answer(raw[p + 4 * n_cig + (l_seq + 1) // 2 + l_seq: off + 4 + bs])
+        recs["xa"].append(a.p_xa.decode("latin-1") if a.has_xa else None)
+        recs["nm"].append(a.p_nm)
         off += 4 + bs
     return header, _to_arrays(recs)
-
-
-def _bam_aux(b: bytes):
-    """first value of every aux tag (cussamtools/bam_aux.c:36-48 walk)"""
-    out, i = {}, 0
-    fixed = {"A": "<c", "c": "<b", "C": "<B", "s": "<h", "S": "<H", "i": "<i", "I": "<I", "f": "<f", "d": "<d"}
-    while i + 3 <= len(b):
-        tag, ty = b[i:i + 2].decode(), chr(b[i + 2])
-        i += 3
-        if ty in fixed:
-            v, = struct.unpack_from(fixed[ty], b, i)
-            i += struct.calcsize(fixed[ty])
-        elif ty in "ZH":
-            j = b.index(b"\0", i)
-            v = b[i:j].decode()
-            i = j + 1
-        elif ty == "B":
-            sub, cnt = chr(b[i]), struct.unpack_from("<I", b, i + 1)[0]
-            i += 5 + cnt * struct.calcsize(fixed[sub])
-            v = None
-        else:
-            break
-        out.setdefault(tag, v)
-    return out
 
 
 # ------------------------------------------------------------------------------ outputs of the reference

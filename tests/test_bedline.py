@@ -1,7 +1,8 @@
 """The bed line of `stat -B / -V` (iteres_amd/csrc/itx_bedline.h, the rule csrc/itx_bed.hip runs per record) built for the host
 (tests/bedline_host.cpp) against lines formatted by Python's own `%` from an independent reading of the records
 (tests/bedcase.py): names of length 0, 1 and 254, a name with a NUL inside, MAPQ 0 and 255, coordinates of 1 to 10 digits, every
-NM type, XA absent / empty / kilobytes long / without its NUL / of a type that is no string, a B array before XA, -C names; and
+NM type, XA absent / empty / kilobytes long / without its NUL / of a type that is no string / behind a float the reference's walk
+gets lost in (tests/auxmodel.py), a B array before XA, -C names; and
 every line laid down in pieces of 1, 7 and 64 bytes, as the device lays it down window by window."""
 import ctypes as C
 import os
@@ -71,10 +72,12 @@ def test_expected_text_has_the_corners_in_it():
     p = bc.params(extension=0)
     want_b, want_v, _, _ = bc.lines(p, HEADER, [n for n, _ in HEADER], [l for _, l in HEADER], bc.corner_records())
     for piece in (b"\t\t37\t", b"\ta\t", b"\t" + b"q" * 254 + b"\t", b"\tab\t", b"\t0\t-", b"\t255\t-", b"\t2147483647\t", b"\t0\t1\tp0\t", b"\t-5\tchr1,", b"\t200\t",
-                  b"\t-30000\t", b"\t65535\t", b"\t-2147483648\t", b"\t-294967296\t", b"\t2147483647\tchr1,", b"\t+\t0\t\n", b"no terminating NUL;\n", b"\t4\t\n",
+                  b"\t-30000\t", b"\t65535\t", b"\t-2147483648\t", b"\t-294967296\t", b"\t2147483647\tchr1,", b"\t+\t0\t\n", b"\t603\t653\tr1\t37\t+\t2\t\n", b"\t4\t\n",
                   b"\t300\tafter,+1,2M,0;\n", b"\t0\t1AE301\n"):
         assert piece in want_b, piece
     assert b"unreachable" not in want_b and b"behind an unknown" not in want_b and b"\tun\t" not in want_b
+    assert b"no terminating NUL" not in want_b                      # a string that runs out of its record reads as empty
+    assert b"\t500\t550\tr1\t37\t+\n" in want_b                      # XA behind NM:f: the reference walks into the float and never finds it
     assert max(len(l) for l in want_b.split(b"\n")) > 5000
     assert b"chr1," not in want_v and 0 < want_v.count(b"\n") < want_b.count(b"\n")
 
