@@ -77,7 +77,7 @@ typedef struct itx_table_info {
 int itx_table_get_info(const itx_table *t, itx_table_info *out);
 /* TEST ONLY: one array of a built table copied to the host, so that the device build and the host build (ITX_TABLE_HOST=1) can be
  * compared array by array. *bytes receives the array's size; dst NULL: nothing else happens; otherwise cap_bytes must hold it.
- * The layouts are internal (csrc/itx_common.h) and may change with any release. */
+ * The layouts are internal (csrc/itx_tablebuild.h, csrc/itx_common.h) and may change with any release. */
 enum { ITX_TABLE_IV = 0, ITX_TABLE_ORIG = 1, ITX_TABLE_BL = 2, ITX_TABLE_ROW_UNIT = 3, ITX_TABLE_PART_UNIT = 4, ITX_TABLE_UNIT_SLOT = 5,
        ITX_TABLE_UNIT_IDS = 6, ITX_TABLE_UNIT_COVOFF = 7, ITX_TABLE_CHROM_OFF = 8, ITX_TABLE_BIN_OFF = 9 };
 int itx_table_debug_copy(const itx_table *t, int which, void *dst, size_t cap_bytes, size_t *bytes);

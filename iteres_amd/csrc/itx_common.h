@@ -6,24 +6,7 @@
 #include <time.h>
 
 #include "../../include/iteres_amd.h"
-
-#define ITX_LOGW 13         // slots per partition / LDS window of the partition path (W = 8192)
-
-// One interval of the device table, 32 bytes (two dwordx4 loads). Intervals of a chromosome are
-// contiguous and sorted by (start, file order).
-struct __attribute__((aligned(16))) ItxIv {
-    // first 16 bytes: all the overlap scan reads
-    int32_t  s, e;        // genomic [s, e)
-    int32_t  pbelow;      // max e over this chromosome's intervals BELOW this one (INT32_MIN for the first): a scan that
-                          // walks down from here goes on only while pbelow > query start
-    uint32_t rank;        // position in binKeeperFind's list order within the chromosome (binRange.c:209-225)
-    // second 16 bytes: read once, for the chosen row
-    uint32_t cs;          // consensus_start as the reference parses it (generic.c:1596-1600)
-    uint32_t jcap;        // min(consensus_end, repeat length): first consensus index NOT incremented
-    uint32_t covslot;     // first slot of the interval's unit inside the slot space (rep_len+1 slots per unit)
-    uint32_t zslot;       // covslot + rep_len: the unit's extra slot (never part of the coverage output)
-};
-static_assert(sizeof(ItxIv) == 32, "ItxIv must be 32 bytes");
+#include "itx_tablebuild.h"         // ITX_LOGW, ItxIv: the table's records, visible to a build without HIP
 
 // Device view of the table (passed to kernels by value).
 struct ItxDevTable {

@@ -14,7 +14,7 @@ at batch_capacity. The partition path was checked for the same alignment: itx_pa
 span from the same itx_stream_plan and hands it to itx_launch_stream, which refuses any span that is not a multiple of
 the tile; only the number of workgroups may be capped there (max_blocks), which moves no tile.
 
-Index (itx_table.hip). The rows of a chromosome are sorted stably by start; bl[g].x is the number of rows with
+Index (itx_tablebuild.h). The rows of a chromosome are sorted stably by start; bl[g].x is the number of rows with
 s < g << shift, bl[g].y the first row whose prefix-maximum end exceeds g << shift. The builders keep the genome below
 about 8 Mbp with a few thousand rows, so shift is 7; the GPU test asserts TableInfo.bin_shift == SHIFT.
 
