@@ -583,6 +583,32 @@ int itx_bamout_get_level(const itx_bamout *bo);
 int itx_bamout_annotate_enable(itx_bamout *bo, const itx_row *rows, size_t n_rows, const char *rep_bytes, const uint64_t *rep_off, uint32_t n_rep,
                                const char *cla_bytes, const uint64_t *cla_off, uint32_t n_cla, const char *fam_bytes, const uint64_t *fam_off, uint32_t n_fam);
 int itx_bamout_annotate_get_stats(const itx_bamout *bo, uint64_t *tag_bytes);
+/* The mates of the counted pairs in the sorted stream (filter -b -s -m, csrc/itx_bamout_mates.hip; the rule is csrc/itx_materule.h).
+ * Without -T a proper pair is counted through its READ1 alone, so the stream holds half of every counted fragment. In mates mode every
+ * record of a batch that could be such a mate (a candidate: paired, not READ1, mapped with a mapped mate, primary) is kept in a candidate
+ * store in device memory beside the held stream. The first sort_next joins: a held counted record that is paired with a mapped mate
+ * (wanted) looks up (mtid, mpos, name) among the candidates, the first candidate in stream order that matches byte for byte is chosen,
+ * and every chosen candidate is appended once to the held stream before it is sorted; the candidate store is freed. Equal sort keys:
+ * counted records first, mates behind, each in input order. With annotate_enable a mate carries the tags of the row its (earliest)
+ * READ1 was counted for.
+ *   mates_enable  after sort_enable, before the first batch (ITX_E_STATE without sort_enable, after the first batch, or when called twice).
+ *   mates_append_host  whole records of a window the caller counted itself, all of them, in stream order between the device batches
+ *               (beside append_host, which takes the counted ones): the candidates among them join the store. Bytes that are not
+ *               whole records: ITX_E_ARG, nothing appended. ITX_E_STATE without mates_enable or once sort_next was called.
+ *   mates_host_rows  with annotate_enable: the chosen rows of the records of the NEXT append_host, one per record (the host-route READ1s'
+ *               mates need them for their tags); append_host is refused with ITX_E_STATE without them and with ITX_E_ARG when their
+ *               number differs. Without annotate_enable the call is not needed.
+ *   mates_get_stats  candidates held and their bytes, times the store grew, wanted and found (after the first sort_next), device time.
+ * 2^32 - 2 candidates or more: ITX_E_LIMIT. The candidates of a paired file are about half its inflated bytes, held beside the -s
+ * stream until the join: ITX_E_NOMEM says to run without -m. */
+typedef struct itx_bamout_mates_stats {
+    uint64_t candidates, candidate_bytes, grows, wanted, found;
+    double gather_ms, join_ms;               /* device time: the batches' candidate measure, gather and entries; the sort, join and append */
+} itx_bamout_mates_stats;
+int itx_bamout_mates_enable(itx_bamout *bo);
+int itx_bamout_mates_append_host(itx_bamout *bo, const void *bytes, size_t len);
+int itx_bamout_mates_host_rows(itx_bamout *bo, const int32_t *rows, size_t n);
+int itx_bamout_mates_get_stats(const itx_bamout *bo, itx_bamout_mates_stats *out);
 
 /* ---- the genome coverage of filter -G on the device (an extension: the reference writes no such file) ------------------------------
  * The depth of the counted reads over the chromosomes of the size file, as two bedGraph texts: all counted reads, and those with

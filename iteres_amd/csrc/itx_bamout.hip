@@ -32,6 +32,9 @@
 // chunks, the held stream of -s (annotated at the first gather; the replay copies byte for byte). Without the call the <false>
 // instantiations run.
 //
+// With itx_bamout_mates_enable (filter -b -s -m, itx_bamout_mates.hip) a batch's candidate mates are gathered into a store of their
+// own behind the counted gather (bm_batch), and the first sort_next joins the wanted ones to the held stream (bm_join).
+//
 // Every buffer that grows (bo_reserve) grows by the two-phase rule of itx_devbuf.h.
 // Byte and integer work. No kernel of this file uses scratch (DESIGN.md has the figures).
 #include "itx_bamout_priv.h"
@@ -159,6 +162,7 @@ extern "C" void itx_bamout_destroy(itx_bamout *bo)
     (void)hipFree(bo->d_hist);
     (void)hipFree(bo->d_soff);
     (void)hipFree(bo->d_ann);
+    bm_destroy(bo);
     itx_bamidx_destroy(bo->ix);
     delete bo;
 }
@@ -246,21 +250,27 @@ out:
     return rc;
 }
 
-int bo_launch_gather(itx_bamout *bo, const uint8_t *u, const void *rec_off, uint32_t n, const int32_t *hit_row)
+int bo_launch_gather_at(itx_bamout *bo, int wide, int ann, const uint8_t *u, const void *rec_off, uint32_t n, const uint32_t *len_in, const ull *tile_base, ull base,
+                        uint8_t *pay, const int32_t *hit_row)
 {
     int rc = ITX_OK;
     const dim3 grid((n + BO_TILE - 1) / BO_TILE), wg(BO_TILE);
-    if (bo->sort == 2)
-        hipLaunchKernelGGL((k_bo_gather<ull, false>), grid, wg, 0, bo->st, u, (const ull *)rec_off, n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->d_pay, hit_row, bo->ann);
-    else if (bo->annotate)
-        hipLaunchKernelGGL((k_bo_gather<uint32_t, true>), grid, wg, 0, bo->st, u, (const uint32_t *)rec_off, n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->d_pay, hit_row,
-                           bo->ann);
+    if (wide && ann)
+        hipLaunchKernelGGL((k_bo_gather<ull, true>), grid, wg, 0, bo->st, u, (const ull *)rec_off, n, len_in, tile_base, base, pay, hit_row, bo->ann);
+    else if (wide)
+        hipLaunchKernelGGL((k_bo_gather<ull, false>), grid, wg, 0, bo->st, u, (const ull *)rec_off, n, len_in, tile_base, base, pay, hit_row, bo->ann);
+    else if (ann)
+        hipLaunchKernelGGL((k_bo_gather<uint32_t, true>), grid, wg, 0, bo->st, u, (const uint32_t *)rec_off, n, len_in, tile_base, base, pay, hit_row, bo->ann);
     else
-        hipLaunchKernelGGL((k_bo_gather<uint32_t, false>), grid, wg, 0, bo->st, u, (const uint32_t *)rec_off, n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->d_pay, hit_row,
-                           bo->ann);
+        hipLaunchKernelGGL((k_bo_gather<uint32_t, false>), grid, wg, 0, bo->st, u, (const uint32_t *)rec_off, n, len_in, tile_base, base, pay, hit_row, bo->ann);
     ITX_TRY(hipGetLastError());
 out:
     return rc;
+}
+
+int bo_launch_gather(itx_bamout *bo, const uint8_t *u, const void *rec_off, uint32_t n, const int32_t *hit_row)
+{
+    return bo_launch_gather_at(bo, bo->sort == 2, bo->sort != 2 && bo->annotate, u, rec_off, n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->d_pay, hit_row);
 }
 
 int bo_reserve(itx_bamout *bo, ull total, ull n_mem)
@@ -350,7 +360,7 @@ int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, 
     if (bo->ix && !bo->sort && (rc = itx_bamidx_reserve(bo->ix, bo->st, bo->h_tot[1], total / BO_P)) != ITX_OK) goto out;
     ITX_TRY(hipEventRecord(bo->ev[2], bo->st));
     if (bo->h_tot[0] && (rc = bo_launch_gather(bo, u, rec_off, (uint32_t)n, d_hit_row)) != ITX_OK) goto out;
-    if (bo->sort && bo->h_tot[1] && (rc = bs_entries(bo, u, rec_off, (uint32_t)n, bo->h_tot[1])) != ITX_OK) goto out;
+    if (bo->sort && bo->h_tot[1] && (rc = bs_entries(bo, u, rec_off, (uint32_t)n, bo->h_tot[1], bo->mates ? d_hit_row : nullptr)) != ITX_OK) goto out;
     ITX_TRY(hipEventRecord(bo->ev[3], bo->st));
     bo->gather_timed = 1;
     if (bo->ix && !bo->sort &&
@@ -362,6 +372,7 @@ int itx_bamout_start(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, 
     bo->tag_bytes += bo->h_tot[4];
     if (bo->sort) bo->carry = (size_t)total;
     else rc = bo_emit(bo, total, 0);
+    if (rc == ITX_OK && bo->mates == 1) rc = bm_batch(bo, u, rec_off, (uint32_t)n);
 out:
     return rc;
 }
@@ -385,6 +396,14 @@ extern "C" int itx_bamout_wait_kernels(itx_bamout *bo)
         ITX_TRY(hipEventSynchronize(bo->ev[3]));
         bo->stats.wait_ms += 1e3 * (itx_wall_now() - t0);
         bo_read_gather_time(bo);
+    }
+    if (bo->mates_timed) {                                                 // (-m: the candidate gather and its entry kernel read the window too)
+        float ms = 0;
+        const double t0 = itx_wall_now();
+        ITX_TRY(hipEventSynchronize(bo->mev[1]));
+        bo->stats.wait_ms += 1e3 * (itx_wall_now() - t0);
+        if (hipEventElapsedTime(&ms, bo->mev[0], bo->mev[1]) == hipSuccess) bo->mstats.gather_ms += (double)ms;
+        bo->mates_timed = 0;
     }
 out:
     return rc;
@@ -420,6 +439,10 @@ extern "C" int itx_bamout_append_host(itx_bamout *bo, const void *bytes, size_t 
         n_rec++;
     }
     if (!len) return ITX_OK;
+    if (bo->mates && bo->annotate && (!bo->host_rows || bo->n_host_rows != n_rec)) {
+        itx_set_error("itx_bamout_append_host: %s", bo->host_rows ? "the rows of itx_bamout_mates_host_rows are not one per record" : "mates mode with tags needs the records' rows first (itx_bamout_mates_host_rows)");
+        return bo->host_rows ? ITX_E_ARG : ITX_E_STATE;
+    }
     int rc = ITX_OK;
     const ull total = (ull)bo->carry + len;
     if (bo->sort) {
@@ -438,7 +461,7 @@ extern "C" int itx_bamout_append_host(itx_bamout *bo, const void *bytes, size_t 
             h_ent[i].low = itx_bamsort_low(&k);
             h_ent[i].off = (ull)bo->carry + at;
             h_ent[i].len = 4u + bs;
-            h_ent[i].pad = 0;
+            h_ent[i].pad = bo->mates ? (bo->host_rows && bo->n_host_rows == n_rec ? (uint32_t)bo->host_rows[i] : BO_NO_ROW) : 0u;
             at += 4 + (size_t)bs;
         }
     } else if (bo->ix) {
@@ -484,6 +507,9 @@ extern "C" int itx_bamout_append_host(itx_bamout *bo, const void *bytes, size_t 
 out:
     free(h_off);
     free(h_ent);
+    free(bo->host_rows);                                                   // (the rows were this call's)
+    bo->host_rows = nullptr;
+    bo->n_host_rows = 0;
     return rc;
 }
 

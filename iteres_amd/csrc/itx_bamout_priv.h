@@ -1,6 +1,7 @@
 // itx_bamout_priv.h — internal: what the files of the BAM writer of `filter -b` share. itx_bamout.hip has the object and the
 // batch path (and says what a batch goes through), itx_bamout_members.hip makes a stream's payloads BGZF members (-l),
-// itx_bamout_sort.hip holds, sorts and replays the stream (-s), itx_bamout_annotate.hip takes the table for the tags (-a).
+// itx_bamout_sort.hip holds, sorts and replays the stream (-s), itx_bamout_annotate.hip takes the table for the tags (-a),
+// itx_bamout_mates.hip holds the candidates and joins the mates of the counted pairs to the held stream (-m).
 // itx_bamwin.hip includes this file for itx_bamout_start alone.
 // One object, one kernel stream: every step below runs on bo->st, and "bo->st is idle" means the caller has waited for it.
 #pragma once
@@ -50,8 +51,9 @@ __device__ __forceinline__ ItxRepTag bo_row_tag(const BoAnn &a, uint32_t row)
 struct BoSortEnt {
     uint32_t tid, low;               // the high and the low sort key (itx_bamsortrule.h)
     ull off;                         // the record's first byte in the held stream
-    uint32_t len, pad;               // 4 + block_size
+    uint32_t len, pad;               // 4 + block_size; pad: in mates mode the row the record was counted for (BO_NO_ROW: none given)
 };
+#define BO_NO_ROW 0xffffffffu
 static_assert(sizeof(BoSortEnt) == 24, "BoSortEnt");
 
 struct bo_slot {                     // one batch's members on their way out
@@ -105,6 +107,22 @@ struct itx_bamout {
     hipEvent_t sev[2];               // around the sort
     int sort_timed;
     double sort_ms, replay_ms;
+    // filter -b -s -m (itx_bamout_mates_enable, itx_bamout_mates.hip)
+    int mates;                       // 0: off; 1: candidates are collected; 2: the join is done and the candidate store gone
+    uint32_t *d_mlen;                // the candidate pass's own lengths, tile sums, tile bases and totals (the counted pass's are
+    ull *d_mtile_sum, *d_mtile_base, *d_mtot, *h_mtot;   // read by the host's totals step and by k_bs_entries); h_mtot page-locked
+    ull *d_moff64;                   // the join's rounds: where a round's candidates lie in the candidate stream, and their rows
+    int32_t *d_mrow;
+    uint8_t *d_cand;                 // the candidate stream: the candidates' bytes one behind the other, in stream order
+    size_t cand_cap, cand_len;
+    struct BmCand *d_cent;           // the candidate pool: an entry per candidate, in stream order
+    ull n_cent, cent_cap;
+    uint32_t cand_maxtid;            // the highest tid among the candidates: it counts the tid passes as n_ref does
+    int32_t *host_rows;              // itx_bamout_mates_host_rows: the rows of the next append_host's records (malloc)
+    size_t n_host_rows;
+    hipEvent_t mev[2];               // around a batch's candidate gather and entries (mev[1]: the window has been read), and the join
+    int mates_timed;
+    itx_bamout_mates_stats mstats;
 };
 
 // ---- the steps the files call across. All are the writer's own: nothing outside it calls them, but for itx_bamout_start.
@@ -136,6 +154,13 @@ int bo_totals(itx_bamout *bo, uint32_t nt, size_t tot_bytes, double *acc_ms);
 // held stream u and hit_row is not read.
 int bo_launch_gather(itx_bamout *bo, const uint8_t *u, const void *rec_off, uint32_t n, const int32_t *hit_row);
 
+// itx_bamout.hip. The same kernel with every array named: n records at rec_off (wide: 64-bit offsets, else uint32_t) of u, of
+// lengths len_in, laid behind `base` bytes of pay by the tile bases of a scan over those lengths; ann: len_in are annotated lengths
+// and hit_row chooses each record's tags. bo_launch_gather is this over the counted pass's arrays; the mates' passes
+// (itx_bamout_mates.hip) gather a window's candidates into the candidate stream and the chosen ones behind the held stream.
+int bo_launch_gather_at(itx_bamout *bo, int wide, int ann, const uint8_t *u, const void *rec_off, uint32_t n, const uint32_t *len_in, const ull *tile_base, ull base,
+                        uint8_t *pay, const int32_t *hit_row);
+
 // itx_bamout.hip. The device time of the last gather (and of the index's entry kernels) is read and added to gather_ms, or to
 // replay_ms during the replay; ev[3] is through, which every caller has waited for. Nothing happens when it was read already.
 void bo_read_gather_time(itx_bamout *bo);
@@ -152,4 +177,17 @@ int bs_reserve(itx_bamout *bo, ull n_more);
 // itx_bamout_sort.hip. k_bs_entries enqueued behind a batch's gather (the kernel lives with the sort, start launches it through
 // here): one entry per counted record of the batch, n_counted of them, behind those of the pool; bs_reserve(n_counted) has
 // succeeded and bo->carry is still the held stream's length before the batch. Called by start while the stream is held (sort == 1).
-int bs_entries(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, uint32_t n, ull n_counted);
+// In mates mode hit_row is the batch's chosen rows and every entry keeps its record's; else it is null.
+int bs_entries(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, uint32_t n, ull n_counted, const int32_t *hit_row);
+
+// itx_bamout_mates.hip. filter -b -s -m: the candidates among a batch's n records (itx_materule.h) go behind those of the candidate
+// store, bytes and entries; the host waits for their totals in between. Called by start behind the counted gather and bs_entries
+// (mates == 1). On return mev[1] is behind the last kernel that reads the window (itx_bamout_wait_kernels waits for it).
+int bm_batch(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, uint32_t n);
+
+// itx_bamout_mates.hip. The join, at the first sort_next before the sort (mates == 1, sort == 1, bo->st idle): the candidates the
+// held counted records want are laid behind the held stream and their entries behind the pool; the candidate store goes.
+int bm_join(itx_bamout *bo);
+
+// itx_bamout_mates.hip. Everything the mates own is freed (destroy).
+void bm_destroy(itx_bamout *bo);

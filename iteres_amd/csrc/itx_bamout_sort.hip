@@ -17,7 +17,8 @@
 // bases and itx_tile_offsets, its place in the pool from the tile's record count the same way (k_bi_entries' arrangement).
 // flag[0] counts the records that cannot be sorted, flag[1] is the highest tid seen; a workgroup adds to them once.
 __global__ __launch_bounds__(BO_TILE) void k_bs_entries(const uint8_t *__restrict__ u, const uint32_t *__restrict__ rec_off, uint32_t n, const uint32_t *__restrict__ len_in,
-                                                         const ull *__restrict__ tile_base, ull stream_at, ull ent_at, BoSortEnt *__restrict__ ent, uint32_t *__restrict__ flag)
+                                                         const ull *__restrict__ tile_base, ull stream_at, ull ent_at, BoSortEnt *__restrict__ ent, uint32_t *__restrict__ flag,
+                                                         const int32_t *__restrict__ hit_row)
 {
     __shared__ uint32_t s_w[BO_TILE / 64u], s_c[BO_TILE / 64u], s_f[2];
     if (threadIdx.x < 2) s_f[threadIdx.x] = 0;                             // (the barriers of itx_tile_offsets order this)
@@ -37,7 +38,7 @@ __global__ __launch_bounds__(BO_TILE) void k_bs_entries(const uint8_t *__restric
         e.low = itx_bamsort_low(&k);
         e.off = stream_at + tile_base[2u * blockIdx.x] + moff;
         e.len = len;
-        e.pad = 0;
+        e.pad = hit_row ? (uint32_t)hit_row[i] : 0u;                      // (mates mode: the mate's tags are made from this row)
         ent[ent_at + tile_base[2u * blockIdx.x + 1u] + rank] = e;
         if (bad) atomicAdd(&s_f[0], 1u);
         else atomicMax(&s_f[1], e.tid);
@@ -139,11 +140,11 @@ int bs_reserve(itx_bamout *bo, ull n_more)
     return ITX_OK;
 }
 
-int bs_entries(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, uint32_t n, ull n_counted)
+int bs_entries(itx_bamout *bo, const uint8_t *u, const uint32_t *rec_off, uint32_t n, ull n_counted, const int32_t *hit_row)
 {
     int rc = ITX_OK;
     hipLaunchKernelGGL(k_bs_entries, dim3((n + BO_TILE - 1) / BO_TILE), dim3(BO_TILE), 0, bo->st, u, rec_off, n, bo->d_len, bo->d_tile_base, (ull)bo->carry, bo->n_sent,
-                       bo->d_sent, bo->d_sflag);
+                       bo->d_sent, bo->d_sflag, hit_row);
     ITX_TRY(hipGetLastError());
     bo->n_sent += n_counted;
 out:
@@ -258,13 +259,16 @@ extern "C" int itx_bamout_sort_next(itx_bamout *bo, int *more)
     }
     int rc = ITX_OK;
     ull total = 0, n_mem = 0;
-    const ull N = bo->n_sent;
+    ull N = 0;
     uint32_t n = 0, nt = 0;
     int last = 0;
     ITX_TRY(hipSetDevice(bo->device));
     ITX_TRY(hipStreamSynchronize(bo->st));
     bo_read_gather_time(bo);
+    // (-m: the mates join the held stream and the pool before the sort sees either)
+    if (bo->sort == 1 && bo->mates == 1 && (rc = bm_join(bo)) != ITX_OK) goto out;
     if (bo->sort == 1 && (rc = bs_begin(bo)) != ITX_OK) goto out;
+    N = bo->n_sent;
     if (!N) {                                                              // nothing was counted: no member
         bs_release(bo);
         bo->finished = 1;

@@ -39,6 +39,7 @@ EXPORTS = [
     "itx_bamout_append_host", "itx_bamout_finish", "itx_bamout_collect", "itx_bamout_pending", "itx_bamout_get_stats", "itx_bamout_index_enable",
     "itx_bamout_index_finish", "itx_bamout_sort_enable", "itx_bamout_sort_next", "itx_bamout_sort_get_stats",
     "itx_bamout_set_level", "itx_bamout_get_level", "itx_bamout_annotate_enable", "itx_bamout_annotate_get_stats",
+    "itx_bamout_mates_enable", "itx_bamout_mates_append_host", "itx_bamout_mates_host_rows", "itx_bamout_mates_get_stats",
     "itx_loci_create", "itx_loci_destroy", "itx_loci_order", "itx_loci_filter_text", "itx_loci_cpg_text",
     "itx_samtext_create", "itx_samtext_destroy", "itx_samtext_parse_begin", "itx_samtext_parse_end", "itx_samtext_fetch",
     "itx_samtext_parse_begin_bgzf", "itx_samtext_bgzf_info", "itx_samtext_text", "itx_samtext_strings",
@@ -158,6 +159,11 @@ class BamoutIndexResult(C.Structure):
 
 class BamoutSortStats(C.Structure):
     _fields_ = [("records", C.c_uint64), ("rounds", C.c_uint64), ("pool_grows", C.c_uint64), ("sort_ms", C.c_double), ("replay_ms", C.c_double)]
+
+
+class BamoutMatesStats(C.Structure):
+    _fields_ = [("candidates", C.c_uint64), ("candidate_bytes", C.c_uint64), ("grows", C.c_uint64), ("wanted", C.c_uint64), ("found", C.c_uint64),
+                ("gather_ms", C.c_double), ("join_ms", C.c_double)]
 
 
 class LociText(C.Structure):
@@ -327,6 +333,10 @@ def load():
     L.itx_bamout_get_level.argtypes = [C.c_void_p]
     L.itx_bamout_annotate_enable.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p, C.c_void_p, C.c_uint32] * 3
     L.itx_bamout_annotate_get_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.itx_bamout_mates_enable.argtypes = [C.c_void_p]
+    L.itx_bamout_mates_append_host.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.itx_bamout_mates_host_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.itx_bamout_mates_get_stats.argtypes = [C.c_void_p, C.POINTER(BamoutMatesStats)]
     L.itx_loci_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                   C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
     L.itx_loci_destroy.argtypes = [C.c_void_p]
@@ -1070,6 +1080,24 @@ class Bamout:
         n = C.c_uint64(0)
         _chk(load().itx_bamout_annotate_get_stats(self._h, C.byref(n)), "itx_bamout_annotate_get_stats")
         return int(n.value)
+
+    def mates_enable(self):
+        """after sort_enable(), before the first batch (filter -b -s -m): the mates of the counted pairs join the sorted stream"""
+        _chk(load().itx_bamout_mates_enable(self._h), "itx_bamout_mates_enable")
+
+    def mates_append_host(self, records: bytes):
+        """all the records of a window the caller counted itself: the candidate mates among them join the candidate store"""
+        _chk(load().itx_bamout_mates_append_host(self._h, records, len(records)), "itx_bamout_mates_append_host")
+
+    def mates_host_rows(self, rows):
+        """with annotate_enable(): the chosen rows of the records of the next append_host, one per record"""
+        a = np.ascontiguousarray(rows, np.int32)
+        _chk(load().itx_bamout_mates_host_rows(self._h, a.ctypes.data, len(a)), "itx_bamout_mates_host_rows")
+
+    def mates_stats(self):
+        s = BamoutMatesStats()
+        _chk(load().itx_bamout_mates_get_stats(self._h, C.byref(s)), "itx_bamout_mates_get_stats")
+        return {k: getattr(s, k) for k, _ in BamoutMatesStats._fields_}
 
     def sort_stats(self):
         s = BamoutSortStats()

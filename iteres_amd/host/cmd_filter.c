@@ -28,6 +28,7 @@ static int filter_usage(void)
     fprintf(stderr, "         -s       with -b: write the counted reads sorted by coordinate, so that -i works on input in any order (an extension) [off]\n");
     fprintf(stderr, "         -l       with -b: level of its BGZF members, 0 (stored), 1 (fast) or 6 (smallest) (an extension) [6]\n");
     fprintf(stderr, "         -a       with -b: tag every emitted read with the repeat it was counted for, ZN/ZC/ZF (repName, repClass, repFamily) and ZS/ZE (genoStart, genoEnd) (an extension) [off]\n");
+    fprintf(stderr, "         -m       with -b -s: also write the mate of every counted pair, found on the device among the reads that were not counted (an extension) [off]\n");
     fprintf(stderr, "         -G       output the genome coverage of the counted reads as <prefix>_<filter>.iteres.bedGraph and, for MAPQ >= -Q, .iteres.unique.bedGraph (an extension) [off]\n");
     fprintf(stderr, "         -W       output that genome coverage as bigWig, <prefix>_<filter>.iteres.bigWig and .iteres.unique.bigWig, with or without -G (an extension) [off]\n");
     fprintf(stderr, "         -R       remove redundant reads [off]\n");
@@ -51,10 +52,10 @@ int main_filter(int argc, char **argv)
     o.isize = 500;
     o.extension = 150;
     o.min_cov = 0.0001f;
-    int optthreshold = 1, optreadlist = 0, optbam = 0, optindex = 0, optsort = 0, optlevel = -1, optannotate = 0, optgcov = 0, optbigwig = 0, optNorm = 0, c, filterField = 0;
+    int optthreshold = 1, optreadlist = 0, optbam = 0, optindex = 0, optsort = 0, optlevel = -1, optannotate = 0, optmates = 0, optgcov = 0, optbigwig = 0, optNorm = 0, c, filterField = 0;
     char *optoutput = NULL, *optname = NULL, *optclass = NULL, *optfamily = NULL;
     const time_t start_time = time(NULL);
-    while ((c = getopt(argc, argv, "SQ:g:N:n:c:t:f:rbisl:aGWRTDCE:I:o:h?")) >= 0) {
+    while ((c = getopt(argc, argv, "SQ:g:N:n:c:t:f:rbisl:amGWRTDCE:I:o:h?")) >= 0) {
         switch (c) {
         case 'S': o.is_sam = 1; break;
         case 'Q': o.mapq = (unsigned)strtol(optarg, 0, 0); break;
@@ -66,6 +67,7 @@ int main_filter(int argc, char **argv)
         case 'i': optindex = 1; break;
         case 's': optsort = 1; break;
         case 'a': optannotate = 1; break;
+        case 'm': optmates = 1; break;
         case 'G': optgcov = 1; break;
         case 'W': optbigwig = 1; break;
         case 'l': {
@@ -97,6 +99,9 @@ int main_filter(int argc, char **argv)
     if (optsort && !optbam) die("-s sorts the BAM that -b writes: it cannot be used without -b");
     if (optlevel >= 0 && !optbam) die("-l chooses the level of the BAM that -b writes: it cannot be used without -b");
     if (optannotate && !optbam) die("-a tags the reads of the BAM that -b writes: it cannot be used without -b");
+    if (optmates && !optbam) die("-m adds the mates to the BAM that -b -s writes: it cannot be used without -b");
+    if (optmates && !optsort) die("-m gives a mate its place in the sorted BAM of -b -s: it cannot be used without -s");
+    if (optmates && o.treat) die("-m completes the pairs counted through their READ1: it cannot be combined with -T, which counts both ends on their own");
     if (optbam && getenv("ITX_HOST_INFLATE"))
         die("-b gathers the records on the device, where the BAM is decoded: it cannot be combined with ITX_HOST_INFLATE (the host decoder)");
     o.chr_size_file = argv[optind];
@@ -142,6 +147,7 @@ int main_filter(int argc, char **argv)
         o.bam_index = optindex;
         o.bam_sort = optsort;
         o.bam_annotate = optannotate;
+        o.bam_mates = optmates;
         o.bam_level_given = optlevel >= 0;
         o.bam_level = optlevel >= 0 ? optlevel : 6;
         aln_keep_header(1);                      /* before the helper thread opens the file */

@@ -228,6 +228,7 @@ typedef struct {
     int bam_level_given;                       /* writer is not told a level and ITX_TIMING's line is the one it always was */
     int bam_index;                             /* filter -b -i: <bam_out_path>.bai beside it, built on the device in the same pass */
     int bam_annotate;                          /* filter -b -a: every emitted record carries the tags of its row (csrc/itx_reptag.h) */
+    int bam_mates;                             /* filter -b -s -m: the mates of the counted pairs are emitted too (csrc/itx_materule.h) */
     int gcov;                                  /* filter -G (an extension): the counted reads' genome coverage as bedGraph (csrc/itx_gcov.hip) */
 } run_opts;
 /* counters of the record loop that only the host sees (generic.c:1048-1060) */

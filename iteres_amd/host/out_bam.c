@@ -1,4 +1,4 @@
-/* out_bam.c — the BAM of filter -b (with -i its index, -s sorted, -a annotated, -l the level), as stream.c's record loop feeds it (the
+/* out_bam.c — the BAM of filter -b (with -i its index, -s sorted, -m with the counted pairs' mates, -a annotated, -l the level), as stream.c's record loop feeds it (the
  * steps: stream_priv.h). The members are made on the device (csrc/itx_bamout.hip); this file sets the object up from the kept header,
  * hands it the host route's records and writes what comes back. */
 #define _GNU_SOURCE
@@ -111,9 +111,18 @@ void bam_host_batch(stream_run *r, int k)
     const itx_staging *st = &r->st[k];
     const aln_side *side = &r->side[k];
     const rmsk_t *rm = r->rm;
-    size_t b = 0;
+    size_t b = 0, n_hit = 0;
+    const int want_rows = r->o->bam_mates && r->o->bam_annotate;          /* -m -a: a host-route READ1's mate takes the tags of its row */
     for (size_t i = 0; i < r->pend[k]; i++) {
         if (st->hit_row[i] < 0) continue;
+        if (want_rows) {
+            if (r->brows_cap <= n_hit) {
+                r->brows_cap = (n_hit + 1) * 2;
+                r->brows = xrealloc(r->brows, r->brows_cap * sizeof(int32_t));
+            }
+            r->brows[n_hit] = st->hit_row[i];
+        }
+        n_hit++;
         uint32_t bs;
         memcpy(&bs, side->raw + side->raw_off[i], 4);
         size_t len = 4 + (size_t)bs;
@@ -138,7 +147,37 @@ void bam_host_batch(stream_run *r, int k)
         b += len;
     }
     r->bam_host_batches++;
+    if (want_rows && n_hit) chk(itx_bamout_mates_host_rows(r->bo, r->brows, n_hit), "itx_bamout_mates_host_rows");
     chk(itx_bamout_append_host(r->bo, r->bbuf.bytes, b), "itx_bamout_append_host");
+    if (r->o->bam_mates && r->pend[k]) {
+        /* -m: every record of the window, counted or not, as the reader kept its bytes: the candidates among them join the store.
+         * The slot's records lie one behind the other as they did in the file; were they ever kept apart, they are laid together first. */
+        const size_t lo = side->raw_off[0];
+        size_t at = lo;
+        int together = 1;
+        for (size_t i = 0; i < r->pend[k]; i++) {
+            uint32_t bs;
+            if (side->raw_off[i] != at) together = 0;
+            memcpy(&bs, side->raw + side->raw_off[i], 4);
+            at = side->raw_off[i] + 4 + (size_t)bs;
+        }
+        if (together) {
+            chk(itx_bamout_mates_append_host(r->bo, side->raw + lo, at - lo), "itx_bamout_mates_append_host");
+        } else {
+            b = 0;
+            for (size_t i = 0; i < r->pend[k]; i++) {
+                uint32_t bs;
+                memcpy(&bs, side->raw + side->raw_off[i], 4);
+                if (r->bbuf.cap < b + 4 + (size_t)bs) {
+                    r->bbuf.cap = (b + 4 + (size_t)bs) * 2;
+                    r->bbuf.bytes = xrealloc(r->bbuf.bytes, r->bbuf.cap);
+                }
+                memcpy(r->bbuf.bytes + b, side->raw + side->raw_off[i], 4 + (size_t)bs);
+                b += 4 + (size_t)bs;
+            }
+            chk(itx_bamout_mates_append_host(r->bo, r->bbuf.bytes, b), "itx_bamout_mates_append_host");
+        }
+    }
     bam_write_out(r, 1);
 }
 
@@ -158,6 +197,7 @@ void bam_open(stream_run *r, stream_file *f)
     chk(itx_bamout_create(multi_device(), BATCH_RECORDS, 0, &r->bo), "itx_bamout_create");
     if (o->bam_level_given) chk(itx_bamout_set_level(r->bo, o->bam_level), "itx_bamout_set_level");
     if (o->bam_sort) chk(itx_bamout_sort_enable(r->bo), "itx_bamout_sort_enable");
+    if (o->bam_mates) chk(itx_bamout_mates_enable(r->bo), "itx_bamout_mates_enable");
     if (o->bam_annotate) bam_annotate_begin(r);
     if (o->bam_index) bam_index_begin(r, hb, hl);
     free(sorted_hb);
@@ -201,6 +241,12 @@ void bam_finish(stream_run *r)
         chk(itx_bamout_finish(r->bo), "itx_bamout_finish");
         bam_write_out(r, 0);
     }
+    itx_bamout_mates_stats ms;
+    memset(&ms, 0, sizeof ms);
+    if (r->bo && r->o->bam_mates) {
+        chk(itx_bamout_mates_get_stats(r->bo, &ms), "itx_bamout_mates_get_stats");
+        if (ms.wanted > ms.found) fprintf(stderr, "[iteres] %llu counted pairs have no mate in the input\n", (unsigned long long)(ms.wanted - ms.found));
+    }
     if (bgzf_write_eof(r->bam_f) != 0 || fclose(r->bam_f) != 0) die("writing %s: %s", r->o->bam_out_path, strerror(errno));
     r->bam_f = NULL;
     itx_bamout_index_result ir;
@@ -226,6 +272,9 @@ void bam_finish(stream_run *r)
             fprintf(stderr, "; sort: %llu records sorted, %llu rounds, %.3f ms in the sort kernels, %.3f ms in the replay gathers", (unsigned long long)ss.records,
                     (unsigned long long)ss.rounds, ss.sort_ms, ss.replay_ms);
         }
+        if (r->o->bam_mates)
+            fprintf(stderr, "; mates: %llu candidates held (%llu bytes), %llu wanted, %llu found, %.3f ms in the candidate gathers, %.3f ms in the join",
+                    (unsigned long long)ms.candidates, (unsigned long long)ms.candidate_bytes, (unsigned long long)ms.wanted, (unsigned long long)ms.found, ms.gather_ms, ms.join_ms);
         if (r->o->bam_index)
             fprintf(stderr, "; index: %llu entries, %llu chunks, %llu bytes, %.3f ms in the entry kernels, %.3f ms in the final kernels", (unsigned long long)ir.entries,
                     (unsigned long long)ir.chunks, (unsigned long long)ir.len, ir.batch_ms, ir.finish_ms);
@@ -237,4 +286,8 @@ void bam_finish(stream_run *r)
     r->bo = NULL;
 }
 
-void bam_free(stream_run *r) { free(r->bbuf.bytes); }
+void bam_free(stream_run *r)
+{
+    free(r->bbuf.bytes);
+    free(r->brows);
+}

@@ -74,6 +74,8 @@ typedef struct {
     struct { uint8_t *bytes; size_t cap; } bbuf;
     unsigned long long bam_dev_batches, bam_host_batches;
     unsigned long long bam_host_tag_bytes;         /* -b -a: tag bytes the host route appended */
+    int32_t *brows;                                /* -b -s -m -a: the chosen rows of a host batch's counted records */
+    size_t brows_cap;
     /* filter -G (csrc/itx_gcov.hip): every counted record adds its interval to the coverage on the device, whatever route it took;
      * the host route derives the intervals of its own records (gcov_host_batch). The files are written after the stream
      * (stream_gcov_write). */
