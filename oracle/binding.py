@@ -5,6 +5,7 @@ Importable only from tests/, __graft_entry__.smoke() and bench.py's cpu_baseline
 from __future__ import annotations
 
 import ctypes as C
+import fcntl
 import os
 import subprocess
 
@@ -23,8 +24,14 @@ class OrcParams(C.Structure):
 def build(force: bool = False) -> str:
     so = os.path.join(_HERE, "liboracle.so")
     src = [os.path.join(_HERE, f) for f in ("iteres_oracle.c", "iteres_oracle.h")]
-    if force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in src):
-        subprocess.check_call(["make", "-s", "-C", _HERE, "oracle"])
+    # one builder at a time (the ranks of a multi-process test all come here at once): the lock is on the directory itself
+    fd = os.open(_HERE, os.O_RDONLY)
+    try:
+        fcntl.flock(fd, fcntl.LOCK_EX)
+        if force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in src):
+            subprocess.check_call(["make", "-s", "-C", _HERE, "oracle"])
+    finally:
+        os.close(fd)
     return so
 
 

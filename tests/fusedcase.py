@@ -100,7 +100,7 @@ class Pipe:
         self.result = {}
 
     def begin(self, k, push):
-        comp, blocks, _ = push
+        comp, blocks = push[0], push[1]
         cbuf = np.zeros(len(comp) + 16, np.uint8)
         cbuf[:len(comp)] = np.frombuffer(comp, np.uint8)
         blocks = np.ascontiguousarray(blocks, eng.BGZF_BLOCK)
@@ -113,7 +113,8 @@ class Pipe:
     def end(self, k, push, hurt=()):
         """status and window of push k; every block but those of `hurt` ({block: status}) must be clean and equal to zlib's bytes"""
         hurt = dict(hurt)
-        _, blocks, want = push
+        blocks, want = push[1], push[2]
+        name = (lambda i: push[3][i]) if len(push) > 3 else (lambda i: "")        # a crafted block's label, for the messages
         status = np.full(len(blocks) + 1, 255, np.uint8)
         n_new = C.c_size_t()
         eng._chk(self.L.itx_bamwin_push_end(self.h, k % SLOTS, eng._p(status), C.byref(n_new)), "push_end")
@@ -131,8 +132,8 @@ class Pipe:
                 assert status[i] == hurt[i], (k, i, int(status[i]))
                 raw[at - len(d):at] = 0               # whatever lies behind a flagged block is not part of the digest
             else:
-                assert status[i] == 0, (k, i, int(status[i]))
-                assert got == zlib.decompress(push[0][int(blocks["coff"][i]) + 18:int(blocks["coff"][i]) + int(blocks["csize"][i]) - 8], -15) == d, (k, i)
+                assert status[i] == 0, (k, i, name(i), int(status[i]))
+                assert got == zlib.decompress(push[0][int(blocks["coff"][i]) + 18:int(blocks["coff"][i]) + int(blocks["csize"][i]) - 8], -15) == d, (k, i, name(i))
         self.result[k] = {"status": [int(x) for x in status], "window": hashlib.sha256(raw[:n_new.value].tobytes()).hexdigest()}
 
     def close(self):
@@ -149,6 +150,31 @@ def in_order(pipe, pushes, hurt=None):
         else:
             pipe.end(ended, pushes[ended], (hurt or {}).get(ended, ()))
             ended += 1
+
+
+def crafted_pushes():
+    """the hand-made members of tests/deflatecraft.py (families B, C and D: the ring's, the bitmap's and the stage's limits, the fullest
+    scratch regions) as pushes of 64, 65 and 3 blocks in turn; then the three fullest regions as the last blocks of one push and
+    the first of the next, cut behind the second and behind the first. In the fused launch four replaying waves share one LDS
+    block and a group's scratch regions abut: what one overruns, a neighbour loses."""
+    import deflatecraft as dc
+    ms = [(dc.member(raw, want), want, label) for name in "BCD" for label, raw, want in dc.cases(name)]
+    d0, d1, d2 = ms[-3:]
+    small = ms[len(dc.cases("B")):-3]                  # family C
+    sets, at, k = [], 0, 0
+    while at < len(ms):
+        n = (64, 65, 3)[k % 3]
+        sets.append(ms[at:at + n])
+        at += n
+        k += 1
+    sets += [(small * 2)[:62] + [d0, d1], [d2] + (small * 2)[:64], [small[0], small[1], d0], [d1, d2] + (small * 2)[:62]]
+    pushes = []
+    for members in sets:
+        comp = b"".join(m for m, _, _ in members)
+        blocks = eng.index_bgzf(comp)
+        assert len(blocks) == len(members)
+        pushes.append((comp, blocks, [w for _, w, _ in members], [label for _, _, label in members]))
+    return pushes
 
 
 def sized(rng, n_pushes, first=0):
@@ -196,6 +222,8 @@ def main():
         sizes = (64, 65, 1, 63, 40, 65, 33, 64, 65, 129, 1)
         pushes = [make_push(rng, n, k, btype3=17 if k == 5 else None, far=5 if k == 6 else None) for k, n in enumerate(sizes)]
         in_order(pipe, pushes, hurt={5: {17: E_BTYPE}, 6: {5: E_DIST}})
+    elif scenario == "crafted":
+        in_order(pipe, crafted_pushes())
     else:
         raise SystemExit("unknown scenario " + scenario)
     pipe.close()

@@ -87,3 +87,13 @@ def test_two_kernels_give_the_same(scenario):
     """ITX_FUSE=0, k_tokens and k_resolve one behind the other as before, against the fused launches: windows and status"""
     a, b = run_case(scenario, 0), run_case(scenario, 1)
     assert a["pushes"] == b["pushes"] and len(a["pushes"]) > 0
+
+
+def test_hand_made_streams_through_both_launches():
+    """tests/deflatecraft.py's families B, C and D (near/far around the ring's limits, the bitmap's and the stage's limits, the fullest
+    scratch regions side by side and across two pushes) in pushes of 64, 65 and 3 blocks: the child holds every block equal to zlib's
+    bytes; the fused launches, where four replaying waves share one LDS block, and the two kernels give the same"""
+    a, b = run_case("crafted", 0), run_case("crafted", 1)
+    sizes = [len(p["status"]) for p in b["pushes"]]
+    assert sizes[:3] == [64, 65, 3] and sizes[-4:] == [64, 65, 3, 64] and sum(sizes) > 200 and clean(a) and clean(b)
+    assert a["pushes"] == b["pushes"]

@@ -3,13 +3,14 @@ inflate, cussamtools/bgzf.c:367-397) built for the host with a one-lane wave (te
 zlib: every block type, every compression level and strategy, matches at every distance up to 32 KiB, self-overlapping
 matches, blocks at odd offsets in the compressed buffer and in the output, and damaged input (must fail cleanly or —
 when it decodes — agree with what zlib makes of the same bytes)."""
-import ctypes as C
 import os
 import subprocess
 import zlib
 
 import numpy as np
 import pytest
+
+from deflatecraft import _Bits, corpus, crafted_cases, host_lib, raw_deflate  # noqa: F401 (corpus, raw_deflate: other test modules take them from here)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -25,17 +26,7 @@ FORM_IDS = ["word_ahead", "fifo", "one_code_per_turn", "three_codes_per_turn", "
 
 @pytest.fixture(scope="module", params=INPUT_FORMS, ids=FORM_IDS)
 def lib(request, tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("inflate") / "libinflate_host.so")
-    subprocess.check_call(["g++", "-O2", "-g", "-shared", "-fPIC", "-Wno-unknown-pragmas"] + request.param + ["-o", so, os.path.join(ROOT, "tests", "inflate_host.cpp")])
-    L = C.CDLL(so)
-    L.itx_inflate_host.restype = C.c_int
-    L.itx_inflate_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    return L
-
-
-def raw_deflate(data, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, wbits=-15, memlevel=8):
-    co = zlib.compressobj(level, zlib.DEFLATED, wbits, memlevel, strategy)
-    return co.compress(data) + co.flush()
+    return host_lib(str(tmp_path_factory.mktemp("inflate") / "libinflate_host.so"), request.param)
 
 
 def run(lib, comp, usize, at=0, g0=0, pad_out=0):
@@ -46,29 +37,6 @@ def run(lib, comp, usize, at=0, g0=0, pad_out=0):
     rc = lib.itx_inflate_host(buf.ctypes.data, at, at + len(comp), out.ctypes.data, g0, usize, None, None)
     assert (out[:g0] == 0xA5).all() and (out[g0 + usize:] == 0xA5).all(), "wrote outside its block"
     return rc, out[g0:g0 + usize].tobytes()
-
-
-def corpus(rng):
-    yield b""
-    yield b"a"
-    yield b"abc" * 5
-    yield bytes(70000 % 65280)
-    yield bytes(rng.integers(0, 256, 65280, dtype=np.uint8))                      # incompressible: stored blocks at level >= 1
-    yield bytes(rng.integers(0, 4, 65280, dtype=np.uint8))                        # tiny alphabet: short codes, long matches
-    yield (b"ACGT" * 7 + b"N") * 2200
-    yield bytes(rng.integers(65, 91, 40000, dtype=np.uint8)) + bytes(25000)
-    # BAM-like records: little-endian ints, names, 4-bit sequence, quality runs
-    rec = bytearray()
-    for i in range(400):
-        rec += int(rng.integers(0, 1 << 28)).to_bytes(4, "little") * 3 + f"read{i}".encode() + b"\0" + bytes(rng.integers(0, 256, 50, dtype=np.uint8)) + bytes([40]) * 100
-    yield bytes(rec)
-    # far matches: a random kilobyte repeated at distances up to the 32 KiB window
-    base = bytes(rng.integers(0, 256, 1000, dtype=np.uint8))
-    for gap in (7000, 7800, 7900, 8200, 20000, 31700):
-        yield base + bytes(rng.integers(0, 256, gap - 1000, dtype=np.uint8)) + base + bytes(rng.integers(0, 256, 500, dtype=np.uint8)) + base[:300]
-    # self-overlapping matches of every small distance
-    for d in (1, 2, 3, 5, 7, 31, 32, 33, 63, 64, 65, 100, 257, 258, 259):
-        yield bytes(rng.integers(0, 256, d, dtype=np.uint8)) * (3000 // d + 2)
 
 
 def test_against_zlib_every_level_and_strategy(lib):
@@ -138,6 +106,18 @@ def _fnv(b):
     return h
 
 
+_crafted_fnv = {}
+
+
+class _Hashed:
+    """a crafted case's expected bytes as their hash, worked out once for all builds"""
+
+    def __init__(self, label, want):
+        if label not in _crafted_fnv:
+            _crafted_fnv[label] = _fnv(want)
+        self.label, self.fnv = label, _crafted_fnv[label]
+
+
 @pytest.mark.parametrize("form", INPUT_FORMS, ids=FORM_IDS)
 def test_address_sanitizer_exact_buffers(form, tmp_path):
     """The same decoder under -fsanitize=address,undefined with EXACT-size buffers (input: the block + its 8-byte trailer + the
@@ -175,6 +155,10 @@ def test_address_sanitizer_exact_buffers(form, tmp_path):
         usize = len(data) if trial % 5 else 65536
         cases.append((int(rng.integers(0, 4)), bytes(comp), usize))
         expect.append(False)                                 # False: don't care
+    # the hand-made streams of tests/deflatecraft.py: the bitmap's, the stage's and the ring's limits in exact buffers
+    for k, (label, raw, want) in enumerate(crafted_cases()):
+        cases.append((k % 4, raw, len(want)))
+        expect.append(_Hashed(label, want))
     path = tmp_path / "cases.bin"
     with open(path, "wb") as f:
         f.write(np.uint32(len(cases)).tobytes())
@@ -189,37 +173,10 @@ def test_address_sanitizer_exact_buffers(form, tmp_path):
         rc, h = ln.split()
         if want is None:
             assert int(rc) != 0
+        elif isinstance(want, _Hashed):
+            assert int(rc) == 0 and int(h) == want.fnv, want.label
         elif want is not False:
             assert int(rc) == 0 and int(h) == _fnv(want)
-
-
-class _Bits:
-    """DEFLATE's bit order: fields LSB first, Huffman codes MSB first"""
-
-    def __init__(self):
-        self.acc, self.n, self.out = 0, 0, bytearray()
-
-    def field(self, v, n):
-        self.acc |= v << self.n
-        self.n += n
-        while self.n >= 8:
-            self.out.append(self.acc & 255)
-            self.acc >>= 8
-            self.n -= 8
-
-    def code(self, c, n):
-        self.field(int(format(c, f"0{n}b")[::-1], 2), n)
-
-    def fixed_sym(self, s):                                      # RFC 1951 3.2.6
-        if s < 144: self.code(0x30 + s, 8)
-        elif s < 256: self.code(0x190 + s - 144, 9)
-        elif s < 280: self.code(s - 256, 7)
-        else: self.code(0xC0 + s - 280, 8)
-
-    def done(self):
-        if self.n:
-            self.out.append(self.acc & 255)
-        return bytes(self.out)
 
 
 def test_code_lengths_staged_in_the_fullest_scratch_region(lib):
