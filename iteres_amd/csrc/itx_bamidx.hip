@@ -359,44 +359,25 @@ struct itx_bamidx {
     int device;
     int reason;                      // ITX_BAI_TOO_MANY_REFS: there will be no index, nothing is collected
     int32_t n_ref;
-    int32_t *d_lref;
-    uint64_t *h_woff, *d_woff;       // [n_ref + 1] where every reference's windows start in the linear array
-    uint32_t *d_flag, *h_flag;
-    BiEnt *d_ent;
-    uint64_t n_ent, ent_cap;
-    uint32_t *d_ms;                  // all member sizes of the run
-    uint64_t n_ms, ms_cap;
-    uint32_t *d_hoff, *d_hlen;       // the host route's offsets and lengths
-    ull *d_hts, *d_htb, *d_htot;
-    uint64_t h_cap;
-    hipEvent_t eb[2], ef[2];
+    uint64_t *h_woff;                // [n_ref + 1] where every reference's windows start in the linear array (the host's heap)
+    ItxBuf d_lref, d_woff, d_flag;
+    ItxPin h_flag;
+    ItxBuf d_ent, d_ms;              // BiEnt[n_ent], and all member sizes of the run: grown together and kept (ItxGrow), cap is theirs in bytes
+    uint64_t n_ent, n_ms;
+    ItxBuf d_hoff, d_hlen;           // the host route's offsets and lengths
+    ItxBuf d_hts, d_htb, d_htot;
+    ItxEvent eb[2], ef[2];
     int batch_timed, done;
     double batch_ms, finish_ms;
     uint64_t grows;
-    uint8_t *d_out, *h_out;          // the finished file
+    ItxBuf d_out;                    // the finished file
+    ItxPin h_out;
 };
 
 void itx_bamidx_destroy(itx_bamidx *ix)
 {
     if (!ix) return;
     (void)hipSetDevice(ix->device);
-    for (auto &e : ix->eb)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : ix->ef)
-        if (e) (void)hipEventDestroy(e);
-    (void)hipFree(ix->d_lref);
-    (void)hipFree(ix->d_woff);
-    (void)hipFree(ix->d_flag);
-    (void)hipFree(ix->d_ent);
-    (void)hipFree(ix->d_ms);
-    (void)hipFree(ix->d_hoff);
-    (void)hipFree(ix->d_hlen);
-    (void)hipFree(ix->d_hts);
-    (void)hipFree(ix->d_htb);
-    (void)hipFree(ix->d_htot);
-    (void)hipFree(ix->d_out);
-    if (ix->h_flag) (void)hipHostFree(ix->h_flag);
-    if (ix->h_out) (void)hipHostFree(ix->h_out);
     free(ix->h_woff);
     delete ix;
 }
@@ -404,6 +385,7 @@ void itx_bamidx_destroy(itx_bamidx *ix)
 int itx_bamidx_create(int device, int32_t n_ref, const int32_t *l_ref, itx_bamidx **out)
 {
     int rc = ITX_OK;
+    const char *const who = "itx_bamout_index_enable";
     itx_bamidx *ix = new itx_bamidx();
     ix->device = device;
     ix->n_ref = n_ref;
@@ -421,19 +403,18 @@ int itx_bamidx_create(int device, int32_t n_ref, const int32_t *l_ref, itx_bamid
     ix->h_woff[0] = 0;
     for (int32_t r = 0; r < n_ref; r++) ix->h_woff[r + 1] = ix->h_woff[r] + itx_bai_windows(l_ref[r]);
     ITX_TRY(hipSetDevice(device));
-    if (hipMalloc((void **)&ix->d_lref, 4 * ((size_t)n_ref + 1)) != hipSuccess || hipMalloc((void **)&ix->d_woff, 8 * ((size_t)n_ref + 1)) != hipSuccess ||
-        hipMalloc((void **)&ix->d_flag, 16) != hipSuccess) {
-        (void)hipGetLastError();
+    if ((rc = itx_buf_need(who, ix->d_lref, 4 * ((size_t)n_ref + 1))) || (rc = itx_buf_need(who, ix->d_woff, 8 * ((size_t)n_ref + 1))) ||
+        (rc = itx_buf_need(who, ix->d_flag, 16))) {
         itx_set_error("itx_bamout_index_enable: no device memory for %d references", n_ref);
-        rc = ITX_E_NOMEM;
         goto out;
     }
-    ITX_TRY(hipHostMalloc((void **)&ix->h_flag, 16, hipHostMallocDefault));
-    if (n_ref) ITX_TRY(hipMemcpy(ix->d_lref, l_ref, 4 * (size_t)n_ref, hipMemcpyHostToDevice));
-    ITX_TRY(hipMemcpy(ix->d_woff, ix->h_woff, 8 * ((size_t)n_ref + 1), hipMemcpyHostToDevice));
-    ITX_TRY(hipMemset(ix->d_flag, 0, 16));
-    for (auto &e : ix->eb) ITX_TRY(hipEventCreate(&e));
-    for (auto &e : ix->ef) ITX_TRY(hipEventCreate(&e));
+    if ((rc = itx_pin_need(who, ix->h_flag, 16)) != ITX_OK) goto out;
+    if (n_ref) ITX_TRY(hipMemcpy(ix->d_lref.p, l_ref, 4 * (size_t)n_ref, hipMemcpyHostToDevice));
+    ITX_TRY(hipMemcpy(ix->d_woff.p, ix->h_woff, 8 * ((size_t)n_ref + 1), hipMemcpyHostToDevice));
+    ITX_TRY(hipMemset(ix->d_flag.p, 0, 16));
+    for (auto *ev : {ix->eb, ix->ef})
+        for (int k = 0; k < 2; k++)
+            if ((rc = itx_event_make(ev[k])) != ITX_OK) goto out;
 out:
     if (rc != ITX_OK) {
         itx_bamidx_destroy(ix);
@@ -451,11 +432,11 @@ int itx_bamidx_reserve(itx_bamidx *ix, hipStream_t st, uint64_t n_entries, uint6
         itx_set_error("itx_bamout: %llu records to index", (ull)(ix->n_ent + n_entries));
         return ITX_E_LIMIT;
     }
-    if (ix->n_ent + n_entries > ix->ent_cap) want_ent = ix->n_ent + n_entries + (ix->n_ent + n_entries) / 2 + 1024;
-    if (ix->n_ms + n_members > ix->ms_cap) want_ms = ix->n_ms + n_members + (ix->n_ms + n_members) / 2 + 1024;
-    const bool first = !ix->d_ent;
+    if (ix->n_ent + n_entries > ix->d_ent.cap / sizeof(BiEnt)) want_ent = ix->n_ent + n_entries + (ix->n_ent + n_entries) / 2 + 1024;
+    if (ix->n_ms + n_members > ix->d_ms.cap / 4) want_ms = ix->n_ms + n_members + (ix->n_ms + n_members) / 2 + 1024;
+    const bool first = !ix->d_ent.p;
     // the entries and the member sizes are taken together (itx_devbuf.h); what they hold is kept
-    ItxGrow g[2] = {{(void **)&ix->d_ent, sizeof(BiEnt) * ix->n_ent, sizeof(BiEnt) * want_ent}, {(void **)&ix->d_ms, 4 * ix->n_ms, 4 * want_ms}};
+    ItxGrow g[2] = {{&ix->d_ent.p, sizeof(BiEnt) * ix->n_ent, sizeof(BiEnt) * want_ent}, {&ix->d_ms.p, 4 * ix->n_ms, 4 * want_ms}};
     if (itx_grow_alloc(g, 2) >= 0) {
         itx_set_error("itx_bamout: no device memory for the index entries of %llu records and %llu members", (ull)(ix->n_ent + n_entries), (ull)(ix->n_ms + n_members));
         return ITX_E_NOMEM;
@@ -463,10 +444,10 @@ int itx_bamidx_reserve(itx_bamidx *ix, hipStream_t st, uint64_t n_entries, uint6
     const int rc = itx_grow_commit(st, g, 2);
     if (rc != ITX_OK) return rc;
     if (want_ent) {
-        ix->ent_cap = want_ent;
+        ix->d_ent.cap = sizeof(BiEnt) * want_ent;
         if (!first) ix->grows++;
     }
-    if (want_ms) ix->ms_cap = want_ms;
+    if (want_ms) ix->d_ms.cap = 4 * want_ms;
     return ITX_OK;
 }
 
@@ -476,13 +457,13 @@ static int bi_entries(itx_bamidx *ix, hipStream_t st, const uint8_t *u, const OF
 {
     if (ix->reason || !n || !n_counted) return ITX_OK;
     int rc = ITX_OK;
-    if (ix->n_ent + n_counted > ix->ent_cap) {
+    if (ix->n_ent + n_counted > ix->d_ent.cap / sizeof(BiEnt)) {
         itx_set_error("itx_bamidx_entries: no room was reserved");
         return ITX_E_STATE;
     }
     ITX_TRY(hipEventRecord(ix->eb[0], st));
     hipLaunchKernelGGL((k_bi_entries<OFF>), dim3((n + BI_TILE - 1) / BI_TILE), dim3(BI_TILE), 0, st, u, rec_off, n, len_in, tile_base, stream_at, (ull)ix->n_ent,
-                       ix->d_ent, ix->n_ref, ix->d_lref, ix->d_flag);
+                       ix->d_ent.as<BiEnt>(), ix->n_ref, ix->d_lref.as<int32_t>(), ix->d_flag.as<uint32_t>());
     ITX_TRY(hipGetLastError());
     ITX_TRY(hipEventRecord(ix->eb[1], st));
     ix->batch_timed = 1;
@@ -508,25 +489,24 @@ int itx_bamidx_host_records(itx_bamidx *ix, hipStream_t st, const uint8_t *d_byt
     if (ix->reason || !n) return ITX_OK;
     int rc = ITX_OK;
     const uint32_t nt = (n + BI_TILE - 1) / BI_TILE;
-    if (n > ix->h_cap) {
+    if (n > ix->d_hoff.cap / 4) {
         const uint64_t want = (uint64_t)n + n / 2 + 1024, wt = (want + BI_TILE - 1) / BI_TILE + 1;
         // the offsets, the lengths, the tiles' sums and bases and the totals are taken together; nothing is kept (st is idle: nothing reads them)
-        ItxGrow g[5] = {{(void **)&ix->d_hoff, 0, 4 * want}, {(void **)&ix->d_hlen, 0, 4 * want}, {(void **)&ix->d_hts, 0, 16 * wt}, {(void **)&ix->d_htb, 0, 16 * wt},
-                        {(void **)&ix->d_htot, 0, 16}};
+        ItxGrow g[5] = {{&ix->d_hoff.p, 0, 4 * want}, {&ix->d_hlen.p, 0, 4 * want}, {&ix->d_hts.p, 0, 16 * wt}, {&ix->d_htb.p, 0, 16 * wt}, {&ix->d_htot.p, 0, 16}};
         if (itx_grow_alloc(g, 5) >= 0) {
             itx_set_error("itx_bamout_append_host: no device memory for the offsets of %u records", n);
             return ITX_E_NOMEM;
         }
         if ((rc = itx_grow_commit(st, g, 5)) != ITX_OK) goto out;
-        ix->h_cap = want;
+        ix->d_hoff.cap = ix->d_hlen.cap = 4 * want, ix->d_hts.cap = ix->d_htb.cap = 16 * wt, ix->d_htot.cap = 16;
     }
-    ITX_TRY(hipMemcpyAsync(ix->d_hoff, h_off, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    ITX_TRY(hipMemcpyAsync(ix->d_hoff.p, h_off, 4 * (size_t)n, hipMemcpyHostToDevice, st));
     ITX_TRY(hipStreamSynchronize(st));
-    hipLaunchKernelGGL(k_bi_measure, dim3(nt), dim3(BI_TILE), 0, st, d_bytes, ix->d_hoff, n, ix->d_hlen, ix->d_hts);
+    hipLaunchKernelGGL(k_bi_measure, dim3(nt), dim3(BI_TILE), 0, st, d_bytes, ix->d_hoff.as<uint32_t>(), n, ix->d_hlen.as<uint32_t>(), ix->d_hts.as<ull>());
     ITX_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, st, ix->d_hts, nt, ix->d_htb, ix->d_htot);
+    hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, st, ix->d_hts.as<ull>(), nt, ix->d_htb.as<ull>(), ix->d_htot.as<ull>());
     ITX_TRY(hipGetLastError());
-    rc = itx_bamidx_entries(ix, st, d_bytes, ix->d_hoff, n, ix->d_hlen, ix->d_htb, stream_at, n);
+    rc = itx_bamidx_entries(ix, st, d_bytes, ix->d_hoff.as<uint32_t>(), n, ix->d_hlen.as<uint32_t>(), ix->d_htb.as<ull>(), stream_at, n);
 out:
     return rc;
 }
@@ -535,11 +515,11 @@ int itx_bamidx_members(itx_bamidx *ix, hipStream_t st, const uint32_t *d_msize, 
 {
     if (ix->reason || !n) return ITX_OK;
     int rc = ITX_OK;
-    if (ix->n_ms + n > ix->ms_cap) {
+    if (ix->n_ms + n > ix->d_ms.cap / 4) {
         itx_set_error("itx_bamidx_members: no room was reserved");
         return ITX_E_STATE;
     }
-    ITX_TRY(hipMemcpyAsync(ix->d_ms + ix->n_ms, d_msize, 4 * (size_t)n, hipMemcpyDeviceToDevice, st));
+    ITX_TRY(hipMemcpyAsync(ix->d_ms.as<uint32_t>() + ix->n_ms, d_msize, 4 * (size_t)n, hipMemcpyDeviceToDevice, st));
     ix->n_ms += n;
 out:
     return rc;
@@ -578,7 +558,14 @@ int itx_bamidx_finish(itx_bamidx *ix, hipStream_t st, uint64_t first, itx_bamout
     uint32_t C = 0, ntC = 0;
     float ms = 0;
     uint64_t total = 0;
-    // work arrays: all freed below, whatever happens
+    // work arrays: the views the kernels take, and their owners
+    ItxBuf coff, cbeg, cend, fbeg, fend, roff, ts, tb, tot, lin, k0, k1, hist, fkey, fbin, binfirst, refs;
+    ItxPin tot_pin;
+    const char *const who = "itx_bamout_index_finish";
+    BiEnt *const d_ent = ix->d_ent.as<BiEnt>();
+    uint32_t *const d_flag = ix->d_flag.as<uint32_t>(), *const h_flag = ix->h_flag.as<uint32_t>();
+    uint64_t *const d_woff = ix->d_woff.as<uint64_t>();
+    uint8_t *d_out = nullptr;
     uint64_t *d_coff = nullptr, *d_cbeg = nullptr, *d_cend = nullptr, *d_fbeg = nullptr, *d_fend = nullptr, *d_roff = nullptr;
     ull *d_ts = nullptr, *d_tb = nullptr, *d_tot = nullptr, *d_lin = nullptr, *h_tot = nullptr;
     uint2 *d_k0 = nullptr, *d_k1 = nullptr, *sorted = nullptr;
@@ -587,30 +574,29 @@ int itx_bamidx_finish(itx_bamidx *ix, hipStream_t st, uint64_t first, itx_bamout
     ITX_TRY(hipSetDevice(ix->device));
     ITX_TRY(hipEventRecord(ix->ef[0], st));
     if (N) {
-        hipLaunchKernelGGL(k_bi_order, dim3((N + 255u) / 256u), dim3(256), 0, st, ix->d_ent, N, ix->d_flag);
+        hipLaunchKernelGGL(k_bi_order, dim3((N + 255u) / 256u), dim3(256), 0, st, d_ent, N, d_flag);
         ITX_TRY(hipGetLastError());
     }
-    ITX_TRY(hipMemcpyAsync(ix->h_flag, ix->d_flag, 4, hipMemcpyDeviceToHost, st));
+    ITX_TRY(hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, st));
     ITX_TRY(hipStreamSynchronize(st));
     itx_bamidx_batch_time(ix);
     res->entries = N;
     res->grows = ix->grows;
     res->batch_ms = ix->batch_ms;
-    if (*ix->h_flag) {
-        const uint32_t f = *ix->h_flag;
+    if (*h_flag) {
+        const uint32_t f = *h_flag;
         res->status = f & BI_FLAG(ITX_BAI_UNSORTED) ? ITX_BAI_UNSORTED : f & BI_FLAG(ITX_BAI_BEYOND_MAX) ? ITX_BAI_BEYOND_MAX : ITX_BAI_BEYOND_REF;
         ix->done = 1;
         goto out;
     }
-    if (hipMalloc((void **)&d_coff, 8 * (M + 1)) != hipSuccess || hipMalloc((void **)&d_ts, 16 * ((size_t)ntN + 1)) != hipSuccess ||
-        hipMalloc((void **)&d_tb, 16 * ((size_t)ntN + 1)) != hipSuccess || hipMalloc((void **)&d_tot, 16) != hipSuccess ||
-        hipMalloc((void **)&d_lin, 8 * (W + 1)) != hipSuccess || hipMalloc((void **)&d_refs, 4 * 7 * ((size_t)n_ref + 1)) != hipSuccess ||
-        hipMalloc((void **)&d_roff, 8 * ((size_t)n_ref + 1)) != hipSuccess || hipHostMalloc((void **)&h_tot, 16, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
+    if ((rc = itx_buf_need(who, coff, 8 * (M + 1))) || (rc = itx_buf_need(who, ts, 16 * ((size_t)ntN + 1))) || (rc = itx_buf_need(who, tb, 16 * ((size_t)ntN + 1))) ||
+        (rc = itx_buf_need(who, tot, 16)) || (rc = itx_buf_need(who, lin, 8 * (W + 1))) || (rc = itx_buf_need(who, refs, 4 * 7 * ((size_t)n_ref + 1))) ||
+        (rc = itx_buf_need(who, roff, 8 * ((size_t)n_ref + 1))) || (rc = itx_pin_need(who, tot_pin, 16))) {
         itx_set_error("itx_bamout_index_finish: no memory for %u entries, %llu members and %llu windows", N, (ull)M, (ull)W);
-        rc = ITX_E_NOMEM;
         goto out;
     }
+    d_coff = coff.as<uint64_t>(), d_roff = roff.as<uint64_t>(), d_refs = refs.as<uint32_t>();
+    d_ts = ts.as<ull>(), d_tb = tb.as<ull>(), d_tot = tot.as<ull>(), d_lin = lin.as<ull>(), h_tot = tot_pin.as<ull>();
     R.f0 = d_refs;
     R.f1 = d_refs + 1 * ((size_t)n_ref + 1);
     R.b0 = d_refs + 2 * ((size_t)n_ref + 1);
@@ -621,10 +607,10 @@ int itx_bamidx_finish(itx_bamidx *ix, hipStream_t st, uint64_t first, itx_bamout
     ITX_TRY(hipMemsetAsync(d_refs, 0, 4 * 7 * ((size_t)n_ref + 1), st));
     ITX_TRY(hipMemsetAsync(d_lin, 0xff, 8 * (W + 1), st));
     ITX_TRY(hipMemsetAsync(d_tot, 0, 16, st));
-    hipLaunchKernelGGL(k_size_scan, dim3(1), dim3(ITX_SCAN_WG), 0, st, ix->d_ms, M, d_coff);
+    hipLaunchKernelGGL(k_size_scan, dim3(1), dim3(ITX_SCAN_WG), 0, st, ix->d_ms.as<uint32_t>(), M, d_coff);
     ITX_TRY(hipGetLastError());
     if (N) {
-        hipLaunchKernelGGL(k_bi_heads, dim3(ntN), dim3(BI_TILE), 0, st, ix->d_ent, N, d_ts);
+        hipLaunchKernelGGL(k_bi_heads, dim3(ntN), dim3(BI_TILE), 0, st, d_ent, N, d_ts);
         ITX_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, st, d_ts, ntN, d_tb, d_tot);
         ITX_TRY(hipGetLastError());
@@ -632,17 +618,17 @@ int itx_bamidx_finish(itx_bamidx *ix, hipStream_t st, uint64_t first, itx_bamout
         ITX_TRY(hipStreamSynchronize(st));                                  // the number of chunks sizes what follows
         C = (uint32_t)h_tot[0];
         ntC = (C + BI_TILE - 1) / BI_TILE;
-        if (hipMalloc((void **)&d_cbeg, 8 * (size_t)C) != hipSuccess || hipMalloc((void **)&d_cend, 8 * (size_t)C) != hipSuccess ||
-            hipMalloc((void **)&d_fbeg, 8 * (size_t)C) != hipSuccess || hipMalloc((void **)&d_fend, 8 * (size_t)C) != hipSuccess ||
-            hipMalloc((void **)&d_k0, 8 * (size_t)C) != hipSuccess || hipMalloc((void **)&d_k1, 8 * (size_t)C) != hipSuccess ||
-            hipMalloc((void **)&d_hist, itx_sort_hist_bytes(C)) != hipSuccess || hipMalloc((void **)&d_fkey, 4 * (size_t)C) != hipSuccess ||
-            hipMalloc((void **)&d_fbin, 4 * (size_t)C) != hipSuccess || hipMalloc((void **)&d_binfirst, 4 * ((size_t)C + 1)) != hipSuccess) {
-            (void)hipGetLastError();
+        if ((rc = itx_buf_need(who, cbeg, 8 * (size_t)C)) || (rc = itx_buf_need(who, cend, 8 * (size_t)C)) || (rc = itx_buf_need(who, fbeg, 8 * (size_t)C)) ||
+            (rc = itx_buf_need(who, fend, 8 * (size_t)C)) || (rc = itx_buf_need(who, k0, 8 * (size_t)C)) || (rc = itx_buf_need(who, k1, 8 * (size_t)C)) ||
+            (rc = itx_buf_need(who, hist, itx_sort_hist_bytes(C))) || (rc = itx_buf_need(who, fkey, 4 * (size_t)C)) || (rc = itx_buf_need(who, fbin, 4 * (size_t)C)) ||
+            (rc = itx_buf_need(who, binfirst, 4 * ((size_t)C + 1)))) {
             itx_set_error("itx_bamout_index_finish: no device memory for %u chunks", C);
-            rc = ITX_E_NOMEM;
             goto out;
         }
-        hipLaunchKernelGGL(k_bi_chunks, dim3(ntN), dim3(BI_TILE), 0, st, ix->d_ent, N, d_tb, d_coff, first, d_k0, d_cbeg, d_cend);
+        d_cbeg = cbeg.as<uint64_t>(), d_cend = cend.as<uint64_t>(), d_fbeg = fbeg.as<uint64_t>(), d_fend = fend.as<uint64_t>();
+        d_k0 = k0.as<uint2>(), d_k1 = k1.as<uint2>(), d_hist = hist.as<uint32_t>();
+        d_fkey = fkey.as<uint32_t>(), d_fbin = fbin.as<uint32_t>(), d_binfirst = binfirst.as<uint32_t>();
+        hipLaunchKernelGGL(k_bi_chunks, dim3(ntN), dim3(BI_TILE), 0, st, d_ent, N, d_tb, d_coff, first, d_k0, d_cbeg, d_cend);
         ITX_TRY(hipGetLastError());
         if ((rc = itx_sort_run(st, d_k0, d_k1, C, 0u, bi_sort_passes(ix->n_ref), d_hist, &sorted)) != ITX_OK) goto out;
         hipLaunchKernelGGL(k_bi_merge_count, dim3(ntC), dim3(BI_TILE), 0, st, sorted, C, d_cbeg, d_cend, d_ts);
@@ -651,68 +637,44 @@ int itx_bamidx_finish(itx_bamidx *ix, hipStream_t st, uint64_t first, itx_bamout
         ITX_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_bi_merge_apply, dim3(ntC), dim3(BI_TILE), 0, st, sorted, C, d_cbeg, d_cend, d_tb, d_fkey, d_fbin, d_fbeg, d_fend, d_binfirst, R);
         ITX_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_bi_windows, dim3((N + 255u) / 256u), dim3(256), 0, st, ix->d_ent, N, d_coff, first, ix->d_woff, d_lin, R);
+        hipLaunchKernelGGL(k_bi_windows, dim3((N + 255u) / 256u), dim3(256), 0, st, d_ent, N, d_coff, first, d_woff, d_lin, R);
         ITX_TRY(hipGetLastError());
     }
     if (n_ref) {
-        hipLaunchKernelGGL(k_bi_fill, dim3(n_ref), dim3(256), 0, st, ix->d_woff, d_lin, R.n_intv);
+        hipLaunchKernelGGL(k_bi_fill, dim3(n_ref), dim3(256), 0, st, d_woff, d_lin, R.n_intv);
         ITX_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(k_bi_refsize, dim3(1), dim3(ITX_SCAN_WG), 0, st, n_ref, R, d_roff);
     ITX_TRY(hipGetLastError());
     ITX_TRY(hipMemcpyAsync(h_tot, d_tot, 16, hipMemcpyDeviceToHost, st));
-    ITX_TRY(hipMemcpyAsync(ix->h_flag + 2, d_roff + n_ref, 8, hipMemcpyDeviceToHost, st));
+    ITX_TRY(hipMemcpyAsync(h_flag + 2, d_roff + n_ref, 8, hipMemcpyDeviceToHost, st));
     ITX_TRY(hipStreamSynchronize(st));                                      // the file's size
-    memcpy(&total, ix->h_flag + 2, 8);
+    memcpy(&total, h_flag + 2, 8);
     total += 8;
-    if (hipMalloc((void **)&ix->d_out, total) != hipSuccess || hipHostMalloc((void **)&ix->h_out, total, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
+    if ((rc = itx_buf_need(who, ix->d_out, total)) || (rc = itx_pin_need(who, ix->h_out, total))) {
         itx_set_error("itx_bamout_index_finish: no memory for an index of %llu bytes", (ull)total);
-        rc = ITX_E_NOMEM;
         goto out;
     }
-    hipLaunchKernelGGL(k_bi_write_refs, dim3(n_ref / 256u + 1u), dim3(256), 0, st, n_ref, R, d_roff, ix->d_ent, d_coff, first, ix->d_out);
+    d_out = ix->d_out.as<uint8_t>();
+    hipLaunchKernelGGL(k_bi_write_refs, dim3(n_ref / 256u + 1u), dim3(256), 0, st, n_ref, R, d_roff, d_ent, d_coff, first, d_out);
     ITX_TRY(hipGetLastError());
     if (C) {
-        hipLaunchKernelGGL(k_bi_write_chunks, dim3(ntC), dim3(256), 0, st, d_tot, d_fkey, d_fbin, d_fbeg, d_fend, d_binfirst, R, d_roff, ix->d_out);
+        hipLaunchKernelGGL(k_bi_write_chunks, dim3(ntC), dim3(256), 0, st, d_tot, d_fkey, d_fbin, d_fbeg, d_fend, d_binfirst, R, d_roff, d_out);
         ITX_TRY(hipGetLastError());
     }
     if (n_ref) {
-        hipLaunchKernelGGL(k_bi_write_linear, dim3(n_ref), dim3(256), 0, st, R, d_roff, ix->d_woff, d_lin, ix->d_out);
+        hipLaunchKernelGGL(k_bi_write_linear, dim3(n_ref), dim3(256), 0, st, R, d_roff, d_woff, d_lin, d_out);
         ITX_TRY(hipGetLastError());
     }
-    ITX_TRY(hipMemcpyAsync(ix->h_out, ix->d_out, total, hipMemcpyDeviceToHost, st));
+    ITX_TRY(hipMemcpyAsync(ix->h_out.p, d_out, total, hipMemcpyDeviceToHost, st));
     ITX_TRY(hipEventRecord(ix->ef[1], st));
     ITX_TRY(hipStreamSynchronize(st));
     if (hipEventElapsedTime(&ms, ix->ef[0], ix->ef[1]) == hipSuccess) ix->finish_ms = (double)ms;
-    res->bytes = ix->h_out;
+    res->bytes = ix->h_out.as<uint8_t>();
     res->len = total;
     res->chunks = C ? h_tot[0] : 0;
     res->finish_ms = ix->finish_ms;
     ix->done = 1;
 out:
-    (void)hipFree(d_coff);
-    (void)hipFree(d_cbeg);
-    (void)hipFree(d_cend);
-    (void)hipFree(d_fbeg);
-    (void)hipFree(d_fend);
-    (void)hipFree(d_roff);
-    (void)hipFree(d_ts);
-    (void)hipFree(d_tb);
-    (void)hipFree(d_tot);
-    (void)hipFree(d_lin);
-    (void)hipFree(d_k0);
-    (void)hipFree(d_k1);
-    (void)hipFree(d_hist);
-    (void)hipFree(d_fkey);
-    (void)hipFree(d_fbin);
-    (void)hipFree(d_binfirst);
-    (void)hipFree(d_refs);
-    if (h_tot) (void)hipHostFree(h_tot);
-    if (rc != ITX_OK) {
-        (void)hipFree(ix->d_out);
-        if (ix->h_out) (void)hipHostFree(ix->h_out);
-        ix->d_out = ix->h_out = nullptr;
-    }
-    return rc;
+    return rc;                                                              // (a finish that failed is not done; the next one sizes d_out, h_out again)
 }

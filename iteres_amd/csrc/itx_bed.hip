@@ -22,6 +22,7 @@
 #include "itx_textpack.h"
 #include "itx_derive.h"
 #include "itx_bedline.h"
+#include "itx_devbuf.h"
 
 #include <string.h>
 
@@ -132,20 +133,22 @@ __global__ __launch_bounds__(BED_TILE) void k_bed_write(BedDev D, const uint8_t 
 }
 
 struct BedSlot {
-    uint8_t *d_out[2], *h_out[2];     // [0] -B, [1] -V
-    size_t dcap[2], hcap[2];
+    ItxBuf d_out[2];                   // [0] -B, [1] -V
+    ItxPin h_out[2];
     uint64_t bytes[2];
     int started;
-    hipEvent_t ev[5];                  // measure: 0 .. 1, write: 2 .. 3, copies done: 4
+    ItxEvent ev[5];                    // measure: 0 .. 1, write: 2 .. 3, copies done: 4
 };
 
 struct itx_bed {
     int device;
     BedDev d;
     std::vector<int64_t> chrom_size;
-    void *d_tid, *d_name, *d_pool;
-    BedFound f;
-    unsigned long long *d_tile_sum, *d_tile_base, *d_tot, *h_tot;
+    ItxBuf d_tid, d_name, d_pool;
+    BedFound f;                        // views of f_mem
+    ItxBuf f_mem[6];
+    ItxBuf d_tile_sum, d_tile_base, d_tot;
+    ItxPin h_tot;
     size_t cap;
     hipStream_t st, st_copy;
     BedSlot slot[2];
@@ -153,41 +156,27 @@ struct itx_bed {
     itx_bed_stats stats;
 };
 
+#define BED_RC(call)                          \
+    do {                                      \
+        const int rc__ = (call);              \
+        if (rc__ != ITX_OK) return rc__;      \
+    } while (0)
+
 extern "C" void itx_bed_destroy(itx_bed *b)
 {
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
     if (b->st_copy) (void)hipStreamSynchronize(b->st_copy);
-    for (auto &s : b->slot) {
-        for (int k = 0; k < 2; k++) {
-            (void)hipFree(s.d_out[k]);
-            if (s.h_out[k]) (void)hipHostFree(s.h_out[k]);
-        }
-        for (auto &e : s.ev)
-            if (e) (void)hipEventDestroy(e);
-    }
     if (b->st) (void)hipStreamDestroy(b->st);
     if (b->st_copy) (void)hipStreamDestroy(b->st_copy);
-    (void)hipFree(b->d_tid);
-    (void)hipFree(b->d_name);
-    (void)hipFree(b->d_pool);
-    (void)hipFree(b->f.len_b);
-    (void)hipFree(b->f.len_v);
-    (void)hipFree(b->f.qlen);
-    (void)hipFree(b->f.xa_off);
-    (void)hipFree(b->f.xa_len);
-    (void)hipFree(b->f.nm);
-    (void)hipFree(b->d_tile_sum);
-    (void)hipFree(b->d_tile_base);
-    (void)hipFree(b->d_tot);
-    if (b->h_tot) (void)hipHostFree(b->h_tot);
     delete b;
 }
 
 // fills the object; on a non-zero return the caller destroys what there is of it
 static int bed_create(itx_bed *b, int device, const int64_t *chrom_size, int n_chrom, const itx_params *p, int want, size_t batch_capacity)
 {
+    const char *const who = "itx_bed_create";
     b->device = device;
     ITX_HIP(hipSetDevice(device));
     b->chrom_size.assign(chrom_size, chrom_size + n_chrom);
@@ -199,17 +188,17 @@ static int bed_create(itx_bed *b, int device, const int64_t *chrom_size, int n_c
     b->d.o.treat = p->treat_pe_as_se;
     b->d.o.discard = p->discard_half_mapped;
     const size_t n = batch_capacity + 64, nt = (batch_capacity + BED_TILE - 1) / BED_TILE + 1;
-    uint32_t **u32s[5] = {&b->f.len_b, &b->f.len_v, &b->f.qlen, &b->f.xa_off, &b->f.xa_len};
-    for (auto pp : u32s) ITX_HIP(hipMalloc((void **)pp, 4 * n));
-    ITX_HIP(hipMalloc((void **)&b->f.nm, 4 * n));
-    ITX_HIP(hipMalloc((void **)&b->d_tile_sum, 16 * nt));
-    ITX_HIP(hipMalloc((void **)&b->d_tile_base, 16 * nt));
-    ITX_HIP(hipMalloc((void **)&b->d_tot, 32));
-    ITX_HIP(hipHostMalloc((void **)&b->h_tot, 32, hipHostMallocDefault));
+    for (auto &m : b->f_mem) BED_RC(itx_buf_need(who, m, 4 * n));
+    b->f = {b->f_mem[0].as<uint32_t>(), b->f_mem[1].as<uint32_t>(), b->f_mem[2].as<uint32_t>(), b->f_mem[3].as<uint32_t>(), b->f_mem[4].as<uint32_t>(),
+            b->f_mem[5].as<int32_t>()};
+    BED_RC(itx_buf_need(who, b->d_tile_sum, 16 * nt));
+    BED_RC(itx_buf_need(who, b->d_tile_base, 16 * nt));
+    BED_RC(itx_buf_need(who, b->d_tot, 32));
+    BED_RC(itx_pin_need(who, b->h_tot, 32));
     ITX_HIP(hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
     ITX_HIP(hipStreamCreateWithFlags(&b->st_copy, hipStreamNonBlocking));
     for (auto &s : b->slot)
-        for (auto &e : s.ev) ITX_HIP(hipEventCreate(&e));
+        for (auto &e : s.ev) BED_RC(itx_event_make(e));
     return ITX_OK;
 }
 
@@ -256,20 +245,17 @@ extern "C" int itx_bed_set_tidmap(itx_bed *b, const int32_t *tid2chrom, const ch
     pool.append(16, '\0');
     ITX_HIP(hipStreamSynchronize(b->st));
     ITX_HIP(hipStreamSynchronize(b->st_copy));
-    void **old[3] = {&b->d_tid, &b->d_name, &b->d_pool};
-    for (auto pp : old) {
-        if (*pp) ITX_HIP(hipFree(*pp));
-        *pp = nullptr;
-    }
-    ITX_HIP(hipMalloc(&b->d_tid, sizeof(int2) * v.size()));
-    ITX_HIP(hipMalloc(&b->d_name, sizeof(uint2) * nm.size()));
-    ITX_HIP(hipMalloc(&b->d_pool, pool.size()));
-    ITX_HIP(hipMemcpy(b->d_tid, v.data(), sizeof(int2) * v.size(), hipMemcpyHostToDevice));
-    ITX_HIP(hipMemcpy(b->d_name, nm.data(), sizeof(uint2) * nm.size(), hipMemcpyHostToDevice));
-    ITX_HIP(hipMemcpy(b->d_pool, pool.data(), pool.size(), hipMemcpyHostToDevice));
-    b->d.tid = (const int2 *)b->d_tid;
-    b->d.name = (const uint2 *)b->d_name;
-    b->d.pool = (const uint8_t *)b->d_pool;
+    b->d.tid = nullptr;                                                     // (no map until the new one is whole)
+    for (ItxBuf *old : {&b->d_tid, &b->d_name, &b->d_pool}) old->drop();
+    BED_RC(itx_buf_need("itx_bed_set_tidmap", b->d_tid, sizeof(int2) * v.size()));
+    BED_RC(itx_buf_need("itx_bed_set_tidmap", b->d_name, sizeof(uint2) * nm.size()));
+    BED_RC(itx_buf_need("itx_bed_set_tidmap", b->d_pool, pool.size()));
+    ITX_HIP(hipMemcpy(b->d_tid.p, v.data(), sizeof(int2) * v.size(), hipMemcpyHostToDevice));
+    ITX_HIP(hipMemcpy(b->d_name.p, nm.data(), sizeof(uint2) * nm.size(), hipMemcpyHostToDevice));
+    ITX_HIP(hipMemcpy(b->d_pool.p, pool.data(), pool.size(), hipMemcpyHostToDevice));
+    b->d.tid = b->d_tid.as<int2>();
+    b->d.name = b->d_name.as<uint2>();
+    b->d.pool = b->d_pool.as<uint8_t>();
     b->d.n_tid = n_tid;
     return ITX_OK;
 }
@@ -292,65 +278,54 @@ int itx_bed_start(itx_bed *b, const uint8_t *u, const uint32_t *rec_off, const i
     s.bytes[0] = s.bytes[1] = 0;
     const BedRecs R = {tid, pos, end, mapq, f5, mpos, isize};
     const uint32_t nt = (uint32_t)((n + BED_TILE - 1) / BED_TILE);
+    unsigned long long *const d_tile_sum = b->d_tile_sum.as<unsigned long long>(), *const d_tile_base = b->d_tile_base.as<unsigned long long>(),
+                             *const d_tot = b->d_tot.as<unsigned long long>(), *const h_tot = b->h_tot.as<unsigned long long>();
     ITX_HIP(hipEventRecord(s.ev[0], b->st));
     if (n) {
-        ITX_HIP(hipMemsetAsync(b->d_tot, 0, 32, b->st));
-        hipLaunchKernelGGL(k_bed_measure, dim3(nt), dim3(BED_TILE), 0, b->st, b->d, u, rec_off, R, (uint32_t)n, b->f, b->d_tile_sum, b->d_tot);
+        ITX_HIP(hipMemsetAsync(d_tot, 0, 32, b->st));
+        hipLaunchKernelGGL(k_bed_measure, dim3(nt), dim3(BED_TILE), 0, b->st, b->d, u, rec_off, R, (uint32_t)n, b->f, d_tile_sum, d_tot);
         ITX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, b->st, b->d_tile_sum, nt, b->d_tile_base, b->d_tot);
+        hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, b->st, d_tile_sum, nt, d_tile_base, d_tot);
         ITX_HIP(hipGetLastError());
     }
     ITX_HIP(hipEventRecord(s.ev[1], b->st));
     if (n) {
         const double t0 = itx_wall_now();
-        ITX_HIP(hipMemcpyAsync(b->h_tot, b->d_tot, 32, hipMemcpyDeviceToHost, b->st));
+        ITX_HIP(hipMemcpyAsync(h_tot, d_tot, 32, hipMemcpyDeviceToHost, b->st));
         ITX_HIP(hipStreamSynchronize(b->st));
         b->stats.wait_s += itx_wall_now() - t0;
-        if (b->h_tot[2]) {                                                 // the host has to look: nothing of this batch is emitted
-            *n_hard = b->h_tot[2];
+        if (h_tot[2]) {                                                 // the host has to look: nothing of this batch is emitted
+            *n_hard = h_tot[2];
             b->stats.hard_batches++;
             return ITX_OK;
         }
         for (int k = 0; k < 2; k++) {
-            const uint64_t need = b->h_tot[k];
+            const uint64_t need = h_tot[k];
             s.bytes[k] = need;
-            if (need > s.dcap[k]) {
-                const size_t want = (size_t)(need + need / 4 + 4096);
-                if (s.d_out[k]) ITX_HIP(hipFree(s.d_out[k]));
-                s.d_out[k] = nullptr;
-                s.dcap[k] = 0;
-                if (hipMalloc((void **)&s.d_out[k], want) != hipSuccess) {
-                    itx_set_error("itx_bed: no device memory for %zu bytes of text", want);
-                    return ITX_E_NOMEM;
-                }
-                s.dcap[k] = want;
+            const size_t want = (size_t)(need + need / 4 + 4096);
+            if (need > s.d_out[k].cap && itx_buf_need("itx_bed", s.d_out[k], want) != ITX_OK) {
+                itx_set_error("itx_bed: no device memory for %zu bytes of text", want);
+                return ITX_E_NOMEM;
             }
-            if (need > s.hcap[k]) {
-                const size_t want = (size_t)(need + need / 4 + 4096);
-                if (s.h_out[k]) ITX_HIP(hipHostFree(s.h_out[k]));
-                s.h_out[k] = nullptr;
-                s.hcap[k] = 0;
-                if (hipHostMalloc((void **)&s.h_out[k], want, hipHostMallocDefault) != hipSuccess) {
-                    itx_set_error("itx_bed: no page-locked memory for %zu bytes of text", want);
-                    return ITX_E_NOMEM;
-                }
-                s.hcap[k] = want;
+            if (need > s.h_out[k].cap && itx_pin_need("itx_bed", s.h_out[k], want) != ITX_OK) {
+                itx_set_error("itx_bed: no page-locked memory for %zu bytes of text", want);
+                return ITX_E_NOMEM;
             }
         }
     }
     ITX_HIP(hipEventRecord(s.ev[2], b->st));
     if (s.bytes[0]) {
-        hipLaunchKernelGGL(k_bed_write<true>, dim3(nt), dim3(BED_TILE), 0, b->st, b->d, u, rec_off, R, (uint32_t)n, b->f, b->d_tile_base, s.d_out[0]);
+        hipLaunchKernelGGL(k_bed_write<true>, dim3(nt), dim3(BED_TILE), 0, b->st, b->d, u, rec_off, R, (uint32_t)n, b->f, d_tile_base, s.d_out[0].as<uint8_t>());
         ITX_HIP(hipGetLastError());
     }
     if (s.bytes[1]) {
-        hipLaunchKernelGGL(k_bed_write<false>, dim3(nt), dim3(BED_TILE), 0, b->st, b->d, u, rec_off, R, (uint32_t)n, b->f, b->d_tile_base, s.d_out[1]);
+        hipLaunchKernelGGL(k_bed_write<false>, dim3(nt), dim3(BED_TILE), 0, b->st, b->d, u, rec_off, R, (uint32_t)n, b->f, d_tile_base, s.d_out[1].as<uint8_t>());
         ITX_HIP(hipGetLastError());
     }
     ITX_HIP(hipEventRecord(s.ev[3], b->st));
     ITX_HIP(hipStreamWaitEvent(b->st_copy, s.ev[3], 0));
     for (int k = 0; k < 2; k++)
-        if (s.bytes[k]) ITX_HIP(hipMemcpyAsync(s.h_out[k], s.d_out[k], s.bytes[k], hipMemcpyDeviceToHost, b->st_copy));
+        if (s.bytes[k]) ITX_HIP(hipMemcpyAsync(s.h_out[k].p, s.d_out[k].p, s.bytes[k], hipMemcpyDeviceToHost, b->st_copy));
     ITX_HIP(hipEventRecord(s.ev[4], b->st_copy));
     s.started = 1;
     b->next ^= 1;
@@ -402,9 +377,9 @@ extern "C" int itx_bed_collect(itx_bed *b, itx_bed_text *out)
     b->stats.kernel_ms += (double)ma + (double)mw;
     b->stats.batches++;
     b->stats.bytes += s.bytes[0] + s.bytes[1];
-    out->all = (const char *)s.h_out[0];
+    out->all = s.h_out[0].as<const char>();
     out->all_bytes = s.bytes[0];
-    out->uniq = (const char *)s.h_out[1];
+    out->uniq = s.h_out[1].as<const char>();
     out->uniq_bytes = s.bytes[1];
     s.started = 0;
     b->in_flight--;

@@ -26,6 +26,7 @@
 // The table grows by rehashing on the device (cells never move otherwise). Everything is exact: hashes only pick cells.
 #include "itx_device.h"
 #include "itx_derive.h"
+#include "itx_devbuf.h"
 
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -242,44 +243,38 @@ struct itx_dedup {
     int n_chrom;
     std::vector<int32_t> chrom_size;
     DdParams p;
-    DdTable t;
+    DdTable t;                             // views of t_mem
+    ItxBuf t_mem[4];
     size_t cap;
-    void *d_tid, *d_tid_name;
-    DdState *d_state;
-    DdOver *d_over;
+    ItxBuf d_tid, d_tid_name, d_state, d_over;
     hipStream_t st;
     uint64_t base;                         // records seen so far (the next window's first number)
     uint32_t n_over_seen;
 };
 
-static int dd_alloc(DdTable *T, size_t cap, hipStream_t st)
+#define DD_RC(call)                           \
+    do {                                      \
+        const int rc__ = (call);              \
+        if (rc__ != ITX_OK) return rc__;      \
+    } while (0)
+
+// a cleared table of cap cells in M, *T its view
+static int dd_alloc(ItxBuf (&M)[4], DdTable *T, size_t cap, hipStream_t st)
 {
-    memset(T, 0, sizeof *T);
-    ITX_HIP(hipMalloc((void **)&T->h, cap * 8));
-    ITX_HIP(hipMalloc((void **)&T->idx, cap * 4));
-    ITX_HIP(hipMalloc((void **)&T->ka, cap * 8));
-    ITX_HIP(hipMalloc((void **)&T->kb, cap * 4));
-    T->mask = (uint32_t)(cap - 1);
+    DD_RC(itx_buf_need("itx_dedup", M[0], cap * 8));
+    DD_RC(itx_buf_need("itx_dedup", M[1], cap * 4));
+    DD_RC(itx_buf_need("itx_dedup", M[2], cap * 8));
+    DD_RC(itx_buf_need("itx_dedup", M[3], cap * 4));
+    *T = {M[0].as<unsigned long long>(), M[1].as<uint32_t>(), M[2].as<unsigned long long>(), M[3].as<uint32_t>(), (uint32_t)(cap - 1)};
     hipLaunchKernelGGL(k_dd_clear, dim3(4096), dim3(256), 0, st, *T, (uint32_t)cap);
     ITX_HIP(hipGetLastError());
     return ITX_OK;
 }
-static void dd_free(DdTable *T)
-{
-    (void)hipFree(T->h);
-    (void)hipFree(T->idx);
-    (void)hipFree(T->ka);
-    (void)hipFree(T->kb);
-    memset(T, 0, sizeof *T);
-}
 
-/* chrom_size[n_chrom] as for itx_table_create; p: mapq_min, extension, isize_max, treat_pe_as_se, discard_half_mapped */
-extern "C" int itx_dedup_create(int device, const int64_t *chrom_size, int n_chrom, const itx_params *p, size_t first_cells, itx_dedup **out)
+// fills the object; on a non-zero return the caller destroys what there is of it
+static int dd_create(itx_dedup *d, int device, const int64_t *chrom_size, int n_chrom, const itx_params *p, size_t first_cells)
 {
-    if (!out || !p || n_chrom < 0 || (n_chrom && !chrom_size)) return ITX_E_ARG;
-    *out = nullptr;
     ITX_HIP(hipSetDevice(device));
-    itx_dedup *d = new itx_dedup();
     d->device = device;
     d->n_chrom = n_chrom;
     d->chrom_size.resize((size_t)n_chrom + 1);
@@ -293,22 +288,34 @@ extern "C" int itx_dedup_create(int device, const int64_t *chrom_size, int n_chr
     d->p.hash_mask = ~0ull;
     if (const char *e = getenv("ITX_DEDUP_HASH_BITS"))
         if (atoi(e) >= 8 && atoi(e) < 64) d->p.hash_mask = (1ull << atoi(e)) - 1ull;
-    d->d_tid = d->d_tid_name = nullptr;
     d->base = 0;
     d->n_over_seen = 0;
     ITX_HIP(hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking));
     size_t cap = 1u << 16;
     while (cap < first_cells && cap < ((size_t)1 << 31)) cap <<= 1;
     d->cap = cap;
-    int rc = dd_alloc(&d->t, cap, d->st);
-    if (rc != ITX_OK) return rc;
-    ITX_HIP(hipMalloc((void **)&d->d_state, sizeof(DdState)));
-    ITX_HIP(hipMalloc((void **)&d->d_over, sizeof(DdOver) * DD_OVER_CAP));
+    DD_RC(dd_alloc(d->t_mem, &d->t, cap, d->st));
+    DD_RC(itx_buf_need("itx_dedup_create", d->d_state, sizeof(DdState)));
+    DD_RC(itx_buf_need("itx_dedup_create", d->d_over, sizeof(DdOver) * DD_OVER_CAP));
     DdState s0;
     memset(&s0, 0, sizeof s0);
     s0.first_ok = DD_NOIDX;
-    ITX_HIP(hipMemcpyAsync(d->d_state, &s0, sizeof s0, hipMemcpyHostToDevice, d->st));
+    ITX_HIP(hipMemcpyAsync(d->d_state.p, &s0, sizeof s0, hipMemcpyHostToDevice, d->st));
     ITX_HIP(hipStreamSynchronize(d->st));
+    return ITX_OK;
+}
+
+/* chrom_size[n_chrom] as for itx_table_create; p: mapq_min, extension, isize_max, treat_pe_as_se, discard_half_mapped */
+extern "C" int itx_dedup_create(int device, const int64_t *chrom_size, int n_chrom, const itx_params *p, size_t first_cells, itx_dedup **out)
+{
+    if (!out || !p || n_chrom < 0 || (n_chrom && !chrom_size)) return ITX_E_ARG;
+    *out = nullptr;
+    itx_dedup *d = new itx_dedup();
+    const int rc = dd_create(d, device, chrom_size, n_chrom, p, first_cells);
+    if (rc) {
+        itx_dedup_destroy(d);
+        return rc;
+    }
     *out = d;
     return ITX_OK;
 }
@@ -321,11 +328,6 @@ extern "C" void itx_dedup_destroy(itx_dedup *d)
         (void)hipStreamSynchronize(d->st);
         (void)hipStreamDestroy(d->st);
     }
-    dd_free(&d->t);
-    (void)hipFree(d->d_tid);
-    (void)hipFree(d->d_tid_name);
-    (void)hipFree(d->d_state);
-    (void)hipFree(d->d_over);
     delete d;
 }
 
@@ -347,15 +349,15 @@ extern "C" int itx_dedup_set_tidmap(itx_dedup *d, const int32_t *tid2chrom, cons
         nm[(size_t)k] = tid2name[k];
     }
     ITX_HIP(hipStreamSynchronize(d->st));
-    (void)hipFree(d->d_tid);
-    (void)hipFree(d->d_tid_name);
-    d->d_tid = d->d_tid_name = nullptr;
-    ITX_HIP(hipMalloc(&d->d_tid, sizeof(int2) * ((size_t)n_tid + 1)));
-    ITX_HIP(hipMalloc(&d->d_tid_name, 4 * ((size_t)n_tid + 1)));
-    ITX_HIP(hipMemcpy(d->d_tid, v.data(), sizeof(int2) * ((size_t)n_tid + 1), hipMemcpyHostToDevice));
-    ITX_HIP(hipMemcpy(d->d_tid_name, nm.data(), 4 * ((size_t)n_tid + 1), hipMemcpyHostToDevice));
-    d->p.tid = (const int2 *)d->d_tid;
-    d->p.tid_name = (const uint32_t *)d->d_tid_name;
+    d->p.tid = nullptr;                                                    // (no map until the new one is whole)
+    d->d_tid.drop();
+    d->d_tid_name.drop();
+    DD_RC(itx_buf_need("itx_dedup_set_tidmap", d->d_tid, sizeof(int2) * ((size_t)n_tid + 1)));
+    DD_RC(itx_buf_need("itx_dedup_set_tidmap", d->d_tid_name, 4 * ((size_t)n_tid + 1)));
+    ITX_HIP(hipMemcpy(d->d_tid.p, v.data(), sizeof(int2) * ((size_t)n_tid + 1), hipMemcpyHostToDevice));
+    ITX_HIP(hipMemcpy(d->d_tid_name.p, nm.data(), 4 * ((size_t)n_tid + 1), hipMemcpyHostToDevice));
+    d->p.tid = d->d_tid.as<int2>();
+    d->p.tid_name = d->d_tid_name.as<uint32_t>();
     d->p.n_tid = n_tid;
     return ITX_OK;
 }
@@ -377,7 +379,7 @@ extern "C" int itx_dedup_run(itx_dedup *d, const int32_t *tid, const int32_t *po
     }
     ITX_HIP(hipSetDevice(d->device));
     DdState s;
-    ITX_HIP(hipMemcpyAsync(&s, d->d_state, sizeof s, hipMemcpyDeviceToHost, d->st));
+    ITX_HIP(hipMemcpyAsync(&s, d->d_state.p, sizeof s, hipMemcpyDeviceToHost, d->st));
     ITX_HIP(hipStreamSynchronize(d->st));
     // room for every record of the window to bring a new key, at a load factor below 0.7
     if (((size_t)s.n_cells + n) * 10 > d->cap * 7) {
@@ -388,29 +390,29 @@ extern "C" int itx_dedup_run(itx_dedup *d, const int32_t *tid, const int32_t *po
             return ITX_E_LIMIT;
         }
         DdTable nt;
-        int rc = dd_alloc(&nt, ncap, d->st);
-        if (rc != ITX_OK) return rc;
+        ItxBuf nt_mem[4];
+        DD_RC(dd_alloc(nt_mem, &nt, ncap, d->st));
         hipLaunchKernelGGL(k_dd_rehash, dim3(4096), dim3(256), 0, d->st, d->t, (uint32_t)d->cap, nt);
         ITX_HIP(hipGetLastError());
         ITX_HIP(hipStreamSynchronize(d->st));
-        dd_free(&d->t);
+        for (int k = 0; k < 4; k++) d->t_mem[k].swap(nt_mem[k]);           // (the old table goes with nt_mem)
         d->t = nt;
         d->cap = ncap;
     }
     const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
     const uint32_t base = (uint32_t)d->base;
-    hipLaunchKernelGGL(k_dd_claim, grid, blk, 0, d->st, d->p, d->t, d->d_state, (const uint8_t *)flag5, tid, pos, tmpend, mapq, mpos, isize, (uint32_t)n, base);
+    hipLaunchKernelGGL(k_dd_claim, grid, blk, 0, d->st, d->p, d->t, d->d_state.as<DdState>(), (const uint8_t *)flag5, tid, pos, tmpend, mapq, mpos, isize, (uint32_t)n, base);
     hipLaunchKernelGGL(k_dd_owner, grid, blk, 0, d->st, d->p, d->t, (const uint8_t *)flag5, tid, pos, tmpend, mapq, mpos, isize, (uint32_t)n, base);
-    hipLaunchKernelGGL(k_dd_verdict, grid, blk, 0, d->st, d->p, d->t, d->d_state, d->d_over, flag5, tid, pos, tmpend, mapq, mpos, isize, (uint32_t)n, base);
+    hipLaunchKernelGGL(k_dd_verdict, grid, blk, 0, d->st, d->p, d->t, d->d_state.as<DdState>(), d->d_over.as<DdOver>(), flag5, tid, pos, tmpend, mapq, mpos, isize, (uint32_t)n, base);
     ITX_HIP(hipGetLastError());
-    ITX_HIP(hipMemcpyAsync(&s, d->d_state, sizeof s, hipMemcpyDeviceToHost, d->st));
+    ITX_HIP(hipMemcpyAsync(&s, d->d_state.p, sizeof s, hipMemcpyDeviceToHost, d->st));
     ITX_HIP(hipStreamSynchronize(d->st));
     if (s.n_over > DD_OVER_CAP) {
         itx_set_error("itx_dedup_run: more than %u keys share a 64-bit hash with another key", DD_OVER_CAP);
         return ITX_E_LIMIT;
     }
     if (s.n_over > d->n_over_seen) {
-        hipLaunchKernelGGL(k_dd_overflow, dim3(1), blk, 0, d->st, d->d_state, (const DdOver *)d->d_over, d->n_over_seen, s.n_over, flag5, base);
+        hipLaunchKernelGGL(k_dd_overflow, dim3(1), blk, 0, d->st, d->d_state.as<DdState>(), d->d_over.as<DdOver>(), d->n_over_seen, s.n_over, flag5, base);
         ITX_HIP(hipGetLastError());
         ITX_HIP(hipStreamSynchronize(d->st));
         d->n_over_seen = s.n_over;
@@ -425,7 +427,7 @@ extern "C" int itx_dedup_counts(itx_dedup *d, uint64_t *dup_unique, uint64_t *dr
     if (!d) return ITX_E_ARG;
     ITX_HIP(hipSetDevice(d->device));
     DdState s;
-    ITX_HIP(hipMemcpy(&s, d->d_state, sizeof s, hipMemcpyDeviceToHost));
+    ITX_HIP(hipMemcpy(&s, d->d_state.p, sizeof s, hipMemcpyDeviceToHost));
     if (dup_unique) *dup_unique = s.dup_unique;
     if (dropped) *dropped = s.dropped;
     if (keys) *keys = (uint64_t)s.n_cells + s.n_over;

@@ -3,37 +3,70 @@
 //   itx_copy_out                      device memory to host memory, in chunks through a page-locked pair
 //   ItxBuf, itx_buf_need              a device buffer that lives as long as its scope (a build's working memory, an object's
 //                                     members): made or enlarged on demand WITHOUT keeping what it held, freed by its destructor
+//   ItxPin, itx_pin_need              the same in page-locked host memory
+//   ItxEvent, itx_event_make          an event that lives as long as its scope
 #pragma once
 #include "itx_common.h"
 
 #include <string.h>
 
-struct ItxBuf {
+template <bool PINNED>
+struct ItxMem {
     void *p = nullptr;
     size_t cap = 0;
-    ItxBuf() = default;
-    ItxBuf(const ItxBuf &) = delete;
-    ItxBuf &operator=(const ItxBuf &) = delete;
-    ~ItxBuf() { drop(); }                    // (the owner has waited for the work that uses it)
-    void drop() { (void)hipFree(p), p = nullptr, cap = 0; }
+    ItxMem() = default;
+    ItxMem(const ItxMem &) = delete;
+    ItxMem &operator=(const ItxMem &) = delete;
+    ~ItxMem() { drop(); }                    // (the owner has waited for the work that uses it)
+    void drop()
+    {
+        if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+        p = nullptr, cap = 0;
+    }
+    void swap(ItxMem &o)
+    {
+        void *const op = o.p;
+        const size_t oc = o.cap;
+        o.p = p, o.cap = cap, p = op, cap = oc;
+    }
     template <class T>
     T *as() const { return (T *)p; }
 };
+typedef ItxMem<false> ItxBuf;
+typedef ItxMem<true> ItxPin;
 
-// ITX_OK, or ITX_E_NOMEM with "who: no device memory for N bytes" (HIP's error is cleared, the buffer is empty)
-static inline int itx_buf_need(const char *who, ItxBuf &b, size_t bytes)
+// ITX_OK, or ITX_E_NOMEM with "who: no device (page-locked) memory for N bytes" (HIP's error is cleared, the buffer is empty)
+template <bool PINNED>
+static inline int itx_mem_need(const char *who, ItxMem<PINNED> &b, size_t bytes)
 {
     if (bytes <= b.cap && b.p) return ITX_OK;
     b.drop();
-    if (hipMalloc(&b.p, bytes ? bytes : 16) != hipSuccess) {
+    const size_t take = bytes ? bytes : 16;
+    if ((PINNED ? hipHostMalloc(&b.p, take, hipHostMallocDefault) : hipMalloc(&b.p, take)) != hipSuccess) {
         (void)hipGetLastError();
         b.p = nullptr;
-        itx_set_error("%s: no device memory for %zu bytes", who, bytes);
+        itx_set_error("%s: no %s memory for %zu bytes", who, PINNED ? "page-locked" : "device", bytes);
         return ITX_E_NOMEM;
     }
     b.cap = bytes;
     return ITX_OK;
 }
+static inline int itx_buf_need(const char *who, ItxBuf &b, size_t bytes) { return itx_mem_need(who, b, bytes); }
+static inline int itx_pin_need(const char *who, ItxPin &b, size_t bytes) { return itx_mem_need(who, b, bytes); }
+
+struct ItxEvent {
+    hipEvent_t e = nullptr;
+    ItxEvent() = default;
+    ItxEvent(const ItxEvent &) = delete;
+    ItxEvent &operator=(const ItxEvent &) = delete;
+    ~ItxEvent()
+    {
+        if (e) (void)hipEventDestroy(e);
+    }
+    operator hipEvent_t() const { return e; }
+};
+
+static inline int itx_event_make(ItxEvent &ev) { return ev.e ? ITX_OK : itx_hip_rc(hipEventCreate(&ev.e), "hipEventCreate", __FILE__, __LINE__); }
 
 // One buffer of a growth: *ptr becomes a buffer of `want` bytes (0: it stays as it is) that holds the first `keep` bytes of the old one.
 struct ItxGrow {

@@ -32,6 +32,7 @@
 #include "itx_derive.h"
 #include "itx_bedline.h"
 #include "itx_gcovbw.h"
+#include "itx_devbuf.h"
 
 #include <string.h>
 
@@ -292,7 +293,7 @@ __global__ __launch_bounds__(GC_TXT_TILE) void k_gc_text_write(GcText T, ull fir
 
 // ---- host side
 struct GcFile {                       // one of the two files, from finish on
-    uint4 *d_pts;
+    ItxBuf d_pts;                     // uint4[n_pts]
     ull n_pts, cursor;
     int started, done, flying;        // flying: a round is in slot `slot`
     int slot;
@@ -302,34 +303,33 @@ struct GcFile {                       // one of the two files, from finish on
 
 struct itx_gcov {
     int device;
-    GcDev d;
+    GcDev d;                          // (its two arrays are allocated and given back by hand: timed, and free before the text)
     std::vector<int64_t> chrom_size;
-    void *d_tid;
-    ull *d_off, *d_cnt, *h_tot;
-    uint32_t *d_size;
+    ItxBuf d_tid, d_off, d_size, d_cnt, d_hits;
+    ItxPin h_tot;
     ull slots;
-    size_t cap;
-    int32_t *d_hits;
     hipStream_t st, last;             // last: where the newest add kernel was enqueued
-    hipEvent_t ev_add[2], ev_rnd[2][3];
+    ItxEvent ev_add[2], ev_rnd[2][3];
     int add_timed;
-    // the host route's intervals on their way up
-    int32_t *d_hc;
-    uint32_t *d_hs, *d_he;
-    uint8_t *d_hu;
+    ItxBuf d_hc, d_hs, d_he, d_hu;    // the host route's intervals on their way up
     // from finish on
     int finished, cur_file;
     GcFile file[2];
-    void *d_vfirst, *d_voff, *d_vsize, *d_vname, *d_pool;
+    ItxBuf d_vfirst, d_voff, d_vsize, d_vname, d_pool;
     GcVisit V;
     uint32_t max_name;
     ull per_round;
-    size_t text_cap;
-    uint8_t *d_text[2], *h_text[2];
-    ull *d_tsum, *d_tbase, *d_ttot;
+    ItxBuf d_text[2];                 // a round's text: both of one size, as are the page-locked two
+    ItxPin h_text[2];
+    ItxBuf d_tsum, d_tbase, d_ttot;
     std::vector<uint32_t> h_vsize, h_vchrom;                               // the visited chromosomes: size, index into chrom_size
     itx_gcov_stats stats;
 };
+
+#define GC_RC(call)                               \
+    do {                                          \
+        if ((rc = (call)) != ITX_OK) goto out;    \
+    } while (0)
 
 static void gc_free_arrays(itx_gcov *g)
 {
@@ -345,38 +345,9 @@ extern "C" void itx_gcov_destroy(itx_gcov *g)
     (void)hipSetDevice(g->device);
     if (g->last) (void)hipStreamSynchronize(g->last);
     if (g->st) (void)hipStreamSynchronize(g->st);
-    for (auto &e : g->ev_add)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &s : g->ev_rnd)
-        for (auto &e : s)
-            if (e) (void)hipEventDestroy(e);
     if (g->st) (void)hipStreamDestroy(g->st);
     gc_free_arrays(g);
-    (void)hipFree(g->d_tid);
-    (void)hipFree(g->d_off);
-    (void)hipFree(g->d_size);
-    (void)hipFree(g->d_cnt);
-    (void)hipFree(g->d_hits);
-    (void)hipFree(g->d_hc);
-    (void)hipFree(g->d_hs);
-    (void)hipFree(g->d_he);
-    (void)hipFree(g->d_hu);
-    for (auto &f : g->file) {
-        (void)hipFree(f.d_pts);
-        gcbw_free(f.bw);
-    }
-    (void)hipFree(g->d_vfirst);
-    (void)hipFree(g->d_voff);
-    (void)hipFree(g->d_vsize);
-    (void)hipFree(g->d_vname);
-    (void)hipFree(g->d_pool);
-    (void)hipFree(g->d_tsum);
-    (void)hipFree(g->d_tbase);
-    (void)hipFree(g->d_ttot);
-    for (auto &p : g->d_text) (void)hipFree(p);
-    for (auto &p : g->h_text)
-        if (p) (void)hipHostFree(p);
-    if (g->h_tot) (void)hipHostFree(g->h_tot);
+    for (auto &f : g->file) gcbw_free(f.bw);
     delete g;
 }
 
@@ -395,7 +366,6 @@ extern "C" int itx_gcov_create(int device, const int64_t *chrom_size, int n_chro
     int rc = ITX_OK;
     itx_gcov *g = new itx_gcov();
     g->device = device;
-    g->cap = batch_capacity;
     g->cur_file = -1;
     g->chrom_size.assign(chrom_size, chrom_size + n_chrom);
     g->d.n_chrom = n_chrom;
@@ -435,31 +405,31 @@ extern "C" int itx_gcov_create(int device, const int64_t *chrom_size, int n_chro
     g->stats.slots = total;
     g->stats.device_bytes = 2ull * bytes;
     ITX_TRY(hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking));
-    for (auto &e : g->ev_add) ITX_TRY(hipEventCreate(&e));
+    for (auto &e : g->ev_add) GC_RC(itx_event_make(e));
     for (auto &s : g->ev_rnd)
-        for (auto &e : s) ITX_TRY(hipEventCreate(&e));
+        for (auto &e : s) GC_RC(itx_event_make(e));
     ITX_TRY(hipEventRecord(g->ev_rnd[0][0], g->st));
     for (auto &a : g->d.arr)
         for (size_t at = 0; at < bytes; at += GC_MEMSET_CHUNK)
             ITX_TRY(hipMemsetAsync((uint8_t *)a + at, 0, bytes - at < GC_MEMSET_CHUNK ? bytes - at : GC_MEMSET_CHUNK, g->st));
     ITX_TRY(hipEventRecord(g->ev_rnd[0][1], g->st));
-    ITX_TRY(hipMalloc((void **)&g->d_off, 8 * off.size()));
-    ITX_TRY(hipMalloc((void **)&g->d_size, 4 * size.size()));
-    ITX_TRY(hipMalloc((void **)&g->d_cnt, 64));
-    ITX_TRY(hipMalloc((void **)&g->d_hits, 4 * (batch_capacity + 64)));
-    ITX_TRY(hipHostMalloc((void **)&g->h_tot, 64, hipHostMallocDefault));
-    ITX_TRY(hipMemcpyAsync(g->d_off, off.data(), 8 * off.size(), hipMemcpyHostToDevice, g->st));
-    ITX_TRY(hipMemcpyAsync(g->d_size, size.data(), 4 * size.size(), hipMemcpyHostToDevice, g->st));
-    ITX_TRY(hipMemsetAsync(g->d_cnt, 0, 64, g->st));
+    GC_RC(itx_buf_need("itx_gcov_create", g->d_off, 8 * off.size()));
+    GC_RC(itx_buf_need("itx_gcov_create", g->d_size, 4 * size.size()));
+    GC_RC(itx_buf_need("itx_gcov_create", g->d_cnt, 64));
+    GC_RC(itx_buf_need("itx_gcov_create", g->d_hits, 4 * (batch_capacity + 64)));
+    GC_RC(itx_pin_need("itx_gcov_create", g->h_tot, 64));
+    ITX_TRY(hipMemcpyAsync(g->d_off.p, off.data(), 8 * off.size(), hipMemcpyHostToDevice, g->st));
+    ITX_TRY(hipMemcpyAsync(g->d_size.p, size.data(), 4 * size.size(), hipMemcpyHostToDevice, g->st));
+    ITX_TRY(hipMemsetAsync(g->d_cnt.p, 0, 64, g->st));
     ITX_TRY(hipStreamSynchronize(g->st));                                   // off, size are this function's
     {
         float ms = 0;
         ITX_TRY(hipEventElapsedTime(&ms, g->ev_rnd[0][0], g->ev_rnd[0][1]));
         g->stats.zero_ms = (double)ms;
     }
-    g->d.off = g->d_off;
-    g->d.size = g->d_size;
-    g->d.cnt = g->d_cnt;
+    g->d.off = g->d_off.as<ull>();
+    g->d.size = g->d_size.as<uint32_t>();
+    g->d.cnt = g->d_cnt.as<ull>();
 out:
     if (rc != ITX_OK) {
         itx_gcov_destroy(g);
@@ -469,7 +439,7 @@ out:
     return ITX_OK;
 }
 
-extern "C" int32_t *itx_gcov_hits(itx_gcov *g) { return g ? g->d_hits : nullptr; }
+extern "C" int32_t *itx_gcov_hits(itx_gcov *g) { return g ? g->d_hits.as<int32_t>() : nullptr; }
 extern "C" void *itx_gcov_stream(itx_gcov *g) { return g ? (void *)g->st : nullptr; }
 
 // the newest add kernel is waited for and its time read
@@ -498,7 +468,7 @@ extern "C" int itx_gcov_set_tidmap(itx_gcov *g, const int32_t *tid2chrom, int n_
         return ITX_E_STATE;
     }
     int rc = ITX_OK;
-    void *nt = nullptr;
+    ItxBuf nt;
     std::vector<int2> v((size_t)n_tid + 1, make_int2(-1, 0));
     for (int k = 0; k < n_tid; k++) {
         const int32_t c = tid2chrom[k];
@@ -506,18 +476,13 @@ extern "C" int itx_gcov_set_tidmap(itx_gcov *g, const int32_t *tid2chrom, int n_
     }
     ITX_TRY(hipSetDevice(g->device));
     if ((rc = gc_settle(g)) != ITX_OK) goto out;                           // no kernel reads the old map any more
-    ITX_TRY(hipMalloc(&nt, sizeof(int2) * v.size()));
-    ITX_TRY(hipMemcpy(nt, v.data(), sizeof(int2) * v.size(), hipMemcpyHostToDevice));
-    {
-        void *old = g->d_tid;
-        g->d_tid = nt;
-        nt = old;
-    }
-    g->d.tid = (const int2 *)g->d_tid;
+    GC_RC(itx_buf_need("itx_gcov_set_tidmap", nt, sizeof(int2) * v.size()));
+    ITX_TRY(hipMemcpy(nt.p, v.data(), sizeof(int2) * v.size(), hipMemcpyHostToDevice));
+    g->d_tid.swap(nt);
+    g->d.tid = g->d_tid.as<int2>();
     g->d.n_tid = n_tid;
 out:
-    (void)hipFree(nt);                                                     // the old map, or the new one that was not taken
-    return rc;
+    return rc;                                                             // (nt goes: the old map, or the new one that was not taken)
 }
 
 extern "C" int itx_gcov_run(itx_gcov *g, const itx_batch *b, const int32_t *d_hit_row, size_t n, void *stream)
@@ -577,21 +542,20 @@ extern "C" int itx_gcov_add_host(itx_gcov *g, const int32_t *chrom, const uint32
     if (!n) return ITX_OK;
     int rc = ITX_OK;
     ITX_TRY(hipSetDevice(g->device));
-    if (!g->d_hc) {
-        ITX_TRY(hipMalloc((void **)&g->d_hc, 4 * GC_HOST_CHUNK));
-        ITX_TRY(hipMalloc((void **)&g->d_hs, 4 * GC_HOST_CHUNK));
-        ITX_TRY(hipMalloc((void **)&g->d_he, 4 * GC_HOST_CHUNK));
-        ITX_TRY(hipMalloc((void **)&g->d_hu, GC_HOST_CHUNK));
-    }
+    GC_RC(itx_buf_need("itx_gcov_add_host", g->d_hc, 4 * GC_HOST_CHUNK));
+    GC_RC(itx_buf_need("itx_gcov_add_host", g->d_hs, 4 * GC_HOST_CHUNK));
+    GC_RC(itx_buf_need("itx_gcov_add_host", g->d_he, 4 * GC_HOST_CHUNK));
+    GC_RC(itx_buf_need("itx_gcov_add_host", g->d_hu, GC_HOST_CHUNK));
     if ((rc = gc_settle(g)) != ITX_OK) goto out;
     for (size_t at = 0; at < n; at += GC_HOST_CHUNK) {
         const size_t m = n - at < GC_HOST_CHUNK ? n - at : GC_HOST_CHUNK;
-        ITX_TRY(hipMemcpyAsync(g->d_hc, chrom + at, 4 * m, hipMemcpyHostToDevice, g->st));
-        ITX_TRY(hipMemcpyAsync(g->d_hs, start + at, 4 * m, hipMemcpyHostToDevice, g->st));
-        ITX_TRY(hipMemcpyAsync(g->d_he, end + at, 4 * m, hipMemcpyHostToDevice, g->st));
-        ITX_TRY(hipMemcpyAsync(g->d_hu, uniq + at, m, hipMemcpyHostToDevice, g->st));
+        ITX_TRY(hipMemcpyAsync(g->d_hc.p, chrom + at, 4 * m, hipMemcpyHostToDevice, g->st));
+        ITX_TRY(hipMemcpyAsync(g->d_hs.p, start + at, 4 * m, hipMemcpyHostToDevice, g->st));
+        ITX_TRY(hipMemcpyAsync(g->d_he.p, end + at, 4 * m, hipMemcpyHostToDevice, g->st));
+        ITX_TRY(hipMemcpyAsync(g->d_hu.p, uniq + at, m, hipMemcpyHostToDevice, g->st));
         ITX_TRY(hipEventRecord(g->ev_add[0], g->st));
-        hipLaunchKernelGGL(k_gc_add_iv, dim3((uint32_t)((m + GC_WG - 1) / GC_WG)), dim3(GC_WG), 0, g->st, g->d, g->d_hc, g->d_hs, g->d_he, g->d_hu, (uint32_t)m);
+        hipLaunchKernelGGL(k_gc_add_iv, dim3((uint32_t)((m + GC_WG - 1) / GC_WG)), dim3(GC_WG), 0, g->st, g->d, g->d_hc.as<int32_t>(), g->d_hs.as<uint32_t>(), g->d_he.as<uint32_t>(),
+                           g->d_hu.as<uint8_t>(), (uint32_t)m);
         ITX_TRY(hipGetLastError());
         ITX_TRY(hipEventRecord(g->ev_add[1], g->st));
         g->add_timed = 1;
@@ -611,23 +575,21 @@ static int gc_points(itx_gcov *g, int w, uint32_t n_tiles, ull *d_tsum, ull *d_t
     if (!n_tiles) return ITX_OK;
     hipLaunchKernelGGL(k_gc_measure, dim3(n_tiles), dim3(GC_WG), 0, g->st, g->d.arr[w], g->V, d_tsum);
     ITX_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, g->st, d_tsum, n_tiles, d_tbase, g->d_cnt + 3);
+    hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, g->st, d_tsum, n_tiles, d_tbase, g->d.cnt + 3);
     ITX_TRY(hipGetLastError());
-    ITX_TRY(hipMemcpyAsync(g->h_tot, g->d_cnt + 3, 8, hipMemcpyDeviceToHost, g->st));
+    ITX_TRY(hipMemcpyAsync(g->h_tot.p, g->d.cnt + 3, 8, hipMemcpyDeviceToHost, g->st));
     {
         const double t0 = itx_wall_now();
         ITX_TRY(hipStreamSynchronize(g->st));
         g->stats.wait_s += itx_wall_now() - t0;
     }
-    F.n_pts = g->h_tot[0];
+    F.n_pts = g->h_tot.as<ull>()[0];
     if (!F.n_pts) return ITX_OK;
-    if (hipMalloc((void **)&F.d_pts, sizeof(uint4) * (size_t)F.n_pts) != hipSuccess) {
-        (void)hipGetLastError();
-        F.d_pts = nullptr;
+    if ((rc = itx_buf_need("itx_gcov_finish", F.d_pts, sizeof(uint4) * (size_t)F.n_pts)) != ITX_OK) {
         itx_set_error("itx_gcov_finish: no device memory for %llu change points", F.n_pts);
-        return ITX_E_NOMEM;
+        return rc;
     }
-    hipLaunchKernelGGL(k_gc_points, dim3(n_tiles), dim3(GC_WG), 0, g->st, g->d.arr[w], g->V, d_tsum, d_tbase, F.d_pts);
+    hipLaunchKernelGGL(k_gc_points, dim3(n_tiles), dim3(GC_WG), 0, g->st, g->d.arr[w], g->V, d_tsum, d_tbase, F.d_pts.as<uint4>());
     ITX_TRY(hipGetLastError());
 out:
     return rc;
@@ -692,52 +654,49 @@ extern "C" int itx_gcov_finish(itx_gcov *g, const uint32_t *order, int n_order, 
     const size_t text_cap = (size_t)(per_round * line_max) + 16;
     const size_t txt_tiles = (size_t)((per_round + GC_TXT_TILE - 1) / GC_TXT_TILE) + 1;
     int rc = ITX_OK;
-    ull *d_tsum = nullptr, *d_tbase = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const char *const who = "itx_gcov_finish";
+    ItxBuf tsum, tbase;                                                    // the dense pass's tile arrays
+    ItxEvent e0, e1;
     float ms = 0;
     ITX_TRY(hipSetDevice(g->device));
     if ((rc = gc_settle(g)) != ITX_OK) goto out;
     ITX_TRY(hipStreamSynchronize(g->st));
-    ITX_TRY(hipMemcpy(g->h_tot, g->d_cnt, 24, hipMemcpyDeviceToHost));
-    g->stats.records = g->h_tot[0];
-    g->stats.out_of_range = g->h_tot[1];
-    g->stats.records_uniq = g->h_tot[2];
-    ITX_TRY(hipEventCreate(&e0));
-    ITX_TRY(hipEventCreate(&e1));
+    ITX_TRY(hipMemcpy(g->h_tot.p, g->d_cnt.p, 24, hipMemcpyDeviceToHost));
+    g->stats.records = g->h_tot.as<ull>()[0];
+    g->stats.out_of_range = g->h_tot.as<ull>()[1];
+    g->stats.records_uniq = g->h_tot.as<ull>()[2];
+    GC_RC(itx_event_make(e0));
+    GC_RC(itx_event_make(e1));
     // everything the rounds will need, before the first point is made: a refusal leaves the arrays as they were
-    if (hipMalloc((void **)&d_tsum, 16 * ((size_t)n_tiles + 1)) != hipSuccess || hipMalloc((void **)&d_tbase, 16 * ((size_t)n_tiles + 1)) != hipSuccess ||
-        hipMalloc(&g->d_vfirst, 4 * vfirst.size()) != hipSuccess || hipMalloc(&g->d_voff, 8 * (voff.size() + 1)) != hipSuccess ||
-        hipMalloc(&g->d_vsize, 4 * (vsize.size() + 1)) != hipSuccess || hipMalloc(&g->d_vname, 8 * (vname.size() + 1)) != hipSuccess ||
-        hipMalloc(&g->d_pool, pool.size()) != hipSuccess || hipMalloc((void **)&g->d_tsum, 16 * txt_tiles) != hipSuccess ||
-        hipMalloc((void **)&g->d_tbase, 16 * txt_tiles) != hipSuccess || hipMalloc((void **)&g->d_ttot, 32) != hipSuccess ||
-        hipMalloc((void **)&g->d_text[0], text_cap) != hipSuccess || hipMalloc((void **)&g->d_text[1], text_cap) != hipSuccess ||
-        hipHostMalloc((void **)&g->h_text[0], text_cap, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void **)&g->h_text[1], text_cap, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
+    if ((rc = itx_buf_need(who, tsum, 16 * ((size_t)n_tiles + 1))) || (rc = itx_buf_need(who, tbase, 16 * ((size_t)n_tiles + 1))) ||
+        (rc = itx_buf_need(who, g->d_vfirst, 4 * vfirst.size())) || (rc = itx_buf_need(who, g->d_voff, 8 * (voff.size() + 1))) ||
+        (rc = itx_buf_need(who, g->d_vsize, 4 * (vsize.size() + 1))) || (rc = itx_buf_need(who, g->d_vname, 8 * (vname.size() + 1))) ||
+        (rc = itx_buf_need(who, g->d_pool, pool.size())) || (rc = itx_buf_need(who, g->d_tsum, 16 * txt_tiles)) ||
+        (rc = itx_buf_need(who, g->d_tbase, 16 * txt_tiles)) || (rc = itx_buf_need(who, g->d_ttot, 32)) ||
+        (rc = itx_buf_need(who, g->d_text[0], text_cap)) || (rc = itx_buf_need(who, g->d_text[1], text_cap)) ||
+        (rc = itx_pin_need(who, g->h_text[0], text_cap)) || (rc = itx_pin_need(who, g->h_text[1], text_cap))) {
         itx_set_error("itx_gcov_finish: no memory for %u tiles and rounds of %zu bytes", n_tiles, text_cap);
-        rc = ITX_E_NOMEM;
         goto out;
     }
-    ITX_TRY(hipMemcpyAsync(g->d_vfirst, vfirst.data(), 4 * vfirst.size(), hipMemcpyHostToDevice, g->st));
+    ITX_TRY(hipMemcpyAsync(g->d_vfirst.p, vfirst.data(), 4 * vfirst.size(), hipMemcpyHostToDevice, g->st));
     if (nv) {
-        ITX_TRY(hipMemcpyAsync(g->d_voff, voff.data(), 8 * voff.size(), hipMemcpyHostToDevice, g->st));
-        ITX_TRY(hipMemcpyAsync(g->d_vsize, vsize.data(), 4 * vsize.size(), hipMemcpyHostToDevice, g->st));
-        ITX_TRY(hipMemcpyAsync(g->d_vname, vname.data(), 8 * vname.size(), hipMemcpyHostToDevice, g->st));
+        ITX_TRY(hipMemcpyAsync(g->d_voff.p, voff.data(), 8 * voff.size(), hipMemcpyHostToDevice, g->st));
+        ITX_TRY(hipMemcpyAsync(g->d_vsize.p, vsize.data(), 4 * vsize.size(), hipMemcpyHostToDevice, g->st));
+        ITX_TRY(hipMemcpyAsync(g->d_vname.p, vname.data(), 8 * vname.size(), hipMemcpyHostToDevice, g->st));
     }
-    ITX_TRY(hipMemcpyAsync(g->d_pool, pool.data(), pool.size(), hipMemcpyHostToDevice, g->st));
+    ITX_TRY(hipMemcpyAsync(g->d_pool.p, pool.data(), pool.size(), hipMemcpyHostToDevice, g->st));
     ITX_TRY(hipStreamSynchronize(g->st));                                   // the vectors are this function's
-    g->V.first = (const uint32_t *)g->d_vfirst;
-    g->V.off = (const ull *)g->d_voff;
-    g->V.size = (const uint32_t *)g->d_vsize;
+    g->V.first = g->d_vfirst.as<uint32_t>();
+    g->V.off = g->d_voff.as<ull>();
+    g->V.size = g->d_vsize.as<uint32_t>();
     g->V.nv = nv;
     g->max_name = max_name;
     g->h_vsize = vsize;
     g->h_vchrom = vchrom;
     g->per_round = per_round;
-    g->text_cap = text_cap;
     ITX_TRY(hipEventRecord(e0, g->st));
     for (int w = 0; w < 2; w++)
-        if ((rc = gc_points(g, w, n_tiles, d_tsum, d_tbase)) != ITX_OK) goto out;
+        if ((rc = gc_points(g, w, n_tiles, tsum.as<ull>(), tbase.as<ull>())) != ITX_OK) goto out;
     ITX_TRY(hipEventRecord(e1, g->st));
     ITX_TRY(hipStreamSynchronize(g->st));
     ITX_TRY(hipEventElapsedTime(&ms, e0, e1));
@@ -747,28 +706,13 @@ extern "C" int itx_gcov_finish(itx_gcov *g, const uint32_t *order, int n_order, 
     g->finished = 1;
 out:
     if (rc != ITX_OK) {
-        // nothing of a refused finish stays: the arrays are as they were, a later finish starts again
+        // a refused finish made no points: the arrays are as they were, a later finish starts again
         if (g->st) (void)hipStreamSynchronize(g->st);
         for (auto &f : g->file) {
-            (void)hipFree(f.d_pts);
-            f.d_pts = nullptr;
+            f.d_pts.drop();
             f.n_pts = 0;
         }
-        void **mine[] = {&g->d_vfirst, &g->d_voff, &g->d_vsize, &g->d_vname, &g->d_pool, (void **)&g->d_tsum, (void **)&g->d_tbase, (void **)&g->d_ttot,
-                         (void **)&g->d_text[0], (void **)&g->d_text[1]};
-        for (auto pp : mine) {
-            (void)hipFree(*pp);
-            *pp = nullptr;
-        }
-        for (auto &p : g->h_text) {
-            if (p) (void)hipHostFree(p);
-            p = nullptr;
-        }
     }
-    (void)hipFree(d_tsum);
-    (void)hipFree(d_tbase);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
     return rc;
 }
 
@@ -779,33 +723,34 @@ static int gc_start_round(itx_gcov *g, int w, int s)
     GcFile &F = g->file[w];
     const ull left = F.n_pts - F.cursor;
     const uint32_t n = (uint32_t)(left < g->per_round ? left : g->per_round), nt = (n + GC_TXT_TILE - 1) / GC_TXT_TILE;
-    const GcText T = {F.d_pts, F.n_pts, (const uint2 *)g->d_vname, (const uint8_t *)g->d_pool};
+    const GcText T = {F.d_pts.as<uint4>(), F.n_pts, g->d_vname.as<uint2>(), g->d_pool.as<uint8_t>()};
+    ull *const d_tsum = g->d_tsum.as<ull>(), *const d_tbase = g->d_tbase.as<ull>(), *const h_tot = g->h_tot.as<ull>();
     ITX_TRY(hipEventRecord(g->ev_rnd[s][0], g->st));
-    hipLaunchKernelGGL(k_gc_text_measure, dim3(nt), dim3(GC_TXT_TILE), 0, g->st, T, F.cursor, n, g->d_tsum);
+    hipLaunchKernelGGL(k_gc_text_measure, dim3(nt), dim3(GC_TXT_TILE), 0, g->st, T, F.cursor, n, d_tsum);
     ITX_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, g->st, g->d_tsum, nt, g->d_tbase, g->d_ttot);
+    hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, g->st, d_tsum, nt, d_tbase, g->d_ttot.as<ull>());
     ITX_TRY(hipGetLastError());
-    ITX_TRY(hipMemcpyAsync(g->h_tot, g->d_ttot, 16, hipMemcpyDeviceToHost, g->st));
+    ITX_TRY(hipMemcpyAsync(h_tot, g->d_ttot.p, 16, hipMemcpyDeviceToHost, g->st));
     {
         const double t0 = itx_wall_now();
         ITX_TRY(hipStreamSynchronize(g->st));
         g->stats.wait_s += itx_wall_now() - t0;
     }
-    F.len[s] = g->h_tot[0];
-    if (F.len[s] + 16 > g->text_cap) {                                     // (a line is never longer than its bound)
-        itx_set_error("itx_gcov_next: a round of %llu bytes in a buffer of %zu", (ull)F.len[s], g->text_cap);
+    F.len[s] = h_tot[0];
+    if (F.len[s] + 16 > g->d_text[s].cap) {                                // (a line is never longer than its bound)
+        itx_set_error("itx_gcov_next: a round of %llu bytes in a buffer of %zu", (ull)F.len[s], g->d_text[s].cap);
         rc = ITX_E_LIMIT;
         goto out;
     }
-    g->stats.lines[w] += g->h_tot[1];
+    g->stats.lines[w] += h_tot[1];
     g->stats.bytes[w] += F.len[s];
     g->stats.rounds[w]++;
     if (F.len[s]) {
-        hipLaunchKernelGGL(k_gc_text_write, dim3(nt), dim3(GC_TXT_TILE), 0, g->st, T, F.cursor, n, g->d_tbase, g->d_text[s]);
+        hipLaunchKernelGGL(k_gc_text_write, dim3(nt), dim3(GC_TXT_TILE), 0, g->st, T, F.cursor, n, d_tbase, g->d_text[s].as<uint8_t>());
         ITX_TRY(hipGetLastError());
     }
     ITX_TRY(hipEventRecord(g->ev_rnd[s][1], g->st));
-    if (F.len[s]) ITX_TRY(hipMemcpyAsync(g->h_text[s], g->d_text[s], (size_t)F.len[s], hipMemcpyDeviceToHost, g->st));
+    if (F.len[s]) ITX_TRY(hipMemcpyAsync(g->h_text[s].p, g->d_text[s].p, (size_t)F.len[s], hipMemcpyDeviceToHost, g->st));
     ITX_TRY(hipEventRecord(g->ev_rnd[s][2], g->st));
     F.cursor += n;
     F.slot = s;
@@ -848,7 +793,7 @@ extern "C" int itx_gcov_next(itx_gcov *g, int which, itx_gcov_text *out)
         ITX_TRY(hipEventElapsedTime(&ms, g->ev_rnd[s][0], g->ev_rnd[s][1]));
         g->stats.text_ms += (double)ms;
         F.flying = 0;
-        out->bytes = F.len[s] ? (const char *)g->h_text[s] : nullptr;
+        out->bytes = F.len[s] ? g->h_text[s].as<const char>() : nullptr;
         out->len = F.len[s];
         // the round after it is formatted and copied while the caller writes this one
         if (F.cursor < F.n_pts) {
@@ -876,7 +821,7 @@ extern "C" int itx_gcov_bigwig_build(itx_gcov *g, int which)
         return ITX_E_STATE;
     }
     GcBw *b = nullptr;
-    const int rc = gcbw_build(g->device, g->st, F.d_pts, F.n_pts, g->h_vsize.data(), g->h_vchrom.data(), (uint32_t)g->h_vsize.size(), &b);
+    const int rc = gcbw_build(g->device, g->st, F.d_pts.as<uint4>(), F.n_pts, g->h_vsize.data(), g->h_vchrom.data(), (uint32_t)g->h_vsize.size(), &b);
     if (rc != ITX_OK) return rc;
     F.bw = b;
     itx_gcov_bw_result r;
@@ -917,7 +862,7 @@ extern "C" int itx_gcov_copy_points(itx_gcov *g, int which, uint32_t *out)
     const GcFile &F = g->file[which];
     ITX_TRY(hipSetDevice(g->device));
     ITX_TRY(hipStreamSynchronize(g->st));
-    if (F.n_pts) ITX_TRY(hipMemcpy(out, F.d_pts, sizeof(uint4) * (size_t)F.n_pts, hipMemcpyDeviceToHost));
+    if (F.n_pts) ITX_TRY(hipMemcpy(out, F.d_pts.p, sizeof(uint4) * (size_t)F.n_pts, hipMemcpyDeviceToHost));
 out:
     return rc;
 }
@@ -933,10 +878,10 @@ extern "C" int itx_gcov_get_stats(itx_gcov *g, itx_gcov_stats *out)
         ITX_TRY(hipSetDevice(g->device));
         if ((rc = gc_settle(g)) != ITX_OK) goto out;
         ITX_TRY(hipStreamSynchronize(g->st));
-        ITX_TRY(hipMemcpy(g->h_tot, g->d_cnt, 24, hipMemcpyDeviceToHost));
-        g->stats.records = g->h_tot[0];
-        g->stats.out_of_range = g->h_tot[1];
-        g->stats.records_uniq = g->h_tot[2];
+        ITX_TRY(hipMemcpy(g->h_tot.p, g->d_cnt.p, 24, hipMemcpyDeviceToHost));
+        g->stats.records = g->h_tot.as<ull>()[0];
+        g->stats.out_of_range = g->h_tot.as<ull>()[1];
+        g->stats.records_uniq = g->h_tot.as<ull>()[2];
     }
     *out = g->stats;
 out:

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "itx_common.h"
+#include "itx_devbuf.h"
 #include "itx_samline.h"
 #include "itx_textpack.h"
 
@@ -327,24 +328,22 @@ static __global__ __launch_bounds__(SAM_STR_TILE) void k_sam_str_write(const uin
 
 // ---- the C ABI ----------------------------------------------------------------------------------------------------------------
 struct SamSlot {
-    uint8_t *d_text = nullptr;
-    uint32_t *d_line_start = nullptr;
-    void *d_rec = nullptr;                 // one allocation behind the arrays of `out`
+    ItxBuf d_text, d_line_start;
+    ItxBuf d_rec;                          // one allocation behind the arrays of `out`
     SamOut out = {};
-    unsigned long long *d_tot = nullptr;   // newlines, NUL bytes
-    uint32_t *d_res = nullptr;
-    uint32_t *h_res = nullptr;             // page-locked: SAM_R_WORDS words, then the two totals
-    hipEvent_t ev_copy = nullptr, ev_k0 = nullptr, ev_k1 = nullptr, ev_done = nullptr;
+    ItxBuf d_tot;                          // newlines, NUL bytes
+    ItxBuf d_res;
+    ItxPin h_res;                          // SAM_R_WORDS words, then the two totals
+    ItxEvent ev_copy, ev_k0, ev_k1, ev_done;
     int state = 0;                         // 0 idle, 1 begun, 2 ended: its records can be fetched
     size_t len = 0;
     uint64_t n_rec = 0;
     // a chunk begun by parse_begin_bgzf: its compressed bytes, block list and status bytes, and what they inflate to
     int bgzf = 0;
-    uint8_t *d_comp = nullptr, *d_infl = nullptr, *d_status = nullptr, *h_status = nullptr;
-    itx_bgzf_block *d_blk = nullptr, *h_blk = nullptr;
-    size_t comp_cap = 0, infl_cap = 0, blk_cap = 0;
+    ItxBuf d_comp, d_infl, d_status, d_blk;
+    ItxPin h_status, h_blk;
     size_t n_blk = 0, carry_len = 0;
-    hipEvent_t ev_d0 = nullptr, ev_d1 = nullptr;
+    ItxEvent ev_d0, ev_d1;
     double inflate_ms = 0;
 };
 
@@ -354,86 +353,45 @@ struct itx_samtext {
     uint32_t cap_lines = 0;
     unsigned n_blocks = 0;
     SamNames names = {};
-    void *d_tab = nullptr, *d_off = nullptr, *d_pool = nullptr;
-    unsigned long long *d_tile_sum = nullptr, *d_tile_base = nullptr;
+    ItxBuf d_tab, d_off, d_pool;
+    ItxBuf d_tile_sum, d_tile_base;
     hipStream_t st = nullptr, st_copy = nullptr;
     SamSlot slot[2];
     // BGZF: the decoder's scratch (one chunk's passes at a time: they all run on st), the slot of the stream's previous chunk (-1:
     // the next chunk has no carry), the last text put together on st (a copy into a slot's text on st_copy waits for it)
-    uint8_t *d_scr = nullptr;
-    uint32_t *d_meta = nullptr;
-    size_t scr_cap = 0, meta_cap = 0;
+    ItxBuf d_scr, d_meta;
     int bgzf_prev = -1;
-    hipEvent_t ev_asm = nullptr;
+    ItxEvent ev_asm;
     bool asm_recorded = false;
     // the string gather: a stream and buffers of its own, so that it does not queue behind the other slot's parse
     hipStream_t st_str = nullptr;
-    hipEvent_t ev_s[4] = {};
-    unsigned long long *d_str_sum = nullptr, *d_str_base = nullptr, *d_str_tot = nullptr, *h_str_tot = nullptr;
-    uint32_t *d_at = nullptr, *h_at = nullptr;       // qname_at[n], then xa_at[n]
-    uint8_t *d_str = nullptr, *h_str = nullptr;
-    size_t str_tiles_cap = 0, at_cap = 0, h_at_cap = 0, str_cap = 0, h_str_cap = 0;
+    ItxEvent ev_s[4];
+    ItxBuf d_str_sum, d_str_base, d_str_tot;
+    ItxPin h_str_tot;
+    ItxBuf d_at, d_str;                    // qname_at[n], then xa_at[n]
+    ItxPin h_at, h_str;
 };
 
-// room for `need` elements at *p, nothing kept (hipFree waits for whatever still uses the old one)
-template <typename T> static int sam_grow(T **p, size_t *cap, size_t need, bool pinned = false)
+#define SAM_RC(call)                          \
+    do {                                      \
+        const int rc__ = (call);              \
+        if (rc__ != ITX_OK) return rc__;      \
+    } while (0)
+
+// room for `need` elements of `size` bytes, nothing kept (the drop's hipFree waits for whatever still uses the old one)
+template <bool PINNED> static int sam_grow(ItxMem<PINNED> &b, size_t need, size_t size)
 {
-    if (need <= *cap) return ITX_OK;
-    if (*p) ITX_HIP(pinned ? hipHostFree(*p) : hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 4 + 64;
-    if (pinned) ITX_HIP(hipHostMalloc((void **)p, want * sizeof(T), hipHostMallocDefault));
-    else ITX_HIP(hipMalloc((void **)p, want * sizeof(T)));
-    *cap = want;
-    return ITX_OK;
+    return need * size <= b.cap ? ITX_OK : itx_mem_need("itx_samtext", b, (need + need / 4 + 64) * size);
 }
 
 extern "C" void itx_samtext_destroy(itx_samtext *x)
 {
     if (!x) return;
     (void)hipSetDevice(x->device);
-    if (x->st) (void)hipStreamSynchronize(x->st);
-    if (x->st_copy) (void)hipStreamSynchronize(x->st_copy);
-    for (auto &s : x->slot) {
-        (void)hipFree(s.d_text);
-        (void)hipFree(s.d_line_start);
-        (void)hipFree(s.d_rec);
-        (void)hipFree(s.d_tot);
-        (void)hipFree(s.d_res);
-        if (s.h_res) (void)hipHostFree(s.h_res);
-        (void)hipFree(s.d_comp);
-        (void)hipFree(s.d_infl);
-        (void)hipFree(s.d_status);
-        (void)hipFree(s.d_blk);
-        if (s.h_status) (void)hipHostFree(s.h_status);
-        if (s.h_blk) (void)hipHostFree(s.h_blk);
-        hipEvent_t *ev[6] = {&s.ev_copy, &s.ev_k0, &s.ev_k1, &s.ev_done, &s.ev_d0, &s.ev_d1};
-        for (auto e : ev)
-            if (*e) (void)hipEventDestroy(*e);
-    }
-    if (x->st_str) (void)hipStreamSynchronize(x->st_str);
-    (void)hipFree(x->d_scr);
-    (void)hipFree(x->d_meta);
-    (void)hipFree(x->d_str_sum);
-    (void)hipFree(x->d_str_base);
-    (void)hipFree(x->d_str_tot);
-    (void)hipFree(x->d_at);
-    (void)hipFree(x->d_str);
-    if (x->h_str_tot) (void)hipHostFree(x->h_str_tot);
-    if (x->h_at) (void)hipHostFree(x->h_at);
-    if (x->h_str) (void)hipHostFree(x->h_str);
-    if (x->ev_asm) (void)hipEventDestroy(x->ev_asm);
-    for (auto e : x->ev_s)
-        if (e) (void)hipEventDestroy(e);
-    if (x->st_str) (void)hipStreamDestroy(x->st_str);
-    (void)hipFree(x->d_tab);
-    (void)hipFree(x->d_off);
-    (void)hipFree(x->d_pool);
-    (void)hipFree(x->d_tile_sum);
-    (void)hipFree(x->d_tile_base);
-    if (x->st) (void)hipStreamDestroy(x->st);
-    if (x->st_copy) (void)hipStreamDestroy(x->st_copy);
+    for (hipStream_t st : {x->st, x->st_copy, x->st_str})
+        if (st) (void)hipStreamSynchronize(st);
+    for (hipStream_t st : {x->st, x->st_copy, x->st_str})
+        if (st) (void)hipStreamDestroy(st);
     delete x;
 }
 
@@ -442,6 +400,7 @@ static inline size_t sam_up256(size_t n) { return (n + 255) & ~(size_t)255; }
 // fills the object; on a non-zero return the caller destroys what there is of it
 static int samtext_create(itx_samtext *x, int device, const char *name_bytes, const uint64_t *name_off, int n_targets, size_t max_chunk)
 {
+    const char *const who = "itx_samtext_create";
     x->device = device;
     ITX_HIP(hipSetDevice(device));
     hipDeviceProp_t prop;
@@ -470,28 +429,28 @@ static int samtext_create(itx_samtext *x, int device, const char *name_bytes, co
             if (!dup) tab[i] = (uint32_t)t + 1u;
         }
         const size_t pool = (size_t)(name_off[n_targets] - name_off[0]);
-        ITX_HIP(hipMalloc(&x->d_tab, 4 * tab.size()));
-        ITX_HIP(hipMalloc(&x->d_off, 4 * off.size()));
-        ITX_HIP(hipMalloc(&x->d_pool, pool + 16));
-        ITX_HIP(hipMemcpy(x->d_tab, tab.data(), 4 * tab.size(), hipMemcpyHostToDevice));
-        ITX_HIP(hipMemcpy(x->d_off, off.data(), 4 * off.size(), hipMemcpyHostToDevice));
-        if (pool) ITX_HIP(hipMemcpy(x->d_pool, nb + name_off[0], pool, hipMemcpyHostToDevice));
-        x->names.tab = (const uint32_t *)x->d_tab;
-        x->names.off = (const uint32_t *)x->d_off;
-        x->names.pool = (const uint8_t *)x->d_pool;
+        SAM_RC(itx_buf_need(who, x->d_tab, 4 * tab.size()));
+        SAM_RC(itx_buf_need(who, x->d_off, 4 * off.size()));
+        SAM_RC(itx_buf_need(who, x->d_pool, pool + 16));
+        ITX_HIP(hipMemcpy(x->d_tab.p, tab.data(), 4 * tab.size(), hipMemcpyHostToDevice));
+        ITX_HIP(hipMemcpy(x->d_off.p, off.data(), 4 * off.size(), hipMemcpyHostToDevice));
+        if (pool) ITX_HIP(hipMemcpy(x->d_pool.p, nb + name_off[0], pool, hipMemcpyHostToDevice));
+        x->names.tab = x->d_tab.as<uint32_t>();
+        x->names.off = x->d_off.as<uint32_t>();
+        x->names.pool = x->d_pool.as<uint8_t>();
         x->names.mask = slots - 1u;
     }
     const size_t nt = (max_chunk + SAM_TILE - 1) / SAM_TILE + 1;
-    ITX_HIP(hipMalloc((void **)&x->d_tile_sum, 16 * nt));
-    ITX_HIP(hipMalloc((void **)&x->d_tile_base, 16 * nt));
+    SAM_RC(itx_buf_need(who, x->d_tile_sum, 16 * nt));
+    SAM_RC(itx_buf_need(who, x->d_tile_base, 16 * nt));
     ITX_HIP(hipStreamCreateWithFlags(&x->st, hipStreamNonBlocking));
     ITX_HIP(hipStreamCreateWithFlags(&x->st_copy, hipStreamNonBlocking));
     const size_t c = (size_t)x->cap_lines, a4 = sam_up256(4 * c), a1 = sam_up256(c);
     for (auto &s : x->slot) {
-        ITX_HIP(hipMalloc((void **)&s.d_text, sam_up256(max_chunk) + 256));
-        ITX_HIP(hipMalloc((void **)&s.d_line_start, 4 * (c + 2)));
-        ITX_HIP(hipMalloc(&s.d_rec, 10 * a4 + 3 * a1));
-        uint8_t *p = (uint8_t *)s.d_rec;
+        SAM_RC(itx_buf_need(who, s.d_text, sam_up256(max_chunk) + 256));
+        SAM_RC(itx_buf_need(who, s.d_line_start, 4 * (c + 2)));
+        SAM_RC(itx_buf_need(who, s.d_rec, 10 * a4 + 3 * a1));
+        uint8_t *p = s.d_rec.as<uint8_t>();
         int32_t **i32s[6] = {&s.out.tid, &s.out.pos, &s.out.tmpend, &s.out.mpos, &s.out.isize, &s.out.nm};
         for (auto pp : i32s) {
             *pp = (int32_t *)p;
@@ -507,17 +466,16 @@ static int samtext_create(itx_samtext *x, int device, const char *name_bytes, co
             *pp = p;
             p += a1;
         }
-        ITX_HIP(hipMalloc((void **)&s.d_tot, 16));
-        ITX_HIP(hipMalloc((void **)&s.d_res, 4 * SAM_R_WORDS));
-        ITX_HIP(hipHostMalloc((void **)&s.h_res, 4 * SAM_R_WORDS + 16, hipHostMallocDefault));
-        hipEvent_t *ev[6] = {&s.ev_copy, &s.ev_k0, &s.ev_k1, &s.ev_done, &s.ev_d0, &s.ev_d1};
-        for (auto e : ev) ITX_HIP(hipEventCreate(e));
+        SAM_RC(itx_buf_need(who, s.d_tot, 16));
+        SAM_RC(itx_buf_need(who, s.d_res, 4 * SAM_R_WORDS));
+        SAM_RC(itx_pin_need(who, s.h_res, 4 * SAM_R_WORDS + 16));
+        for (ItxEvent *e : {&s.ev_copy, &s.ev_k0, &s.ev_k1, &s.ev_done, &s.ev_d0, &s.ev_d1}) SAM_RC(itx_event_make(*e));
     }
     ITX_HIP(hipStreamCreateWithFlags(&x->st_str, hipStreamNonBlocking));
-    ITX_HIP(hipEventCreate(&x->ev_asm));
-    for (auto &e : x->ev_s) ITX_HIP(hipEventCreate(&e));
-    ITX_HIP(hipMalloc((void **)&x->d_str_tot, 16));
-    ITX_HIP(hipHostMalloc((void **)&x->h_str_tot, 16, hipHostMallocDefault));
+    SAM_RC(itx_event_make(x->ev_asm));
+    for (auto &e : x->ev_s) SAM_RC(itx_event_make(e));
+    SAM_RC(itx_buf_need(who, x->d_str_tot, 16));
+    SAM_RC(itx_pin_need(who, x->h_str_tot, 16));
     return ITX_OK;
 }
 
@@ -575,7 +533,7 @@ extern "C" int itx_samtext_parse_begin(itx_samtext *x, int slot, const void *tex
     s.bgzf = 0;
     if (x->bgzf_prev == slot) x->bgzf_prev = -1;                           // the tail a BGZF chunk left here is overwritten
     if (x->asm_recorded) ITX_HIP(hipStreamWaitEvent(x->st_copy, x->ev_asm, 0));       // ... but not before the chunk that took it has it
-    if (len) ITX_HIP(hipMemcpyAsync(s.d_text, text, len, hipMemcpyHostToDevice, x->st_copy));
+    if (len) ITX_HIP(hipMemcpyAsync(s.d_text.as<uint8_t>(), text, len, hipMemcpyHostToDevice, x->st_copy));
     ITX_HIP(hipEventRecord(s.ev_copy, x->st_copy));
     ITX_HIP(hipStreamWaitEvent(x->st, s.ev_copy, 0));
     const int rc = sam_enqueue_parse(x, s, len, final);
@@ -586,25 +544,29 @@ extern "C" int itx_samtext_parse_begin(itx_samtext *x, int slot, const void *tex
 // the four kernels over the slot's text[0 .. len) and the copies of what they leave, on x->st
 static int sam_enqueue_parse(itx_samtext *x, SamSlot &s, size_t len, int final)
 {
+    const uint8_t *const d_text = s.d_text.as<uint8_t>();
+    uint32_t *const d_res = s.d_res.as<uint32_t>(), *const h_res = s.h_res.as<uint32_t>(), *const line_start = s.d_line_start.as<uint32_t>();
+    unsigned long long *const d_tot = s.d_tot.as<unsigned long long>(), *const tile_sum = x->d_tile_sum.as<unsigned long long>(),
+                             *const tile_base = x->d_tile_base.as<unsigned long long>();
     ITX_HIP(hipEventRecord(s.ev_k0, x->st));
-    ITX_HIP(hipMemsetAsync(s.d_res, 0, 4 * SAM_R_WORDS, x->st));
-    ITX_HIP(hipMemsetAsync(s.d_res + SAM_R_FIRST, 0xff, 4, x->st));
-    ITX_HIP(hipMemsetAsync(s.d_tot, 0, 16, x->st));
+    ITX_HIP(hipMemsetAsync(d_res, 0, 4 * SAM_R_WORDS, x->st));
+    ITX_HIP(hipMemsetAsync(d_res + SAM_R_FIRST, 0xff, 4, x->st));
+    ITX_HIP(hipMemsetAsync(d_tot, 0, 16, x->st));
     const uint32_t nt = (uint32_t)((len + SAM_TILE - 1) / SAM_TILE);
     if (nt) {
-        hipLaunchKernelGGL(k_sam_count, dim3(nt), dim3(SAM_TILE_WG), 0, x->st, s.d_text, (uint32_t)len, x->d_tile_sum);
+        hipLaunchKernelGGL(k_sam_count, dim3(nt), dim3(SAM_TILE_WG), 0, x->st, d_text, (uint32_t)len, tile_sum);
         ITX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, x->st, x->d_tile_sum, nt, x->d_tile_base, s.d_tot);
+        hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, x->st, tile_sum, nt, tile_base, d_tot);
         ITX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_sam_starts, dim3(nt), dim3(SAM_TILE_WG), 0, x->st, s.d_text, (uint32_t)len, x->d_tile_base, s.d_line_start, x->cap_lines);
+        hipLaunchKernelGGL(k_sam_starts, dim3(nt), dim3(SAM_TILE_WG), 0, x->st, d_text, (uint32_t)len, tile_base, line_start, x->cap_lines);
         ITX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_sam_parse, dim3(x->n_blocks), dim3(SAM_WAVES * 64u), 0, x->st, s.d_text, (uint32_t)len, final ? 1 : 0, s.d_line_start, s.d_tot, x->cap_lines,
-                           x->names, s.out, s.d_res);
+        hipLaunchKernelGGL(k_sam_parse, dim3(x->n_blocks), dim3(SAM_WAVES * 64u), 0, x->st, d_text, (uint32_t)len, final ? 1 : 0, line_start, d_tot, x->cap_lines,
+                           x->names, s.out, d_res);
         ITX_HIP(hipGetLastError());
     }
     ITX_HIP(hipEventRecord(s.ev_k1, x->st));
-    ITX_HIP(hipMemcpyAsync(s.h_res, s.d_res, 4 * SAM_R_WORDS, hipMemcpyDeviceToHost, x->st));
-    ITX_HIP(hipMemcpyAsync(s.h_res + SAM_R_WORDS, s.d_tot, 16, hipMemcpyDeviceToHost, x->st));
+    ITX_HIP(hipMemcpyAsync(h_res, d_res, 4 * SAM_R_WORDS, hipMemcpyDeviceToHost, x->st));
+    ITX_HIP(hipMemcpyAsync(h_res + SAM_R_WORDS, d_tot, 16, hipMemcpyDeviceToHost, x->st));
     ITX_HIP(hipEventRecord(s.ev_done, x->st));
     return ITX_OK;
 }
@@ -614,7 +576,7 @@ static size_t sam_count_bad(const SamSlot &s, size_t *first)
 {
     size_t n = 0;
     for (size_t i = 0; i < s.n_blk; i++)
-        if (s.h_status[i]) {
+        if (s.h_status.as<uint8_t>()[i]) {
             if (!n) *first = i;
             n++;
         }
@@ -660,35 +622,36 @@ extern "C" int itx_samtext_parse_begin_bgzf(itx_samtext *x, int slot, const void
         prev = x->bgzf_prev = -1;
     }
     ITX_HIP(hipSetDevice(x->device));
-    int rc;
-    size_t st_cap = s.blk_cap, hb_cap = s.blk_cap, hs_cap = s.blk_cap;
-    if ((rc = sam_grow(&s.d_comp, &s.comp_cap, comp_len + 64)) != ITX_OK) return rc;
-    if ((rc = sam_grow(&s.d_infl, &s.infl_cap, x->max_chunk + 65536u + 64)) != ITX_OK) return rc;
-    if ((rc = sam_grow(&s.d_status, &st_cap, n_blk + 1)) != ITX_OK) return rc;
-    if ((rc = sam_grow(&s.h_blk, &hb_cap, n_blk + 1, true)) != ITX_OK) return rc;
-    if ((rc = sam_grow(&s.h_status, &hs_cap, n_blk + 1, true)) != ITX_OK) return rc;
-    if ((rc = sam_grow(&s.d_blk, &s.blk_cap, n_blk + 1)) != ITX_OK) return rc;
-    if ((rc = sam_grow(&x->d_scr, &x->scr_cap, itx_inflate_scratch_bytes(n_blk))) != ITX_OK) return rc;
-    if ((rc = sam_grow(&x->d_meta, &x->meta_cap, 3 * n_blk)) != ITX_OK) return rc;
+    SAM_RC(sam_grow(s.d_comp, comp_len + 64, 1));
+    SAM_RC(sam_grow(s.d_infl, x->max_chunk + 65536u + 64, 1));
+    SAM_RC(sam_grow(s.d_status, n_blk + 1, 1));
+    SAM_RC(sam_grow(s.h_blk, n_blk + 1, sizeof *blk));
+    SAM_RC(sam_grow(s.h_status, n_blk + 1, 1));
+    SAM_RC(sam_grow(s.d_blk, n_blk + 1, sizeof *blk));
+    SAM_RC(sam_grow(x->d_scr, itx_inflate_scratch_bytes(n_blk), 1));
+    SAM_RC(sam_grow(x->d_meta, 3 * n_blk, 4));
+    itx_bgzf_block *const h_blk = s.h_blk.as<itx_bgzf_block>(), *const d_blk = s.d_blk.as<itx_bgzf_block>();
+    uint8_t *const h_status = s.h_status.as<uint8_t>(), *const d_status = s.d_status.as<uint8_t>();
+    uint8_t *const d_comp = s.d_comp.as<uint8_t>(), *const d_infl = s.d_infl.as<uint8_t>(), *const d_text = s.d_text.as<uint8_t>();
     s.state = 0;
     s.n_blk = 0;
     // 1. the compressed bytes cross the link on the copy stream, both passes of the decoder run behind them
-    memcpy(s.h_blk, blk, n_blk * sizeof *blk);
-    memset(s.h_status, 0xff, n_blk);
-    if (n_blk) ITX_HIP(hipMemcpyAsync(s.d_blk, s.h_blk, n_blk * sizeof *blk, hipMemcpyHostToDevice, x->st_copy));
-    if (comp_len) ITX_HIP(hipMemcpyAsync(s.d_comp, comp, comp_len, hipMemcpyHostToDevice, x->st_copy));
+    memcpy(h_blk, blk, n_blk * sizeof *blk);
+    memset(h_status, 0xff, n_blk);
+    if (n_blk) ITX_HIP(hipMemcpyAsync(d_blk, h_blk, n_blk * sizeof *blk, hipMemcpyHostToDevice, x->st_copy));
+    if (comp_len) ITX_HIP(hipMemcpyAsync(d_comp, comp, comp_len, hipMemcpyHostToDevice, x->st_copy));
     ITX_HIP(hipEventRecord(s.ev_copy, x->st_copy));
     ITX_HIP(hipStreamWaitEvent(x->st, s.ev_copy, 0));
     ITX_HIP(hipEventRecord(s.ev_d0, x->st));
-    if ((rc = itx_inflate_enqueue(x->st, s.d_comp, s.d_blk, (uint32_t)n_blk, s.d_infl, s.d_status, x->d_scr, x->d_meta)) != ITX_OK) return rc;
+    SAM_RC(itx_inflate_enqueue(x->st, d_comp, d_blk, (uint32_t)n_blk, d_infl, d_status, x->d_scr.as<uint8_t>(), x->d_meta.as<uint32_t>()));
     ITX_HIP(hipEventRecord(s.ev_d1, x->st));
-    if (n_blk) ITX_HIP(hipMemcpyAsync(s.h_status, s.d_status, n_blk, hipMemcpyDeviceToHost, x->st));
+    if (n_blk) ITX_HIP(hipMemcpyAsync(h_status, d_status, n_blk, hipMemcpyDeviceToHost, x->st));
     // 2. where the previous chunk's parse stopped: its tail is this text's front
     size_t carry = 0, carry_at = 0;
     if (prev >= 0) {
         const SamSlot &p = x->slot[prev];
         ITX_HIP(hipEventSynchronize(p.ev_done));
-        carry_at = p.len ? p.h_res[SAM_R_CONSUMED] : 0;
+        carry_at = p.len ? p.h_res.as<uint32_t>()[SAM_R_CONSUMED] : 0;
         carry = sam_count_bad(p, &unused) || carry_at > p.len ? 0 : p.len - carry_at;
     }
     x->bgzf_prev = -1;
@@ -700,8 +663,8 @@ extern "C" int itx_samtext_parse_begin_bgzf(itx_samtext *x, int slot, const void
         return ITX_E_LIMIT;
     }
     // 3. the text, put together on the device
-    if (carry) ITX_HIP(hipMemcpyAsync(s.d_text, x->slot[prev].d_text + carry_at, carry, hipMemcpyDeviceToDevice, x->st));
-    if (total > from) ITX_HIP(hipMemcpyAsync(s.d_text + carry, s.d_infl + from, total - from, hipMemcpyDeviceToDevice, x->st));
+    if (carry) ITX_HIP(hipMemcpyAsync(d_text, x->slot[prev].d_text.as<uint8_t>() + carry_at, carry, hipMemcpyDeviceToDevice, x->st));
+    if (total > from) ITX_HIP(hipMemcpyAsync(d_text + carry, d_infl + from, total - from, hipMemcpyDeviceToDevice, x->st));
     ITX_HIP(hipEventRecord(x->ev_asm, x->st));
     x->asm_recorded = true;
     // 4. the parse
@@ -709,7 +672,7 @@ extern "C" int itx_samtext_parse_begin_bgzf(itx_samtext *x, int slot, const void
     s.bgzf = 1;
     s.n_blk = n_blk;
     s.carry_len = carry;
-    if ((rc = sam_enqueue_parse(x, s, len, final)) != ITX_OK) return rc;
+    SAM_RC(sam_enqueue_parse(x, s, len, final));
     s.state = 1;
     if (!final) x->bgzf_prev = slot;
     return ITX_OK;
@@ -728,20 +691,21 @@ extern "C" int itx_samtext_parse_end(itx_samtext *x, int slot, itx_samtext_resul
     }
     ITX_HIP(hipSetDevice(x->device));
     ITX_HIP(hipEventSynchronize(s.ev_done));
+    const uint32_t *const h_res = s.h_res.as<uint32_t>();
     float ms = 0;
     ITX_HIP(hipEventElapsedTime(&ms, s.ev_k0, s.ev_k1));
     unsigned long long tot[2];
-    memcpy(tot, s.h_res + SAM_R_WORDS, 16);
+    memcpy(tot, h_res + SAM_R_WORDS, 16);
     memset(res, 0, sizeof *res);
-    res->n_lines = s.h_res[SAM_R_LINES];
-    res->consumed = s.len ? s.h_res[SAM_R_CONSUMED] : 0;
-    res->n_hard = s.h_res[SAM_R_NHARD];
-    res->first_hard_line = s.h_res[SAM_R_FIRST] >= 0x7fffffffu ? 0 : s.h_res[SAM_R_FIRST];
+    res->n_lines = h_res[SAM_R_LINES];
+    res->consumed = s.len ? h_res[SAM_R_CONSUMED] : 0;
+    res->n_hard = h_res[SAM_R_NHARD];
+    res->first_hard_line = h_res[SAM_R_FIRST] >= 0x7fffffffu ? 0 : h_res[SAM_R_FIRST];
     if (tot[0] >= x->cap_lines) {                  // as many lines as the arrays hold, or more: one of them is too short for 11 fields
         if (!res->n_hard) res->first_hard_line = x->cap_lines;
         res->n_hard++;
     }
-    res->flags = (int)(s.h_res[SAM_R_FLAGS] | (tot[1] ? ITX_SAMTEXT_NUL : 0));
+    res->flags = (int)(h_res[SAM_R_FLAGS] | (tot[1] ? ITX_SAMTEXT_NUL : 0));
     res->n_rec = res->n_hard ? 0 : res->n_lines;
     res->kernel_ms = ms;
     if (s.bgzf) {
@@ -769,7 +733,7 @@ extern "C" int itx_samtext_bgzf_info(itx_samtext *x, int slot, itx_samtext_bgzf_
     }
     memset(out, 0, sizeof *out);
     size_t first = 0;
-    const size_t consumed = s.len ? s.h_res[SAM_R_CONSUMED] : 0;
+    const size_t consumed = s.len ? s.h_res.as<uint32_t>()[SAM_R_CONSUMED] : 0;
     out->text_len = s.len;
     out->carry_len = s.carry_len;
     out->tail_len = s.len - consumed;
@@ -796,7 +760,7 @@ extern "C" int itx_samtext_text(itx_samtext *x, int slot, size_t off, void *dst,
     }
     if (!len) return ITX_OK;
     ITX_HIP(hipSetDevice(x->device));
-    ITX_HIP(hipMemcpyAsync(dst, s.d_text + off, len, hipMemcpyDeviceToHost, x->st_str));
+    ITX_HIP(hipMemcpyAsync(dst, s.d_text.as<uint8_t>() + off, len, hipMemcpyDeviceToHost, x->st_str));
     ITX_HIP(hipStreamSynchronize(x->st_str));
     return ITX_OK;
 }
@@ -820,44 +784,45 @@ extern "C" int itx_samtext_strings(itx_samtext *x, int slot, size_t first, size_
     if (!n) return ITX_OK;
     ITX_HIP(hipSetDevice(x->device));
     const uint32_t nt = (uint32_t)((n + SAM_STR_TILE - 1) / SAM_STR_TILE);
-    int rc;
-    size_t cap2 = x->str_tiles_cap;
-    if ((rc = sam_grow(&x->d_str_sum, &cap2, 2 * (size_t)nt)) != ITX_OK) return rc;
-    if ((rc = sam_grow(&x->d_str_base, &x->str_tiles_cap, 2 * (size_t)nt)) != ITX_OK) return rc;
-    if ((rc = sam_grow(&x->d_at, &x->at_cap, 2 * n)) != ITX_OK) return rc;
-    if ((rc = sam_grow(&x->h_at, &x->h_at_cap, 2 * n, true)) != ITX_OK) return rc;
+    SAM_RC(sam_grow(x->d_str_sum, 2 * (size_t)nt, 8));
+    SAM_RC(sam_grow(x->d_str_base, 2 * (size_t)nt, 8));
+    SAM_RC(sam_grow(x->d_at, 2 * n, 4));
+    SAM_RC(sam_grow(x->h_at, 2 * n, 4));
+    unsigned long long *const d_sum = x->d_str_sum.as<unsigned long long>(), *const d_base = x->d_str_base.as<unsigned long long>(),
+                             *const d_tot = x->d_str_tot.as<unsigned long long>(), *const h_tot = x->h_str_tot.as<unsigned long long>();
+    uint32_t *const d_at = x->d_at.as<uint32_t>(), *const h_at = x->h_at.as<uint32_t>();
     hipStream_t st = x->st_str;
     ITX_HIP(hipEventRecord(x->ev_s[0], st));
-    hipLaunchKernelGGL(k_sam_str_measure, dim3(nt), dim3(SAM_STR_TILE), 0, st, s.out, (uint32_t)first, (uint32_t)n, want, x->d_str_sum);
+    hipLaunchKernelGGL(k_sam_str_measure, dim3(nt), dim3(SAM_STR_TILE), 0, st, s.out, (uint32_t)first, (uint32_t)n, want, d_sum);
     ITX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, st, x->d_str_sum, nt, x->d_str_base, x->d_str_tot);
+    hipLaunchKernelGGL(k_tile_scan2, dim3(1), dim3(ITX_SCAN_WG), 0, st, d_sum, nt, d_base, d_tot);
     ITX_HIP(hipGetLastError());
     ITX_HIP(hipEventRecord(x->ev_s[1], st));
-    ITX_HIP(hipMemcpyAsync(x->h_str_tot, x->d_str_tot, 16, hipMemcpyDeviceToHost, st));
+    ITX_HIP(hipMemcpyAsync(h_tot, d_tot, 16, hipMemcpyDeviceToHost, st));
     ITX_HIP(hipStreamSynchronize(st));                                     // the total is all the host waits for before the write
-    const size_t total = (size_t)x->h_str_tot[0];
+    const size_t total = (size_t)h_tot[0];
     if (total > s.len + n) {                                               // disjoint slices of the text and a NUL each: cannot be more
         itx_set_error("itx_samtext_strings: %zu bytes of strings out of a text of %zu", total, s.len);
         return ITX_E_STATE;
     }
-    if ((rc = sam_grow(&x->d_str, &x->str_cap, total + SAM_STR_GUARD + 16)) != ITX_OK) return rc;
-    if ((rc = sam_grow(&x->h_str, &x->h_str_cap, total + SAM_STR_GUARD, true)) != ITX_OK) return rc;
-    ITX_HIP(hipMemsetAsync(x->d_str + total, 0xa5, SAM_STR_GUARD, st));
+    SAM_RC(sam_grow(x->d_str, total + SAM_STR_GUARD + 16, 1));
+    SAM_RC(sam_grow(x->h_str, total + SAM_STR_GUARD, 1));
+    ITX_HIP(hipMemsetAsync(x->d_str.as<uint8_t>() + total, 0xa5, SAM_STR_GUARD, st));
     ITX_HIP(hipEventRecord(x->ev_s[2], st));
-    hipLaunchKernelGGL(k_sam_str_write, dim3(nt), dim3(SAM_STR_TILE), 0, st, s.d_text, s.out, (uint32_t)first, (uint32_t)n, want, x->d_str_base, x->d_str, x->d_at,
-                       x->d_at + n);
+    hipLaunchKernelGGL(k_sam_str_write, dim3(nt), dim3(SAM_STR_TILE), 0, st, s.d_text.as<uint8_t>(), s.out, (uint32_t)first, (uint32_t)n, want, d_base,
+                       x->d_str.as<uint8_t>(), d_at, d_at + n);
     ITX_HIP(hipGetLastError());
     ITX_HIP(hipEventRecord(x->ev_s[3], st));
-    ITX_HIP(hipMemcpyAsync(x->h_str, x->d_str, total + SAM_STR_GUARD, hipMemcpyDeviceToHost, st));
-    ITX_HIP(hipMemcpyAsync(x->h_at, x->d_at, 8 * n, hipMemcpyDeviceToHost, st));
+    ITX_HIP(hipMemcpyAsync(x->h_str.as<uint8_t>(), x->d_str.as<uint8_t>(), total + SAM_STR_GUARD, hipMemcpyDeviceToHost, st));
+    ITX_HIP(hipMemcpyAsync(h_at, d_at, 8 * n, hipMemcpyDeviceToHost, st));
     ITX_HIP(hipStreamSynchronize(st));
     float a = 0, b = 0;
     ITX_HIP(hipEventElapsedTime(&a, x->ev_s[0], x->ev_s[1]));
     ITX_HIP(hipEventElapsedTime(&b, x->ev_s[2], x->ev_s[3]));
-    out->text = (const char *)x->h_str;
+    out->text = x->h_str.as<const char>();
     out->text_len = total;
-    out->qname_at = x->h_at;
-    out->xa_at = x->h_at + n;
+    out->qname_at = h_at;
+    out->xa_at = h_at + n;
     out->kernel_ms = (double)a + (double)b;
     return ITX_OK;
 }

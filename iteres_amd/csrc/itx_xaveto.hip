@@ -22,6 +22,7 @@
 #include "itx_device.h"
 #include "itx_derive.h"
 #include "itx_auxwalk.h"
+#include "itx_devbuf.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -55,10 +56,10 @@ struct itx_xaveto {
     int device;
     const itx_table *t;
     XaDev d;
-    void *d_rep_word, *d_row_rep, *d_chrom, *d_names, *d_pool, *d_tid;
-    int32_t *d_hit;               // chosen rows of the batch being judged
-    uint8_t *d_verdict;
-    uint32_t *d_count;            // [0] vetoed, [1] needs the host
+    ItxBuf d_rep_word, d_row_rep, d_chrom, d_names, d_pool, d_tid;
+    ItxBuf d_hit;                 // int32: chosen rows of the batch being judged
+    ItxBuf d_verdict;
+    ItxBuf d_count;               // u32: [0] vetoed, [1] needs the host
     size_t cap;
     hipStream_t st;
 };
@@ -199,18 +200,19 @@ __global__ __launch_bounds__(256) void k_xa_apply(const uint8_t *__restrict__ ve
 }
 
 
-extern "C" int itx_xaveto_create(const itx_table *t, const itx_params *p, const uint32_t *row_rep, const uint32_t *rep_word, const char *const *chrom_name, int n_chrom,
-                                 size_t batch_capacity, itx_xaveto **out)
+#define XA_RC(call)                           \
+    do {                                      \
+        const int rc__ = (call);              \
+        if (rc__ != ITX_OK) return rc__;      \
+    } while (0)
+
+// fills the object; on a non-zero return the caller destroys what there is of it
+static int xa_create(itx_xaveto *x, const itx_table *t, const itx_params *p, const uint32_t *row_rep, const uint32_t *rep_word, const char *const *chrom_name, int n_chrom,
+                     size_t batch_capacity)
 {
-    if (!t || !p || !row_rep || !rep_word || !chrom_name || !out || n_chrom != t->n_chrom || batch_capacity == 0) {
-        itx_set_error("itx_xaveto_create: bad argument");
-        return ITX_E_ARG;
-    }
-    *out = nullptr;
-    ITX_HIP(hipSetDevice(t->device));
-    itx_xaveto *x = new itx_xaveto();
-    memset((void *)x, 0, sizeof *x);
+    const char *const who = "itx_xaveto_create";
     x->device = t->device;
+    ITX_HIP(hipSetDevice(t->device));
     x->t = t;
     x->cap = batch_capacity;
     // chromosomes: what a lookup needs, and the table of their names
@@ -240,31 +242,48 @@ extern "C" int itx_xaveto_create(const itx_table *t, const itx_params *p, const 
         pool.append(nm, len);
     }
     pool.append(16, '\0');
-    auto up = [&](void **dst, const void *src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(dst, bytes ? bytes : 16);
-        if (e != hipSuccess) return e;
-        return bytes ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+    auto up = [&](ItxBuf &dst, const void *src, size_t bytes) -> int {
+        XA_RC(itx_buf_need(who, dst, bytes));                             // (an empty one is 16 bytes all the same)
+        if (bytes) ITX_HIP(hipMemcpy(dst.p, src, bytes, hipMemcpyHostToDevice));
+        return ITX_OK;
     };
-    ITX_HIP(up(&x->d_rep_word, rep_word, sizeof(uint32_t) * (size_t)t->n_rep));
-    ITX_HIP(up(&x->d_row_rep, row_rep, sizeof(uint32_t) * (size_t)t->n_rows));
-    ITX_HIP(up(&x->d_chrom, ch.data(), sizeof(XaChrom) * ch.size()));
-    ITX_HIP(up(&x->d_names, names.data(), sizeof(XaName) * names.size()));
-    ITX_HIP(up(&x->d_pool, pool.data(), pool.size()));
-    ITX_HIP(hipMalloc((void **)&x->d_hit, sizeof(int32_t) * (batch_capacity + 64)));
-    ITX_HIP(hipMalloc((void **)&x->d_verdict, batch_capacity + 64));
-    ITX_HIP(hipMalloc((void **)&x->d_count, 16));
+    XA_RC(up(x->d_rep_word, rep_word, sizeof(uint32_t) * (size_t)t->n_rep));
+    XA_RC(up(x->d_row_rep, row_rep, sizeof(uint32_t) * (size_t)t->n_rows));
+    XA_RC(up(x->d_chrom, ch.data(), sizeof(XaChrom) * ch.size()));
+    XA_RC(up(x->d_names, names.data(), sizeof(XaName) * names.size()));
+    XA_RC(up(x->d_pool, pool.data(), pool.size()));
+    XA_RC(itx_buf_need(who, x->d_hit, sizeof(int32_t) * (batch_capacity + 64)));
+    XA_RC(itx_buf_need(who, x->d_verdict, batch_capacity + 64));
+    XA_RC(itx_buf_need(who, x->d_count, 16));
     ITX_HIP(hipStreamCreateWithFlags(&x->st, hipStreamNonBlocking));
-    x->d.rep_word = (const uint32_t *)x->d_rep_word;
-    x->d.row_rep = (const uint32_t *)x->d_row_rep;
-    x->d.chrom = (const XaChrom *)x->d_chrom;
-    x->d.names = (const XaName *)x->d_names;
-    x->d.pool = (const uint8_t *)x->d_pool;
+    x->d.rep_word = x->d_rep_word.as<uint32_t>();
+    x->d.row_rep = x->d_row_rep.as<uint32_t>();
+    x->d.chrom = x->d_chrom.as<XaChrom>();
+    x->d.names = x->d_names.as<XaName>();
+    x->d.pool = x->d_pool.as<uint8_t>();
     x->d.name_mask = cells - 1;
     x->d.o.mapq_min = (uint32_t)p->mapq_min;
     x->d.o.extension = p->extension;
     x->d.o.isize_max = p->isize_max;
     x->d.o.treat = p->treat_pe_as_se;
     x->d.o.discard = p->discard_half_mapped;
+    return ITX_OK;
+}
+
+extern "C" int itx_xaveto_create(const itx_table *t, const itx_params *p, const uint32_t *row_rep, const uint32_t *rep_word, const char *const *chrom_name, int n_chrom,
+                                 size_t batch_capacity, itx_xaveto **out)
+{
+    if (!t || !p || !row_rep || !rep_word || !chrom_name || !out || n_chrom != t->n_chrom || batch_capacity == 0) {
+        itx_set_error("itx_xaveto_create: bad argument");
+        return ITX_E_ARG;
+    }
+    *out = nullptr;
+    itx_xaveto *x = new itx_xaveto();
+    const int rc = xa_create(x, t, p, row_rep, rep_word, chrom_name, n_chrom, batch_capacity);
+    if (rc) {
+        itx_xaveto_destroy(x);
+        return rc;
+    }
     *out = x;
     return ITX_OK;
 }
@@ -277,15 +296,6 @@ extern "C" void itx_xaveto_destroy(itx_xaveto *x)
         (void)hipStreamSynchronize(x->st);
         (void)hipStreamDestroy(x->st);
     }
-    (void)hipFree(x->d_rep_word);
-    (void)hipFree(x->d_row_rep);
-    (void)hipFree(x->d_chrom);
-    (void)hipFree(x->d_names);
-    (void)hipFree(x->d_pool);
-    (void)hipFree(x->d_tid);
-    (void)hipFree(x->d_hit);
-    (void)hipFree(x->d_verdict);
-    (void)hipFree(x->d_count);
     delete x;
 }
 
@@ -300,16 +310,16 @@ extern "C" int itx_xaveto_set_tidmap(itx_xaveto *x, const int32_t *tid2chrom, in
         v[(size_t)k] = make_int2(c, (c >= 0 && c < x->t->n_chrom) ? x->t->h_chrom_size[c] : 0);
     }
     ITX_HIP(hipStreamSynchronize(x->st));
-    if (x->d_tid) ITX_HIP(hipFree(x->d_tid));
-    x->d_tid = nullptr;
-    ITX_HIP(hipMalloc(&x->d_tid, sizeof(int2) * ((size_t)n_tid + 1)));
-    ITX_HIP(hipMemcpy(x->d_tid, v.data(), sizeof(int2) * ((size_t)n_tid + 1), hipMemcpyHostToDevice));
-    x->d.tid = (const int2 *)x->d_tid;
+    x->d.tid = nullptr;                                               // (no map until the new one is whole)
+    x->d_tid.drop();
+    XA_RC(itx_buf_need("itx_xaveto_set_tidmap", x->d_tid, sizeof(int2) * ((size_t)n_tid + 1)));
+    ITX_HIP(hipMemcpy(x->d_tid.p, v.data(), sizeof(int2) * ((size_t)n_tid + 1), hipMemcpyHostToDevice));
+    x->d.tid = x->d_tid.as<int2>();
     x->d.n_tid = n_tid;
     return ITX_OK;
 }
 
-extern "C" int32_t *itx_xaveto_hits(itx_xaveto *x) { return x ? x->d_hit : nullptr; }
+extern "C" int32_t *itx_xaveto_hits(itx_xaveto *x) { return x ? x->d_hit.as<int32_t>() : nullptr; }
 extern "C" void *itx_xaveto_stream(itx_xaveto *x) { return x ? (void *)x->st : nullptr; }
 
 // the judgement over n records whose window bytes / offsets / marks / SoA the caller (the inflater) holds; chosen rows in x->d_hit
@@ -323,18 +333,20 @@ int itx_xaveto_run(itx_xaveto *x, const uint8_t *u, const uint32_t *rec_off, con
     *n_vetoed = *n_hard = 0;
     if (n == 0) return ITX_OK;
     ITX_HIP(hipSetDevice(x->device));
-    ITX_HIP(hipMemsetAsync(x->d_count, 0, 8, x->st));
-    hipLaunchKernelGGL(k_xa_verdict, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, x->st, x->t->dev, x->d, u, rec_off, xa_mark, tid, pos, end, f5, mpos, isize, x->d_hit,
-                       (uint32_t)n, x->d_verdict, x->d_count);
+    uint32_t *const d_count = x->d_count.as<uint32_t>();
+    uint8_t *const d_verdict = x->d_verdict.as<uint8_t>();
+    ITX_HIP(hipMemsetAsync(d_count, 0, 8, x->st));
+    hipLaunchKernelGGL(k_xa_verdict, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, x->st, x->t->dev, x->d, u, rec_off, xa_mark, tid, pos, end, f5, mpos, isize,
+                       x->d_hit.as<int32_t>(), (uint32_t)n, d_verdict, d_count);
     ITX_HIP(hipGetLastError());
     uint32_t c[2] = {0, 0};
-    ITX_HIP(hipMemcpyAsync(c, x->d_count, 8, hipMemcpyDeviceToHost, x->st));
+    ITX_HIP(hipMemcpyAsync(c, d_count, 8, hipMemcpyDeviceToHost, x->st));
     ITX_HIP(hipStreamSynchronize(x->st));
     *n_hard = c[1];
     if (c[1]) return ITX_OK;                                          // the host has to look: nothing is marked
-    hipLaunchKernelGGL(k_xa_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, x->st, x->d_verdict, f5, (uint32_t)n, x->d_count);
+    hipLaunchKernelGGL(k_xa_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, x->st, d_verdict, f5, (uint32_t)n, d_count);
     ITX_HIP(hipGetLastError());
-    ITX_HIP(hipMemcpyAsync(c, x->d_count, 8, hipMemcpyDeviceToHost, x->st));
+    ITX_HIP(hipMemcpyAsync(c, d_count, 8, hipMemcpyDeviceToHost, x->st));
     ITX_HIP(hipStreamSynchronize(x->st));
     *n_vetoed = c[0];
     return ITX_OK;

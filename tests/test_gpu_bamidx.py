@@ -192,6 +192,19 @@ def test_three_runs_with_host_appends_between_and_a_pool_that_grows(big):
     assert levels >= {2, 3, 4, 5}, levels
 
 
+def test_lifecycle_and_host_record_buffers_that_regrow():
+    """an index enabled and destroyed with no call between; then, twice in one process: a host append of one record, whose offsets
+    leave room for 1 + 0 + 1024 records, then one of 1500, so that the five buffers of the host route are taken anew under one object;
+    the index is the restatement's"""
+    bo = eng.Bamout(batch_capacity=16)
+    bo.index_enable([100_000])
+    bo.close()
+    steps = [("host", [rec(0, 100)]), ("host", [rec(0, 200 + 40 * i, L=60 + i % 90) for i in range(1500)])]
+    for _ in range(2):
+        got, stream, idx, info = check([100_000], steps, first=7)
+        assert info["entries"] == 1501 and refio.bgzf_decompress(got) == stream
+
+
 def test_fetch_equivalence(big):
     l_ref, steps, first, got, stream, idx, info = big
     sizes = [size for off, size, isize in bai.member_walk(got)]

@@ -179,6 +179,23 @@ def test_geometries(inf):
     assert want_b.count(b"\n") > 1025 * TILE > want_v.count(b"\n") > 0
 
 
+def test_lifecycle_and_slot_outputs_that_regrow(inf):
+    """made and destroyed with no call between; then, twice in one process: made, a batch of one record into either slot, then a batch
+    of 1000 into either slot, so that all four outputs of both slots (device and page-locked, -B and -V) are dropped and taken anew
+    under one object, both texts byte for byte the expectation's; destroyed"""
+    eng.Bed([1000], batch_capacity=16).close()
+    p = bc.params(extension=0)
+    recs = [bc.record(pos=41, qname=b"only\0"), bc.record(pos=42, qname=b"next\0")] + bulk_records(13, 2000)
+    for _ in range(2):
+        got_b, got_v, want_b, want_v, _, st = device_texts(inf, recs, p, batches=[1, 1, 1000, 1000], cap=1000)
+        assert got_b == want_b and got_v == want_v and st["batches"] == 4
+        assert got_b.startswith(b"chr1\t41\t91\tonly\t37\t+\nchr1\t42\t92\tnext\t37\t+\n") and got_v.startswith(b"chr1\t41\t91\tonly\t37\t+\n")
+    # a batch of one line (23 bytes) leaves room for need + need / 4 + 4096 bytes: either text of either large batch is beyond it
+    names, sizes = [nm for nm, _ in HEADER], [l for _, l in HEADER]
+    for lo in (2, 1002):
+        assert min(len(t) for t in bc.lines(p, HEADER, names, sizes, recs[lo:lo + 1000])[:2]) > 23 + 23 // 4 + 4096
+
+
 def test_plain_device_arrays_and_two_batches_in_flight(inf):
     """itx_bed_run over torch tensors gives the window route's text; two batches may be started before the first is collected, and
     come back oldest first"""

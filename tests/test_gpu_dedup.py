@@ -103,19 +103,43 @@ def test_device_set_equals_the_reference_loop(k, hash_bits, monkeypatch):
     dd.close()
 
 
-def test_without_mates_and_in_one_piece():
-    """unpaired input: no mpos / isize arrays at all; one call for everything"""
-    import torch
+@pytest.fixture(scope="module")
+def one_piece():
+    """unpaired input, the smallest case here: (parameters, records, the records the reference drops)"""
     recs = list(make_records(5, 100_000))
     recs[4] = (recs[4] & ~np.uint8(1 | 4 | 16)).astype(np.uint8)
     p = dict(mapq_min=10, extension=150, isize_max=500, treat_pe_as_se=False, discard_half_mapped=False)
     want, _ = model(p, [0, 1, 2, 3], [0, 1, 2, 3], recs, [set(), None])
+    return p, recs, want
+
+
+def test_without_mates_and_in_one_piece(one_piece):
+    """unpaired input: no mpos / isize arrays at all; one call for everything"""
+    import torch
+    p, recs, want = one_piece
     dd = eng.Dedup(CHROM_SIZE, p)
     dd.set_tidmap([0, 1, 2, 3], [0, 1, 2, 3])
     dev = [torch.from_numpy(a).cuda() for a in recs[:5]]
     dd.run(*dev)
     assert np.array_equal((dev[4].cpu().numpy() & NOLOOKUP) != 0, want)
     dd.close()
+
+
+def test_lifecycle(one_piece):
+    """made and destroyed with no call between; then made, used on the smallest case here (the map set twice: the old one goes; the
+    table grows once under the 100 000 records) and destroyed, twice in one process"""
+    import torch
+    p, recs, want = one_piece
+    eng.Dedup(CHROM_SIZE, p).close()
+    for _ in range(2):
+        dd = eng.Dedup(CHROM_SIZE, p)
+        dd.set_tidmap([0, 1, 2, 3], [3, 2, 1, 0])
+        dd.set_tidmap([0, 1, 2, 3], [0, 1, 2, 3])
+        dev = [torch.from_numpy(a).cuda() for a in recs[:5]]
+        dd.run(*dev)
+        assert np.array_equal((dev[4].cpu().numpy() & NOLOOKUP) != 0, want)
+        assert dd.counts()["dropped"] == int(want.sum())
+        dd.close()
 
 
 # ---- the command ----------------------------------------------------------------------------------------------------------

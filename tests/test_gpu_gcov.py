@@ -154,6 +154,24 @@ def test_a_chromosome_of_size_three_alone():
     assert check([("c", 3)], recs([se(0, 0, 2), se(0, 1, 2), se(0, 0, 1)]))[0] == b"c\t0\t2\t2\n"      # equal depths on both sides: one line
 
 
+def test_lifecycle():
+    """made and destroyed with no call between; then made, used at the smallest shape here (both routes, the text rounds, the bigWig
+    content) and destroyed, twice in one process: what a double free or a buffer freed under a running stream would break"""
+    eng.Gcov([3], dict(P0), batch_capacity=1).close()
+    ch, rd = [("c", 3)], recs([se(0, 0, 2), se(0, 1, 2)])
+    for _ in range(2):
+        g = eng.Gcov([3], dict(P0), batch_capacity=2)
+        g.set_tidmap([0])
+        g.set_tidmap([0])                                                  # the map is replaced: the old one goes
+        feed_run(g, rd)
+        feed_host(g, ch, rd, P0)
+        g.finish([0], ["c"])
+        g.bigwig_build(0)
+        assert g.bigwig(0)["n_items"] == 2
+        assert g.text(0)[0] == g.text(1)[0] == b"c\t0\t1\t2\nc\t1\t2\t4\n"
+        g.close()
+
+
 # ---- abutting, identical, nested
 
 def test_abutting_identical_and_nested_reads():

@@ -225,6 +225,26 @@ def test_strings_gathered_on_the_device():
     x.close()
 
 
+def test_lifecycle_and_buffers_that_regrow():
+    """made and destroyed with no call between; then, twice in one process: made, a BGZF chunk of three lines in a few members, then
+    one of 1500 lines in members of 100 bytes in the same slot: its compressed bytes, block lists, status bytes, the decoder's scratch
+    and the string gather's buffers are all far beyond need + need / 4 + 64 of the first and are taken anew under one object; text,
+    records and strings as for every chunk here; destroyed"""
+    eng.SamText(NAMES, 1 << 16).close()
+    few = body(3)
+    room = lambda need: need + need // 4 + 64                              # what a buffer made for `need` elements holds
+    chunks = [(text, members(text, 100)) for text in (few, TEXT)]
+    (_, m0), (_, m1) = chunks
+    assert len(m1) > 3 * room(len(m0) + 1) and len(b"".join(m1)) > 3 * room(len(b"".join(m0)) + 64) and 2 * 1500 > 3 * room(2 * 3)
+    for _ in range(2):
+        x = eng.SamText(NAMES, 1 << 20)
+        for text, ms in chunks:
+            res, _, a = check(x, b"".join(ms), text, slot=0)
+            assert res["n_rec"] == text.count(b"\n")
+            check_strings(x, 0, text, a, 0, res["n_rec"], 3)
+        x.close()
+
+
 def test_damaged_member(sam):
     ms = [bytearray(m) for m in members(TEXT, 9000)]
     ms[5][18] |= 6                                                          # one byte of its deflate data: a block type that does not exist

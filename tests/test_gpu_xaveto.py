@@ -162,6 +162,26 @@ def test_numbers_only_strtol_can_read_go_to_the_host(exe, tmp_path):
         _same(str(tmp_path / "dev"), str(tmp_path / "ref"))
 
 
+def test_lifecycle():
+    """the object itself, without the command: made and destroyed with no call between; then made, one window of 64 records judged
+    against the model of tests/auxcases.py (the rig of tests/test_gpu_auxwalk.py) and destroyed, twice in one process"""
+    import bedcase as bc
+    import test_gpu_auxwalk as aw
+    from iteres_amd import engine as eng
+    for k in range(2):
+        rig = aw.Rig()
+        if k == 0:
+            eng.XaVeto(rig.eng, np.zeros(rig.tab.n_rows, np.uint32), np.zeros(rig.tab.n_rep, np.uint32), [nm for nm, _ in rig.header], batch_capacity=16).close()
+        rig.xv.set_tidmap([0, 1, 2])                                        # a second map: the first one goes
+        recs = aw.spread([r for r in rig.R if rig.judged[r.k][1] is not aw.am.HARD], 64)
+        n = aw.window(rig.inf, bc.bam_bytes(rig.header, [r.rec for r in recs]))
+        assert n == 64
+        want = np.array([bool(c and v is True) for c, v in (rig.judged[r.k] for r in recs)])
+        assert rig.xv.judge(rig.inf, 0, n) == (int(want.sum()), 0)
+        assert np.array_equal((aw.fetch(rig.inf, n)[0]["flag5"] & eng.F5_NOLOOKUP) != 0, want)
+        rig.close()
+
+
 def test_windows_of_several_batches_stay_on_the_device(exe, tmp_path):
     """A BAM whose records carry no sequence: one decoded window holds more records than a batch of the engine (4 M). The
     veto runs batch by batch inside the window (it used to send such windows to the host, silently 3.7x slower): 9 M records,
